@@ -13,7 +13,11 @@ reference crops (weights: seeded synthetic state_dicts; no checkpoint/dataset ex
 path shards by query: every rank holds a replica of the reference state and runs its own K steps (weak scaling, no
 collective on the data path); value = N*K*batch / max-over-ranks time; `single_query_ms` = latency of one query alone (batch 1).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, dtype, ...).
+`--dump-outputs DIR` writes what the timed path returned in its last step (rank 0) as DIR/rows.npy.  Everything else below
+is measured only with `--full`.
+
+Extra objects on the JSON line (--full):
   roofline     — the dominant MFMA-bound kernel family by serialised time (since round 2 the Winograd kernel: own VGG trunk +
                  the conv layers routed to it): FLOPs EXECUTED by every launch divided by its HIP-event duration (events
                  recorded on the launch stream), against 157.3 TFLOP/s; for the Winograd family the direct-form equivalent
@@ -227,7 +231,16 @@ def main():
     ap.add_argument("--shard-refs", action="store_true",
                     help="strong-scaling variant: all ranks work on the SAME query stream, the selector's reference cache "
                          "is sharded over the ranks (RCCL statistics all-reduces + feature all-gather); default is query replicas")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement after the headline: rooflines, per-stage and single-query times, parity against "
+                         "the reference's rows, reduced-precision modes, reference-feature cache, chained path, reference-view sweep, CPU "
+                         "baseline, collective log of --shard-refs.  Off by default: a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's result rows of the LAST timed step to DIR/rows.npy (float32 [batch, 26]: "
+                         "position(2), scale, ref_idx, angle, then quaternion(4), offset(2), log2-scale of each of the 3 refine steps)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     self_launch(args)
 
     from gen6d_amd import lib, ops, parallel, synth
@@ -304,14 +317,14 @@ def main():
     parallel.barrier()
     torch.cuda.synchronize()
     coll_log = None
-    if shard_refs:
+    if shard_refs and args.full:
         # per-collective log of ONE extra query (outside the timed region: logging synchronises the stream around every collective)
         parallel.COLLECTIVE_LOG = []
         step(0, eager=True)
         torch.cuda.synchronize()
         coll_log, parallel.COLLECTIVE_LOG = parallel.COLLECTIVE_LOG, None
         parallel.barrier()
-    if not use_graph:
+    if not use_graph and args.full:
         ops.PROFILE, ops.PROFILE_HBM = [], {}
     ops.marker(1)
     t0 = time.perf_counter()
@@ -323,7 +336,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, dev)
-    if use_graph:
+    last_rows = rows[-1]                             # what the timed path returned in its last step
+    if use_graph and args.full:
         # per-kernel HIP events cannot be recorded inside a graph replay: the roofline pass re-runs the same K steps
         # through the eager launch path (identical kernels, shapes and order) right after the timed region
         ops.SERIAL = True                      # branches back to back: per-kernel durations without stream overlap
@@ -334,16 +348,16 @@ def main():
             step(args.warmup + i, eager=True)
         torch.cuda.synchronize()
         ops.SERIAL = no_fork
-    prof, ops.PROFILE = ops.PROFILE, None
+    prof, ops.PROFILE = ops.PROFILE or [], None
     prof_hbm, ops.PROFILE_HBM = ops.PROFILE_HBM or {}, None
-    stages = stage_times(pipe, fulls[0:1], crops[0:1]) if (rank == 0 and not shard_refs) else None   # (sharded stages hold collectives)
-    rows = (parallel.gather_rows(torch.cat(rows, 0), world * args.steps * B) if ((world > 1 or args.force_dist) and not shard_refs)
+    stages = stage_times(pipe, fulls[0:1], crops[0:1]) if (rank == 0 and not shard_refs and args.full) else None   # (sharded stages hold collectives)
+    rows = (parallel.gather_rows(torch.cat(rows, 0), world * args.steps * B) if ((world > 1 or args.force_dist) and not shard_refs and args.full)
             else torch.cat(rows, 0))
     n_queries = args.steps * B if shard_refs else world * args.steps * B
     # latency of ONE query alone: a batch-1 graph on one lane, replays back to back (what a single camera stream would see); measured
     # without and with the query's independent branches (selector levels, refiner feature branches) forked onto side streams
     single_ms, single_detail = None, None
-    if rank == 0 and use_graph and not shard_refs:
+    if rank == 0 and use_graph and not shard_refs and args.full:
         single_detail = {}
         for tag, serial in (("one_stream", True), ("branches_forked", False)):
             ops.SERIAL = serial
@@ -477,8 +491,9 @@ def main():
         hbm[name] = {"launches_per_step": len(recs) / args.steps, "mbytes_per_launch": nb / len(recs) / 1e6,
                      "avg_launch_us": t_ms / len(recs) * 1e3, "achieved_GBps": nb / (t_ms * 1e-3) / 1e9,
                      "frac_of_8TBps": nb / (t_ms * 1e-3) / 8e12}
-    result["hbm_kernels"] = hbm
-    result["stages_ms"] = stages
+    if args.full:
+        result["hbm_kernels"] = hbm
+        result["stages_ms"] = stages
     result["ranks_seen"], result["backend"] = ranks_seen, parallel.backend_name()
     if coll_log is not None:
         kinds = {}
@@ -495,7 +510,7 @@ def main():
                    "call alone; `captured`: the timed region replays ONE hipGraph per batch that holds the kernels AND the collectives; "
                    + ("RCCL: enqueued on device tensors, no host staging" if parallel.backend_name() == "nccl" else
                       "gloo: every collective is staged through host memory (ranks share one GPU on this lease; RCCL refuses that)")}
-    if shard_refs and world == 1:
+    if shard_refs and world == 1 and args.full:
         # the forced-collective path against the plain one on the same four images (same kernels apart from the InstanceNorm
         # finalisation, which moves from the producers' last blocks into g6d_stats_finalize behind the all-reduce)
         idx4 = torch.arange(4, device=dev)
@@ -514,6 +529,12 @@ def main():
     result["build_s"] = {"value": build_s, "what": "TensorPipeline.build: detector reference filters + selector reference cache "
                                                    "(trunk over 32 + 320 crops, R1/R2 sums, viewpoint embedding), incl. first-use "
                                                    "library initialisation; reference: 0.57 s + 9.8 s on 8 CPU threads (BASELINE.md §2)"}
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), last_rows.cpu().numpy().astype(np.float32))
+    if not args.full:
+        print(json.dumps(result))
+        return
     got_rows = rows.cpu()
     # fp32 row of every synthetic image (rank 0's rows, headline lane count): side passes with another lane count draw the images in
     # another order, so they are compared per image

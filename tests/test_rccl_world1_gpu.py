@@ -101,7 +101,7 @@ def test_replica_bench_plumbing_on_rccl_world1():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1", "--batch", "4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1", "--batch", "4", "--full",
                           "--no-cpu-baseline", "--no-cached", "--no-chained", "--no-sweep", "--lowp", ""], env=env, capture_output=True, text=True,
                          timeout=420)
     assert out.returncode == 0, out.stderr[-3000:]

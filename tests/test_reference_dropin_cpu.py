@@ -1,11 +1,11 @@
-"""The drop-in under the REFERENCE's own estimator: /root/reference/estimator.py is imported
-unchanged (import-time stubs of tests/golden/make_golden.py + a test-only cv2 warp shim), `network.name2network` is
-updated with gen6d_amd's classes, and the reference's `Gen6DEstimator(cfg).build(db, 'all')` / `.predict(img, K)`
-run on database objects that ARE instances of the reference's own `LINEMODDatabase` / `GenMOPDatabase` classes — no
-per-dataset adapter, no extra attributes.  The HIP ops are emulated by tests/ref_ops.py (there is no GPU here), so this
-is a test of the host contracts: numpy APIs, checkpoint loading, object meta resolved through the reference's
-dataset.database helpers.  Runs in a subprocess because the reference's top-level package names (`network`, `utils`,
-`dataset`) and the stubs must not leak into the rest of the suite.  Skipped where /root/reference is absent."""
+"""The drop-in under the REFERENCE's own estimator, held against its recorded results: tests/golden/make_golden_dropin.py
+ran the reference's estimator.py unchanged, with gen6d_amd's classes in `network.name2network`, on database objects that ARE instances of
+the reference's own `LINEMODDatabase` / `GenMOPDatabase` classes (no per-dataset adapter, no extra attributes), and stored its reference
+crops, detection, selected view and refined pose (tests/golden/dropin_{linemod,genmop}.npz, with the SHA-256 of the synthetic query and
+weights).  Here gen6d_amd's own estimator runs the same networks on the same objects and must reproduce them: same detection, same selected
+view, same refined pose up to the 1-grey-level rounding of intermediate uint8 crops.  The HIP ops are emulated by tests/ref_ops.py (there
+is no GPU here), so this is a test of the host contracts: numpy APIs, checkpoint state, object meta resolved per database type.  Runs in a
+subprocess because the op emulation is patched into gen6d_amd.ops and must not leak into the rest of the suite."""
 import os
 import subprocess
 import sys
@@ -14,63 +14,33 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 SCRIPT = textwrap.dedent("""
     import os, sys, types
-    import numpy as np, torch, yaml
-    ROOT, REF, KIND = %r, %r, sys.argv[1]
+    import numpy as np, torch
+    ROOT, KIND = %r, sys.argv[1]
     POSE_ATOL = 1e-4            # measured 3.2e-5 (linemod) / 1.9e-5 (genmop) with damped heads; was 2e-2 with the random heads (VERDICT r03 weak #3)
-    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]
-    import make_golden as MG
-    MG.install_stubs()
-    if not hasattr(np, "bool"): np.bool = bool
-    if not hasattr(np, "str"): np.str = str
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import ref_ops
-    import cv2                                      # the stub module: give it a real (float bilinear) warp for this test
-
-    def warp(img, H, size, flags=0):
-        img = np.asarray(img)
-        squeeze = img.ndim == 2
-        src = torch.from_numpy(np.ascontiguousarray(img[..., None] if squeeze else img))
-        if src.dtype == torch.uint8:
-            out = ref_ops.warp_perspective(src, H, size[1], size[0]).numpy()
-        else:                                       # float masks: warp the 0..255 image and rescale
-            out = ref_ops.warp_perspective((src.float() * 255).round().clamp(0, 255).to(torch.uint8), H, size[1], size[0],
-                                           out_float=True).numpy().astype(img.dtype)
-        return out[..., 0] if squeeze else out
-    cv2.warpPerspective = warp
-    cv2.warpAffine = warp
-
-    sys.path.insert(0, REF)
-    import network.pretrain_models as pm
-    pm.VGGBNPretrain._initialize_weights = lambda self: None
-    import network                                               # the REFERENCE's registry ...
-    from gen6d_amd.network import name2network as amd
-    network.name2network.update(amd)                             # ... with the drop-in classes (INTEGRATION.md §1)
     from gen6d_amd import ops, synth
+    from gen6d_amd.network import name2network
     from gen6d_amd.synth_db import SyntheticDatabase
     for name in dir(ops):                                        # no GPU in this container: per-op PyTorch references
         if not name.startswith("_") and callable(getattr(ops, name)) and hasattr(ref_ops, name):
             setattr(ops, name, getattr(ref_ops, name))
-    torch.nn.Module.cuda = lambda self, *a, **k: self            # estimator.py:123 calls .cuda()
+    g = np.load(os.path.join(ROOT, "tests", "golden", f"dropin_{KIND}.npz"))
 
-    # checkpoints + YAML exactly where the reference looks for them (estimator.py:117-125)
-    os.makedirs("configs", exist_ok=True)
-    cfg = {"name": "gen6d_synth", "type": "gen6d", "ref_view_num": 8, "det_ref_view_num": 8, "refine_iter": 1, "ref_resolution": 128}
+    # the networks as the reference's estimator loaded them: name2network[cfg["network"]](cfg) + the checkpoint's state_dict, eval()
+    mods = {}
     for kind in ("detector", "selector", "refiner"):
-        name = kind + "_synth"
-        with open(f"configs/{kind}.yaml", "w") as f:
-            yaml.safe_dump({"name": name, "network": kind}, f)
-        os.makedirs(f"data/model/{name}", exist_ok=True)
         sd = synth.synth_state_dict(kind)
         if kind == "refiner":                                    # pose heads around the identity update, as a trained refiner's
             sd = synth.damp_refiner_head(sd)                     # (the seeded random heads amplify one grey level to 1e-2 on the pose)
-        torch.save({"step": 1, "network_state_dict": sd}, f"data/model/{name}/model_best.pth")
-        cfg[kind] = f"configs/{kind}.yaml"
+        net = name2network[kind]({"name": kind + "_synth", "network": kind})
+        net.load_state_dict(sd)
+        mods[kind] = net.eval()
+    assert synth.fingerprint({k: m.state_dict() for k, m in mods.items()}) == str(g["sha_weights"]), "weights differ from the recorded run"
 
-    import dataset.database as refdb
-    from estimator import name2estimator                         # the reference's estimator.py, unchanged
     inner = SyntheticDatabase(n_views=24, size=(96, 128), focal=140.0)
 
     class _Proto:                                                # image / pose access only; NO object_* attributes
@@ -81,50 +51,48 @@ SCRIPT = textwrap.dedent("""
         def get_mask(self, i): return inner.get_mask(i)
 
     if KIND == "linemod":
-        class DB(_Proto, refdb.LINEMODDatabase):                 # isinstance(db, LINEMODDatabase) is what the reference tests
+        class LINEMODDatabase(_Proto):                           # the reference's attributes of a LINEMOD object (database.py:67-68)
             def __init__(self):
-                refdb.BaseDatabase.__init__(self, "linemod/cat")
-                self.object_center = inner.object_center.copy()   # LINEMODDatabase's own attributes (database.py:67-68)
+                self.database_name = "linemod/cat"
+                self.object_center = inner.object_center.copy()
                 self.object_vert = np.asarray([0, 0, 1], np.float32)
+        db = LINEMODDatabase()
         os.makedirs("data/LINEMOD/cat", exist_ok=True)
         np.savetxt("data/LINEMOD/cat/distance.txt", [inner.object_diameter * 100.0])     # cm, as database.py:349
     else:
-        class DB(_Proto, refdb.GenMOPDatabase):
+        class GenMOPDatabase(_Proto):
             def __init__(self):
-                refdb.BaseDatabase.__init__(self, "genmop/blob-ref")
+                self.database_name = "genmop/blob-ref"
                 self.meta_info = types.SimpleNamespace(center=inner.object_center.copy())   # database.py:369
+        db = GenMOPDatabase()
         inner.object_diameter = 2.0                              # GenMOP objects are pre-scaled to diameter 2 (database.py:351)
-    db = DB()
     assert not hasattr(db, "object_diameter") and not hasattr(db, "diameter")
-
-    est = name2estimator[cfg["type"]](cfg)
-    assert type(est.detector).__module__.startswith("gen6d_amd") and type(est.refiner).__module__.startswith("gen6d_amd")
-    est.build(db, "all")
-    assert est.ref_info["imgs"].shape == (8, 128, 128, 3) and est.ref_info["masks"].shape == (8, 128, 128)
     img, K = inner.get_image("21"), inner.get_K("21")
-    pose, inter = est.predict(img, K)
-    pose = np.asarray(pose)
+    assert synth.fingerprint({"img": torch.from_numpy(np.ascontiguousarray(img)), "K": torch.from_numpy(np.asarray(K))}) == str(g["sha_inputs"]), \
+        "synthetic query differs from the recorded run"
+
+    # what the reference's estimator returned (recorded)
+    pose = g["pose"]
     assert pose.shape == (3, 4) and np.isfinite(pose).all()
     np.testing.assert_allclose(pose[:, :3] @ pose[:, :3].T, np.eye(3), atol=1e-4)
-    assert len(inter["refine_poses"]) == 2 and inter["sel_scores"].shape == (8,)
+    assert g["refine_poses"].shape[0] == 2 and g["sel_scores"].shape == (8,)
+    assert g["ref_imgs"].shape == (8, 128, 128, 3) and tuple(g["ref_masks_shape"]) == (8, 128, 128)
 
     # the same object through gen6d_amd's own estimator (device-warp flow, here emulated): same detection, same
     # selected view, same refined pose up to the 1-grey-level rounding of intermediate uint8 crops
     from gen6d_amd.estimator import Gen6DEstimator
-    mods = {k: getattr(est, k) for k in ("detector", "selector", "refiner")}
     own = Gen6DEstimator({"ref_view_num": 8, "det_ref_view_num": 8, "refine_iter": 1}, modules=mods)
     own.build(db, "all")
-    assert (np.abs(own.ref_info["imgs"].astype(int) - est.ref_info["imgs"].astype(int)) <= 1).all()
+    assert (np.abs(own.ref_info["imgs"].astype(int) - g["ref_imgs"].astype(int)) <= 1).all()
     pose2, inter2 = own.predict(img, K)
-    assert inter2["sel_ref_idx"] == inter["sel_ref_idx"]
-    np.testing.assert_allclose(inter2["det_position"], inter["det_position"], atol=0.5)
-    print("POSE_DIFF", float(np.abs(pose2 - pose).max()), float(np.abs(np.asarray(inter2["refine_poses"][0]) - np.asarray(inter["refine_poses"][0])).max()))
+    assert inter2["sel_ref_idx"] == int(g["sel_ref_idx"])
+    np.testing.assert_allclose(inter2["det_position"], g["det_position"], atol=0.5)
+    print("POSE_DIFF", float(np.abs(pose2 - pose).max()), float(np.abs(np.asarray(inter2["refine_poses"][0]) - g["refine_poses"][0]).max()))
     np.testing.assert_allclose(pose2, pose, atol=POSE_ATOL)
-    print("DROPIN_OK", KIND, inter["sel_ref_idx"])
-""") % (ROOT, REF)
+    print("DROPIN_OK", KIND, inter2["sel_ref_idx"])
+""") % (ROOT,)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "network")), reason="needs the reference checkout (build container only)")
 @pytest.mark.parametrize("kind", ["linemod", "genmop"])
 def test_reference_estimator_runs_on_amd_networks(tmp_path, kind):
     script = tmp_path / "dropin.py"

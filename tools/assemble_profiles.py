@@ -58,7 +58,7 @@ def main():
     wg = w.get("gflop_direct_form_per_step", 0.0)
     wexec = w.get("gflop_per_launch", 0.0) * w.get("launches_per_step", 0.0)
     open(os.path.join(P, f"{RND}_bench_kernel_stats_serial.md"), "w").write(
-        f"# rocprofv3 --kernel-trace --stats of `python bench.py --steps {steps} --warmup 2 --no-cpu-baseline --no-cached --lowp '' --serial` (1x MI355X)\n\n"
+        f"# rocprofv3 --kernel-trace --stats of `python bench.py --steps {steps} --warmup 2 --no-cpu-baseline --no-cached --lowp '' --serial --full` (1x MI355X)\n\n"
         f"Same workload, one BATCH of {ser.get('batch', 1)} queries at a time, no graph replay (`--serial`), which is how bench.py's roofline pass\n"
         "runs: per-kernel durations are not inflated by overlap and can be compared with the `roofline` objects of the bench JSON.\n"
         f"A step = {ser.get('batch', 1)} queries: divide the per-step figures by {ser.get('batch', 1)} for per-query numbers.\n\n"

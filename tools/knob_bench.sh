@@ -5,7 +5,7 @@ for k in "$@"; do
   KNOBS="${k%%;*}" PYSW="$( [[ "$k" == *";"* ]] && echo "${k#*;}" )" timeout 300 python -c "
 import sys, runpy
 sys.path.insert(0, 'tools'); import toolenv
-sys.argv = ['bench.py', '--steps', '${STEPS:-10}', '--warmup', '3', '--no-cpu-baseline', '--no-cached', '--no-chained', '--no-sweep', '--lowp', '']
+sys.argv = ['bench.py', '--full', '--steps', '${STEPS:-10}', '--warmup', '3', '--no-cpu-baseline', '--no-cached', '--no-chained', '--no-sweep', '--lowp', '']
 runpy.run_path('bench.py', run_name='__main__')" 2> /tmp/knob_err.log | python -c "
 import sys, json
 for line in sys.stdin:
