@@ -48,6 +48,7 @@ struct C16Params {
   double* stats; int stat_rows_per_group;                    // optional: [groups][Cout][2]
   float acc_scale;                                           // y = acc * acc_scale + bias (the filters may carry a power-of-two scale)
   int ablate;                                                // knob c16_ablate (timing experiments)
+  G6dRange16 rng;                                            // pair exponents / range record (zero: unscaled, not recorded)
 };
 
 template <int MM> struct C16T;
@@ -66,7 +67,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t c16_rsrc(const void* p, unsign
 // NT = threads that share the pass (256: the whole block, NPX = 128; 64: one wave, tid = lane, no block-wide synchronisation inside).
 template <int MM, int NT, int NPX, int CH = 64>
 __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16Seg& sg, const float* ep, double* red, int tid, int cbase, int g0, int x0,
-                                                  int tw_log2, int ylim, int px0) {
+                                                  int tw_log2, int ylim, int px0, unsigned& amax) {
   typedef typename C16T<MM>::T T;
   typedef typename C16T<MM>::V V8;
   static_assert(NT == 64 || (NPX == 128 && CH == 64), "the block-wide form handles whole tiles of 64 channels");
@@ -78,6 +79,10 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
     g = g0 + py; x = x0 + (px & (TW - 1));
     return py < ylim && g < sg.rows && x < W;
   };
+  // pair outputs hold split16(v * 2^-eo); amax: max bits(|v|) of the stored unscaled values, recorded by the caller once per wave
+  // after its last pass (G6dRange16)
+  const bool pairs = p.full_type == 3 || p.pool_type == 3;
+  const int eo = pairs ? g6d_exp_out(p.rng) : 0;
   if (p.full_type == 1) {
 #pragma unroll
     for (int j = 0; j < NPX * C8 / NT; ++j) {
@@ -101,8 +106,10 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
         V8 hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          hi[e] = (T)v0[e]; lo[e] = (T)(v0[e] - (float)hi[e]);
-          hi[4 + e] = (T)v1[e]; lo[4 + e] = (T)(v1[e] - (float)hi[4 + e]);
+          amax = max(amax, max(g6d_abs_bits(v0[e]), g6d_abs_bits(v1[e])));
+          const float u0 = ldexpf(v0[e], -eo), u1 = ldexpf(v1[e], -eo);
+          hi[e] = (T)u0; lo[e] = (T)(u0 - (float)hi[e]);
+          hi[4 + e] = (T)u1; lo[4 + e] = (T)(u1 - (float)hi[4 + e]);
         }
         char* o = sg.full + (((long)g * W + x) * sg.ld_full + cbase + ch) * 2;
         *reinterpret_cast<V8*>(o) = hi;
@@ -145,7 +152,11 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
         } else if (p.pool_type == 3) {
           V8 hi, lo;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { hi[e] = (T)m[e]; lo[e] = (T)(m[e] - (float)hi[e]); }
+          for (int e = 0; e < 8; ++e) {
+            amax = max(amax, g6d_abs_bits(m[e]));
+            const float u = ldexpf(m[e], -eo);
+            hi[e] = (T)u; lo[e] = (T)(u - (float)hi[e]);
+          }
           *reinterpret_cast<V8*>(sg.pool + o * 2) = hi;
           *reinterpret_cast<V8*>(sg.pool + (o + p.Cout) * 2) = lo;
         } else {
@@ -174,18 +185,19 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
       }
     } else {
       // one wave: lane = channel; fp32 partial sums of 32 pixels each, combined in fp64
-      if (tid >= CH) return;
-      double d1 = 0.0, d2 = 0.0;
-      for (int q = 0; q < NPX / 32; ++q) {
-        float s1 = 0.f, s2 = 0.f;
-        for (int lp = 32 * q; lp < 32 * q + 32; ++lp) {
-          int g, x;
-          if (inside(lp, g, x)) { const float v = ep[lp * C16_EP_LD + tid]; s1 += v; s2 += v * v; }
+      if (tid < CH) {                  // (no early return: the caller's range record needs every lane)
+        double d1 = 0.0, d2 = 0.0;
+        for (int q = 0; q < NPX / 32; ++q) {
+          float s1 = 0.f, s2 = 0.f;
+          for (int lp = 32 * q; lp < 32 * q + 32; ++lp) {
+            int g, x;
+            if (inside(lp, g, x)) { const float v = ep[lp * C16_EP_LD + tid]; s1 += v; s2 += v * v; }
+          }
+          d1 += (double)s1; d2 += (double)s2;
         }
-        d1 += (double)s1; d2 += (double)s2;
+        atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2, d1);
+        atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2 + 1, d2);
       }
-      atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2, d1);
-      atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2 + 1, d2);
     }
   }
 }
@@ -198,20 +210,23 @@ __device__ __forceinline__ void c16_epilogue(const C16Params& p, const C16Seg& s
   // tile's 128 pixels into ep[pixel * C16_EP_LD + channel - cbase];  ylim: tile rows below it lie inside the image
   float* ep = reinterpret_cast<float*>(lds);
   double* red = reinterpret_cast<double*>(lds + C16_BM * C16_EP_LD * 4);       // [4 quarters][64 ch][2] statistics partials
+  unsigned amax = 0;
 #pragma unroll 1
   for (int h = 0; h < 2; ++h) {
     const int cbase = nt * C16_BN + 64 * h;
     write_tile(h, ep, cbase);
     __syncthreads();
-    c16_epilogue_pass<MM, 256, 128>(p, sg, ep, red, tid, cbase, g0, x0, tw_log2, ylim, 0);
+    c16_epilogue_pass<MM, 256, 128>(p, sg, ep, red, tid, cbase, g0, x0, tw_log2, ylim, 0, amax);
     __syncthreads();
   }
+  if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
 }
 
 // The 2 x 2 wave layout of conv16_kernel / conv16r_kernel: wave (wm, wn) holds pixels 64 wm .. + 63 x channels 64 wn .. + 63.
 __device__ __forceinline__ void c16_write22(const C16Params& p, const f32x16 (&acc)[2][2], int lane, int wv, int h, float* ep, int cbase) {
   const int wm = wv >> 1, wn = wv & 1;
   if (wn != h) return;
+  const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -220,7 +235,7 @@ __device__ __forceinline__ void c16_write22(const C16Params& p, const f32x16 (&a
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int px = 64 * wm + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        float v = fmaf(acc[mt][nt2][r], p.acc_scale, bv);
+        float v = fmaf(acc[mt][nt2][r], as, bv);
         if (p.relu) v = fmaxf(v, 0.f);
         ep[px * C16_EP_LD + 32 * nt2 + (lane & 31)] = v;
       }
@@ -823,6 +838,8 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
 #pragma unroll
   for (int n2 = 0; n2 < NT2; ++n2) bv[n2] = p.bias ? p.bias[chan0 + 32 * n2 + (lane & 31)] : 0.f;
   constexpr int MTP = R::NPX / 32;                              // m-tiles per pass
+  const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
+  unsigned amax = 0;
 #pragma unroll
   for (int ps = 0; ps < 4 / MTP; ++ps) {
 #pragma unroll
@@ -832,12 +849,13 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int px = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          float v = fmaf(acc[ps * MTP + m][n2][r], p.acc_scale, bv[n2]);
+          float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
           if (p.relu) v = fmaxf(v, 0.f);
           ep[px * C16_EP_LD + 32 * n2 + (lane & 31)] = v;
         }
-    c16_epilogue_pass<MM == 3 ? 2 : MM, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX);
+    c16_epilogue_pass<MM == 3 ? 2 : MM, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
   }
+  if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -847,13 +865,16 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
 // HBM-bound: one 16-byte (pairs: two) store per 8 channels; the reference cache (D P C floats) is re-read per query out of L2 / MALL.
 template <int MM>
 __global__ void __launch_bounds__(256) product_split_kernel(const float* __restrict__ ref, const float* __restrict__ que, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift, char* __restrict__ out, int D, int P, int C, long total) {
+                                                           const float* __restrict__ shift, char* __restrict__ out, int D, int P, int C, long total,
+                                                           const G6dRange16 rng) {
   // a work item = 8 channels of one (query, pixel) for a run of PS_RUN hypotheses: the query's values and tables are loaded once per run
   // (one reference load and one / two 16-byte stores per output instead of four loads)
   typedef typename C16T3<MM>::T T;
   typedef typename C16T3<MM>::V V8;
   constexpr int PS_RUN = 8;
   const int c8 = C >> 3, nrun = (D + PS_RUN - 1) / PS_RUN;
+  const int eo = MM == 3 ? g6d_exp_out(rng) : 0;              // pairs hold split16(v * 2^-eo); amax: max bits(|v|) (G6dRange16)
+  unsigned amax = 0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int cg = (int)(i % c8);
     long r = i / c8;
@@ -872,6 +893,10 @@ __global__ void __launch_bounds__(256) product_split_kernel(const float* __restr
       float v[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v[e] = fmaf(r0[e] * q0[e], s0[e], t0[e]); v[4 + e] = fmaf(r1[e] * q1[e], s1[e], t1[e]); }
+      if constexpr (MM == 3) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { amax = max(amax, g6d_abs_bits(v[e])); v[e] = ldexpf(v[e], -eo); }
+      }
       V8 hi;
 #pragma unroll
       for (int e = 0; e < 8; ++e) hi[e] = (T)v[e];
@@ -888,6 +913,7 @@ __global__ void __launch_bounds__(256) product_split_kernel(const float* __restr
       }
     }
   }
+  if constexpr (MM == 3) g6d_range_record_block<4>(rng, amax);
 }
 
 // affine_split16_kernel: y = pool2x2?(relu?(x * scale[g][c] + shift[g][c])) of an fp32 channels-last map written in the 16-bit activation
@@ -896,10 +922,13 @@ __global__ void __launch_bounds__(256) product_split_kernel(const float* __restr
 // kernel cannot.  HBM-bound elementwise pass; image n uses table n / per_n (0: one table).
 template <int MM>
 __global__ void __launch_bounds__(256) affine_split16_kernel(const float* __restrict__ in, int ld_in, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                            int per_n, int relu, int pool, int H, int W, int C, char* __restrict__ out, long total) {
+                                                            int per_n, int relu, int pool, int H, int W, int C, char* __restrict__ out, long total,
+                                                            const G6dRange16 rng) {
   typedef typename C16T3<MM>::T T;
   typedef typename C16T3<MM>::V V8;
   const int c8 = C >> 3, Ho = pool ? H >> 1 : H, Wo = pool ? W >> 1 : W;
+  const int eo = MM == 3 ? g6d_exp_out(rng) : 0;              // pairs hold split16(v * 2^-eo); amax: max bits(|v|) (G6dRange16)
+  unsigned amax = 0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int cg = (int)(i % c8);
     const long r = i / c8;                                     // output pixel (n Ho + y) Wo + x
@@ -929,6 +958,10 @@ __global__ void __launch_bounds__(256) affine_split16_kernel(const float* __rest
           v[e] = fmaxf(v[e], u0); v[4 + e] = fmaxf(v[4 + e], u1);
         }
       }
+    if constexpr (MM == 3) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { amax = max(amax, g6d_abs_bits(v[e])); v[e] = ldexpf(v[e], -eo); }
+    }
     V8 hi;
 #pragma unroll
     for (int e = 0; e < 8; ++e) hi[e] = (T)v[e];
@@ -943,6 +976,7 @@ __global__ void __launch_bounds__(256) affine_split16_kernel(const float* __rest
       *reinterpret_cast<V8*>(out + (r * C + c) * 2) = hi;
     }
   }
+  if constexpr (MM == 3) g6d_range_record_block<4>(rng, amax);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -969,6 +1003,7 @@ struct Corr16Params {
   int nseg, Cin, K, ptiles, nslice;
   const char* w;
   float acc_scale;
+  G6dRange16 rng;                                            // slot_in: the input map's exponent
 };
 constexpr int CORR16_NW = 11;                                // computing waves per block (+ one loader wave)
 constexpr int CORR16_STAGE = 42 * 1024;                      // 672 patch rows of 64 B (K = 15, 8 x 16 tile: 660)
@@ -1175,12 +1210,13 @@ __global__ __launch_bounds__(64 * (CORR16_NW + 1), 1) void corr16_kernel(const C
     }
     __syncthreads();
   }
+  const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
   if (wv < 8)
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int o = tid + 512 * e, px = o >> 5, ch = o & 31;
     const int y = y0 + (px >> tw_log2), x = x0 + (px & (TW - 1));
-    if (y < sg.H && x < sg.W) sg.out[(((long)n * sg.H + y) * sg.W + x) * sg.ld_out + ch] = sum[e] * p.acc_scale;
+    if (y < sg.H && x < sg.W) sg.out[(((long)n * sg.H + y) * sg.W + x) * sg.ld_out + ch] = sum[e] * as;
   }
 }
 
@@ -1224,9 +1260,9 @@ int c16_pick_tw(int W, int pool) {
 
 }  // namespace
 
-extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
-                                       const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,
-                                       int stat_rows_per_group, g6d_stream_t stream) {
+extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
+                                          const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,
+                                          int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("conv16_direct: 1..4 segments and filters expected"); return G6D_EINVAL; }
   if (math_mode < 1 || math_mode > 3 || (w_layout != 0 && w_layout != 1) || (math_mode == 3 && w_layout != 1)) {
     g6d_set_error("conv16_direct: math_mode 1 (bf16) / 2 (fp16) / 3 (fp16 hi-lo pairs, fragment-major filters only)"); return G6D_EINVAL;
@@ -1244,6 +1280,7 @@ extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int C
   p.w = static_cast<const char*>(W16); p.bias = bias; p.stats = stats; p.stat_rows_per_group = stat_rows_per_group;
   p.acc_scale = acc_scale != 0.f ? acc_scale : 1.f;
   p.ablate = (int)g6d_knob(G6D_KNOB_C16_ABLATE);
+  if (range) p.rng = *range;
   const long wb = (long)(half_tile ? 128 : Cout) * 9 * kd * Cin * 2 * planes;
   if (wb >= (1L << 31)) { g6d_set_error("conv16_direct: filters beyond 2 GB"); return G6D_EINVAL; }
   p.w_bytes = (unsigned)wb;
@@ -1344,8 +1381,15 @@ extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int C
   return g6d_check_launch("conv16r_direct");
 }
 
-extern "C" int g6d_corr16_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
-                                g6d_stream_t stream) {
+extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
+                                       const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,
+                                       int stat_rows_per_group, g6d_stream_t stream) {
+  return g6d_conv16_direct_multi_ex(segs, nseg, Cin, W16, w_layout, acc_scale, bias, Cout, kd, relu, full_type, pool_type, math_mode, stats,
+                                    stat_rows_per_group, nullptr, stream);
+}
+
+extern "C" int g6d_corr16_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
+                                   const G6dRange16* range, g6d_stream_t stream) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("corr16: 1..4 segments and filters expected"); return G6D_EINVAL; }
   if (math_mode < 1 || math_mode > 3 || Cout != 32 || (k != 15 && k != 7) || Cin % 32) {
     g6d_set_error("corr16: math_mode 1 (bf16) / 2 (fp16) / 3 (fp16 pairs), Cout = 32, k in {7, 15}, Cin % 32 == 0 expected"); return G6D_EINVAL;
@@ -1354,6 +1398,7 @@ extern "C" int g6d_corr16_multi(const G6dConv16Seg* segs, int nseg, int Cin, con
   Corr16Params p = {};
   p.nseg = nseg; p.Cin = Cin; p.K = k; p.w = static_cast<const char*>(W16); p.acc_scale = acc_scale != 0.f ? acc_scale : 1.f;
   p.nslice = Cin / (math_mode == 3 ? 16 : 32);
+  if (range) p.rng = *range;
   int tiles = 0;
   for (int i = 0; i < nseg; ++i) {
     const G6dConv16Seg& s = segs[i];
@@ -1396,8 +1441,13 @@ extern "C" int g6d_corr16_multi(const G6dConv16Seg* segs, int nseg, int Cin, con
   return g6d_check_launch("corr16");
 }
 
-extern "C" int g6d_product_split16(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,
-                                   int math_mode, g6d_stream_t stream) {
+extern "C" int g6d_corr16_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
+                                g6d_stream_t stream) {
+  return g6d_corr16_multi_ex(segs, nseg, Cin, W16, acc_scale, Cout, k, math_mode, nullptr, stream);
+}
+
+extern "C" int g6d_product_split16_ex(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P,
+                                      int C, int math_mode, const G6dRange16* range, g6d_stream_t stream) {
   if (!ref || !que || !scale || !shift || !out || qn < 1 || D < 1 || P < 1 || C < 8 || (C & 7) || math_mode < 1 || math_mode > 3 ||
       !g6d_aligned16(ref) || !g6d_aligned16(que) || !g6d_aligned16(scale) || !g6d_aligned16(shift) || !g6d_aligned16(out)) {
     g6d_set_error("product_split16: bad args (C % 8 == 0, 16-byte aligned pointers, math_mode 1..3)"); return G6D_EINVAL;
@@ -1406,14 +1456,20 @@ extern "C" int g6d_product_split16(const float* ref, const float* que, const flo
   const int blocks = (int)((total + 255) / 256 < 256 * 64 ? (total + 255) / 256 : 256 * 64);
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* o = static_cast<char*>(out);
-  if (math_mode == 1) hipLaunchKernelGGL(product_split_kernel<1>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total);
-  else if (math_mode == 2) hipLaunchKernelGGL(product_split_kernel<2>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total);
-  else hipLaunchKernelGGL(product_split_kernel<3>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total);
+  const G6dRange16 rng = range ? *range : G6dRange16{};
+  if (math_mode == 1) hipLaunchKernelGGL(product_split_kernel<1>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total, rng);
+  else if (math_mode == 2) hipLaunchKernelGGL(product_split_kernel<2>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total, rng);
+  else hipLaunchKernelGGL(product_split_kernel<3>, dim3(blocks), dim3(256), 0, st, ref, que, scale, shift, o, D, P, C, total, rng);
   return g6d_check_launch("product_split16");
 }
 
-extern "C" int g6d_affine_split16(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H, int W,
-                                  int C, void* out, int math_mode, g6d_stream_t stream) {
+extern "C" int g6d_product_split16(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,
+                                   int math_mode, g6d_stream_t stream) {
+  return g6d_product_split16_ex(ref, que, scale, shift, out, qn, D, P, C, math_mode, nullptr, stream);
+}
+
+extern "C" int g6d_affine_split16_ex(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
+                                     int W, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream) {
   if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || ld_in < C || (ld_in & 3) || (scale && !shift) || affine_per_n < 0 || math_mode < 1 ||
       math_mode > 3 || (pool && ((H | W) & 1)) || !g6d_aligned16(in) || !g6d_aligned16(out) || (scale && (!g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("affine_split16: bad args (C % 8 == 0, 16-byte aligned rows, even map with pooling, math_mode 1..3)"); return G6D_EINVAL;
@@ -1422,8 +1478,14 @@ extern "C" int g6d_affine_split16(const float* in, int ld_in, const float* scale
   const int blocks = (int)((total + 255) / 256 < 256 * 64 ? (total + 255) / 256 : 256 * 64);
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* o = static_cast<char*>(out);
-  if (math_mode == 1) hipLaunchKernelGGL(affine_split16_kernel<1>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total);
-  else if (math_mode == 2) hipLaunchKernelGGL(affine_split16_kernel<2>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total);
-  else hipLaunchKernelGGL(affine_split16_kernel<3>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total);
+  const G6dRange16 rng = range ? *range : G6dRange16{};
+  if (math_mode == 1) hipLaunchKernelGGL(affine_split16_kernel<1>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
+  else if (math_mode == 2) hipLaunchKernelGGL(affine_split16_kernel<2>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
+  else hipLaunchKernelGGL(affine_split16_kernel<3>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
   return g6d_check_launch("affine_split16");
+}
+
+extern "C" int g6d_affine_split16(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H, int W,
+                                  int C, void* out, int math_mode, g6d_stream_t stream) {
+  return g6d_affine_split16_ex(in, ld_in, scale, shift, affine_per_n, relu, pool, N, H, W, C, out, math_mode, nullptr, stream);
 }

@@ -53,6 +53,41 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// Range control of fp16 pair maps (G6dRange16, include/gen6d_hip.h).  Every branch below is on kernel arguments (wave-uniform).
+__device__ __forceinline__ int g6d_exp_in(const G6dRange16& r) { return r.exps && r.slot_in >= 0 ? r.exps[r.slot_in] : 0; }
+__device__ __forceinline__ int g6d_exp_out(const G6dRange16& r) { return r.exps && r.slot_out >= 0 ? r.exps[r.slot_out] : 0; }
+__device__ __forceinline__ unsigned g6d_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+// wave-wide integer max of the |v| bits, one atomicMax per wave (all 64 lanes must call it)
+__device__ __forceinline__ unsigned g6d_wave_max_u(unsigned m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+  return m;
+}
+// The record only grows between clears, so an atomic whose value does not exceed a coherent read of it is skipped: thousands of waves of
+// a launch would otherwise serialise on ONE address at the memory-side atomic unit (measured 4 % of the fp32 headline).
+__device__ __forceinline__ void g6d_range_max(unsigned* rec, unsigned m) {
+  if (m > __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(rec, m);
+}
+__device__ __forceinline__ void g6d_range_record(const G6dRange16& r, unsigned m) {
+  if (!r.rec || r.slot_out < 0) return;
+  m = g6d_wave_max_u(m);
+  if ((threadIdx.x & 63) == 0) g6d_range_max(r.rec + r.slot_out, m);
+}
+// block-wide form for the grid-stride elementwise kernels (one atomic per block of NW waves; all threads call it)
+template <int NW>
+__device__ __forceinline__ void g6d_range_record_block(const G6dRange16& r, unsigned m) {
+  if (!r.rec || r.slot_out < 0) return;
+  __shared__ unsigned red[NW];
+  m = g6d_wave_max_u(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < NW; ++w) m = max(m, red[w]);
+    g6d_range_max(r.rec + r.slot_out, m);
+  }
+}
+
 // Launch-policy knobs (common.hip): every dispatch decision that used to hide behind an environment variable is a named knob with the
 // product default; tools/ and tests set them through the C ABI (g6d_set_knob / g6d_reset_knobs, include/gen6d_hip.h) to force a kernel
 // variant or to sweep a model constant.  The library itself reads no environment variable.

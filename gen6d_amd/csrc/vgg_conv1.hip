@@ -142,11 +142,12 @@ __global__ void __launch_bounds__(C1_THREADS) vgg_conv1_pool_kernel(const float*
 // OT: element type of the channels-last result — float, or (round 6, the reduced-precision mode's 16-bit activation path: the input of
 // g6d_conv16_direct_multi) _Float16 / __bf16, rounded once here.
 // PAIR (round 6): fp16 hi / lo pairs [pixel][2][64] — hi = rn16(v), lo = rn16(v - hi) — the input format of the fp32 path's
-// split-precision trunk kernel (g6d_conv16_direct_multi, math_mode 3).
+// split-precision trunk kernel (g6d_conv16_direct_multi, math_mode 3); with a G6dRange16 the pairs hold split16(v * 2^-e_out) and the
+// stored unscaled values are recorded (rng zero: unscaled, not recorded).
 template <typename OT, bool PAIR = false>
 __global__ void __launch_bounds__(256) vgg_conv1_pool_mfma_kernel(const float* __restrict__ in, const float* __restrict__ w_oihw,
                                                                   const float* __restrict__ bias, int H, int W, int Ho, int Wo,
-                                                                  OT* __restrict__ out, const Conv1Norm nm) {
+                                                                  OT* __restrict__ out, const Conv1Norm nm, const G6dRange16 rng) {
   __shared__ float tile[C1_CIN][M1_IH][M1_IWP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
@@ -177,6 +178,8 @@ __global__ void __launch_bounds__(256) vgg_conv1_pool_mfma_kernel(const float* _
   const float* tbase = &tile[0][0][0];
   const int q = li >> 2, p = li & 3;
   const int lane_off = (p >> 1) * M1_IWP + 2 * q + (p & 1);          // pixel p of pool window q inside a group
+  const int eo = PAIR ? g6d_exp_out(rng) : 0;
+  unsigned amax = 0;
 #pragma unroll 1
   for (int g = 0; g < 8; ++g) {
     const int ty = 2 * wave + (g >> 2), gx = g & 3;                    // pooled row of the tile, group of 8 windows along x
@@ -199,13 +202,18 @@ __global__ void __launch_bounds__(256) vgg_conv1_pool_mfma_kernel(const float* _
           const float m0 = fmaxf(fmaxf(acc0[4 * j], acc0[4 * j + 1]), fmaxf(acc0[4 * j + 2], acc0[4 * j + 3])) + b0;   // max(a)+b == max(a+b)
           const float m1 = fmaxf(fmaxf(acc1[4 * j], acc1[4 * j + 1]), fmaxf(acc1[4 * j + 2], acc1[4 * j + 3])) + b1;
           OT* o = out + ((size_t)(n * Ho + py) * Wo + px) * (PAIR ? 2 * C1_COUT : C1_COUT);
-          const float r0 = fmaxf(m0, 0.f), r1 = fmaxf(m1, 0.f);               // relu(max) == max(relu)
+          float r0 = fmaxf(m0, 0.f), r1 = fmaxf(m1, 0.f);                     // relu(max) == max(relu)
+          if constexpr (PAIR) {
+            amax = max(amax, max(g6d_abs_bits(r0), g6d_abs_bits(r1)));
+            r0 = ldexpf(r0, -eo); r1 = ldexpf(r1, -eo);
+          }
           o[li] = (OT)r0; o[li + 32] = (OT)r1;
           if constexpr (PAIR) { o[C1_COUT + li] = (OT)(r0 - (float)(OT)r0); o[C1_COUT + li + 32] = (OT)(r1 - (float)(OT)r1); }
         }
       }
     }
   }
+  if constexpr (PAIR) g6d_range_record(rng, amax);
 }
 
 int conv1_launch(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout, float* out,
@@ -224,7 +232,8 @@ int conv1_launch(const float* in, int N, int H, int W, const float* w_oihw, cons
   const bool use_mfma = g6d_knob(G6D_KNOB_CONV1_MFMA) != 0;
   if (nhwc && use_mfma) {
     hipLaunchKernelGGL(vgg_conv1_pool_mfma_kernel<float>, dim3((Wo + M1_PTX - 1) / M1_PTX, (Ho + M1_PTY - 1) / M1_PTY, N), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), in, w_oihw, bias, H, W, Ho, Wo, out, nm);
+                       reinterpret_cast<hipStream_t>(stream), in, w_oihw, bias, H, W, Ho, Wo, out, nm,
+                       G6dRange16{});
     return g6d_check_launch("vgg_conv1_pool_mfma");
   }
   hipLaunchKernelGGL(vgg_conv1_pool_kernel, dim3((Wo + C1_PTX - 1) / C1_PTX, (Ho + C1_PTY - 1) / C1_PTY, N), dim3(C1_THREADS),
@@ -257,8 +266,9 @@ extern "C" int g6d_vgg_conv1_pool_nhwc_norm(const float* in, int N, int H, int W
 // The same layer with a 16-BIT channels-last result (math_mode 1 = bf16, 2 = fp16; ABI v11): the first layer of the reduced-precision
 // mode's 16-bit activation path, rounded once in the epilogue; math_mode 3: fp16 hi / lo pairs [N][H/2][W/2][2][64], the first layer of
 // the fp32 path's split-precision trunk.  mean_host / std_host may be NULL (already normalised input).
-extern "C" int g6d_vgg_conv1_pool_nhwc16(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout,
-                                         const float* mean_host, const float* std_host, void* out16, int math_mode, g6d_stream_t stream) {
+extern "C" int g6d_vgg_conv1_pool_nhwc16_ex(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout,
+                                            const float* mean_host, const float* std_host, void* out16, int math_mode, const G6dRange16* range,
+                                            g6d_stream_t stream) {
   if (!in || !w_oihw || !bias || !out16 || N <= 0 || N > 65535 || H < 2 || W < 2 || Cin != C1_CIN || Cout != C1_COUT ||
       math_mode < 1 || math_mode > 3 || (long long)N * Cout * (H / 2) * (W / 2) >= (1ll << 30)) {
     g6d_set_error("vgg_conv1_pool_nhwc16: bad args (3 -> 64 channels, H, W >= 2, math_mode 1 / 2 / 3)"); return G6D_EINVAL;
@@ -270,16 +280,22 @@ extern "C" int g6d_vgg_conv1_pool_nhwc16(const float* in, int N, int H, int W, c
     nm.on = 1;
   }
   const dim3 grid((Wo + M1_PTX - 1) / M1_PTX, (Ho + M1_PTY - 1) / M1_PTY, N);
+  const G6dRange16 rng = range ? *range : G6dRange16{};
   if (math_mode == 1)
     hipLaunchKernelGGL(vgg_conv1_pool_mfma_kernel<__bf16>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, w_oihw, bias, H, W, Ho, Wo,
-                       static_cast<__bf16*>(out16), nm);
+                       static_cast<__bf16*>(out16), nm, rng);
   else if (math_mode == 2)
     hipLaunchKernelGGL(vgg_conv1_pool_mfma_kernel<_Float16>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, w_oihw, bias, H, W, Ho, Wo,
-                       static_cast<_Float16*>(out16), nm);
+                       static_cast<_Float16*>(out16), nm, rng);
   else
     hipLaunchKernelGGL((vgg_conv1_pool_mfma_kernel<_Float16, true>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, w_oihw, bias, H, W,
-                       Ho, Wo, static_cast<_Float16*>(out16), nm);
+                       Ho, Wo, static_cast<_Float16*>(out16), nm, rng);
   return g6d_check_launch("vgg_conv1_pool_mfma16");
+}
+
+extern "C" int g6d_vgg_conv1_pool_nhwc16(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout,
+                                         const float* mean_host, const float* std_host, void* out16, int math_mode, g6d_stream_t stream) {
+  return g6d_vgg_conv1_pool_nhwc16_ex(in, N, H, W, w_oihw, bias, Cin, Cout, mean_host, std_host, out16, math_mode, nullptr, stream);
 }
 
 #else   // ---- host emulation of the two phases, thread by thread (tests only) -------------------------------------

@@ -13,6 +13,7 @@ import torch
 
 from . import geometry as G
 from . import ops
+from .network.params import range_guarded
 
 
 # ------------------------------------------------------------------------------------------------ database helpers
@@ -301,20 +302,30 @@ class Gen6DEstimator:
             rots.append(torch.stack([ops.warp_perspective(self.cache.get(database, i), Hr @ ref_Hs[k], size, size)
                                      for k, i in enumerate(ref_ids)], 0))
         ref_imgs_rots = torch.stack(rots, 0)                    # an,rfn,h,w,3 uint8 on the device
-        with torch.no_grad():
+        def load():
             det = ref_imgs[:self.cfg["det_ref_view_num"]].float().div_(255).permute(0, 3, 1, 2).contiguous()
             self.detector.load_impl(det)
             f = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(self.device)
             self.selector.extract_ref_feats(ref_imgs_rots.float().div_(255).permute(0, 1, 4, 2, 3).contiguous(),
                                             f(ref_poses), f(center), f(vert))
+        with torch.no_grad():
+            self._range_guarded(load)
         self.ref_info = {"imgs": ref_imgs.cpu().numpy(), "ref_imgs": ref_imgs_rots.cpu().numpy(), "masks": ref_masks.cpu().numpy(),
                          "Ks": ref_Ks, "poses": ref_poses, "center": center}
         if self.refiner is not None:
             self.refiner.image_cache = self.cache
             self.refiner.load_ref_imgs(database, ref_ids_all)
 
+    def _range_guarded(self, fn, recompute=None):
+        """fn() checked for fp16 pair maps that left the representable window (network.params.range_guarded): the networks whose maps
+        did are recomputed on their fp32-core routes."""
+        return range_guarded((self.detector, self.selector, self.refiner), fn, recompute)
+
     def predict(self, que_img, que_K, pose_init=None):
         """que_img uint8 [H,W,3], que_K [3,3] -> pose [3,4], intermediate results (reference estimator.py:173-216)."""
+        return self._range_guarded(lambda: self._predict(que_img, que_K, pose_init))
+
+    def _predict(self, que_img, que_K, pose_init=None):
         inter = {}
         que_dev = (que_img if torch.is_tensor(que_img) else torch.from_numpy(np.ascontiguousarray(que_img))).to(self.device)
         if pose_init is None:
@@ -360,7 +371,7 @@ class Gen6DEstimator:
         chain = self.device_chain()
         img = que_img if torch.is_tensor(que_img) else torch.from_numpy(np.ascontiguousarray(que_img))
         K = torch.from_numpy(np.ascontiguousarray(que_K, dtype=np.float32)).to(self.device)
-        out = chain.query(img.to(self.device), K, use_feat_cache=use_feat_cache)
+        out = self._range_guarded(lambda: chain.query(img.to(self.device), K, use_feat_cache=use_feat_cache))
         det, sel = out["det"].cpu().numpy(), out["sel"].cpu().numpy()
         inter = {"det_position": det[:2], "det_scale_r2q": float(det[2]), "det_que_img": None, "sel_angle_r2q": float(sel[1]),
                  "sel_scores": out["logits"].cpu().numpy(), "sel_ref_idx": int(sel[0]),
@@ -371,7 +382,9 @@ class Gen6DEstimator:
         """Several queries in flight at once (one captured hipGraph of the whole chain per lane, `batch` queries per graph sharing
         every launch), one synchronisation at the end: [(pose, inter)] in query order (BASELINE configs[4]: batched multi-query
         stream)."""
-        return self.device_chain().predict_many(que_imgs, que_Ks, lanes, batch)
+        # the captured graphs run on the pairs whatever a network's routes are: a call whose maps left the window is recomputed eagerly
+        return self._range_guarded(lambda: self.device_chain().predict_many(que_imgs, que_Ks, lanes, batch),
+                                   lambda: [self.predict_device(q, K) for q, K in zip(que_imgs, que_Ks)])
 
 
 name2estimator = {"gen6d": Gen6DEstimator}

@@ -22,6 +22,11 @@ class G6dConv16Seg(C.Structure):
                 ("ld_pool", C.c_int32)]
 
 
+class G6dRange16(C.Structure):
+    """include/gen6d_hip.h: exponent table / range record of fp16 pair maps (the *_ex entry points)."""
+    _fields_ = [("exps", C.c_void_p), ("rec", C.c_void_p), ("slot_in", C.c_int32), ("slot_out", C.c_int32)]
+
+
 class G6dCorrSeg(C.Structure):
     """include/gen6d_hip.h: one map of g6d_corr2d_patch_multi."""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("ld_in", C.c_int32), ("ld_out", C.c_int32),
@@ -70,6 +75,11 @@ SIGNATURES = {
     "g6d_corr16_multi": [_P, _I, _I, _P, _F, _I, _I, _I, _P],
     "g6d_product_split16": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "g6d_affine_split16": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    "g6d_vgg_conv1_pool_nhwc16_ex": [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P],
+    "g6d_conv16_direct_multi_ex": [_P, _I, _I, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
+    "g6d_corr16_multi_ex": [_P, _I, _I, _P, _F, _I, _I, _I, _P, _P],
+    "g6d_product_split16_ex": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "g6d_affine_split16_ex": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
     "g6d_vgg_conv1_pool_nhwc_norm": [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P],
     "g6d_wino_conv3x3": [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P, _I, _P, C.c_size_t, _P],
     "g6d_wino_conv3x3_multi": [_P, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P],

@@ -223,13 +223,14 @@ def pack_trunk(folded):
 _IMG_NORM = (tuple(specs.IMAGENET_MEAN), tuple(specs.IMAGENET_STD))
 
 
-def vgg_taps_cl(packed, x, taps, norm=None, f43=False):
+def vgg_taps_cl(packed, x, taps, norm=None, f43=False, rng=None, split16=True):
     """Own trunk, channels-last: x [n,3,h,w] normalised image (or an image in [0,1] with norm = (mean, std): the first layer
     normalises while it stages its input) -> {'c3': [n,h/4,w/4,256] post-ReLU, 'c5': [n,h/8,w/8,512] post-ReLU,
-    'c7_pre': [n,h/16,w/16,512] pre-ReLU, 'p7': max-pool of c7_pre} (only the requested taps + c7_pre)."""
-    if (ops.MATH_MODE and LOWP_TRUNK) or f43 or (SPLIT16_TRUNK and SPLIT16_ALWAYS and hasattr(packed[1], "w16") and _conv16_eligible([x], taps)):
+    'c7_pre': [n,h/16,w/16,512] pre-ReLU, 'p7': max-pool of c7_pre} (only the requested taps + c7_pre).  rng / split16: as
+    vgg_taps_cl_multi."""
+    if (ops.MATH_MODE and LOWP_TRUNK) or f43 or (split16 and SPLIT16_TRUNK and SPLIT16_ALWAYS and hasattr(packed[1], "w16") and _conv16_eligible([x], taps)):
         # reduced precision: the multi-segment 16-bit kernel; f43: the F(4x4,3x3) kernel (one segment); fp32 path: the split-precision kernel
-        return vgg_taps_cl_multi(packed, [x], taps, norm=norm, f43=f43)[0]
+        return vgg_taps_cl_multi(packed, [x], taps, norm=norm, f43=f43, rng=rng, split16=split16)[0]
     w0, b0 = packed[0]
     x = ops.vgg_conv1_pool_nhwc(x.contiguous(), w0, b0, norm=norm)              # (normalise +) conv0 + ReLU + pool
     _, x = ops.wino_conv3x3(x, *packed[1], relu=True, full=False, pool=True)    # conv1 + ReLU + pool
@@ -250,18 +251,22 @@ def _conv16_eligible(xs, taps):
     return all(x.shape[2] % need == 0 and x.shape[3] % need == 0 for x in xs) and len(xs) <= 4
 
 
-def _vgg_taps_conv16(packed, xs, taps, norm, mode, taps16=()):
+def _vgg_taps_conv16(packed, xs, taps, norm, mode, taps16=(), rng=None):
     """The trunk on 16-bit activations (round 6): from the first layer's epilogue on the maps are fp16 / bf16 channels-last (mode 1 / 2:
     the reduced-precision mode) or fp16 hi / lo PAIRS (mode 3: the fp32 path), the seven 3x3 layers run on the direct kernel
     (DMA-staged activation tiles, filters in registers, v_mfma_f32_32x32x16), and only the requested taps are written in fp32 for their
-    consumers."""
+    consumers.  rng (an ops.RangeTable, pairs only): layer i's pair maps carry the exponent of slot "trunk<i>" and are recorded; the pair
+    taps come back as ops.PairMaps."""
     w0, b0 = packed[0]
     t16 = "t16"
     f32 = torch.float32
-    cur = [ops.vgg_conv1_pool_nhwc16(x.contiguous(), w0, b0, norm=norm, mode=mode) for x in xs]       # conv0 + ReLU + pool, per size
+    use = rng is not None and mode == 3
+    slot = lambda i: {"rng": (rng, rng.slot(f"trunk{i}"))} if use else {}
+    cur = [ops.vgg_conv1_pool_nhwc16(x.contiguous(), w0, b0, norm=norm, mode=mode, **slot(0)) for x in xs]   # conv0 + ReLU + pool, per size
 
     def layer(i, cur, relu=True, full=None, pool=None):
-        return ops.conv16_direct_multi(cur, packed[i].w16(mode), packed[i][1], relu=relu, full=full, pool=pool)
+        return ops.conv16_direct_multi(cur, packed[i].w16(mode), packed[i][1], relu=relu, full=full, pool=pool,
+                                       **(slot(i) if t16 in (full, pool) else {}))
 
     _, cur = layer(1, cur, pool=t16)
     cur, _ = layer(2, cur, full=t16)
@@ -278,14 +283,16 @@ def _vgg_taps_conv16(packed, xs, taps, norm, mode, taps16=()):
     return outs
 
 
-def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=()):
+def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=(), rng=None, split16=True):
     """vgg_taps_cl for several image sizes at once (the scales of the detector's pyramid): every Winograd layer is ONE launch
     over all sizes (ops.wino_conv3x3_multi).  xs: list of [1,3,h_i,w_i] images (normalised, or in [0,1] with norm) -> list of
-    tap dicts.  f43: the seven Winograd layers on the F(4x4,3x3) kernel (fp32 mode only)."""
+    tap dicts.  f43: the seven Winograd layers on the F(4x4,3x3) kernel (fp32 mode only).  rng: the caller's ops.RangeTable for the
+    split-precision trunk's pair maps (their taps then come back as ops.PairMaps); split16 = False: that trunk is not taken (the network's
+    recompute of a call whose pair maps left the window)."""
     if ops.MATH_MODE and LOWP_TRUNK and CONV16_TRUNK and hasattr(packed[1], "w16") and _conv16_eligible(xs, taps):
         return _vgg_taps_conv16(packed, xs, taps, norm, ops.MATH_MODE, taps16)
-    if (f43 or SPLIT16_ALWAYS) and not ops.MATH_MODE and SPLIT16_TRUNK and hasattr(packed[1], "w16") and _conv16_eligible(xs, taps):
-        return _vgg_taps_conv16(packed, xs, taps, norm, 3, taps16)
+    if split16 and (f43 or SPLIT16_ALWAYS) and not ops.MATH_MODE and SPLIT16_TRUNK and hasattr(packed[1], "w16") and _conv16_eligible(xs, taps):
+        return _vgg_taps_conv16(packed, xs, taps, norm, 3, taps16, rng)
     w0, b0 = packed[0]
     dev = xs[0].device
     cur = ops.alloc_like_segments([(x.shape[0], x.shape[2] // 2, x.shape[3] // 2, w0.shape[0]) for x in xs], dev)
@@ -305,21 +312,26 @@ def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=()):
     return outs
 
 
-def trunk_features_multi(packed, imgs_list, keys, f43=False, taps16=()):
+def trunk_features_multi(packed, imgs_list, keys, f43=False, taps16=(), rng=None, split16=True):
     """trunk_features (no L2 normalisation) for a list of [1,3,h_i,w_i] images of different sizes -> list of lists of
     [1,1,h_l,w_l,C] maps.  One launch per layer for all sizes (up to 4 per launch).  taps16: keys that may come back in the 16-bit
-    activation format of the direct kernel ([n,h,w,C] fp16 / bf16, or [n,h,w,2,C] fp16 pairs on the fp32 path) when the trunk runs on it —
-    the caller checks the dtype."""
+    activation format of the direct kernel ([n,h,w,C] fp16 / bf16, or [n,h,w,2,C] fp16 pairs on the fp32 path, ops.PairMaps with rng) when
+    the trunk runs on it — the caller checks the type.  rng / split16: as vgg_taps_cl_multi."""
     if len(imgs_list) > 4:
-        return [trunk_features(packed, im, keys, False) for im in imgs_list]
-    taps = vgg_taps_cl_multi(packed, imgs_list, set(keys), norm=_IMG_NORM, f43=f43, taps16=taps16)
-    return [[(t[k] if t[k].dtype != torch.float32 else t[k].unsqueeze(1)) for k in keys] for t in taps]
+        return [trunk_features(packed, im, keys, False, rng=rng, split16=split16) for im in imgs_list]
+    taps = vgg_taps_cl_multi(packed, imgs_list, set(keys), norm=_IMG_NORM, f43=f43, taps16=taps16, rng=rng, split16=split16)
+    return [[(t[k] if is_16bit(t[k]) else t[k].unsqueeze(1)) for k in keys] for t in taps]
 
 
-def trunk_features(packed, imgs, keys, l2norm, f43=False):
+def is_16bit(t):
+    """A tap in the direct kernel's 16-bit / pair format (an ops.PairMap or a 16-bit tensor) rather than an fp32 map."""
+    return isinstance(t, ops.PairMap) or t.dtype != torch.float32
+
+
+def trunk_features(packed, imgs, keys, l2norm, f43=False, rng=None, split16=True):
     """Normalised images [n,3,h,w] in [0,1] -> channels-last 5-D feature maps [n,1,h_l,w_l,C] for `keys`, optionally
     L2-normalised over C (F.normalize, reference selector.py:118 / refiner.py:69-71)."""
-    t = vgg_taps_cl(packed, imgs, set(keys), norm=_IMG_NORM, f43=f43)
+    t = vgg_taps_cl(packed, imgs, set(keys), norm=_IMG_NORM, f43=f43, rng=rng, split16=split16)
     outs = []
     for k in keys:
         f = t[k]

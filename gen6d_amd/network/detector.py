@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops, parallel, specs
-from .backbone import (pack_trunk, trunk_features, trunk_features_multi, winograd_corr_filters, winograd43_corr_filters,
+from .backbone import (is_16bit, pack_trunk, trunk_features, trunk_features_multi, winograd_corr_filters, winograd43_corr_filters,
                        winograd43_corr_filters_padded)
 from .params import ParamBank, fold_vgg
 
@@ -97,7 +97,7 @@ class Detector(ParamBank):
     # ------------------------------------------------------------------ trunk
     def extract_feats(self, imgs):
         """imgs [n,3,h,w] in [0,1] -> channels-last x0,x1,x2: [n,1,h/8,w/8,512], [.. /16 ..], [.. /32 ..]."""
-        return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), False)
+        return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), False, rng=self._pair_rng(), split16=self.pairs_on)
 
     def load_impl(self, ref_imgs):
         """ref_imgs [rfn,3,h,w] in [0,1]; nearest resize to 120x120, trunk, keep as correlation filters
@@ -141,10 +141,10 @@ class Detector(ParamBank):
         maps = [[None] * 3 for _ in feats]
         for l, (wref, k) in enumerate(zip(self.ref_center_feats, self.ref_ksize)):
             xs = [f[l] for f in feats]
-            if xs[0].dtype != torch.float32:
+            if is_16bit(xs[0]):
                 # the trunk handed this level over as 16-bit activations (reduced precision) or fp16 hi / lo pairs (fp32 path): the halo-patch
                 # correlation kernel on the 16-bit matrix cores (csrc/conv16_direct.hip, corr16_kernel)
-                mode = 3 if xs[0].dim() == 5 else (1 if xs[0].dtype == torch.bfloat16 else 2)
+                mode = 3 if len(xs[0].shape) == 5 else (1 if xs[0].dtype == torch.bfloat16 else 2)
                 filt = self._corr16_filters(l, mode)
                 outs = [torch.empty((qn, 1, x.shape[1], x.shape[2], rfn), dtype=torch.float32, device=dev) for x in xs]
                 ops.corr16_multi(xs, filt, outs)
@@ -182,7 +182,7 @@ class Detector(ParamBank):
             for i, o in enumerate(outs):
                 maps[i][l] = o.reshape(qn * o.shape[2] * o.shape[3], rfn)
         for f, si, m in zip(feats, scale_ids, maps):
-            hc, wc = (f[0].shape[2], f[0].shape[3]) if f[0].dtype == torch.float32 else (f[0].shape[1], f[0].shape[2])
+            hc, wc = (f[0].shape[1], f[0].shape[2]) if is_16bit(f[0]) else (f[0].shape[2], f[0].shape[3])
             ops.detector_assemble(m[0], m[1], m[2], hc, wc, self.cfg["vgg_score_stats"],
                                   float(self.cfg["vgg_score_max"]), hs, ws, si, stacked, batch=qn)
 
@@ -232,10 +232,11 @@ class Detector(ParamBank):
             # the image pyramid in ONE launch (g6d_resize_bilinear_pyramid; the scale of the query's own size is the query itself)
             pyr = ops.resize_bilinear_pyramid(que_imgs, [self._scale_size(hq, wq, sc) for _, sc in order])
             # (CORR16: the 15x15 level's input in the trunk kernel's 16-bit / pair format -> g6d_corr16_multi)
+            # (pairs_on False: the recompute of a call whose pair maps left the window, on the routes the module switches select when off)
             t16 = ()
-            if CORR16 and self.ref_center_feats[0].shape[0] == 32:
+            if CORR16 and self.pairs_on and self.ref_center_feats[0].shape[0] == 32:
                 t16 = (("c5",) if self.ref_ksize[0] == 15 else ()) + (("c7_pre",) if (CORR16_7 and self.ref_ksize[1] == 7) else ())
-            feats = trunk_features_multi(pk["vgg"], pyr, ("c5", "c7_pre", "p7"), f43=F43, taps16=t16)
+            feats = trunk_features_multi(pk["vgg"], pyr, ("c5", "c7_pre", "p7"), f43=F43, taps16=t16, rng=self._pair_rng(), split16=self.pairs_on)
             self._scores_from_pyramid(feats, [si for si, _ in order], stacked, hs, ws)
         else:
             ops.fork_join([(lambda si=si, sc=sc: self._scores_one_scale(resized(sc), si, stacked, hs, ws)) for si, sc in order], dev)
@@ -302,11 +303,11 @@ class Detector(ParamBank):
         """ref_imgs: uint8 [rfn,h,w,3] (reference detector.py:277-289)."""
         x = torch.from_numpy(np.ascontiguousarray(ref_imgs)).to(self.device_()).float().div_(255).permute(0, 3, 1, 2)
         with torch.no_grad():
-            self.load_impl(x.contiguous())
+            self.range_guarded(lambda: self.load_impl(x.contiguous()))
 
     def detect_que_imgs(self, que_imgs):
         """que_imgs: uint8 [qn,h,w,3] -> {'positions': [qn,2], 'scales': [qn]} numpy (reference detector.py:291-304)."""
         x = torch.from_numpy(np.ascontiguousarray(que_imgs)).to(self.device_()).float().div_(255).permute(0, 3, 1, 2)
         with torch.no_grad():
-            out = self.detect_impl(x.contiguous())
+            out = self.range_guarded(lambda: self.detect_impl(x.contiguous()))
         return {"positions": out["positions"].cpu().numpy(), "scales": out["scales"].cpu().numpy()}

@@ -4,7 +4,7 @@
 import torch
 import torch.nn as nn
 
-from .. import specs
+from .. import ops, specs
 
 
 class ConvW(tuple):
@@ -39,14 +39,85 @@ class ParamBank(nn.Module):
             self._roles[key] = role
         self._packed = None
 
-    # any weight change invalidates the packed copies
-    def load_state_dict(self, *a, **k):
+    # any weight change invalidates the packed copies: the packed trunks / heads, the 16-bit filter caches of the selector's products and
+    # the refiner's feature net (keyed on data_ptr(), which load_state_dict keeps), and the pair maps' exponents and record
+    # (the range table is reset in place, not dropped: captured graphs hold pointers into it)
+    sharded = False                      # reference-sharded mode (Detector / ViewpointSelector.set_shard)
+
+    def _reset_derived(self):
         self._packed = None
+        for k in ("_prod16", "_feat16", "_range_seen"):
+            self.__dict__.pop(k, None)
+        t = self.__dict__.get("_range")
+        if t is not None:
+            t.reset()
+
+    def load_state_dict(self, *a, **k):
+        self._reset_derived()
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
-        self._packed = None
+        self._reset_derived()
         return super()._apply(fn, *a, **k)
+
+    # ---- range control of the fp32 path's fp16 hi / lo pair maps (ops.RangeTable, ops.pair_exponent) -------------------------------------
+    @property
+    def pairs_on(self):
+        """False while a call is recomputed on the fp32-core routes (instance-level: the module switches stay untouched)."""
+        return not self.__dict__.get("_pairs_off", False)
+
+    @property
+    def range_fallbacks(self):
+        """Calls recomputed on the fp32-core routes because a pair map left the window."""
+        return self.__dict__.get("_range_fallbacks", 0)
+
+    def range_table(self):
+        """The network's exponent table and range record (one slot per pair-producing call site), created on first use."""
+        t = self.__dict__.get("_range")
+        if t is None or t.device != self.device_():
+            t = self._range = ops.RangeTable(self.device_())
+        return t
+
+    def _pair_rng(self):
+        """The range table for this network's pair maps: None while its pair routes are off, in a reduced-precision mode or off the GPU."""
+        return self.range_table() if (self.pairs_on and not ops.MATH_MODE and self.device_().type == "cuda") else None
+
+    def range_check(self):
+        """Read and clear the record (synchronises).  If a map left the window since the last check: raise in the reference-sharded mode
+        (a per-rank recompute would desynchronise the collectives), else update the exponents of the slots that left it, count a fallback
+        and return True (the caller recomputes on the fp32-core routes)."""
+        t = self.__dict__.get("_range")
+        if t is None or not t.names:
+            return False
+        a = t.read()
+        t.clear()
+        self._range_seen = {n: max(v, self.__dict__.get("_range_seen", {}).get(n, 0.0)) if v == v else v for n, v in a.items()}
+        bad = {n: v for n, v in a.items() if ops.pair_out_of_window(v, t.e[t.names[n]])}
+        if not bad:
+            return False
+        if self.sharded:
+            raise RuntimeError(f"{type(self).__name__}: fp16 pair maps left the representable window in the reference-sharded mode "
+                               f"({', '.join(f'{n}: max |v| = {v:g}' for n, v in bad.items())}); a per-rank fp32 recompute would desynchronise "
+                               "the collectives")
+        t.set_exponents({n: ops.pair_exponent(v, t.e[t.names[n]]) for n, v in bad.items()})
+        self._range_fallbacks = self.range_fallbacks + 1
+        return True
+
+    def range_guarded(self, fn):
+        """fn() (one call of this network that ends in a synchronisation anyway), checked: recomputed once on the fp32-core routes when a
+        pair map left the window.  Non-finite values the fp32 routes produce as well are returned as they are."""
+        return range_guarded((self,), fn)
+
+    def _range_fallback(self):
+        """Hook: drop state derived from a call whose pair maps left the window (before its recompute)."""
+
+    def range_report(self):
+        """{slot name: {"A": largest |v| recorded since the weights were loaded, "e": current exponent}}."""
+        t = self.__dict__.get("_range")
+        if t is None:
+            return {}
+        seen = self.__dict__.get("_range_seen", {})
+        return {n: {"A": seen.get(n, 0.0), "e": t.e[i]} for n, i in t.names.items()}
 
     def p(self, key):
         *path, leaf = key.split(".")
@@ -89,3 +160,27 @@ def fold_vgg(bank, prefix):
         s = g / torch.sqrt(var + 1e-5)
         out.append(((w * s.view(-1, 1, 1, 1)).contiguous(), ((b - mu) * s + beta).contiguous()))
     return out
+
+
+def range_guarded(nets, fn, recompute=None):
+    """fn() over the networks `nets` (None entries skipped), then their range records checked (ParamBank.range_check): the networks whose
+    pair maps left the window run `recompute` (default fn) once more with their pair routes off.  The records are cleared first, so maps
+    from earlier unchecked calls (captured graphs) do not count against this one."""
+    nets = [n for n in nets if n is not None]
+    for n in nets:
+        t = n.__dict__.get("_range")
+        if t is not None and t.names:
+            t.clear()
+    out = fn()
+    left = [n for n in nets if n.range_check()]
+    if left:
+        for n in left:
+            n._range_fallback()
+            n._pairs_off = True
+        try:
+            out = (recompute or fn)()
+        finally:
+            for n in left:
+                n._pairs_off = False
+    return out
+

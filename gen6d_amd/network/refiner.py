@@ -175,7 +175,9 @@ class VolumeRefiner(ParamBank):
         dev = imgs.device
         big = (n >= F43_MIN_QUERIES * 7) if f43 is None else bool(f43)
         with self._mm("trunk"):
-            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), True, f43=TRUNK_F43 and big)      # channels-last, L2-normalised
+            r = self._pair_rng()
+            rk = ({"rng": r} if r is not None else {}) | ({} if self.pairs_on else {"split16": False})
+            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), True, f43=TRUNK_F43 and big, **rk)   # channels-last, L2-normalised
 
         def pair(name, x):
             """conv, IN, ReLU, conv, (IN returned as affine) — per-image statistics."""
@@ -187,15 +189,17 @@ class VolumeRefiner(ParamBank):
             s0 = ops.new_stats(n, w0.shape[0], dev)
             y1 = torch.empty((n, 1, hh, ww, w1.shape[0]), dtype=torch.float32, device=dev)
             s1 = ops.new_stats(n, w1.shape[0], dev)
-            if FEAT16 and ops.MATH_MODE == 0 and (hh * ww) % 128 == 0 and all(w_.shape[2] % 32 == 0 and w_.shape[0] % 64 == 0 for w_ in (w0, w1)):
+            if FEAT16 and ops.MATH_MODE == 0 and self.pairs_on and (hh * ww) % 128 == 0 and all(w_.shape[2] % 32 == 0 and w_.shape[0] % 64 == 0 for w_ in (w0, w1)):
                 # round 6: both convs on the direct split-precision kernel (fp16 hi / lo pairs, fp32-class results, csrc/conv16_direct.hip): the
                 # input / the first norm's affine + ReLU are written in the kernel's format by one elementwise pass each, the per-image
                 # InstanceNorm sums come out of the convs' epilogues
                 f0, f1 = self._feat16_filters(name, 0, w0), self._feat16_filters(name, 1, w1)
-                ops.conv16_direct_multi([ops.affine_split16(x, None, None, 0, False, False, 3)], f0, b0, relu=False, full=torch.float32, pool=None,
-                                        stats=s0, rows_per_group=hh * ww, out_full=[y0[:, 0]])
+                r = self._pair_rng()
+                rk = (lambda i: {"rng": (r, r.slot(f"{name}.{i}"))}) if r is not None else (lambda i: {})
+                ops.conv16_direct_multi([ops.affine_split16(x, None, None, 0, False, False, 3, **rk(0))], f0, b0, relu=False, full=torch.float32,
+                                        pool=None, stats=s0, rows_per_group=hh * ww, out_full=[y0[:, 0]])
                 sc0, sh0 = ops.stats_finalize(s0, hh * ww)
-                ops.conv16_direct_multi([ops.affine_split16(y0, sc0, sh0, 1, True, False, 3)], f1, b1, relu=False, full=torch.float32, pool=None,
+                ops.conv16_direct_multi([ops.affine_split16(y0, sc0, sh0, 1, True, False, 3, **rk(1))], f1, b1, relu=False, full=torch.float32, pool=None,
                                         stats=s1, rows_per_group=hh * ww, out_full=[y1[:, 0]])
                 sc1, sh1 = ops.stats_finalize(s1, hh * ww)
                 return y1, sc1, sh1
@@ -408,25 +412,33 @@ class VolumeRefiner(ParamBank):
         que_t = que_warp.float().div_(255).permute(2, 0, 1)[None].contiguous()
         step = self.angle_step()
         with torch.no_grad():
-            if step > 0:
-                # alignment angles snapped to the grid: the crop of a view depends on (view, bucket) only -> cached features
-                ref_Ks, ref_poses, Hs, buckets = E.reference_view_params(db, ref_ids, size, margin, True, pose_warp, K_warp, angle_step=step)
-                keys = [(id(self.ref_database), str(i), int(b), int(size)) for i, b in zip(ref_ids, buckets)]
-                make = lambda miss: torch.stack([ops.warp_perspective(cache.get(db, ref_ids[k]), Hs[k], size, size) for k in miss], 0) \
-                    .float().div_(255).permute(0, 3, 1, 2).contiguous()
-                ref_feats = self.cached_ref_feats(keys, make)
-                rot, off, scl = self._step(que_t, f(K_warp), f(pose_warp), None, f(ref_Ks), f(ref_poses), ref_feats=ref_feats)
-            else:
-                ref_imgs, _, ref_Ks, ref_poses, _ = E.normalize_reference_views(db, ref_ids, size, margin, cache, True, pose_warp, K_warp,
-                                                                             with_masks=False)
-                rot, off, scl = self._step(que_t, f(K_warp), f(pose_warp), ref_imgs.float().div_(255).permute(0, 3, 1, 2).contiguous(),
-                                           f(ref_Ks), f(ref_poses))
-            out = torch.cat([rot[0], off[0], scl[0]]).cpu().numpy()
+            out = self.range_guarded(lambda: self._refine_step(step, db, ref_ids, size, margin, pose_warp, K_warp, cache, que_t, f))
         quat, offset, scale_pr = out[:4], out[4:6], 2 ** out[6]
         pose_sim = G.compose_sim_pose(scale_pr, quat, offset, pose_warp, center)
         pose_pr = G.pose_sim_to_pose_rigid(pose_sim, pose_warp, K_warp, K_warp, center)
         pose_pr = G.pose_compose(pose_pr, G.pose_inverse(pose_rect))
         return G.denormalize_pose(pose_pr, db.scale, db.offset)
+
+    def _range_fallback(self):
+        # reference-crop features cached from pair maps that left the window are not reused
+        self.feat_cache.clear()
+
+    def _refine_step(self, step, db, ref_ids, size, margin, pose_warp, K_warp, cache, que_t, f):
+        from .. import estimator as E
+        if step > 0:
+            # alignment angles snapped to the grid: the crop of a view depends on (view, bucket) only -> cached features
+            ref_Ks, ref_poses, Hs, buckets = E.reference_view_params(db, ref_ids, size, margin, True, pose_warp, K_warp, angle_step=step)
+            keys = [(id(self.ref_database), str(i), int(b), int(size)) for i, b in zip(ref_ids, buckets)]
+            make = lambda miss: torch.stack([ops.warp_perspective(cache.get(db, ref_ids[k]), Hs[k], size, size) for k in miss], 0) \
+                .float().div_(255).permute(0, 3, 1, 2).contiguous()
+            ref_feats = self.cached_ref_feats(keys, make)
+            rot, off, scl = self._step(que_t, f(K_warp), f(pose_warp), None, f(ref_Ks), f(ref_poses), ref_feats=ref_feats)
+        else:
+            ref_imgs, _, ref_Ks, ref_poses, _ = E.normalize_reference_views(db, ref_ids, size, margin, cache, True, pose_warp, K_warp,
+                                                                         with_masks=False)
+            rot, off, scl = self._step(que_t, f(K_warp), f(pose_warp), ref_imgs.float().div_(255).permute(0, 3, 1, 2).contiguous(),
+                                       f(ref_Ks), f(ref_poses))
+        return torch.cat([rot[0], off[0], scl[0]]).cpu().numpy()
 
     def refine_step_tensors(self, que_img_u8, K_in, pose_in, ref_imgs_u8, ref_Ks, ref_poses):
         """Numpy boundary of one step after the host-side warps: uint8 crops [h,w,3] / [rfn,h,w,3], float32 K/poses

@@ -146,7 +146,12 @@ class ViewpointSelector(ParamBank):
     def get_feats(self, imgs):
         """imgs [n,3,h,w] in [0,1] -> 3 channels-last, L2-normalised maps [n,1,h_l,w_l,512] (selector.py:113-119)."""
         with self._mm("trunk"):
-            return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), True)
+            return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), True, **self._trunk_range())
+
+    def _trunk_range(self):
+        """Range arguments of the trunk (only when they are not the defaults: the trunk also runs with SPLIT16_ALWAYS)."""
+        r = self._pair_rng()
+        return ({"rng": r} if r is not None else {}) | ({} if self.pairs_on else {"split16": False})
 
     def extract_ref_feats(self, ref_imgs, ref_poses, object_center, object_vert, is_train=False):
         """ref_imgs [an,rfn,3,h,w]; builds the reference cache, its R1/R2 sums and the viewpoint embedding
@@ -217,7 +222,7 @@ class ViewpointSelector(ParamBank):
                 if mode16 and not first:
                     # round 6: the stack layers too — the InstanceNorm affine + ReLU of the previous layer is applied by one elementwise pass that
                     # writes the map in the direct kernel's format (g6d_affine_split16), the conv adds this layer's sums in its epilogue
-                    x16 = ops.affine_split16(x, scale, shift, grp if scale is not None else 0, relu, False, mode16)
+                    x16 = ops.affine_split16(x, scale, shift, grp if scale is not None else 0, relu, False, mode16, **self._rng_kw(mode16, f"stack{l}.{li}"))
                     filt = self._product16_filters(l, li, wgt, mode16)
                     ci = wgt.shape[2]
                     per = max(1, ((1 << 31) - 1) // (D * h * w * ci * (4 if mode16 == 3 else 2)))
@@ -231,7 +236,7 @@ class ViewpointSelector(ParamBank):
                     # round 6: the product layer on the direct 16-bit convolution (csrc/conv16_direct.hip): the normalised query x reference
                     # product is written once in the kernel's activation format (fp32 path: fp16 hi / lo pairs, fp32-class results), the conv
                     # adds this level's InstanceNorm sums in its epilogue, the affine of that norm comes from one small finalize launch
-                    prod = ops.product_split16(cache.view(D, h * w, 512), q.view(qn, h * w, 512), scale, shift, mode16)
+                    prod = ops.product_split16(cache.view(D, h * w, 512), q.view(qn, h * w, 512), scale, shift, mode16, **self._rng_kw(mode16, f"prod{l}"))
                     prod = prod.view(qn * D, h, w, 2, 512) if mode16 == 3 else prod.view(qn * D, h, w, 512)
                     filt = self._product16_filters(l, li, wgt, mode16)
                     # (a launch addresses its input with 32-bit offsets: 2^31 bytes = 8 queries of the 16 x 16 level in pairs)
@@ -269,7 +274,7 @@ class ViewpointSelector(ParamBank):
             return 0
         mm = ops.MATH_MODE
         if mm == 0:
-            return 3
+            return 3 if self.pairs_on else 0         # (pairs off: the recompute of a call whose pair maps left the window)
         # (Cout = 64 — level 0 — stays on the 16-bit Winograd kernel there: on the direct kernel's 32-channel waves it is 1 % faster end to end, but
         # the product rounded once to 16 bits takes the fp16 schemes' logits past their quarter-margin bar: measured, fp16ref32 `ok` true -> false)
         return mm if co % 128 == 0 else 0
@@ -280,8 +285,13 @@ class ViewpointSelector(ParamBank):
             return 0
         mm = ops.MATH_MODE
         if mm == 0:
-            return 3 if (co % 64 == 0 and ci % 32 == 0) else 0
+            return 3 if (co % 64 == 0 and ci % 32 == 0 and self.pairs_on) else 0
         return mm if (co % 128 == 0 and ci % 64 == 0) else 0
+
+    def _rng_kw(self, mode16, name):
+        """rng argument of a pair producer (slot `name` of this network's range table), none for the 16-bit modes."""
+        r = self._pair_rng() if mode16 == 3 else None
+        return {"rng": (r, r.slot(name))} if r is not None else {}
 
     def _product16_filters(self, l, li, wgt, mode):
         cache = self.__dict__.setdefault("_prod16", {})
@@ -431,14 +441,14 @@ class ViewpointSelector(ParamBank):
         x = torch.from_numpy(np.ascontiguousarray(ref_imgs)).to(dev).float().div_(255).permute(0, 1, 4, 2, 3)
         f = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32)).to(dev)
         with torch.no_grad():
-            self.extract_ref_feats(x, f(ref_poses), f(object_center), f(object_vert))
+            self.range_guarded(lambda: self.extract_ref_feats(x, f(ref_poses), f(object_center), f(object_vert)))
 
     def select_que_imgs(self, que_imgs):
         """uint8 [qn,h,w,3] -> {'ref_idx','angles','scores'} numpy; the raw network angle at the arg-max reference
         (reference selector.py:165-175)."""
         x = torch.from_numpy(np.ascontiguousarray(que_imgs)).to(self.device_()).float().div_(255).permute(0, 3, 1, 2)
         with torch.no_grad():
-            logits, angles = self.compute_view_point_feats(x.contiguous())
+            logits, angles = self.range_guarded(lambda: self.compute_view_point_feats(x.contiguous()))
             idx = torch.argmax(logits, 1)
             ang = angles[torch.arange(idx.shape[0], device=idx.device), idx]
         return {"ref_idx": idx.cpu().numpy(), "angles": ang.cpu().numpy(), "scores": logits.cpu().numpy()}

@@ -10,7 +10,9 @@ per-op PyTorch references of tests/ref_ops.py to validate host orchestration wit
 has no fallback — `lib.load()` raises if libgen6d_hip.so is absent.
 """
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import lib as _lib
@@ -675,6 +677,126 @@ def wino16_conv3x3_multi(xs, U16, bias, relu=True, full=True, pool=False):
 
 _T16 = {1: torch.bfloat16, 2: torch.float16, 3: torch.float16}
 
+# ---- range control of fp16 hi / lo pair maps (G6dRange16, include/gen6d_hip.h) ---------------------------------------------------------
+# A pair map holds v * 2^-e: e = 0 while the map's largest |v| (A) lies in [2^-4, 2^14) — today's bits — else floor(log2 A), so the scaled
+# maximum lies in [1, 2).  A call whose scaled maximum reaches 2^15 (fp16 overflows at 65504), falls below 2^-4 for a non-zero map (the lo
+# plane turns subnormal) or is not finite leaves the window: the networks recompute it on their fp32 routes (RangeGuard).
+PAIR_KEEP = (2.0 ** -4, 2.0 ** 14)
+PAIR_LIMIT = (2.0 ** -4, 2.0 ** 15)
+PAIR_EXP_MAX = 100                    # |e| bound: acc_scale * 2^e and v * 2^-e stay normal fp32 numbers.  A map beyond it (non-zero max
+                                      # below 2^-96 or at least 2^115) cannot be held in pairs: every call on it takes the fp32 routes
+
+
+def pair_exponent(a, e=0):
+    """The exponent rule: recorded max `a` -> the map's exponent (`e`, the current one, stays for a non-finite record)."""
+    if not math.isfinite(a):
+        return e
+    if a == 0.0 or PAIR_KEEP[0] <= a < PAIR_KEEP[1]:
+        return 0
+    return max(-PAIR_EXP_MAX, min(PAIR_EXP_MAX, math.frexp(a)[1] - 1))          # floor(log2 a), exact
+
+
+def pair_out_of_window(a, e):
+    """True if a map with recorded max `a` stored at exponent `e` left the window (recompute on the fp32 routes)."""
+    if not math.isfinite(a):
+        return True
+    if a == 0.0:
+        return False
+    s = math.ldexp(a, -e)
+    return s >= PAIR_LIMIT[1] or s < PAIR_LIMIT[0]
+
+
+def bits_to_float(bits):
+    """Recorded uint32 bit patterns (any integer array) -> float values (NaN / inf kept)."""
+    return np.asarray(bits, dtype=np.int64).astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+class RangeTable:
+    """The exponents and range record of one network's pair maps: slot i (one per pair-producing call site, by name) has its exponent
+    in `exps` (device int32; a captured graph reads it at replay, so rewriting it needs no recapture) and the largest |v| its launches
+    stored since the last clear() in `rec` (device, uint32 bits).  The host rewrites `exps` only between calls, ordered on the stream."""
+    CAP = 64
+
+    def __init__(self, device):
+        self.device = device
+        self.exps = torch.zeros(self.CAP, dtype=torch.int32, device=device)
+        self.rec = torch.zeros(self.CAP, dtype=torch.int32, device=device)
+        self.e = [0] * self.CAP
+        self.names = {}
+
+    def slot(self, name):
+        if name not in self.names:
+            if len(self.names) == self.CAP:
+                raise RuntimeError("RangeTable: out of slots")
+            self.names[name] = len(self.names)
+        return self.names[name]
+
+    def arg(self, slot_in=-1, slot_out=-1):
+        return _lib.G6dRange16(exps=self.exps.data_ptr(), rec=self.rec.data_ptr(), slot_in=int(slot_in), slot_out=int(slot_out))
+
+    def clear(self):
+        _lib.check(_lib.load().g6d_zero_bytes(_ptr(self.rec), self.rec.numel() * 4, _stream()), "g6d_zero_bytes")
+
+    def reset(self):
+        """Exponents 0 and an empty record IN PLACE (new weights): graphs captured earlier keep valid pointers."""
+        self.e = [0] * self.CAP
+        self.set_exponents({})
+        self.clear()
+
+    def read(self):
+        """{name: recorded max |v|} (synchronises with the stream)."""
+        a = bits_to_float(self.rec.cpu().numpy())
+        return {n: float(a[i]) for n, i in self.names.items()}
+
+    def set_exponents(self, es):
+        """{name: exponent} -> the device table (a copy on the current stream)."""
+        for n, e in es.items():
+            self.e[self.slot(n)] = int(e)
+        self.exps.copy_(torch.tensor(self.e, dtype=torch.int32), non_blocking=False)
+
+
+class PairMap:
+    """An fp16 hi / lo pair map ([..., 2, C] fp16) that holds v * 2^-e with e = table.exps[slot]: what a producer with a range returns and
+    what the pair consumers (conv16_direct_multi, corr16_multi) take, so that no reader forgets the exponent."""
+    __slots__ = ("data", "table", "slot")
+
+    def __init__(self, data, table, slot):
+        self.data, self.table, self.slot = data, table, slot
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    def __getitem__(self, idx):                 # a slice of the map keeps its exponent
+        return PairMap(self.data[idx], self.table, self.slot)
+
+    def view(self, *shape):
+        return PairMap(self.data.view(*shape), self.table, self.slot)
+
+
+def _pair_inputs(xs):
+    """Plain tensors and PairMaps -> (tensors, table or None, slot_in): the maps of one launch share one slot."""
+    maps = [x for x in xs if isinstance(x, PairMap)]
+    if not maps:
+        return list(xs), None, -1
+    if len(maps) != len(xs) or len({(id(m.table), m.slot) for m in maps}) != 1:
+        raise ValueError("pair inputs of one launch must all be PairMaps of one slot")
+    return [m.data for m in maps], maps[0].table, maps[0].slot
+
+
+def _range_arg(table_in, slot_in, rng):
+    """G6dRange16 pointer for a launch (None: the legacy behaviour).  rng: (RangeTable, output slot) or None."""
+    table = rng[0] if rng is not None else table_in
+    if table is None:
+        return None
+    if table_in is not None and table_in is not table:
+        raise ValueError("pair input and output belong to different range tables")
+    return C.byref(table.arg(slot_in, rng[1] if rng is not None else -1))
+
+
+def _wrap(t, rng):
+    return PairMap(t, rng[0], rng[1]) if (rng is not None and t is not None) else t
+
 
 class Conv16Filters:
     """Filters of g6d_conv16_direct_multi: `data` (16-bit, flat), `layout` (0 = [Cout][taps][Cin] rows, 1 = fragment-major), `mode`
@@ -720,9 +842,12 @@ def conv16_pack(w_taps, mode, layout=1):
     return Conv16Filters(x.reshape(-1), 1, mode, acc_scale, co_true, taps, ci)
 
 
-def product_split16(ref, que, scale, shift, mode):
+def product_split16(ref, que, scale, shift, mode, rng=None):
     """The selector's query x reference product in the activation format of conv16_direct_multi (g6d_product_split16): ref [D,P,C], que
-    [qn,P,C], scale / shift [qn,C] fp32 -> [qn*D, P, C] (mode 1 / 2) or [qn*D, P, 2, C] fp16 pairs (mode 3)."""
+    [qn,P,C], scale / shift [qn,C] fp32 -> [qn*D, P, C] (mode 1 / 2) or [qn*D, P, 2, C] fp16 pairs (mode 3).  rng = (RangeTable, slot):
+    mode 3 only, the pairs carry the slot's exponent and are recorded (returns a PairMap)."""
+    if rng is not None and mode != 3:
+        raise ValueError("product_split16: a range applies to pairs (mode 3) only")
     _need_gpu(ref, que, scale, shift)
     D, P, Cc = ref.shape
     qn = que.shape[0]
@@ -731,34 +856,40 @@ def product_split16(ref, que, scale, shift, mode):
         raise ValueError("product_split16: dense fp32 ref [D,P,C], que [qn,P,C], scale / shift [qn,C] expected")
     out = torch.empty((qn * D, P, 2, Cc) if mode == 3 else (qn * D, P, Cc), dtype=_T16[mode], device=ref.device)
     nbytes = 4.0 * (ref.numel() + que.numel()) + 2.0 * out.numel()
-    _timed_hbm("product_split16", nbytes, lambda: _lib.check(_lib.load().g6d_product_split16(
-        _ptr(ref), _ptr(que), _ptr(scale), _ptr(shift), _ptr(out), qn, D, P, Cc, int(mode), _stream()), "g6d_product_split16"))
-    return out
+    ra = _range_arg(None, -1, rng)
+    _timed_hbm("product_split16", nbytes, lambda: _lib.check(_lib.load().g6d_product_split16_ex(
+        _ptr(ref), _ptr(que), _ptr(scale), _ptr(shift), _ptr(out), qn, D, P, Cc, int(mode), ra, _stream()), "g6d_product_split16"))
+    return _wrap(out, rng)
 
 
-def affine_split16(x, scale, shift, per_n, relu, pool, mode):
+def affine_split16(x, scale, shift, per_n, relu, pool, mode, rng=None):
     """affine_act_pool (pool False / True = 2x2 max) with the result in the activation format of conv16_direct_multi (g6d_affine_split16):
-    x [N,1,H,W,C] fp32 view -> [N,Ho,Wo,C] (mode 1 / 2) or [N,Ho,Wo,2,C] fp16 pairs (mode 3)."""
+    x [N,1,H,W,C] fp32 view -> [N,Ho,Wo,C] (mode 1 / 2) or [N,Ho,Wo,2,C] fp16 pairs (mode 3).  rng as product_split16."""
+    if rng is not None and mode != 3:
+        raise ValueError("affine_split16: a range applies to pairs (mode 3) only")
     _need_gpu(x)
     N, D, H, W, Cc, ld_in = _cl5(x, "affine_split16.x")
     if D != 1:
         raise ValueError("affine_split16: 2-D maps expected")
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
     out = torch.empty((N, Ho, Wo, 2, Cc) if mode == 3 else (N, Ho, Wo, Cc), dtype=_T16[mode], device=x.device)
-    _timed_hbm("affine_split16", 4.0 * N * H * W * Cc + 2.0 * out.numel(), lambda: _lib.check(_lib.load().g6d_affine_split16(
-        _ptr(x), ld_in, _ptr(scale), _ptr(shift), int(per_n), int(bool(relu)), int(bool(pool)), N, H, W, Cc, _ptr(out), int(mode), _stream()),
+    ra = _range_arg(None, -1, rng)
+    _timed_hbm("affine_split16", 4.0 * N * H * W * Cc + 2.0 * out.numel(), lambda: _lib.check(_lib.load().g6d_affine_split16_ex(
+        _ptr(x), ld_in, _ptr(scale), _ptr(shift), int(per_n), int(bool(relu)), int(bool(pool)), N, H, W, Cc, _ptr(out), int(mode), ra, _stream()),
         "g6d_affine_split16"))
-    return out
+    return _wrap(out, rng)
 
 
-def vgg_conv1_pool_nhwc16(x, w_oihw, bias, out=None, norm=None, mode=None):
+def vgg_conv1_pool_nhwc16(x, w_oihw, bias, out=None, norm=None, mode=None, rng=None):
     """vgg_conv1_pool_nhwc with a 16-bit channels-last result (g6d_vgg_conv1_pool_nhwc16): mode 1 / 2 (default: the current math mode) =
     bf16 / fp16 [N,H/2,W/2,64], the first layer of the reduced-precision mode's 16-bit activation path; mode 3 = fp16 hi / lo pairs
-    [N,H/2,W/2,2,64], the first layer of the fp32 path's split-precision trunk."""
+    [N,H/2,W/2,2,64], the first layer of the fp32 path's split-precision trunk.  rng as product_split16."""
     _need_gpu(x, w_oihw, bias)
     mode = MATH_MODE if mode is None else mode
     if mode not in _T16:
         raise RuntimeError("vgg_conv1_pool_nhwc16: mode 1 (bf16), 2 (fp16) or 3 (fp16 pairs)")
+    if rng is not None and mode != 3:
+        raise ValueError("vgg_conv1_pool_nhwc16: a range applies to pairs (mode 3) only")
     N, Cin, H, W = x.shape
     Cout = w_oihw.shape[0]
     shape = (N, H // 2, W // 2, 2, Cout) if mode == 3 else (N, H // 2, W // 2, Cout)
@@ -769,19 +900,26 @@ def vgg_conv1_pool_nhwc16(x, w_oihw, bias, out=None, norm=None, mode=None):
     mean = std = None
     if norm is not None:
         mean, std = (C.c_float * 3)(*norm[0]), (C.c_float * 3)(*norm[1])
-    _lib.check(_lib.load().g6d_vgg_conv1_pool_nhwc16(_ptr(x.contiguous()), N, H, W, _ptr(w_oihw.contiguous()), _ptr(bias), Cin, Cout,
-                                                     mean, std, _ptr(out), int(mode), _stream()), "g6d_vgg_conv1_pool_nhwc16")
-    return out
+    _lib.check(_lib.load().g6d_vgg_conv1_pool_nhwc16_ex(_ptr(x.contiguous()), N, H, W, _ptr(w_oihw.contiguous()), _ptr(bias), Cin, Cout,
+                                                        mean, std, _ptr(out), int(mode), _range_arg(None, -1, rng), _stream()),
+               "g6d_vgg_conv1_pool_nhwc16")
+    return _wrap(out, rng)
 
 
-def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, stats=None, rows_per_group=0, out_full=None):
+def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, stats=None, rows_per_group=0, out_full=None, rng=None):
     """Direct 3x3 / 3x3x3 convolution on 16-bit activations (g6d_conv16_direct_multi).  filt: Conv16Filters (conv16_pack); its mode
     decides the arithmetic: 1 / 2 = bf16 / fp16 operands (the reduced-precision mode), 3 = fp16 hi / lo pairs (fp32-class results: the
     fp32 path's trunk).  xs: 1..4 dense channels-last tensors of the mode's 16-bit type, [N,H,W,Cin] (kd = 1) or [N,D,H,W,Cin] (kd = 3);
     pairs carry an extra plane axis in front of the channels: [N,H,W,2,Cin].
     full / pool: None = not produced, torch.float32, or "t16" = the mode's 16-bit format (pairs for mode 3) -> lists of dense outputs
     (None where not produced).  stats [G,Cout,2] fp64 (zeroed): sum / sum of squares of the fp32 results are added.  out_full: optional list
-    of caller-provided dense output tensors."""
+    of caller-provided dense output tensors.
+    Range control (mode 3): the inputs may be PairMaps (all of one slot: the kernel scales by their exponent); rng = (RangeTable, slot): the
+    pair outputs carry that slot's exponent, are recorded and come back as PairMaps (fp32 outputs and statistics stay unscaled)."""
+    xs, table_in, slot_in = _pair_inputs(xs)
+    if (table_in is not None or rng is not None) and filt.mode != 3:
+        raise ValueError("conv16_direct_multi: ranges apply to pairs (mode 3) only")
+    ra = _range_arg(table_in, slot_in, rng)
     _need_gpu(filt.data, *xs)
     mode = filt.mode
     t16 = _T16[mode]
@@ -832,14 +970,18 @@ def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, s
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    _lib.check(_lib.load().g6d_conv16_direct_multi(segs, len(xs), Cin, _ptr(filt.data), int(filt.layout), float(filt.acc_scale), _ptr(bias), Cout, int(kd),
-                                                  int(bool(relu)), code[full], code[pool], int(mode), _ptr(stats), int(rows_per_group), _stream()),
+    _lib.check(_lib.load().g6d_conv16_direct_multi_ex(segs, len(xs), Cin, _ptr(filt.data), int(filt.layout), float(filt.acc_scale), _ptr(bias), Cout,
+                                                     int(kd), int(bool(relu)), code[full], code[pool], int(mode), _ptr(stats), int(rows_per_group), ra,
+                                                     _stream()),
                "g6d_conv16_direct_multi")
     if PROFILE is not None:
         e1.record()
         # mode 3 executes three 16-bit MFMAs per product: booked as "conv16x3" with the DIRECT-FORM flops (what the fp32 kernels it replaces are booked with / 4)
         PROFILE.append((flops, e0, e1, f"{'conv16x3' if pair else 'conv16'} direct in={'+'.join(sizes)}x{Cin} out={Cout} k={'3x' if kd == 3 else ''}3x3"
                         f"{' full' if full is not None else ''}{' pool' if pool is not None else ''}{' stats' if stats is not None else ''}", nbytes, flops))
+    if rng is not None:
+        fulls = [_wrap(f, rng) if full == "t16" else f for f in fulls]
+        pools = [_wrap(q, rng) if pool == "t16" else q for q in pools]
     return fulls, pools
 
 
@@ -872,7 +1014,12 @@ def corr16_pack(w_taps, mode):
 
 def corr16_multi(xs, filt, outs):
     """The detector's k x k correlation on 16-bit activations (g6d_corr16_multi).  xs: 1..4 dense channels-last maps [N,H,W,Cin] of the
-    mode's 16-bit type (pairs: [N,H,W,2,Cin]); outs: fp32 [N,1,H,W,32] (or [N,H,W,32]) dense; filt: corr16_pack(...)."""
+    mode's 16-bit type (pairs: [N,H,W,2,Cin], or PairMaps of one slot: scaled back by their exponent); outs: fp32 [N,1,H,W,32] (or
+    [N,H,W,32]) dense; filt: corr16_pack(...)."""
+    xs, table_in, slot_in = _pair_inputs(xs)
+    if table_in is not None and filt.mode != 3:
+        raise ValueError("corr16_multi: PairMaps need pair filters (mode 3)")
+    ra = _range_arg(table_in, slot_in, None)
     _need_gpu(filt.data, *xs, *outs)
     mode, Cin = filt.mode, filt.Cin
     pair = mode == 3
@@ -893,7 +1040,7 @@ def corr16_multi(xs, filt, outs):
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    _lib.check(_lib.load().g6d_corr16_multi(segs, len(xs), Cin, _ptr(filt.data), float(filt.acc_scale), 32, int(filt.k), int(mode), _stream()),
+    _lib.check(_lib.load().g6d_corr16_multi_ex(segs, len(xs), Cin, _ptr(filt.data), float(filt.acc_scale), 32, int(filt.k), int(mode), ra, _stream()),
                "g6d_corr16_multi")
     if PROFILE is not None:
         e1.record()

@@ -45,6 +45,12 @@ class TensorPipeline:
         self.iter_poses = [torch.from_numpy(synth.perturb_pose(self.ref_case["poses_in"][0].numpy(), 2.0 * i, 0.01 * i))[None].to(d)
                            for i in range(self.refine_iter)]
 
+    def range_check(self):
+        """For callers that synchronise themselves: read and clear the fp16 pair maps' range records of the three networks
+        (ParamBank.range_check; synchronises).  Returns the names of the networks whose maps left the window since the last check — their
+        exponents are updated for the next calls (a captured graph reads them at replay); results of those calls should be recomputed."""
+        return [k for k, net in (("detector", self.detector), ("selector", self.selector), ("refiner", self.refiner)) if net.range_check()]
+
     def _canned(self, n, it):
         """(Ks_in, pose_in of iteration `it`, ref_Ks, ref_poses) of the canned refinement case replicated for n queries (dense)."""
         key = (n, it)

@@ -326,6 +326,33 @@ int g6d_affine_split16(const float* in, int ld_in, const float* scale, const flo
 int g6d_corr16_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
                      g6d_stream_t stream);
 
+/* Range control of fp16 hi / lo PAIR maps (the math_mode 3 activations above; additive to ABI v12).  A pair map may hold v * 2^-e instead
+ * of v: its exponent e sits in a small DEVICE table `exps` (int32, one slot per pair-producing call site of a network), so a captured graph
+ * stays valid when the host rewrites an exponent between calls.  NULL range pointer (or the entry points without _ex) = today's unscaled maps.
+ *   exps      NULL = every exponent 0
+ *   rec       NULL = no record; else rec[slot_out] = max(rec[slot_out], max over the stored UNSCALED values v of bits(|v|)) — an integer
+ *             max of the IEEE bits, so NaN > inf > every finite value (at most one atomicMax per wave; clear it with g6d_zero_bytes)
+ *   slot_in   pair input read with exponent exps[slot_in] (the consumer multiplies its accumulator scale by 2^e_in); < 0 = exponent 0
+ *   slot_out  pair outputs written as split16(v * 2^-exps[slot_out]) and recorded in rec[slot_out]; < 0 = unscaled, not recorded
+ * Only the 16-bit pair outputs carry the exponent: fp32 outputs and fp64 statistics stay unscaled. */
+typedef struct G6dRange16 {
+  const int32_t* exps;
+  uint32_t* rec;
+  int32_t slot_in, slot_out;
+} G6dRange16;
+int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale, const float* bias,
+                               int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group,
+                               const G6dRange16* range, g6d_stream_t stream);
+int g6d_corr16_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
+                        const G6dRange16* range, g6d_stream_t stream);
+int g6d_product_split16_ex(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,
+                           int math_mode, const G6dRange16* range, g6d_stream_t stream);
+int g6d_affine_split16_ex(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
+                          int W, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream);
+int g6d_vgg_conv1_pool_nhwc16_ex(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout,
+                                 const float* mean_host, const float* std_host, void* out16, int math_mode, const G6dRange16* range,
+                                 g6d_stream_t stream);
+
 /* g6d_wino_conv3x3_multi on the Winograd F(4x4,3x3) kernel (ABI v8, fp32 on v_mfma_f32_16x16x4_f32): 36 multiplications per 16
  * outputs — 4x fewer than the direct form, 1.78x fewer than F(2x2,3x3) — with the interpolation points (0, +-3/4, +-3/2, inf), whose
  * fp32 error is ~1.3e-6 of the output range at Cin = 512 (F(2x2,3x3): 2.5e-7; the textbook points 0, +-1, +-2: 4.6e-6).  Meant for the
