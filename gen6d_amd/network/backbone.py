@@ -189,28 +189,33 @@ class TrunkLayer(tuple):
 
 
 _LOWP_DTYPE = {1: torch.bfloat16, 2: torch.float16}
-LOWP_TRUNK = True        # reduced-precision mode: trunk on the 16-bit Winograd kernel (False, set by tools / tests: stays on the fp32 kernel)
-CONV16_TRUNK = True      # reduced-precision mode (round 6): trunk on 16-bit ACTIVATIONS and the direct 16-bit kernel (g6d_conv16_direct_multi:
-                         # 1.5-1.8x the 16-bit Winograd kernel per layer); False (tools / tests): the round-5 path above
-SPLIT16_TRUNK = True     # fp32 path (round 6): the trunks that ran on the F(4x4,3x3) kernel (detector pyramid, refiner crops) on the SAME direct
-                         # kernel with every operand a pair of fp16 values (hi + lo, 22+ significand bits; 3 MFMAs per product on the 16-bit
-                         # matrix cores instead of the fp32 ones): fp32-class results — smaller error than F(4x4,3x3)'s — at 1.3-1.6x its speed.
-                         # False (tools / tests): the F(4x4,3x3) kernel of rounds 4-5
-SPLIT16_ALWAYS = False   # ... and EVERY fp32 trunk call whose map sizes the kernel takes (the selector's query crops, the refiner's crops at
-                         # any batch size, the reference-side trunks at build time): the trunk's kernel is then a function of the layer, not
-                         # of how many queries share the launch, and its error (2e-6 of range) is below both Winograd kernels'.
-                         # False (default): only where F(4x4,3x3) ran — measured neutral on the batched step (270.9 vs 270.2 images/s) and
-                         # 0.2 ms slower on a single query (7.84 vs 7.62 ms: a crop's 224 tiles do not fill the chip)
 
 
-def _wino_layer(xs, layer, relu=True, full=True, pool=False, f43=False):
-    """One trunk layer over the segments xs on the kernel of the current math mode: fp32 Winograd — F(2x2,3x3), or with f43 the
-    F(4x4,3x3) kernel (1.78x fewer multiplications at ~5x the rounding error: the detector's pyramid, whose parity budget has the
-    room) — or (ops.MATH_MODE 1 / 2, Cin % 16 == 0) the 16-bit one."""
-    mm = ops.MATH_MODE
-    if mm and LOWP_TRUNK and hasattr(layer, "u16") and xs[0].shape[3] % 16 == 0:
-        return ops.wino16_conv3x3_multi(xs, layer.u16(_LOWP_DTYPE[mm]), layer[1], relu=relu, full=full, pool=pool)
-    if f43 and not mm and layer[1].numel() % 64 == 0:
+def trunk_route(packed, sizes, taps, f43=False, pairs=True):
+    """The kernels of one trunk call over images of `sizes` [(h, w)] in the current math mode:
+      "direct"  the direct kernel on 16-bit activations (g6d_conv16_direct_multi): the reduced-precision modes (ops.MATH_MODE 1 / 2)
+                wherever the maps pool whole windows; on the fp32 path fp16 hi / lo pairs (mode 3: fp32-class results, 1.3-1.6x
+                F(4x4,3x3)'s speed) for the calls that may take F(4x4,3x3) (f43) while `pairs` allows them
+      "wino16"  the 16-bit Winograd kernel (reduced precision, other map sizes)
+      "f43"     Winograd F(4x4,3x3) on fp32 MFMA (1.78x fewer multiplications at ~5x the rounding error: the detector's pyramid and the
+                refiner's batched crops, whose parity budgets have the room)
+      "f23"     Winograd F(2x2,3x3) on fp32 MFMA.
+    Plain (U, bias) packs (no TrunkLayer) take the fp32 Winograd kernels only."""
+    own = isinstance(packed[1], TrunkLayer)
+    direct = own and _conv16_eligible(sizes, taps)
+    if ops.MATH_MODE and own:
+        return "direct" if direct else "wino16"
+    if f43 and not ops.MATH_MODE:
+        return "direct" if (pairs and direct) else "f43"
+    return "f23"
+
+
+def _wino_layer(xs, layer, route, relu=True, full=True, pool=False):
+    """One trunk layer over the segments xs on the Winograd kernel of `route` (trunk_route: "wino16" needs Cin % 16 == 0, "f43" Cout % 64
+    == 0; otherwise F(2x2,3x3))."""
+    if route == "wino16" and xs[0].shape[3] % 16 == 0:
+        return ops.wino16_conv3x3_multi(xs, layer.u16(_LOWP_DTYPE[ops.MATH_MODE]), layer[1], relu=relu, full=full, pool=pool)
+    if route == "f43" and layer[1].numel() % 64 == 0:
         return ops.wino43_conv3x3_multi(xs, layer.u43(), layer[1], relu=relu, full=full, pool=pool)
     return ops.wino_conv3x3_multi(xs, layer[0], layer[1], relu=relu, full=full, pool=pool)
 
@@ -223,14 +228,14 @@ def pack_trunk(folded):
 _IMG_NORM = (tuple(specs.IMAGENET_MEAN), tuple(specs.IMAGENET_STD))
 
 
-def vgg_taps_cl(packed, x, taps, norm=None, f43=False, rng=None, split16=True):
+def vgg_taps_cl(packed, x, taps, norm=None, f43=False, rng=None, pairs=True):
     """Own trunk, channels-last: x [n,3,h,w] normalised image (or an image in [0,1] with norm = (mean, std): the first layer
     normalises while it stages its input) -> {'c3': [n,h/4,w/4,256] post-ReLU, 'c5': [n,h/8,w/8,512] post-ReLU,
-    'c7_pre': [n,h/16,w/16,512] pre-ReLU, 'p7': max-pool of c7_pre} (only the requested taps + c7_pre).  rng / split16: as
+    'c7_pre': [n,h/16,w/16,512] pre-ReLU, 'p7': max-pool of c7_pre} (only the requested taps + c7_pre).  f43 / rng / pairs: as
     vgg_taps_cl_multi."""
-    if (ops.MATH_MODE and LOWP_TRUNK) or f43 or (split16 and SPLIT16_TRUNK and SPLIT16_ALWAYS and hasattr(packed[1], "w16") and _conv16_eligible([x], taps)):
-        # reduced precision: the multi-segment 16-bit kernel; f43: the F(4x4,3x3) kernel (one segment); fp32 path: the split-precision kernel
-        return vgg_taps_cl_multi(packed, [x], taps, norm=norm, f43=f43, rng=rng, split16=split16)[0]
+    if trunk_route(packed, [x.shape[2:]], taps, f43, pairs) != "f23":
+        # every route but F(2x2,3x3) runs on the multi-segment kernels (one segment)
+        return vgg_taps_cl_multi(packed, [x], taps, norm=norm, f43=f43, rng=rng, pairs=pairs)[0]
     w0, b0 = packed[0]
     x = ops.vgg_conv1_pool_nhwc(x.contiguous(), w0, b0, norm=norm)              # (normalise +) conv0 + ReLU + pool
     _, x = ops.wino_conv3x3(x, *packed[1], relu=True, full=False, pool=True)    # conv1 + ReLU + pool
@@ -244,11 +249,11 @@ def vgg_taps_cl(packed, x, taps, norm=None, f43=False, rng=None, split16=True):
     return {k: v for k, v in out.items() if v is not None and (k in taps or k == "c7_pre")}
 
 
-def _conv16_eligible(xs, taps):
+def _conv16_eligible(sizes, taps):
     """The 16-bit activation path pools whole 2x2 windows only: every pooled layer's map must have even sides (the detector's pyramid
     sizes are multiples of 32, the crops 128: always true there; other sizes keep the round-5 path, whose kernels pool with floor)."""
     need = 32 if "p7" in taps else 16
-    return all(x.shape[2] % need == 0 and x.shape[3] % need == 0 for x in xs) and len(xs) <= 4
+    return all(h % need == 0 and w % need == 0 for h, w in sizes) and len(sizes) <= 4
 
 
 def _vgg_taps_conv16(packed, xs, taps, norm, mode, taps16=(), rng=None):
@@ -283,28 +288,27 @@ def _vgg_taps_conv16(packed, xs, taps, norm, mode, taps16=(), rng=None):
     return outs
 
 
-def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=(), rng=None, split16=True):
-    """vgg_taps_cl for several image sizes at once (the scales of the detector's pyramid): every Winograd layer is ONE launch
-    over all sizes (ops.wino_conv3x3_multi).  xs: list of [1,3,h_i,w_i] images (normalised, or in [0,1] with norm) -> list of
-    tap dicts.  f43: the seven Winograd layers on the F(4x4,3x3) kernel (fp32 mode only).  rng: the caller's ops.RangeTable for the
-    split-precision trunk's pair maps (their taps then come back as ops.PairMaps); split16 = False: that trunk is not taken (the network's
-    recompute of a call whose pair maps left the window)."""
-    if ops.MATH_MODE and LOWP_TRUNK and CONV16_TRUNK and hasattr(packed[1], "w16") and _conv16_eligible(xs, taps):
-        return _vgg_taps_conv16(packed, xs, taps, norm, ops.MATH_MODE, taps16)
-    if split16 and (f43 or SPLIT16_ALWAYS) and not ops.MATH_MODE and SPLIT16_TRUNK and hasattr(packed[1], "w16") and _conv16_eligible(xs, taps):
-        return _vgg_taps_conv16(packed, xs, taps, norm, 3, taps16, rng)
+def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=(), rng=None, pairs=True):
+    """vgg_taps_cl for several image sizes at once (the scales of the detector's pyramid): every layer is ONE launch over all sizes, on
+    the kernels of trunk_route.  xs: list of [1,3,h_i,w_i] images (normalised, or in [0,1] with norm) -> list of tap dicts.  f43: the
+    call may take the faster fp32 kernels (fp16 hi / lo pairs, or F(4x4,3x3)).  rng: the caller's ops.RangeTable for the pair maps (their
+    taps then come back as ops.PairMaps); pairs = False: no pairs (the network's cfg 'fp32_cores', or the recompute of a call whose pair
+    maps left the window)."""
+    route = trunk_route(packed, [x.shape[2:] for x in xs], taps, f43, pairs)
+    if route == "direct":
+        return _vgg_taps_conv16(packed, xs, taps, norm, ops.MATH_MODE or 3, taps16, rng)
     w0, b0 = packed[0]
     dev = xs[0].device
     cur = ops.alloc_like_segments([(x.shape[0], x.shape[2] // 2, x.shape[3] // 2, w0.shape[0]) for x in xs], dev)
     for x, o in zip(xs, cur):
         ops.vgg_conv1_pool_nhwc(x.contiguous(), w0, b0, out=o, norm=norm)               # conv0 + ReLU + pool, per size
-    _, cur = _wino_layer(cur, packed[1], relu=True, full=False, pool=True, f43=f43)
-    cur, _ = _wino_layer(cur, packed[2], relu=True, f43=f43)
-    c3, cur = _wino_layer(cur, packed[3], relu=True, full="c3" in taps, pool=True, f43=f43)
-    cur, _ = _wino_layer(cur, packed[4], relu=True, f43=f43)
-    c5, cur = _wino_layer(cur, packed[5], relu=True, full="c5" in taps, pool=True, f43=f43)
-    cur, _ = _wino_layer(cur, packed[6], relu=True, f43=f43)
-    c7, p7 = _wino_layer(cur, packed[7], relu=False, full=True, pool="p7" in taps, f43=f43)
+    _, cur = _wino_layer(cur, packed[1], route, relu=True, full=False, pool=True)
+    cur, _ = _wino_layer(cur, packed[2], route, relu=True)
+    c3, cur = _wino_layer(cur, packed[3], route, relu=True, full="c3" in taps, pool=True)
+    cur, _ = _wino_layer(cur, packed[4], route, relu=True)
+    c5, cur = _wino_layer(cur, packed[5], route, relu=True, full="c5" in taps, pool=True)
+    cur, _ = _wino_layer(cur, packed[6], route, relu=True)
+    c7, p7 = _wino_layer(cur, packed[7], route, relu=False, full=True, pool="p7" in taps)
     outs = []
     for i in range(len(xs)):
         d = {"c3": c3, "c5": c5, "c7_pre": c7, "p7": p7}
@@ -312,14 +316,14 @@ def vgg_taps_cl_multi(packed, xs, taps, norm=None, f43=False, taps16=(), rng=Non
     return outs
 
 
-def trunk_features_multi(packed, imgs_list, keys, f43=False, taps16=(), rng=None, split16=True):
+def trunk_features_multi(packed, imgs_list, keys, f43=False, taps16=(), rng=None, pairs=True):
     """trunk_features (no L2 normalisation) for a list of [1,3,h_i,w_i] images of different sizes -> list of lists of
     [1,1,h_l,w_l,C] maps.  One launch per layer for all sizes (up to 4 per launch).  taps16: keys that may come back in the 16-bit
     activation format of the direct kernel ([n,h,w,C] fp16 / bf16, or [n,h,w,2,C] fp16 pairs on the fp32 path, ops.PairMaps with rng) when
-    the trunk runs on it — the caller checks the type.  rng / split16: as vgg_taps_cl_multi."""
+    the trunk runs on it — the caller checks the type.  f43 / rng / pairs: as vgg_taps_cl_multi."""
     if len(imgs_list) > 4:
-        return [trunk_features(packed, im, keys, False, rng=rng, split16=split16) for im in imgs_list]
-    taps = vgg_taps_cl_multi(packed, imgs_list, set(keys), norm=_IMG_NORM, f43=f43, taps16=taps16, rng=rng, split16=split16)
+        return [trunk_features(packed, im, keys, False) for im in imgs_list]
+    taps = vgg_taps_cl_multi(packed, imgs_list, set(keys), norm=_IMG_NORM, f43=f43, taps16=taps16, rng=rng, pairs=pairs)
     return [[(t[k] if is_16bit(t[k]) else t[k].unsqueeze(1)) for k in keys] for t in taps]
 
 
@@ -328,10 +332,10 @@ def is_16bit(t):
     return isinstance(t, ops.PairMap) or t.dtype != torch.float32
 
 
-def trunk_features(packed, imgs, keys, l2norm, f43=False, rng=None, split16=True):
+def trunk_features(packed, imgs, keys, l2norm, f43=False, rng=None, pairs=True):
     """Normalised images [n,3,h,w] in [0,1] -> channels-last 5-D feature maps [n,1,h_l,w_l,C] for `keys`, optionally
     L2-normalised over C (F.normalize, reference selector.py:118 / refiner.py:69-71)."""
-    t = vgg_taps_cl(packed, imgs, set(keys), norm=_IMG_NORM, f43=f43, rng=rng, split16=split16)
+    t = vgg_taps_cl(packed, imgs, set(keys), norm=_IMG_NORM, f43=f43, rng=rng, pairs=pairs)
     outs = []
     for k in keys:
         f = t[k]

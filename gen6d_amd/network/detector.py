@@ -2,11 +2,13 @@
 output dicts), driving hand-written HIP kernels end to end.
 
 For the 4 detection scales of a batch of queries at once (reference detect_impl, detector.py:232-266):
-    own Winograd trunk              F(4x4,3x3) on fp32 MFMA, one launch per layer over the whole pyramid -> x0 @1/8, x1 @1/16, x2 @1/32
+    own trunk                       one launch per layer over the whole pyramid (backbone.trunk_route: fp16 hi / lo pairs on the direct
+                                    kernel, or F(4x4,3x3) on fp32 MFMA) -> x0 @1/8, x1 @1/16, x2 @1/32
     correlation x3                  query features correlated with the reference feature maps used as filters
-                                    (F.conv2d(que_x, ref_x, padding=7/3/1), detector.py:222-224): the 15x15 level as 5x5 blocks of 3x3
-                                    and the 7x7 level as 3x3 blocks (filters zero-extended to 9x9) in the F(4x4,3x3) domain
-                                    (g6d_corr2d_wino43_multi), the 3x3 level on g6d_corr2d_patch_multi
+                                    (F.conv2d(que_x, ref_x, padding=7/3/1), detector.py:222-224), on the kernel Detector.corr_routes names:
+                                    at 32 references the 15x15 and 7x7 levels on g6d_corr16_multi (the trunk hands them over in its
+                                    pair format), otherwise as blocks of 3x3 in the F(4x4,3x3) domain (g6d_corr2d_wino43_multi; the 7x7
+                                    filters zero-extended to 9x9); the 3x3 level on g6d_corr2d_patch_multi
     g6d_detector_assemble           nearest up-sampling, (x-mu)/sigma, clip, bilinear resize to (h/8,w/8), stack
 then g6d_detector_score_mlp_max     score_conv MLP + max over references, never materialising [64,rfn,hs,ws]
      g6d_conv_igemm x7              the three 3x3 heads (first layers merged into one 64->192 conv)
@@ -17,24 +19,11 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops, parallel, specs
-from .backbone import (is_16bit, pack_trunk, trunk_features, trunk_features_multi, winograd_corr_filters, winograd43_corr_filters,
+from .backbone import (is_16bit, pack_trunk, trunk_features, trunk_features_multi, trunk_route, winograd43_corr_filters,
                        winograd43_corr_filters_padded)
 from .params import ParamBank, fold_vgg
 
-# Launch-structure switches; the product runs with all of them True, tools / tests flip the attribute for A/B runs:
-TRUNK_MULTI = True       # one launch per trunk layer over all pyramid scales (False: one trunk pass per scale)
-CORR3_MULTI = True       # the 3x3 correlation level as one corr_patch launch over all scales (False: one generic conv launch per scale)
-CORR_WINO = True         # the 15x15 correlation level in the Winograd domain, 5x5 blocks of 3x3, when rfn % 32 == 0 and fp32 (False: corr_patch)
-# Winograd F(4x4,3x3) (csrc/wino43_conv.hip) for the query pyramid's trunk and the 15x15 correlation level: 1.78x fewer fp32
-# multiplications than F(2x2,3x3) at ~5x its rounding error — the detector holds ~4e-6 of the score range against the 1e-4 bar
-# (tests/test_parity_timed_gpu.py).  False: the F(2x2,3x3) kernels of round 3 (tools/ A/B runs and tests flip this attribute).
-F43 = True
-CORR16 = True            # round 6: the 15x15 correlation level on the halo-patch kernel of the 16-bit matrix cores (g6d_corr16_multi) whenever the
-                         # trunk hands its input over as 16-bit activations (reduced precision) or fp16 hi / lo pairs (fp32 path: fp32-class
-                         # results); False (tools / tests): the F(4x4,3x3) / corr16_patch kernels of rounds 4-5
-CORR16_7 = True          # ... and the 7x7 level (its input c7_pre in the same format)
-CORR7_F43 = True         # the 7x7 level as 3x3 blocks of 3x3 on zero-extended 9x9 filters in the F(4x4,3x3) domain (20.25 instead of 49
-                         # multiplications per output) when rfn % 32 == 0 and fp32; False: corr_patch
+_TAPS = ("c5", "c7_pre", "p7")   # the trunk taps of the three correlation levels (15x15, 7x7, 3x3 filters at 120 x 120 references)
 MAX_BATCH = 16       # most queries that share one set of launches; _detect_impl_fp cuts the chunk further for larger images (the pyramid's
                      # first layers address all scales of the batch with 32-bit offsets from one base, < 2^29 floats: 16 images of
                      # 480x640 at 64 channels; 32 would not fit)
@@ -55,9 +44,9 @@ class Detector(ParamBank):
             raise NotImplementedError("score_conv expects 3 levels x 4 detection scales (12 channels)")
         self.pool_ratio = 8
         self.ref_center_feats = None     # three [rfn, k*k, 512] correlation filters
-        self.ref_wino15 = None           # the 15x15 level's filters in the Winograd domain (winograd_corr_filters), F(2x2,3x3)
-        self.ref_wino15_43 = None        # ... for the F(4x4,3x3) kernel (winograd43_corr_filters); one of the two is built
+        self.ref_wino15_43 = None        # the 15x15 level's filters for the F(4x4,3x3) kernel (winograd43_corr_filters), rfn % 32 == 0
         self.ref_wino7_43 = None         # the 7x7 level's filters, zero-extended to 9x9, for the F(4x4,3x3) kernel
+        self._corr16 = {}                # (level, mode) -> the level's filters for g6d_corr16_multi, built on first use
         self.ref_shape = None
         self.rank, self.world, self.group = 0, 1, None
         self.sharded = False
@@ -97,7 +86,7 @@ class Detector(ParamBank):
     # ------------------------------------------------------------------ trunk
     def extract_feats(self, imgs):
         """imgs [n,3,h,w] in [0,1] -> channels-last x0,x1,x2: [n,1,h/8,w/8,512], [.. /16 ..], [.. /32 ..]."""
-        return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), False, rng=self._pair_rng(), split16=self.pairs_on)
+        return trunk_features(self._pack()["vgg"], imgs, _TAPS, False)
 
     def load_impl(self, ref_imgs):
         """ref_imgs [rfn,3,h,w] in [0,1]; nearest resize to 120x120, trunk, keep as correlation filters
@@ -109,41 +98,60 @@ class Detector(ParamBank):
         feats = self.extract_feats(ref_imgs)                       # [rfn_local,1,k,k,512]
         self.ref_center_feats = [f.reshape(f.shape[0], f.shape[2] * f.shape[3], 512).contiguous() for f in feats]
         self.ref_ksize = [f.shape[2] for f in feats]               # 15, 7, 3
-        self._corr16 = {}                                          # (packed filters of g6d_corr16_multi, built on first use)
+        self._corr16 = {}
         self.ref_shape = [120, 120]
-        # Winograd-domain filters of the 15x15 level (the reference views used as filters: transformed once per object)
-        rfn = self.ref_center_feats[0].shape[0]
-        ok15 = CORR_WINO and self.ref_ksize[0] == 15 and rfn % 32 == 0
-        self.ref_wino15 = winograd_corr_filters(self.ref_center_feats[0], 15) if (ok15 and not F43) else None
-        self.ref_wino15_43 = winograd43_corr_filters(self.ref_center_feats[0], 15) if (ok15 and F43) else None
-        ok7 = CORR_WINO and F43 and CORR7_F43 and self.ref_ksize[1] == 7 and rfn % 32 == 0
-        self.ref_wino7_43 = winograd43_corr_filters_padded(self.ref_center_feats[1], 7)[0] if ok7 else None
+        # F(4x4,3x3)-domain filters of the 15x15 and 7x7 levels for the "wino43" route (the reference views used as filters: transformed
+        # once per object; whether a call takes the route depends on its math mode and pair setting, so they exist whenever it can)
+        wino43 = self.ref_center_feats[0].shape[0] % 32 == 0
+        self.ref_wino15_43 = winograd43_corr_filters(self.ref_center_feats[0], 15) if wino43 else None
+        self.ref_wino7_43 = winograd43_corr_filters_padded(self.ref_center_feats[1], 7)[0] if wino43 else None
 
     def _corr16_filters(self, level, mode):
         """The reference-centre features of a level packed for g6d_corr16_multi (ops.corr16_pack), built on first use per (level, mode)."""
-        cache = self.__dict__.setdefault("_corr16", {})
-        key = (level, mode, self.ref_center_feats[level].data_ptr())
-        if key not in cache:
-            cache[key] = ops.corr16_pack(self.ref_center_feats[level], mode)
-        return cache[key]
+        if (level, mode) not in self._corr16:
+            self._corr16[level, mode] = ops.corr16_pack(self.ref_center_feats[level], mode)
+        return self._corr16[level, mode]
+
+    def corr_routes(self, hq, wq):
+        """The kernel that correlates each level (15x15, 7x7, 3x3 filters) with the references for [qn,3,hq,wq] queries in the current math
+        mode and pair setting:
+          "corr16"  g6d_corr16_multi: the pyramid trunk runs on the direct kernel and hands the level over in its 16-bit / pair format
+                    (32 references)
+          "wino43"  blocks of 3x3 in the F(4x4,3x3) domain (fp32, rfn % 32 == 0: 20.25 instead of 49 multiplications per output at 7x7)
+          "patch"   g6d_corr2d_patch_multi, one launch over all scales (rfn <= 32)
+          "conv"    the generic conv, one launch per scale."""
+        sizes = [self._scale_size(hq, wq, sc) for sc in self.cfg["detection_scales"]]
+        trunk16 = trunk_route(self._pack()["vgg"], sizes, _TAPS, f43=True, pairs=self.pairs_on) == "direct"
+        rfn = self.ref_center_feats[0].shape[0]
+        routes = []
+        for k in self.ref_ksize:
+            if k in (15, 7) and trunk16 and rfn == 32:
+                routes.append("corr16")
+            elif k in (15, 7) and rfn % 32 == 0 and not ops.MATH_MODE:
+                routes.append("wino43")
+            else:
+                routes.append("patch" if rfn <= 32 else "conv")
+        return routes
 
     # ------------------------------------------------------------------ detection
     def _scores_one_scale(self, que_img, scale_idx, stacked, hs, ws):
         self._scores_from_feats(self.extract_feats(que_img), scale_idx, stacked, hs, ws)
 
-    def _scores_from_pyramid(self, feats, scale_ids, stacked, hs, ws):
-        """All scales (and all queries of the batch) at once: every correlation level is ONE launch over the maps of all scales
-        (the tiles of all maps form one work list: fewer splits, the small maps fill the chip the large one leaves over); the
-        assembly is one launch per scale.  feats[i][l]: [qn,1,h,w,512]."""
+    def _scores_from_pyramid(self, feats, routes, scale_ids, stacked, hs, ws):
+        """All scales (and all queries of the batch) at once: every correlation level is ONE launch over the maps of all scales on
+        the kernel routes[l] names (corr_routes; the tiles of all maps form one work list: fewer splits, the small maps fill the chip the
+        large one leaves over); the assembly is one launch per scale.  feats[i][l]: [qn,1,h,w,512], or the trunk's 16-bit / pair format
+        on the "corr16" route."""
         rfn = self.ref_center_feats[0].shape[0]
         dev = stacked.device
         qn = feats[0][0].shape[0]
         maps = [[None] * 3 for _ in feats]
-        for l, (wref, k) in enumerate(zip(self.ref_center_feats, self.ref_ksize)):
+        for l, (wref, k, route) in enumerate(zip(self.ref_center_feats, self.ref_ksize, routes)):
             xs = [f[l] for f in feats]
-            if is_16bit(xs[0]):
-                # the trunk handed this level over as 16-bit activations (reduced precision) or fp16 hi / lo pairs (fp32 path): the halo-patch
-                # correlation kernel on the 16-bit matrix cores (csrc/conv16_direct.hip, corr16_kernel)
+            assert is_16bit(xs[0]) == (route == "corr16"), "the trunk did not hand the level over in the format of its route"
+            if route == "corr16":
+                # 16-bit activations (reduced precision) or fp16 hi / lo pairs (fp32 path): the halo-patch correlation kernel on the 16-bit
+                # matrix cores (csrc/conv16_direct.hip, corr16_kernel)
                 mode = 3 if len(xs[0].shape) == 5 else (1 if xs[0].dtype == torch.bfloat16 else 2)
                 filt = self._corr16_filters(l, mode)
                 outs = [torch.empty((qn, 1, x.shape[1], x.shape[2], rfn), dtype=torch.float32, device=dev) for x in xs]
@@ -160,25 +168,18 @@ class Detector(ParamBank):
                 for d_, x in zip(seg, xs):
                     d_.copy_(x)
                 xs = seg
-            if k == 15 and self.ref_wino15_43 is not None and ops.MATH_MODE == 0 and len(xs) <= 4:
-                outs = ops.alloc_like_segments([(qn, 1, x.shape[2], x.shape[3], rfn) for x in xs], dev)
-                ops.corr2d_wino43_multi([x.contiguous() for x in xs], self.ref_wino15_43, outs, 5)
-            elif k == 7 and self.ref_wino7_43 is not None and ops.MATH_MODE == 0 and len(xs) <= 4:
-                outs = ops.alloc_like_segments([(qn, 1, x.shape[2], x.shape[3], rfn) for x in xs], dev)
-                ops.corr2d_wino43_multi([x.contiguous() for x in xs], self.ref_wino7_43, outs, 3, k_true=7)
-            elif k == 15 and self.ref_wino15 is not None and ops.MATH_MODE == 0 and len(xs) <= 4:
-                outs = ops.alloc_like_segments([(qn, 1, x.shape[2], x.shape[3], rfn) for x in xs], dev)
-                ops.corr2d_wino_multi([x.contiguous() for x in xs], self.ref_wino15, outs, 5)
-            elif rfn <= 32 and len(xs) <= 4 and (k >= 7 or CORR3_MULTI):
-                outs = ops.alloc_like_segments([(qn, 1, x.shape[2], x.shape[3], rfn) for x in xs], dev)
-                ops.corr2d_patch_multi(xs, wref, outs, k)
-            else:
+            if route == "conv":
                 outs = [torch.empty((qn, 1, x.shape[2], x.shape[3], rfn), dtype=torch.float32, device=dev) for x in xs]
                 for x, o in zip(xs, outs):
-                    if k >= 7 and rfn <= 32 and qn == 1:
-                        ops.corr2d_patch(x, wref, o, k)
-                    else:
-                        ops.conv(x, wref, None, o, ksize=(1, k, k), pad=(0, k // 2, k // 2))
+                    ops.conv(x, wref, None, o, ksize=(1, k, k), pad=(0, k // 2, k // 2))
+            else:
+                outs = ops.alloc_like_segments([(qn, 1, x.shape[2], x.shape[3], rfn) for x in xs], dev)
+                if route == "patch":
+                    ops.corr2d_patch_multi(xs, wref, outs, k)
+                elif k == 15:
+                    ops.corr2d_wino43_multi([x.contiguous() for x in xs], self.ref_wino15_43, outs, 5)
+                else:
+                    ops.corr2d_wino43_multi([x.contiguous() for x in xs], self.ref_wino7_43, outs, 3, k_true=7)
             for i, o in enumerate(outs):
                 maps[i][l] = o.reshape(qn * o.shape[2] * o.shape[3], rfn)
         for f, si, m in zip(feats, scale_ids, maps):
@@ -226,18 +227,15 @@ class Detector(ParamBank):
 
         # the scales are independent until `stacked` is complete: largest first on the main stream
         order = sorted(enumerate(self.cfg["detection_scales"]), key=lambda t: -t[1])
-        if TRUNK_MULTI and multi and len(order) <= 4:
+        if multi:
             # every trunk layer is ONE launch over the whole pyramid (the small scales fill the blocks the large ones leave
             # over); the correlations of the scales then run side by side
             # the image pyramid in ONE launch (g6d_resize_bilinear_pyramid; the scale of the query's own size is the query itself)
             pyr = ops.resize_bilinear_pyramid(que_imgs, [self._scale_size(hq, wq, sc) for _, sc in order])
-            # (CORR16: the 15x15 level's input in the trunk kernel's 16-bit / pair format -> g6d_corr16_multi)
-            # (pairs_on False: the recompute of a call whose pair maps left the window, on the routes the module switches select when off)
-            t16 = ()
-            if CORR16 and self.pairs_on and self.ref_center_feats[0].shape[0] == 32:
-                t16 = (("c5",) if self.ref_ksize[0] == 15 else ()) + (("c7_pre",) if (CORR16_7 and self.ref_ksize[1] == 7) else ())
-            feats = trunk_features_multi(pk["vgg"], pyr, ("c5", "c7_pre", "p7"), f43=F43, taps16=t16, rng=self._pair_rng(), split16=self.pairs_on)
-            self._scores_from_pyramid(feats, [si for si, _ in order], stacked, hs, ws)
+            routes = self.corr_routes(hq, wq)
+            t16 = tuple(tap for tap, r in zip(_TAPS, routes) if r == "corr16")     # taps handed over in the trunk's 16-bit / pair format
+            feats = trunk_features_multi(pk["vgg"], pyr, _TAPS, f43=True, taps16=t16, rng=self._pair_rng(), pairs=self.pairs_on)
+            self._scores_from_pyramid(feats, routes, [si for si, _ in order], stacked, hs, ws)
         else:
             ops.fork_join([(lambda si=si, sc=sc: self._scores_one_scale(resized(sc), si, stacked, hs, ws)) for si, sc in order], dev)
         feats = ops.detector_score_mlp_max(stacked, *pk["mlp"])               # [qn*P,64], max over the local references

@@ -9,13 +9,20 @@ from .. import ops, specs
 
 class ConvW(tuple):
     """(weight [Cout,taps,Cin], bias) as the conv kernels take them, plus `.u`: the same filters transformed for the Winograd
-    kernel (None when the layer never qualifies), and `.u43`: the same for the F(4x4,3x3) kernel (G6dConv.weight_wino43; only for the
-    layers that ask for it).  Unpacks like the plain pair."""
+    kernel (None when the layer never qualifies), `.u43`: the same for the F(4x4,3x3) kernel (G6dConv.weight_wino43; only for the
+    layers that ask for it), and `.w16(mode)`: the filters of the direct 16-bit kernel.  Unpacks like the plain pair."""
 
     def __new__(cls, w, b, u=None, u43=None):
         t = super().__new__(cls, (w, b))
-        t.u, t.u43 = u, u43
+        t.u, t.u43, t._w16 = u, u43, {}
         return t
+
+    def w16(self, mode):
+        """The filters for the direct kernel on 16-bit activations (ops.conv16_pack, fragment-major) in `mode` (1 / 2 = rounded to bf16 /
+        fp16, 3 = fp16 hi / lo pairs), built on first use."""
+        if mode not in self._w16:
+            self._w16[mode] = ops.conv16_pack(self[0], mode, layout=1)
+        return self._w16[mode]
 
 
 class ParamBank(nn.Module):
@@ -39,15 +46,13 @@ class ParamBank(nn.Module):
             self._roles[key] = role
         self._packed = None
 
-    # any weight change invalidates the packed copies: the packed trunks / heads, the 16-bit filter caches of the selector's products and
-    # the refiner's feature net (keyed on data_ptr(), which load_state_dict keeps), and the pair maps' exponents and record
-    # (the range table is reset in place, not dropped: captured graphs hold pointers into it)
+    # any weight change invalidates the packed copies (the packed trunks / heads with their transformed and 16-bit filters) and the pair
+    # maps' exponents and record (the range table is reset in place, not dropped: captured graphs hold pointers into it)
     sharded = False                      # reference-sharded mode (Detector / ViewpointSelector.set_shard)
 
     def _reset_derived(self):
         self._packed = None
-        for k in ("_prod16", "_feat16", "_range_seen"):
-            self.__dict__.pop(k, None)
+        self.__dict__.pop("_range_seen", None)
         t = self.__dict__.get("_range")
         if t is not None:
             t.reset()
@@ -63,8 +68,9 @@ class ParamBank(nn.Module):
     # ---- range control of the fp32 path's fp16 hi / lo pair maps (ops.RangeTable, ops.pair_exponent) -------------------------------------
     @property
     def pairs_on(self):
-        """False while a call is recomputed on the fp32-core routes (instance-level: the module switches stay untouched)."""
-        return not self.__dict__.get("_pairs_off", False)
+        """Whether the fp32 path may store activations as fp16 hi / lo pairs (products on the 16-bit matrix cores): not with the cfg key
+        'fp32_cores' (read at call time, like 'math_mode') and not while a call is recomputed on the fp32-core routes."""
+        return not (self.cfg.get("fp32_cores") or self.__dict__.get("_pairs_off", False))
 
     @property
     def range_fallbacks(self):

@@ -18,21 +18,17 @@ from .backbone import pack_trunk, trunk_features
 from .operator import pose_apply_th
 from .params import ParamBank, fold_vgg
 
-# Winograd F(4x4,3x3) filters for the stride-1 3x3x3 layers of the volume net (csrc/wino43_conv.hip); VOLUME_F43_LAYERS: which of
-# conv0 (32^3), conv2 (16^3), conv4 (8^3) take it beside the two embed pairs (32^3)
-# Both pay from ~4 queries per launch on: one query's 7 crops / single volume leave most CUs without a block and the kernel's longer
+# Winograd F(4x4,3x3) (csrc/wino43_conv.hip) for the crops' VGG trunk (1.31-1.35x over F(2x2,3x3) at 56 crops, profiles/r04_w43_bench_v5.md;
+# on the fp32 path the trunk then runs on fp16 hi / lo pairs, backbone.trunk_route), the feature-net layers of FEATNET_F43_LAYERS and the
+# stride-1 3x3x3 layers of the volume net: the two embed pairs and VOLUME_F43_LAYERS of conv0 (32^3), conv2 (16^3), conv4 (8^3).
+# All of it pays from ~4 queries per launch on: one query's 7 crops / single volume leave most CUs without a block and the kernel's longer
 # per-block prologue / epilogue shows (measured per step at batch 1: crops' trunk 475 vs 320 us, volume layers 541 vs 418 us on
 # F(2x2,3x3); at batch 8: 1.06 vs 1.43 ms and 1.96 vs 3.06 ms the other way round)
-FEAT16 = False          # round 6 experiment: the 2-D feature net's convs on the direct split-precision kernel where a map fills whole 128-pixel
-                        # tiles (32 x 32 and 16 x 16 maps).  Correct (refiner goldens hold) but no faster at 112 crops: 300.8 against 304.1
-                        # images/s — the two extra elementwise passes per pair and the small grids eat what the matrix cores save; off
 F43_MIN_QUERIES = 4
-TRUNK_F43 = True        # the crops' VGG trunk on the F(4x4,3x3) kernel (1.31-1.35x over F(2x2,3x3) at 56 crops, profiles/r04_w43_bench_v5.md)
 # feature-net layers (name, index in the Sequential) that carry F(4x4,3x3) filters — measured per layer at 56 crops against F(2x2,3x3)
 # (profiles/r04_layer_table_featnet_f43.md): 512->256 @16x16 159 vs 173 us, 192->128 @32x32 119 vs 148, 128->128 @32x32 107 vs 129 kept;
 # 256->64 @32x32 131 vs 94, 256->64 @16x16 88 vs 60, 512->256 @8x8 108 vs 80 stay on F(2x2,3x3)
 FEATNET_F43_LAYERS = {("conv1", 0), ("conv_out", 0), ("conv_out", 3)}
-VOLUME_F43 = True
 VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
@@ -140,13 +136,13 @@ class VolumeRefiner(ParamBank):
             pk = {"vgg": pack_trunk(fold_vgg(self, "feature_net.backbone.features"))}
             for name in ("conv0", "conv1", "conv2", "conv_out"):
                 pk[name] = [self.conv_w(f"feature_net.{name}.{i}", wino_kd=1, f43=(name, i) in FEATNET_F43_LAYERS) for i in (0, 3)]
-            # the 32^3 volume layers (mean_embed, var_embed, conv0) also carry F(4x4,3x3) filters (VOLUME_F43): 1.4-1.5x faster there
+            # the 32^3 volume layers (mean_embed, var_embed, conv0) also carry F(4x4,3x3) filters: 1.4-1.5x faster there
             # at 1.3-3.4e-6 of the layer's range (profiles/r04_w43_bench_v5.md)
             for name in ("mean_embed", "var_embed", "conv5"):         # conv5 works on 8^3 -> 4^3 maps: never on the Winograd kernel
-                pk["v_" + name] = [self.conv_w(f"volume_net.{name}.{i}", wino_kd=0 if name == "conv5" else 3, f43=VOLUME_F43) for i in (0, 3)]
+                pk["v_" + name] = [self.conv_w(f"volume_net.{name}.{i}", wino_kd=0 if name == "conv5" else 3, f43=True) for i in (0, 3)]
             for name in ("conv0", "conv1", "conv2", "conv3", "conv4"):
                 pk["v_" + name] = self.conv_w(f"volume_net.{name}.0", wino_kd=3 if name in ("conv0", "conv2", "conv4") else 0,
-                                              f43=VOLUME_F43 and name in VOLUME_F43_LAYERS)
+                                              f43=name in VOLUME_F43_LAYERS)
             # fc.0.0 consumes x.flatten(1) of [512,4,4,4] (index c*64+v); our code is [v][c] -> permute once
             w = self.p("regressor.fc.0.0.weight")
             pk["fc0"] = (w.reshape(512, 512, 64).permute(0, 2, 1).reshape(512, 32768).contiguous(),
@@ -158,13 +154,6 @@ class VolumeRefiner(ParamBank):
             self._packed = pk
         return self._packed
 
-    def _feat16_filters(self, name, idx, w):
-        cache = self.__dict__.setdefault("_feat16", {})
-        key = (name, idx, w.data_ptr())
-        if key not in cache:
-            cache[key] = ops.conv16_pack(w, 3, layout=1)
-        return cache[key]
-
     # ------------------------------------------------------------------ 2-D feature net
     def run_feature_net(self, imgs, f43=None):
         """imgs [n,3,h,w] in [0,1] -> channels-last features [n,h/4,w/4,128] (reference refiner.py:64-78).
@@ -175,9 +164,8 @@ class VolumeRefiner(ParamBank):
         dev = imgs.device
         big = (n >= F43_MIN_QUERIES * 7) if f43 is None else bool(f43)
         with self._mm("trunk"):
-            r = self._pair_rng()
-            rk = ({"rng": r} if r is not None else {}) | ({} if self.pairs_on else {"split16": False})
-            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), True, f43=TRUNK_F43 and big, **rk)   # channels-last, L2-normalised
+            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), True, f43=big, rng=self._pair_rng(),
+                                        pairs=self.pairs_on)            # channels-last, L2-normalised
 
         def pair(name, x):
             """conv, IN, ReLU, conv, (IN returned as affine) — per-image statistics."""
@@ -189,20 +177,6 @@ class VolumeRefiner(ParamBank):
             s0 = ops.new_stats(n, w0.shape[0], dev)
             y1 = torch.empty((n, 1, hh, ww, w1.shape[0]), dtype=torch.float32, device=dev)
             s1 = ops.new_stats(n, w1.shape[0], dev)
-            if FEAT16 and ops.MATH_MODE == 0 and self.pairs_on and (hh * ww) % 128 == 0 and all(w_.shape[2] % 32 == 0 and w_.shape[0] % 64 == 0 for w_ in (w0, w1)):
-                # round 6: both convs on the direct split-precision kernel (fp16 hi / lo pairs, fp32-class results, csrc/conv16_direct.hip): the
-                # input / the first norm's affine + ReLU are written in the kernel's format by one elementwise pass each, the per-image
-                # InstanceNorm sums come out of the convs' epilogues
-                f0, f1 = self._feat16_filters(name, 0, w0), self._feat16_filters(name, 1, w1)
-                r = self._pair_rng()
-                rk = (lambda i: {"rng": (r, r.slot(f"{name}.{i}"))}) if r is not None else (lambda i: {})
-                ops.conv16_direct_multi([ops.affine_split16(x, None, None, 0, False, False, 3, **rk(0))], f0, b0, relu=False, full=torch.float32,
-                                        pool=None, stats=s0, rows_per_group=hh * ww, out_full=[y0[:, 0]])
-                sc0, sh0 = ops.stats_finalize(s0, hh * ww)
-                ops.conv16_direct_multi([ops.affine_split16(y0, sc0, sh0, 1, True, False, 3, **rk(1))], f1, b1, relu=False, full=torch.float32, pool=None,
-                                        stats=s1, rows_per_group=hh * ww, out_full=[y1[:, 0]])
-                sc1, sh1 = ops.stats_finalize(s1, hh * ww)
-                return y1, sc1, sh1
             sc0, sh0 = ops.conv(x, w0, b0, y0, ksize=_K2, pad=_P2, stats=s0, rows_per_group=hh * ww, w_wino=u0, w_wino43=v0, finalize=hh * ww)
             sc1, sh1 = ops.conv(y0, w1, b1, y1, ksize=_K2, pad=_P2, in_scale=sc0, in_shift=sh0, in_relu=True, per_n=True,
                                 stats=s1, rows_per_group=hh * ww, w_wino=u1, w_wino43=v1, finalize=hh * ww)

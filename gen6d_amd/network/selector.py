@@ -36,11 +36,6 @@ _CORR = (
     ((1, 1, 1, 0), (4, 0, 0, 0)),
 )
 _K133, _P011 = (1, 3, 3), (0, 1, 1)
-PRODUCT16 = True       # round 6: the first conv of every level (query x reference product) on the direct 16-bit convolution — the product written
-                       # once as fp16 hi / lo pairs (fp32 path) or 16-bit activations; False (tools / tests): the product prologue of the Winograd /
-                       # implicit-GEMM kernels
-STACK16 = True         # ... and the levels' other 3x3 convs (InstanceNorm stacks): the previous norm's affine + ReLU as an elementwise pass into the
-                       # kernel's format (g6d_affine_split16); False: the operand prologues of the Winograd / implicit-GEMM kernels
 MAX_BATCH = 32         # queries that share one set of launches (BASELINE configs[4]: 32 concurrent queries; g6d_selector_levels runs them
                        # in groups of 8 query rows per pass over the reference cache)
 FEAT_LD = 516          # 512 corr channels + 3 vps channels + 1 zero pad (16-byte rows)
@@ -146,12 +141,7 @@ class ViewpointSelector(ParamBank):
     def get_feats(self, imgs):
         """imgs [n,3,h,w] in [0,1] -> 3 channels-last, L2-normalised maps [n,1,h_l,w_l,512] (selector.py:113-119)."""
         with self._mm("trunk"):
-            return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), True, **self._trunk_range())
-
-    def _trunk_range(self):
-        """Range arguments of the trunk (only when they are not the defaults: the trunk also runs with SPLIT16_ALWAYS)."""
-        r = self._pair_rng()
-        return ({"rng": r} if r is not None else {}) | ({} if self.pairs_on else {"split16": False})
+            return trunk_features(self._pack()["vgg"], imgs, ("c5", "c7_pre", "p7"), True)
 
     def extract_ref_feats(self, ref_imgs, ref_poses, object_center, object_vert, is_train=False):
         """ref_imgs [an,rfn,3,h,w]; builds the reference cache, its R1/R2 sums and the viewpoint embedding
@@ -223,7 +213,7 @@ class ViewpointSelector(ParamBank):
                     # round 6: the stack layers too — the InstanceNorm affine + ReLU of the previous layer is applied by one elementwise pass that
                     # writes the map in the direct kernel's format (g6d_affine_split16), the conv adds this layer's sums in its epilogue
                     x16 = ops.affine_split16(x, scale, shift, grp if scale is not None else 0, relu, False, mode16, **self._rng_kw(mode16, f"stack{l}.{li}"))
-                    filt = self._product16_filters(l, li, wgt, mode16)
+                    filt = pk["corr"][l][li].w16(mode16)
                     ci = wgt.shape[2]
                     per = max(1, ((1 << 31) - 1) // (D * h * w * ci * (4 if mode16 == 3 else 2)))
                     for q0 in range(0, qn, per):
@@ -238,7 +228,7 @@ class ViewpointSelector(ParamBank):
                     # adds this level's InstanceNorm sums in its epilogue, the affine of that norm comes from one small finalize launch
                     prod = ops.product_split16(cache.view(D, h * w, 512), q.view(qn, h * w, 512), scale, shift, mode16, **self._rng_kw(mode16, f"prod{l}"))
                     prod = prod.view(qn * D, h, w, 2, 512) if mode16 == 3 else prod.view(qn * D, h, w, 512)
-                    filt = self._product16_filters(l, li, wgt, mode16)
+                    filt = pk["corr"][l][li].w16(mode16)
                     # (a launch addresses its input with 32-bit offsets: 2^31 bytes = 8 queries of the 16 x 16 level in pairs)
                     per = max(1, ((1 << 31) - 1) // (D * h * w * 512 * (4 if mode16 == 3 else 2)))
                     for q0 in range(0, qn, per):
@@ -267,21 +257,23 @@ class ViewpointSelector(ParamBank):
                 x, relu = out, bool(has_relu)
 
     def _product16_mode(self, first, rows_per_query, co):
-        """conv16 math mode of a level's first (product) layer, or 0 = the Winograd / implicit-GEMM kernels with the product prologue: the
-        fp32 path takes fp16 hi / lo pairs (3); the reduced-precision modes their own 16-bit type.
+        """conv16 math mode of a level's first (product) layer — the product written once in the direct 16-bit kernel's format — or 0 = the
+        Winograd / implicit-GEMM kernels with the product prologue: the fp32 path takes fp16 hi / lo pairs (3) while its pairs are on
+        (ParamBank.pairs_on); the reduced-precision modes their own 16-bit type.
         A query's hypothesis images must fill whole 128-pixel tiles (its InstanceNorm sums are taken per tile): true for 64 x 5 views."""
-        if not (PRODUCT16 and first and rows_per_query % 128 == 0):
+        if not (first and rows_per_query % 128 == 0):
             return 0
         mm = ops.MATH_MODE
         if mm == 0:
-            return 3 if self.pairs_on else 0         # (pairs off: the recompute of a call whose pair maps left the window)
+            return 3 if self.pairs_on else 0
         # (Cout = 64 — level 0 — stays on the 16-bit Winograd kernel there: on the direct kernel's 32-channel waves it is 1 % faster end to end, but
         # the product rounded once to 16 bits takes the fp16 schemes' logits past their quarter-margin bar: measured, fp16ref32 `ok` true -> false)
         return mm if co % 128 == 0 else 0
 
     def _stack16_mode(self, rows_per_query, co, ci):
-        """conv16 math mode of a stack layer (see _product16_mode), or 0."""
-        if not (STACK16 and rows_per_query % 128 == 0):
+        """conv16 math mode of a stack layer (see _product16_mode; the previous norm's affine + ReLU is one elementwise pass into the kernel's
+        format, g6d_affine_split16), or 0 = the operand prologues of the Winograd / implicit-GEMM kernels."""
+        if rows_per_query % 128:
             return 0
         mm = ops.MATH_MODE
         if mm == 0:
@@ -292,13 +284,6 @@ class ViewpointSelector(ParamBank):
         """rng argument of a pair producer (slot `name` of this network's range table), none for the 16-bit modes."""
         r = self._pair_rng() if mode16 == 3 else None
         return {"rng": (r, r.slot(name))} if r is not None else {}
-
-    def _product16_filters(self, l, li, wgt, mode):
-        cache = self.__dict__.setdefault("_prod16", {})
-        key = (l, li, mode, wgt.data_ptr())
-        if key not in cache:
-            cache[key] = ops.conv16_pack(wgt, mode, layout=1)
-        return cache[key]
 
     def _query_batch(self, que_imgs):
         """que_imgs [qn,3,128,128], qn <= MAX_BATCH (32) -> logits [qn,rfn], angles [qn,rfn]; one set of launches for the whole batch

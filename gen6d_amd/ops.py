@@ -248,11 +248,6 @@ def corr2d_patch(x, w, out, k):
     return out
 
 
-# reduced-precision mode: correlation on corr16_patch_kernel (False, set by tools / tests: corr_patch_kernel with 16-bit operands, one
-# hand-over per tap)
-CORR16 = True
-
-
 def corr_filters16(w, k, dtype):
     """Correlation filters [Cout, k*k, Cin] (tap = ky*k + kx, Cin % 32 == 0, Cout <= 32) -> the unit-major 16-bit layout of
     g6d_corr2d_patch16_multi: [(Cin/32) * k units][k taps kx][32 co][40] (32 channels + 8 zeros per row; rows co >= Cout zero),
@@ -289,7 +284,7 @@ def corr2d_patch_multi(xs, w, outs, k):
     # reduced-precision mode: the 16-bit kernel with all kw weight tiles of a unit staged at once (g6d_corr2d_patch16_multi); its
     # host-rounded, unit-major filters are built once per (filter tensor, type) and kept on the fp32 tensor
     w16 = None
-    if MATH_MODE and CORR16 and Cin % 32 == 0 and k <= 15:
+    if MATH_MODE and Cin % 32 == 0 and k <= 15:
         cache = w.__dict__.setdefault("_g6d_c16", {})
         if MATH_MODE not in cache:
             cache[MATH_MODE] = corr_filters16(w, k, {1: torch.bfloat16, 2: torch.float16}[MATH_MODE])

@@ -48,7 +48,7 @@ def vgg_taps(folded, x, taps):
     return {k: v for k, v in out.items() if k in taps or k == "c7_pre"}
 
 
-def trunk_features(folded, imgs, keys, l2norm, f43=False, rng=None, split16=True):
+def trunk_features(folded, imgs, keys, l2norm, f43=False, rng=None, pairs=True):
     t = vgg_taps(folded, img_norm(imgs), set(keys))
     outs = []
     for k in keys:
@@ -58,7 +58,7 @@ def trunk_features(folded, imgs, keys, l2norm, f43=False, rng=None, split16=True
     return outs
 
 
-def trunk_features_multi(folded, imgs_list, keys, f43=False, taps16=(), rng=None, split16=True):
+def trunk_features_multi(folded, imgs_list, keys, f43=False, taps16=(), rng=None, pairs=True):
     return [trunk_features(folded, im, keys, False) for im in imgs_list]
 
 

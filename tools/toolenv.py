@@ -12,7 +12,7 @@ if os.environ.get("G6D_LIB_PATH"):
 for item in filter(None, os.environ.get("KNOBS", "").split(",")):
     name, val = item.split("=")
     lib.set_knob(name.strip(), float(val))
-# PYSW="gen6d_amd.network.backbone.SPLIT16_TRUNK=0,...": module-level A/B switches of the package (tools only)
+# PYSW="gen6d_amd.ops.FUSED_FINALIZE=0,...": module-level launch-structure attributes of the package (tools only)
 for item in filter(None, os.environ.get("PYSW", "").split(",")):
     path, val = item.split("=")
     mod, attr = path.strip().rsplit(".", 1)
