@@ -560,7 +560,9 @@ __global__ __launch_bounds__(256, 2) void conv16r_kernel(const C16Params p) {
 //     barrier): blocks and waves drift apart freely, one block's epilogue runs beside its neighbours' MFMAs.
 //   MM = 1 / 2: bf16 / fp16, a wave owns 128 px x 64 ch.  MM = 3: fp16 hi / lo pairs (see conv16r_kernel), two planes per patch, three
 //   MFMAs per product; a wave owns 128 px x 32 ch (64 accumulator registers: with the two-plane fragment and filter sets a 64-channel
-//   wave needs > 256 registers = one block per CU, every prologue and epilogue exposed).  Two blocks per CU in every mode.
+//   wave needs > 256 registers = one block per CU, every prologue and epilogue exposed).  Two blocks per CU in every mode.  The pair
+//   path runs on v_mfma_f32_16x16x32_f16 (8 x 2 accumulators of 16 x 16): at two waves per SIMD the chip holds a higher clock on that
+//   shape than on 32x32x16 at equal cycles per FLOP (tools/ubench/mfma16_peak.hip) — its own fragment scheme and slot swizzle below.
 // timing experiments only (WRONG results), a compile-time switch (make FLAGS_conv16_direct=-DC16W_ABLATE=n): after the first slice, bit 0 = no
 // patch requests, bit 1 = no filter requests, bit 2 = no fragment reads
 #ifndef C16W_ABLATE
@@ -692,8 +694,16 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   const int nkp = (MM == 3 ? nchunk : nchunk >> 1) * 9;
   const char* wtile = p.w + (long)(chan0 >> 7) * nkp * 16384;
   unsigned bvo[KS * NP];
+  if constexpr (MM == 3) {
+    // 16x16x32 B fragment q = n2 NP + plane: lane l needs co = 32 j + 16 n2 + (l & 15), ci = 8 (l >> 4) + e — in the packed piece
+    // (ks = l >> 5, plane) the lane 32 ((l >> 4) & 1) + 16 n2 + (l & 15) of group j: four 256-byte runs of the 1 KB pieces
 #pragma unroll
-  for (int q = 0; q < KS * NP; ++q) bvo[q] = q * 4096 + ((chan0 >> 5) & 3) * 1024 + lane * 16;
+    for (int q = 0; q < KS * NP; ++q)
+      bvo[q] = ((lane >> 5) * NP + q % NP) * 4096 + ((chan0 >> 5) & 3) * 1024 + (32 * ((lane >> 4) & 1) + 16 * (q / NP) + (lane & 15)) * 16;
+  } else {
+#pragma unroll
+    for (int q = 0; q < KS * NP; ++q) bvo[q] = q * 4096 + ((chan0 >> 5) & 3) * 1024 + lane * 16;
+  }
   // The requests walk the packed filters in step order with a running pointer: + 16 KB per tap; at a slice boundary + 16 KB for pairs,
   // and for the 16-bit modes (two 32-channel slices per packed step) + 8 KB - 8 x 16 KB into an odd slice, + 8 KB out of it.  Past the
   // last step the pointer stays on the first one (a harmless reload: the request count per step stays uniform).
@@ -713,149 +723,274 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     else wp += (c & 1) ? 8192 : 8192 - 8 * 16384;
   };
 
-  // ---- fragment geometry of this wave's tile: m-tile mt = tile pixels 32 mt + (lane & 31) -> patch row of tap (0, 0)
-  const C16Geom gm = c16w_geom(p, min(tg * WM + wm, p.ptiles - 1));
-  const int fhalf = lane >> 5;
-  // slot swizzle of patch (row, column): ((column >> swa) + row * swd) & 3, and swd != 0 only with swa == 0 (c16_halo_tiling): with
-  // fe = column + row * swd (swa == 0) or column (swd == 0) the swizzle of tap (ky, kx) is ((fe + kx) >> swa) + ky * swd
-  int qb[4], fe[4];
+  if constexpr (MM == 3) {
+    // ---- pairs on v_mfma_f32_16x16x32_f16.  m-tile mt = tile pixels 16 mt + (lane & 15): the lane reads logical slot lane >> 4 (channels
+    // 8 (lane >> 4) .. + 7 of the slice) of the pixel's patch row in each plane, so one read per (m-tile, plane) covers the whole slice and
+    // feeds one MFMA per (16-channel n-tile, term).  The pair tilings have swd = 0 and swa <= 2 (c16_halo_tiling): the slot swizzle
+    // (column >> swa) & 3 of tap column kx is then the same for the eight m-tiles (their columns differ by multiples of 16) — xs[kx],
+    // the logical slot folded in — and a fragment address is qb[mt] + the tap's offset: one VALU per two reads (hi and lo plane).
+    const C16Geom gm = c16w_geom(p, min(tg * WM + wm, p.ptiles - 1));
+    int qb[8], xs[3];
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int r = 32 * mt + (lane & 31), py = r >> gm.tw_log2, px = r & ((1 << gm.tw_log2) - 1);
-    const int b = py / gm.segh, ly = py - b * gm.segh;
-    const int frow = b * gm.bandr + ly;
-    qb[mt] = (frow * gm.PW + px) * 64 + wm * TILE_B; fe[mt] = px + frow * gm.swd;
-  }
-  const int PW64 = gm.PW * 64, swa = gm.swa, swd = gm.swd;
-  auto tap_addr = [&](int ky, int kx, int stage, int (&tb)[4]) {
-    const int so = stage * STAGE + (ky * PW64 + kx * 64);
+    for (int mt = 0; mt < 8; ++mt) {
+      const int r = 16 * mt + (lane & 15), py = r >> gm.tw_log2, px = r & ((1 << gm.tw_log2) - 1);
+      const int b = py / gm.segh, ly = py - b * gm.segh;
+      qb[mt] = ((b * gm.bandr + ly) * gm.PW + px) * 64 + wm * TILE_B;
+    }
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) xs[kx] = ((lane >> 4) ^ ((((lane & 15 & ((1 << gm.tw_log2) - 1)) + kx) >> gm.swa) & 3)) << 4;
+    const int PW64 = gm.PW * 64;
+    auto tap_off = [&](int t, int stg) { return xs[t % 3] + (stg * STAGE + (t / 3) * PW64 + (t % 3) * 64); };
+    auto read_pair = [&](int mp, int off, V8 (&a)[2][NP]) {      // the fragments of m-tiles 2 mp, 2 mp + 1
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int addr = qb[2 * mp + i] + off;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) a[i][pl] = *reinterpret_cast<const V8*>(lds + pl * R::PLANE + addr);
+      }
+    };
+    f32x4 acc[8][2];
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
+    // the 12 MFMAs of an m-tile pair: b[n2 NP + plane], terms hi x hi, hi x lo, lo x hi; four independent accumulators between two
+    // dependent MFMAs
+    auto mfmas = [&](int mp, const V8 (&a)[2][NP], const V8 (&b)[NBL]) {
+#pragma unroll
+      for (int term = 0; term < 3; ++term) {
+        const int pa = term == 2 ? 1 : 0, pb = term == 1 ? 1 : 0;
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            acc[2 * mp + i][n2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][pa], b[n2 * NP + pb], acc[2 * mp + i][n2], 0, 0, 0);
+      }
+    };
+
+    // ---- K loop as in the 16-bit modes below (filter ring, counted waits, one barrier per slice).  A ROLLING set of three m-tile pairs'
+    // fragments: pair g = 4 tap + (pair of the tap) sits in fa[g % 3]; right after its MFMAs have issued, the same registers receive
+    // pair g + 3 — consumed 24 MFMAs later.  The first three pairs of a slice are read after its barrier.
+    V8 bs[3][NBL];
+    V8 fa[3][2][NP];
+    issue_patch(0, 0);
+    load_b(0, 0, bs[0]);
+    load_b(0, 1, bs[1]);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (lgkmcnt: the zeroed halo pieces)
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mp = 0; mp < 3; ++mp) read_pair(mp, tap_off(0, 0), fa[mp]);
+    int stage = 0;
+#pragma unroll 1
+    for (int c = 0; c < ((C16W_ABLATE & 8) ? 0 : nchunk); ++c) {      // (ablation bit 3: no K loop at all — what a block costs outside it)
+      // (opaque to the optimiser: it would otherwise hoist the per-(tap, m-tile) addresses out of the slice loop and spill them)
+#pragma unroll
+      for (int mt = 0; mt < 8; ++mt) asm volatile("" : "+v"(qb[mt]));
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) asm volatile("" : "+v"(xs[kx]));
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int t2 = (t + 2) % 9, c2 = c + (t + 2) / 9;
+        if (!((C16W_ABLATE & 2) && c > 0)) load_b(c2, t2, bs[(t + 2) % 3]);
+        if (t == 0 && !SINGLE && !((C16W_ABLATE & 1) && c > 0)) issue_patch(c + 1, stage ^ 1);
+        if (C16W_ABLATE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBL) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        const int off = tap_off(t, stage), noff = tap_off(t < 8 ? t + 1 : 0, stage);
+#pragma unroll
+        for (int mp = 0; mp < 4; ++mp) {
+          const int g = 4 * t + mp, gn = g + 3;                       // (36 pairs per slice)
+          mfmas(mp, fa[g % 3], bs[t % 3]);
+          if (gn < 36 && !((C16W_ABLATE & 4) && c > 0)) read_pair(gn % 4, gn / 4 == t ? off : noff, fa[g % 3]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t == 8) {
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (vmcnt: this wave's pieces of the next patch, see below)
+          __builtin_amdgcn_s_barrier();                          // every wave has read this patch and received its share of the next
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (SINGLE) {
+            // one LDS stage (the two-tile form: two stages would be 147 KB = one block per CU): the next patch is requested only now,
+            // into the stage everybody has just left; the other block of the CU computes while it arrives
+            issue_patch(c + 1, 0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+          } else stage ^= 1;
+          if (c + 1 < nchunk) {
+#pragma unroll
+            for (int mp = 0; mp < 3; ++mp) read_pair(mp, tap_off(0, stage), fa[mp]);
+          }
+        }
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the look-ahead filter requests past the end have landed
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- epilogue, private to the wave (as in the 16-bit modes): the 16 x 16 accumulator holds pixel 4 (lane >> 4) + r of its m-tile and
+    // channel lane & 15 of its n-tile
+    if (tg * WM + wm >= p.ptiles) return;                         // (the odd tile of the last group)
+    const C16Seg& sg = p.seg[gm.si];
+    float* ep = reinterpret_cast<float*>(lds + wv * R::EPW);
+    float bv[2];
+#pragma unroll
+    for (int n2 = 0; n2 < 2; ++n2) bv[n2] = p.bias ? p.bias[chan0 + 16 * n2 + (lane & 15)] : 0.f;
+    constexpr int MTP = R::NPX / 16;                              // m-tiles per pass
+    const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
+    unsigned amax = 0;
+#pragma unroll
+    for (int ps = 0; ps < 8 / MTP; ++ps) {
+#pragma unroll
+      for (int m = 0; m < MTP; ++m)
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int px = 16 * m + 4 * (lane >> 4) + r;
+            float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
+            if (p.relu) v = fmaxf(v, 0.f);
+            ep[px * C16_EP_LD + 16 * n2 + (lane & 15)] = v;
+          }
+      c16_epilogue_pass<2, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
+    }
+    g6d_range_record(p.rng, amax);
+  } else {
+    // ---- fragment geometry of this wave's tile: m-tile mt = tile pixels 32 mt + (lane & 31) -> patch row of tap (0, 0)
+    const C16Geom gm = c16w_geom(p, min(tg * WM + wm, p.ptiles - 1));
+    const int fhalf = lane >> 5;
+    // slot swizzle of patch (row, column): ((column >> swa) + row * swd) & 3, and swd != 0 only with swa == 0 (c16_halo_tiling): with
+    // fe = column + row * swd (swa == 0) or column (swd == 0) the swizzle of tap (ky, kx) is ((fe + kx) >> swa) + ky * swd
+    int qb[4], fe[4];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-      const int sw = ((fe[mt] + kx) >> swa) + ky * swd;
-      tb[mt] = qb[mt] + so + (((fhalf ^ sw) & 3) << 4);
+      const int r = 32 * mt + (lane & 31), py = r >> gm.tw_log2, px = r & ((1 << gm.tw_log2) - 1);
+      const int b = py / gm.segh, ly = py - b * gm.segh;
+      const int frow = b * gm.bandr + ly;
+      qb[mt] = (frow * gm.PW + px) * 64 + wm * TILE_B; fe[mt] = px + frow * gm.swd;
     }
-  };
-  auto frag_read = [&](int addr, V8 (&a)[NP]) {
+    const int PW64 = gm.PW * 64, swa = gm.swa, swd = gm.swd;
+    auto tap_addr = [&](int ky, int kx, int stage, int (&tb)[4]) {
+      const int so = stage * STAGE + (ky * PW64 + kx * 64);
 #pragma unroll
-    for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const V8*>(lds + pl * R::PLANE + addr);
-  };
-  f32x16 acc[4][NT2];
+      for (int mt = 0; mt < 4; ++mt) {
+        const int sw = ((fe[mt] + kx) >> swa) + ky * swd;
+        tb[mt] = qb[mt] + so + (((fhalf ^ sw) & 3) << 4);
+      }
+    };
+    auto frag_read = [&](int addr, V8 (&a)[NP]) {
 #pragma unroll
-  for (int a = 0; a < 4; ++a)
+      for (int pl = 0; pl < NP; ++pl) a[pl] = *reinterpret_cast<const V8*>(lds + pl * R::PLANE + addr);
+    };
+    f32x16 acc[4][NT2];
 #pragma unroll
-    for (int b = 0; b < NT2; ++b)
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-  // the MFMAs of one m-tile and one 16-channel group: b[(ks * NP + plane) * NT2 + n2];  pairs: hi x hi, hi x lo, lo x hi
-  auto mfmas = [&](int mt, const V8 (&a)[NP], const V8 (&b)[NBL], int ks) {
+      for (int b = 0; b < NT2; ++b)
 #pragma unroll
-    for (int term = 0; term < (MM == 3 ? 3 : 1); ++term) {
-      const int pa = term == 2 ? 1 : 0, pb = term == 1 ? 1 : 0;
+        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    // the MFMAs of one m-tile and one 16-channel group: b[ks * NT2 + n2]
+    auto mfmas = [&](int mt, const V8 (&a)[NP], const V8 (&b)[NBL], int ks) {
 #pragma unroll
-      for (int n2 = 0; n2 < NT2; ++n2) acc[mt][n2] = c16_mfma<MM>(a[pa], b[(ks * NP + pb) * NT2 + n2], acc[mt][n2]);
-    }
-  };
+      for (int n2 = 0; n2 < NT2; ++n2) acc[mt][n2] = c16_mfma<MM>(a[0], b[ks * NT2 + n2], acc[mt][n2]);
+    };
 
-  // ---- K loop: slices outermost (one patch, one barrier each), the nine taps unrolled inside.  FILTER loads return in order among
-  // themselves, so before the MFMAs of step (c, t) vmcnt(2 NBL) — the two younger filter sets — proves B(c, t) has arrived.  LDS-DMA
-  // requests are NOT ordered against them (measured on corr16_kernel: a counted wait that budgeted the younger patch pieces let MFMAs
-  // start on filters still in flight once the filters missed L2 — the DMA of L2-resident activations overtakes them): the wait therefore
-  // never budgets for DMA pieces (while some are in flight it is merely stricter than needed), and the wave's own pieces of the next
-  // patch are drained with vmcnt(0) before the slice's barrier.
-  // ONE set of activation fragments, replaced m-tile by m-tile: right after the MFMAs of (m-tile, 16-channel group) have issued, the
-  // same registers receive the m-tile's fragment of the NEXT group (the other half of the slice, or the next tap) — consumed eight
-  // MFMAs later.
-  V8 bs[3][NBL];
-  V8 fa[4][NP];
-  int tb[4], ntb[4];
-  issue_patch(0, 0);
-  load_b(0, 0, bs[0]);
-  load_b(0, 1, bs[1]);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (lgkmcnt: the zeroed halo pieces)
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  tap_addr(0, 0, 0, tb);
+    // ---- K loop: slices outermost (one patch, one barrier each), the nine taps unrolled inside.  FILTER loads return in order among
+    // themselves, so before the MFMAs of step (c, t) vmcnt(2 NBL) — the two younger filter sets — proves B(c, t) has arrived.  LDS-DMA
+    // requests are NOT ordered against them (measured on corr16_kernel: a counted wait that budgeted the younger patch pieces let MFMAs
+    // start on filters still in flight once the filters missed L2 — the DMA of L2-resident activations overtakes them): the wait therefore
+    // never budgets for DMA pieces (while some are in flight it is merely stricter than needed), and the wave's own pieces of the next
+    // patch are drained with vmcnt(0) before the slice's barrier.
+    // ONE set of activation fragments, replaced m-tile by m-tile: right after the MFMAs of (m-tile, 16-channel group) have issued, the
+    // same registers receive the m-tile's fragment of the NEXT group (the other half of the slice, or the next tap) — consumed eight
+    // MFMAs later.
+    V8 bs[3][NBL];
+    V8 fa[4][NP];
+    int tb[4], ntb[4];
+    issue_patch(0, 0);
+    load_b(0, 0, bs[0]);
+    load_b(0, 1, bs[1]);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (lgkmcnt: the zeroed halo pieces)
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    tap_addr(0, 0, 0, tb);
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt) frag_read(tb[mt], fa[mt]);
-  int stage = 0;
+    for (int mt = 0; mt < 4; ++mt) frag_read(tb[mt], fa[mt]);
+    int stage = 0;
 #pragma unroll 1
-  for (int c = 0; c < ((C16W_ABLATE & 8) ? 0 : nchunk); ++c) {      // (ablation bit 3: no K loop at all — what a block costs outside it)
-    // (opaque to the optimiser: it would otherwise hoist the 36 per-(tap, m-tile) swizzle terms out of the slice loop and spill them)
+    for (int c = 0; c < ((C16W_ABLATE & 8) ? 0 : nchunk); ++c) {      // (ablation bit 3: no K loop at all — what a block costs outside it)
+      // (opaque to the optimiser: it would otherwise hoist the 36 per-(tap, m-tile) swizzle terms out of the slice loop and spill them)
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(fe[mt]), "+v"(qb[mt]));
+      for (int mt = 0; mt < 4; ++mt) asm volatile("" : "+v"(fe[mt]), "+v"(qb[mt]));
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int t2 = (t + 2) % 9, c2 = c + (t + 2) / 9;
-      if (!((C16W_ABLATE & 2) && c > 0)) load_b(c2, t2, bs[(t + 2) % 3]);
-      if (t == 0 && !SINGLE && !((C16W_ABLATE & 1) && c > 0)) issue_patch(c + 1, stage ^ 1);
-      if (C16W_ABLATE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBL) : "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (t < 8) tap_addr((t + 1) / 3, (t + 1) % 3, stage, ntb);
-      else tap_addr(0, 0, SINGLE ? 0 : stage ^ 1, ntb);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        mfmas(mt, fa[mt], bs[t % 3], 0);
-        if (!((C16W_ABLATE & 4) && c > 0)) frag_read(tb[mt] ^ 32, fa[mt]);
+      for (int t = 0; t < 9; ++t) {
+        const int t2 = (t + 2) % 9, c2 = c + (t + 2) / 9;
+        if (!((C16W_ABLATE & 2) && c > 0)) load_b(c2, t2, bs[(t + 2) % 3]);
+        if (t == 0 && !((C16W_ABLATE & 1) && c > 0)) issue_patch(c + 1, stage ^ 1);
+        if (C16W_ABLATE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBL) : "memory");
         __builtin_amdgcn_sched_barrier(0);
-      }
+        if (t < 8) tap_addr((t + 1) / 3, (t + 1) % 3, stage, ntb);
+        else tap_addr(0, 0, stage ^ 1, ntb);
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        mfmas(mt, fa[mt], bs[t % 3], 1);
-        if (t < 8 && !((C16W_ABLATE & 4) && c > 0)) frag_read(ntb[mt], fa[mt]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) tb[mt] = ntb[mt];
-      if (t == 8) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (vmcnt: this wave's pieces of the next patch, see above)
-        __builtin_amdgcn_s_barrier();                          // every wave has read this patch and received its share of the next
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (SINGLE) {
-          // one LDS stage (the pair kernel's two-tile form: two stages would be 147 KB = one block per CU): the next patch is requested
-          // only now, into the stage everybody has just left; the other block of the CU computes while it arrives
-          issue_patch(c + 1, 0);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
+        for (int mt = 0; mt < 4; ++mt) {
+          mfmas(mt, fa[mt], bs[t % 3], 0);
+          if (!((C16W_ABLATE & 4) && c > 0)) frag_read(tb[mt] ^ 32, fa[mt]);
           __builtin_amdgcn_sched_barrier(0);
-        } else stage ^= 1;
-        if (c + 1 < nchunk) {
+        }
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt) frag_read(tb[mt], fa[mt]);
+        for (int mt = 0; mt < 4; ++mt) {
+          mfmas(mt, fa[mt], bs[t % 3], 1);
+          if (t < 8 && !((C16W_ABLATE & 4) && c > 0)) frag_read(ntb[mt], fa[mt]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) tb[mt] = ntb[mt];
+        if (t == 8) {
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (vmcnt: this wave's pieces of the next patch, see above)
+          __builtin_amdgcn_s_barrier();                          // every wave has read this patch and received its share of the next
+          __builtin_amdgcn_sched_barrier(0);
+          stage ^= 1;
+          if (c + 1 < nchunk) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) frag_read(tb[mt], fa[mt]);
+          }
         }
       }
     }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the look-ahead filter requests past the end have landed
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the look-ahead filter requests past the end have landed
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
 
-  // ---- epilogue, private to the wave: its 128 px x 64 ch go through its own fp32 LDS tile in passes of NPX pixels
-  if (tg * WM + wm >= p.ptiles) return;                         // (the odd tile of the last group)
-  const C16Seg& sg = p.seg[gm.si];
-  float* ep = reinterpret_cast<float*>(lds + wv * R::EPW);
-  float bv[NT2];
+    // ---- epilogue, private to the wave: its 128 px x 64 ch go through its own fp32 LDS tile in passes of NPX pixels
+    if (tg * WM + wm >= p.ptiles) return;                         // (the odd tile of the last group)
+    const C16Seg& sg = p.seg[gm.si];
+    float* ep = reinterpret_cast<float*>(lds + wv * R::EPW);
+    float bv[NT2];
 #pragma unroll
-  for (int n2 = 0; n2 < NT2; ++n2) bv[n2] = p.bias ? p.bias[chan0 + 32 * n2 + (lane & 31)] : 0.f;
-  constexpr int MTP = R::NPX / 32;                              // m-tiles per pass
-  const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
-  unsigned amax = 0;
+    for (int n2 = 0; n2 < NT2; ++n2) bv[n2] = p.bias ? p.bias[chan0 + 32 * n2 + (lane & 31)] : 0.f;
+    constexpr int MTP = R::NPX / 32;                              // m-tiles per pass
+    const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
+    unsigned amax = 0;
 #pragma unroll
-  for (int ps = 0; ps < 4 / MTP; ++ps) {
+    for (int ps = 0; ps < 4 / MTP; ++ps) {
 #pragma unroll
-    for (int m = 0; m < MTP; ++m)
+      for (int m = 0; m < MTP; ++m)
 #pragma unroll
-      for (int n2 = 0; n2 < NT2; ++n2)
+        for (int n2 = 0; n2 < NT2; ++n2)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int px = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
-          if (p.relu) v = fmaxf(v, 0.f);
-          ep[px * C16_EP_LD + 32 * n2 + (lane & 31)] = v;
-        }
-    c16_epilogue_pass<MM == 3 ? 2 : MM, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
+          for (int r = 0; r < 16; ++r) {
+            const int px = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
+            if (p.relu) v = fmaxf(v, 0.f);
+            ep[px * C16_EP_LD + 32 * n2 + (lane & 31)] = v;
+          }
+      c16_epilogue_pass<MM, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
+    }
+    if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
   }
-  if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1222,8 +1357,8 @@ __global__ __launch_bounds__(64 * (CORR16_NW + 1), 1) void corr16_kernel(const C
 
 
 // Tiling of one segment for the halo-patch kernel: the tile width (32 / 16 / 8 / 4) with the least overhang; false if none fits
-// (a map lower than the tile must divide it: tiles of whole images)
-bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles) {
+// (a map lower than the tile must divide it: tiles of whole images).  pairs: the fp16 pair kernel's slot swizzle (its fragment reads differ)
+bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs) {
   double best = 1e30;
   bool found = false;
   for (int tw = 32; tw >= 4; tw >>= 1) {
@@ -1241,8 +1376,11 @@ bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles) {
       int l2 = 0; while ((1 << l2) < tw) ++l2;
       o.h_tw_log2 = l2; o.h_tiles_x = tx; o.h_tpi = tpi; o.h_segh = segh; o.h_bands = bands;
       tiles = (int)nt;
-      // conflict-free slot swizzles found by tools/ubench/conv16_swizzle.py: ((pcol >> a) + prow * d) & (slots - 1)
-      o.h_swa = tw == 32 ? 2 : (tw == 16 ? 1 : 0); o.h_swd = tw <= 8 ? 1 : 0;             // (64-byte patch rows: 4 slots)
+      // conflict-free slot swizzles found by tools/ubench/conv16_swizzle.py: ((pcol >> a) + prow * d) & (slots - 1)  (64-byte patch rows:
+      // 4 slots).  The pair kernel reads 16 pixels x 4 slots per 16 lanes (16x16x32 fragments), the 16-bit modes 32 pixels x 2 slots;
+      // the pair kernel relies on d = 0 and a <= 2
+      if (pairs) { o.h_swa = tw >= 16 ? 1 : 0; o.h_swd = 0; }
+      else { o.h_swa = tw == 32 ? 2 : (tw == 16 ? 1 : 0); o.h_swd = tw <= 8 ? 1 : 0; }
     }
   }
   return found;
@@ -1321,7 +1459,7 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
     int htiles = 0;
     for (int i = 0; i < nseg && ok; ++i) {
       int nt_ = 0;
-      ok = c16_halo_tiling(segs[i], p.seg[i], nt_);
+      ok = c16_halo_tiling(segs[i], p.seg[i], nt_, math_mode == 3);
       p.seg[i].h_tile0 = htiles; htiles += nt_;
       if (stats && stat_rows_per_group > 0 && ok) {
         const C16Seg& o = p.seg[i];

@@ -1,31 +1,61 @@
+"""LDS slot swizzle search for the halo-patch kernel (conv16w_kernel): patch rows of 64 B (4 slots of 16 B); physical slot s of patch
+(row, column) holds logical slot s ^ sw(row, column), sw = ((column >> a) + row * d) & 3.  For every tile width and banded layout of
+c16_halo_tiling, all nine tap shifts and every ds_read_b128 lane group (4 x 16 lanes, one LDS cycle each when the 16 lanes hit 16
+distinct 16-byte bank slots), prints the LDS cycles per lane group (1 = conflict-free) of the best (a, d) for the two read patterns:
+  16-bit modes (32x32x16 fragments): lane l reads tile pixel 32 mt + (l & 31), logical slot 2 ks + (l >> 5);
+  fp16 pairs (16x16x32 fragments):   lane l reads tile pixel 16 mt + (l & 15), logical slot l >> 4."""
 import itertools
-G1=[0,1,2,3,12,13,14,15,20,21,22,23,24,25,26,27]; G2=[4,5,6,7,8,9,10,11,16,17,18,19,28,29,30,31]
-def cost(TW, rowb, fn, mtiles=4):
-    PW=TW+2; nslot=rowb//16; rows_per_bankrow=256//rowb
-    worst=0; total=0; n=0
-    for mt in range(mtiles):
-      for ky in range(3):
-        for kx in range(3):
-          for ks in range(nslot//2):
-            for half in (0,1):
-              for G in (G1,G2):
-                pos={}
-                for l in G:
-                    r=32*mt+l; py,px=r//TW,r%TW
-                    prow,pcol=py+ky,px+kx
-                    q=prow*PW+pcol
-                    logical=2*ks+half
-                    phys=logical^fn(prow,pcol)
-                    bank=(q%rows_per_bankrow)*nslot+phys     # 16-byte slot within the 256-byte bank row
-                    pos[bank]=pos.get(bank,0)+1
-                m=max(pos.values()); worst=max(worst,m); total+=m; n+=1
-    return worst,total/n
-for rowb in (128,64):
-    nsl=rowb//16
-    for TW in (4,8,16,32):
-        best=None
-        for a,b,c,d in itertools.product(range(0,4),range(0,8),range(0,4),range(0,8)):
-            fn=lambda prow,pcol,a=a,b=b,c=c,d=d:(((pcol>>a)*1+ (prow>>c)*d + b*0)&(nsl-1)) if True else 0
-            w,avg=cost(TW,rowb,fn)
-            if best is None or (avg,w)<(best[0],best[1]): best=(avg,w,(a,c,d))
-        print("rowb",rowb,"TW",TW,"best avg cycles",best)
+
+GROUPS = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
+GROUPS += [[l + 32 for l in g] for g in GROUPS]
+
+
+def layouts():
+    """(tile width, rows per band) of every halo tiling: bands of segh + 2 patch rows, at most 288 patch rows of TW + 2."""
+    for tw in (4, 8, 16, 32):
+        th = 128 // tw
+        for segh in (1, 2, 4, 8, 16, 32):
+            if segh <= th and th % segh == 0 and (th // segh) * (segh + 2) * (tw + 2) <= 288:
+                yield tw, segh
+
+
+def reads(pattern):
+    """(m-tile, k-group, lane) -> (tile pixel, logical slot) of one fragment read."""
+    if pattern == "pairs":
+        return [[[(16 * mt + (l & 15), l >> 4) for l in range(64)]] for mt in range(8)]
+    return [[[(32 * mt + (l & 31), 2 * ks + (l >> 5)) for l in range(64)] for ks in range(2)] for mt in range(4)]
+
+
+def patch_rc(p, tw, segh, ky, kx):
+    py, px = p // tw, p % tw
+    b, ly = py // segh, py % segh
+    return b * (segh + 2) + ly + ky, px + kx
+
+
+def cycles(tw, segh, sw, pattern):
+    """(worst, mean) LDS cycles per lane group over m-tiles, k-groups, taps and groups."""
+    worst, tot, n = 0, 0, 0
+    for per_mt in reads(pattern):
+        for lanes in per_mt:
+            for ky, kx in itertools.product(range(3), range(3)):
+                for g in GROUPS:
+                    cnt = {}
+                    for l in g:
+                        p, s = lanes[l]
+                        r, col = patch_rc(p, tw, segh, ky, kx)
+                        k = (4 * (r * (tw + 2) + col) + (s ^ sw(r, col))) % 16
+                        cnt[k] = cnt.get(k, 0) + 1
+                    m = max(cnt.values())
+                    worst, tot, n = max(worst, m), tot + m, n + 1
+    return worst, tot / n
+
+
+if __name__ == "__main__":
+    for pattern in ("16-bit", "pairs"):
+        for tw, segh in layouts():
+            res = []
+            for a, d in itertools.product(range(4), range(4)):
+                w, avg = cycles(tw, segh, lambda r, c, a=a, d=d: ((c >> a) + r * d) & 3, pattern)
+                res.append((avg, w, d, a))
+            avg, w, d, a = min(res)
+            print(f"{pattern:7s} TW {tw:2d} rows per band {segh:2d}: best a = {a}, d = {d}: {avg:.2f} cycles per group (worst {w})")
