@@ -114,27 +114,35 @@ class DeviceChain:
         return {"pose": pose, "det": det5, "sel": sel, "logits": logits[0], "refine_poses": poses, "crop": crop}
 
     # ------------------------------------------------------------------ a batch of queries, no host synchronisation
-    def query_batch(self, que_imgs, que_Ks):
+    def query_batch(self, que_imgs, que_Ks, pose_init=None, refine_iter=None):
         """que_imgs uint8 [B,H,W,3], que_Ks float32 [B,3,3] on the device (B <= 8) -> dict of device tensors: 'pose' [B,3,4], 'det'
         [B,5], 'sel' [B,2], 'logits' [B,rfn], 'refine_poses' (list of [B,3,4]).  The B queries share every launch (round 3): the
         networks' batched paths, one launch of every chain kernel (blockIdx = query), one warp launch per stage for all crops —
-        the estimator-level counterpart of `TensorPipeline.query` with the data flow between the stages real."""
+        the estimator-level counterpart of `TensorPipeline.query` with the data flow between the stages real.
+        pose_init [B,3,4] (device; tracking, gen6d_amd/tracking.py): detection and selection are skipped ('det', 'sel', 'logits' and
+        'crop' are None) and `refine_iter` steps (default 1) run from it; B <= refiner.MAX_BATCH then."""
         est, size = self.est, self.size
         astep = est.refiner.angle_step() if est.refiner is not None else 0.0
         B = que_imgs.shape[0]
         with torch.no_grad():
             ar = torch.arange(B, dtype=torch.int32, device=self.dev)
             K9 = que_Ks.reshape(B, 9).contiguous()
-            x = que_imgs.permute(0, 3, 1, 2).float().div_(255)
-            det = est.detector.detect_impl(x.contiguous())
-            det5 = torch.cat([det["positions"], det["scales"][:, None], det["que_select_id"].float()], 1).contiguous()
-            crop = ops.warp_batch(que_imgs, None, ar, ops.chain_crop_from_detection(det5, size), size, size)
-            logits, angles = est.selector.compute_view_point_feats(crop)
-            pose, sel = ops.chain_pose_from_selection(det5, logits.contiguous(), angles.contiguous(), self.ref_poses, self.ref_Ks, K9,
-                                                      self.center)
+            if pose_init is None:
+                x = que_imgs.permute(0, 3, 1, 2).float().div_(255)
+                det = est.detector.detect_impl(x.contiguous())
+                det5 = torch.cat([det["positions"], det["scales"][:, None], det["que_select_id"].float()], 1).contiguous()
+                crop = ops.warp_batch(que_imgs, None, ar, ops.chain_crop_from_detection(det5, size), size, size)
+                logits, angles = est.selector.compute_view_point_feats(crop)
+                pose, sel = ops.chain_pose_from_selection(det5, logits.contiguous(), angles.contiguous(), self.ref_poses, self.ref_Ks, K9,
+                                                          self.center)
+                steps = self.refine_iter if refine_iter is None else int(refine_iter)
+            else:
+                pose = pose_init.reshape(B, 3, 4).to(self.dev, torch.float32).contiguous()
+                det5 = sel = logits = crop = None
+                steps = 1 if refine_iter is None else int(refine_iter)
             poses = [pose]
             R, rs = self.REF_NUM, self.refine_size
-            for _ in range(self.refine_iter):
+            for _ in range(steps):
                 prep = ops.chain_refine_prepare(pose.reshape(B, 12), K9, self.norm, rs, self.MARGIN, self.sub_poses, self.sub_Ks, R,
                                                 angle_step=astep)
                 geo, idx = prep[0], prep[1]

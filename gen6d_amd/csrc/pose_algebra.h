@@ -270,4 +270,173 @@ PA_HD double view_cos(const P34& a, const P34& b) {
   return (ca.x * cb.x + ca.y * cb.y + ca.z * cb.z) / (norm3(ca) * norm3(cb));
 }
 
+// ---- tracking (reference predict.py:49-72): the object's 3-D box projected under each frame's pose, the corners averaged over the last
+//      frames with Gaussian weights (weighted_pts) and a pose solved back from the averaged corners (cv2.solvePnP, SOLVEPNP_ITERATIVE)
+// The 8 box corners (box[8][3], utils/draw_utils.py pts_range_to_bbox_pts order) -> pixels uv[8][2], with project_point's depth clamp
+PA_HD void box_project(const double* box, const P34& p, const M3& K, double* uv) {
+  for (int c = 0; c < 8; ++c) {
+    double d;
+    project_point(V3{box[3 * c], box[3 * c + 1], box[3 * c + 2]}, p, K, uv[2 * c], uv[2 * c + 1], d);
+  }
+}
+// predict.py weighted_pts: the frame i steps older than the newest has weight exp(-(i/std)^2); only the last `num` frames count
+PA_HD double smooth_weight(int i, double std) { const double a = i / std; return exp(-a * a); }
+// One corner's weighted mean over a ring of frames: ring[k][8][2] for k < num, the newest frame at k = newest, n frames held (n <= num).
+// `cur` (u, v) is the newest frame's corner (passed in registers: the caller has just projected it).
+PA_HD void weighted_corner(const double* ring, int num, int newest, int n, double std, int corner, double cu, double cv, double& u,
+                           double& v) {
+  double su = cu, sv = cv, sw = 1.0;
+  for (int i = 1; i < n; ++i) {
+    const int k = (newest - i + num) % num;
+    const double w = smooth_weight(i, std);
+    su += w * ring[(k * 8 + corner) * 2];
+    sv += w * ring[(k * 8 + corner) * 2 + 1];
+    sw += w;
+  }
+  u = su / sw; v = sv / sw;
+}
+
+// Rodrigues vector <-> rotation matrix (cv2.Rodrigues).  exp: R = I + A [r]x + B [r]x^2, A = sin(th)/th, B = (1-cos th)/th^2
+PA_HD M3 skew(const V3& a) { return M3{{0, -a.z, a.y, a.z, 0, -a.x, -a.y, a.x, 0}}; }
+PA_HD M3 rodrigues(const V3& r) {
+  const double th2 = r.x * r.x + r.y * r.y + r.z * r.z, th = sqrt(th2);
+  double A, B;
+  if (th < 1e-2) { A = 1.0 - th2 / 6.0 + th2 * th2 / 120.0; B = 0.5 - th2 / 24.0 + th2 * th2 / 720.0; }
+  else { const double s = sin(0.5 * th); A = sin(th) / th; B = 2.0 * s * s / th2; }
+  const M3 S = skew(r), S2 = mul(S, S);
+  M3 R = eye3();
+  for (int i = 0; i < 9; ++i) R.m[i] += A * S.m[i] + B * S2.m[i];
+  return R;
+}
+// log map through the quaternion (Shepperd's choice of the largest pivot: accurate for every angle up to pi); R need not be exactly
+// orthogonal (a float32 pose): the result is the rotation of the quaternion fitted to it
+PA_HD V3 rot_log(const M3& R) {
+  const double* m = R.m;
+  const double tr = m[0] + m[4] + m[8];
+  double w, x, y, z;
+  if (tr >= m[0] && tr >= m[4] && tr >= m[8]) {
+    const double s = 2.0 * sqrt(1.0 + tr); w = 0.25 * s; x = (m[7] - m[5]) / s; y = (m[2] - m[6]) / s; z = (m[3] - m[1]) / s;
+  } else if (m[0] >= m[4] && m[0] >= m[8]) {
+    const double s = 2.0 * sqrt(1.0 + m[0] - m[4] - m[8]); w = (m[7] - m[5]) / s; x = 0.25 * s; y = (m[1] + m[3]) / s; z = (m[2] + m[6]) / s;
+  } else if (m[4] >= m[8]) {
+    const double s = 2.0 * sqrt(1.0 + m[4] - m[0] - m[8]); w = (m[2] - m[6]) / s; x = (m[1] + m[3]) / s; y = 0.25 * s; z = (m[5] + m[7]) / s;
+  } else {
+    const double s = 2.0 * sqrt(1.0 + m[8] - m[0] - m[4]); w = (m[3] - m[1]) / s; x = (m[2] + m[6]) / s; y = (m[5] + m[7]) / s; z = 0.25 * s;
+  }
+  if (w < 0) { w = -w; x = -x; y = -y; z = -z; }
+  const double n = sqrt(w * w + x * x + y * y + z * z);
+  w /= n; x /= n; y /= n; z /= n;
+  const double sv = sqrt(x * x + y * y + z * z);
+  const double f = sv > 1e-8 ? 2.0 * atan2(sv, w) / sv : 2.0 / w;
+  return V3{f * x, f * y, f * z};
+}
+// Right Jacobian of the Rodrigues map: R(r + d) ~ R(r) exp([Jr d]x), Jr = I - a [r]x + b [r]x^2, a = (1-cos th)/th^2, b = (th-sin th)/th^3
+PA_HD M3 rodrigues_jr(const V3& r) {
+  const double th2 = r.x * r.x + r.y * r.y + r.z * r.z, th = sqrt(th2);
+  double a, b;
+  if (th < 1e-2) { a = 0.5 - th2 / 24.0 + th2 * th2 / 720.0; b = 1.0 / 6.0 - th2 / 120.0 + th2 * th2 / 5040.0; }
+  else { const double s = sin(0.5 * th); a = 2.0 * s * s / th2; b = (th - sin(th)) / (th2 * th); }
+  const M3 S = skew(r), S2 = mul(S, S);
+  M3 J = eye3();
+  for (int i = 0; i < 9; ++i) J.m[i] += -a * S.m[i] + b * S2.m[i];
+  return J;
+}
+
+// PnP of 8 corners by Levenberg-Marquardt on x = (Rodrigues vector, t): the objective of SOLVEPNP_ITERATIVE (summed squared reprojection
+// error, no distortion).  Normal equations: 21 entries of J^T J (upper triangle, row-major), 6 of J^T r and the error, 28 sums.
+constexpr int PNP_SUMS = 28;
+constexpr int PNP_MAX_ITER = 20;           // cv2's iteration limit (calib3d cvFindExtrinsicCameraParams2)
+constexpr double PNP_STEP_EPS = 1e-10;     // stop once |dx| <= eps (|x| + eps)
+// Residual rows (u, v) of one corner X observed at (ou, ov) and their derivatives in x, added into acc[PNP_SUMS]
+PA_HD void pnp_corner_sums(const V3& X, double ou, double ov, const M3& R, const M3& RJx, const V3& t, const M3& K, double* acc) {
+  const V3 c = add(mulv(R, X), t);
+  const V3 q = mulv(K, c);
+  const double iz = 1.0 / q.z, u = q.x * iz, v = q.y * iz;
+  const double r[2] = {u - ou, v - ov};
+  // d(u, v)/dc = (K row 0 / 1 - (u, v) K row 2) / q.z; dc/dt = I, dc/dr = -R [X]x Jr = RJx
+  double du[3], dv[3];
+  for (int k = 0; k < 3; ++k) { du[k] = (K.m[k] - u * K.m[6 + k]) * iz; dv[k] = (K.m[3 + k] - v * K.m[6 + k]) * iz; }
+  double J[2][6];
+  for (int k = 0; k < 3; ++k) {
+    J[0][k] = du[0] * RJx.m[k] + du[1] * RJx.m[3 + k] + du[2] * RJx.m[6 + k];
+    J[1][k] = dv[0] * RJx.m[k] + dv[1] * RJx.m[3 + k] + dv[2] * RJx.m[6 + k];
+    J[0][3 + k] = du[k];
+    J[1][3 + k] = dv[k];
+  }
+  int o = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) acc[o++] += J[0][i] * J[0][j] + J[1][i] * J[1][j];
+  for (int i = 0; i < 6; ++i) acc[21 + i] += J[0][i] * r[0] + J[1][i] * r[1];
+  acc[27] += r[0] * r[0] + r[1] * r[1];
+}
+// The sums over corners [c0, c1) at x, then `reduce` (identity on the host; a cross-lane sum on the device)
+template <class Reduce>
+PA_HD void pnp_sums(const double* box, const double* uv, int c0, int c1, const double* x, const M3& K, double* acc, Reduce reduce) {
+  const V3 r{x[0], x[1], x[2]}, t{x[3], x[4], x[5]};
+  const M3 R = rodrigues(r), Jr = rodrigues_jr(r);
+  for (int i = 0; i < PNP_SUMS; ++i) acc[i] = 0.0;
+  for (int c = c0; c < c1; ++c) {
+    const V3 X{box[3 * c], box[3 * c + 1], box[3 * c + 2]};
+    const M3 RJx = mul(R, mul(skew(X), Jr));
+    M3 nRJx;
+    for (int i = 0; i < 9; ++i) nRJx.m[i] = -RJx.m[i];
+    pnp_corner_sums(X, uv[2 * c], uv[2 * c + 1], R, nRJx, t, K, acc);
+  }
+  reduce(acc);
+}
+// (A + lam diag(A)) dx = -g by Cholesky (A = the packed upper triangle); false if a pivot is not positive
+PA_HD bool pnp_solve(const double* A, double lam, const double* g, double* dx) {
+  double L[6][6];
+  int o = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { L[j][i] = A[o++]; if (j == i) L[i][i] *= 1.0 + lam; }
+  for (int j = 0; j < 6; ++j) {
+    double d = L[j][j];
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+    if (!(d > 0.0)) return false;
+    L[j][j] = sqrt(d);
+    for (int i = j + 1; i < 6; ++i) {
+      double s = L[i][j];
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      L[i][j] = s / L[j][j];
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) { double s = -g[i]; for (int k = 0; k < i; ++k) s -= L[i][k] * y[k]; y[i] = s / L[i][i]; }
+  for (int i = 5; i >= 0; --i) { double s = y[i]; for (int k = i + 1; k < 6; ++k) s -= L[k][i] * dx[k]; dx[i] = s / L[i][i]; }
+  return true;
+}
+// Levenberg-Marquardt from `init` (the frame's refined pose; cv2 starts from a DLT estimate instead): Marquardt's diagonal scaling,
+// lam 1e-3, /10 after a step that lowers the error, x10 otherwise, as cv2's CvLevMarq.  Every decision depends on the reduced sums
+// only, so lanes that share them take the same path.  Returns the iterations run.
+template <class Reduce>
+PA_HD int pnp_lm(const double* box, const double* uv, int c0, int c1, const M3& K, const P34& init, P34& out, Reduce reduce) {
+  const V3 r0 = rot_log(rot_of(init));
+  double x[6] = {r0.x, r0.y, r0.z, init.m[3], init.m[7], init.m[11]};
+  double acc[PNP_SUMS], nacc[PNP_SUMS];
+  pnp_sums(box, uv, c0, c1, x, K, acc, reduce);
+  double lam = 1e-3;
+  int it = 0;
+  while (it < PNP_MAX_ITER) {
+    ++it;
+    double dx[6];
+    if (!pnp_solve(acc, lam, acc + 21, dx)) { lam = fmin(lam * 10.0, 1e16); continue; }
+    double xn[6], nd = 0.0, nx = 0.0;
+    for (int i = 0; i < 6; ++i) { xn[i] = x[i] + dx[i]; nd += dx[i] * dx[i]; }
+    pnp_sums(box, uv, c0, c1, xn, K, nacc, reduce);
+    if (nacc[27] < acc[27]) {
+      for (int i = 0; i < 6; ++i) x[i] = xn[i];
+      for (int i = 0; i < PNP_SUMS; ++i) acc[i] = nacc[i];
+      lam = fmax(lam * 0.1, 1e-16);
+    } else {
+      lam = fmin(lam * 10.0, 1e16);
+    }
+    for (int i = 0; i < 6; ++i) nx += x[i] * x[i];
+    if (sqrt(nd) <= PNP_STEP_EPS * (sqrt(nx) + PNP_STEP_EPS)) break;
+  }
+  out = make_pose(rodrigues(V3{x[0], x[1], x[2]}), V3{x[3], x[4], x[5]});
+  return it;
+}
+struct NoReduce { PA_HD void operator()(double*) const {} };
+
 }  // namespace pa

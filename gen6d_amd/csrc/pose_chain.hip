@@ -139,6 +139,63 @@ __global__ void __launch_bounds__(256) warp_batch_kernel(const unsigned char* __
   }
 }
 
+// ---- multi-stream tracking (gen6d_amd/tracking.py): per-stream state lives in tables indexed by stream id; slot b of a launch serves
+// stream slot_stream[b] (-1: unused slot).
+// Input pose of every slot: its stream's last raw pose, or the parking pose for an unused slot (finite, looks at the object).
+__global__ void track_gather_kernel(const float* __restrict__ pose_table, const int* __restrict__ slot_stream,
+                                    const float* __restrict__ parking, float* __restrict__ pose_out) {
+  const int b = blockIdx.x, i = threadIdx.x;
+  if (i >= 12) return;
+  const int s = slot_stream[b];
+  pose_out[12 * b + i] = s < 0 ? parking[i] : pose_table[(size_t)12 * s + i];
+}
+
+// One 64-thread block per slot.  Lane l works on box corner l & 7 (every 8-lane group holds the same corners, so the xor-butterfly sums
+// are bitwise identical in all lanes and every branch of the solver is wave-uniform); lanes 0..7 store the corners, lane 0 the poses.
+// hist: [streams][num][8][2] float64 ring, hist_count: frames pushed since the stream's last reset.
+__global__ void __launch_bounds__(64) track_commit_kernel(const float* __restrict__ pose, const float* __restrict__ Ks,
+                                                          const int* __restrict__ slot_stream, int reset, const float* __restrict__ box,
+                                                          int num, float std_, float* __restrict__ pose_table, double* __restrict__ hist,
+                                                          int* __restrict__ hist_count, float* __restrict__ smooth_table,
+                                                          float* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x, c = lane & 7;
+  const int s = slot_stream[b];
+  if (s < 0) return;
+  const P34 p = ld_p34(pose + 12 * b);
+  const M3 K = ld_m3(Ks + 9 * b);
+  const double X[3] = {box[3 * c], box[3 * c + 1], box[3 * c + 2]};       // this lane's corner
+  // 1-2: raw pose into the table; this frame's corner into the ring (the count restarts on reset)
+  const int n0 = reset ? 0 : hist_count[s];
+  const int newest = n0 % num, n = min(n0 + 1, num);
+  double u, v, d;
+  project_point(V3{X[0], X[1], X[2]}, p, K, u, v, d);
+  double* ring = hist + (size_t)s * num * 16;
+  // 3: weighted mean of this corner (older frames from the ring, the newest from registers)
+  double mu, mv;
+  weighted_corner(ring, num, newest, n, (double)std_, c, u, v, mu, mv);
+  // 4: PnP on the 8 averaged corners, from the raw pose; each lane supplies its corner's terms and the butterfly sums them
+  const double uv[2] = {mu, mv};
+  auto reduce = [](double* a) {
+    for (int k = 0; k < PNP_SUMS; ++k) {
+      double x = a[k];
+      x += __shfl_xor(x, 1); x += __shfl_xor(x, 2); x += __shfl_xor(x, 4);
+      a[k] = x;
+    }
+  };
+  P34 sm;
+  pnp_lm(X, uv, 0, 1, K, p, sm, reduce);
+  if (lane < 8) { ring[(newest * 8 + c) * 2] = u; ring[(newest * 8 + c) * 2 + 1] = v; }
+  if (lane == 0) {
+    hist_count[s] = n0 + 1;
+    for (int i = 0; i < 12; ++i) {
+      pose_table[(size_t)12 * s + i] = pose[12 * b + i];
+      out[24 * b + i] = pose[12 * b + i];
+    }
+    st_p34(smooth_table + (size_t)12 * s, sm);           // 5-6: the smoothed pose is output only
+    st_p34(out + 24 * b + 12, sm);
+  }
+}
+
 }  // namespace
 
 #define CHAIN_STREAM(s) reinterpret_cast<hipStream_t>(s)
@@ -188,4 +245,23 @@ extern "C" int g6d_warp_batch(const unsigned char* stack, const unsigned char* s
   hipLaunchKernelGGL(warp_batch_kernel, dim3((dh * dw + 255) / 256, B), dim3(256), 0, CHAIN_STREAM(stream), stack, single, idx, sh, sw,
                      ch, hinv, dst, dh, dw);
   return g6d_check_launch("warp_batch");
+}
+
+extern "C" int g6d_track_gather(const float* pose_table, const int* slot_stream, const float* parking_pose, float* pose_out, int batch,
+                                g6d_stream_t stream) {
+  if (!pose_table || !slot_stream || !parking_pose || !pose_out || batch < 1) { g6d_set_error("track_gather: bad args"); return G6D_EINVAL; }
+  hipLaunchKernelGGL(track_gather_kernel, dim3(batch), dim3(64), 0, CHAIN_STREAM(stream), pose_table, slot_stream, parking_pose, pose_out);
+  return g6d_check_launch("track_gather");
+}
+
+extern "C" int g6d_track_commit(const float* pose, const float* K, const int* slot_stream, int reset, const float* box, int num, float std,
+                                float* pose_table, double* hist, int* hist_count, float* smooth_table, float* out, int batch,
+                                g6d_stream_t stream) {
+  if (!pose || !K || !slot_stream || !box || num < 1 || num > G6D_TRACK_MAX_NUM || !(std > 0.f) || !pose_table || !hist || !hist_count ||
+      !smooth_table || !out || batch < 1) {
+    g6d_set_error("track_commit: bad args (1 <= num <= 64, std > 0)"); return G6D_EINVAL;
+  }
+  hipLaunchKernelGGL(track_commit_kernel, dim3(batch), dim3(64), 0, CHAIN_STREAM(stream), pose, K, slot_stream, reset ? 1 : 0, box, num, std,
+                     pose_table, hist, hist_count, smooth_table, out);
+  return g6d_check_launch("track_commit");
 }

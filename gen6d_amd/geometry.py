@@ -238,3 +238,124 @@ def view_correlation(que_poses, ref_poses, center):
         cams = np.stack([pose_inverse(p)[:, 3] for p in poses]) - center[None]
         return cams / np.linalg.norm(cams, 2, 1, keepdims=True)
     return dirs(que_poses) @ dirs(ref_poses).T
+
+
+# ------------------------------------------------------------------------------------------------ tracking: box smoothing + PnP
+# reference predict.py:34-35,62-72.  float64 throughout; the same arithmetic as csrc/pose_algebra.h (box_project, weighted_corner,
+# pnp_lm), which the tests check against these functions.
+PNP_MAX_ITER = 20
+PNP_STEP_EPS = 1e-10
+
+
+def box_corners(points):
+    """Object points [n,3] -> the 8 corners of their axis-aligned box [8,3] in the order of the reference's pts_range_to_bbox_pts
+    (utils/draw_utils.py), as predict.py:34 builds object_bbox_3d."""
+    p = np.asarray(points, np.float64)
+    (X, Y, Z), (x, y, z) = p.max(0), p.min(0)
+    return np.asarray([[x, y, z], [x, Y, z], [X, Y, z], [X, y, z], [x, y, Z], [x, Y, Z], [X, Y, Z], [X, y, Z]], np.float64)
+
+
+def weighted_points(pts_list, num=5, std=2.5):
+    """predict.py weighted_pts(pts_list, weight_num=num, std_inv=std): the newest entry has weight 1, the one i steps older
+    exp(-(i/std)^2); only the last `num` entries count (fewer: the weights of those that exist)."""
+    w = np.exp(-(np.arange(num) / std) ** 2)[::-1]
+    pts = np.asarray(pts_list, np.float64)
+    if len(pts) < num:
+        w = w[-len(pts):]
+    else:
+        pts = pts[-num:]
+    return np.sum(pts * w[:, None, None], 0) / np.sum(w)
+
+
+def _skew(a):
+    return np.asarray([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]], np.float64)
+
+
+def rodrigues(r):
+    """Rodrigues vector -> rotation matrix (cv2.Rodrigues)."""
+    r = np.asarray(r, np.float64)
+    th2 = float(r @ r)
+    th = np.sqrt(th2)
+    if th < 1e-2:
+        A, B = 1 - th2 / 6 + th2 * th2 / 120, 0.5 - th2 / 24 + th2 * th2 / 720
+    else:
+        A, B = np.sin(th) / th, 2 * np.sin(0.5 * th) ** 2 / th2
+    S = _skew(r)
+    return np.eye(3) + A * S + B * (S @ S)
+
+
+def rotation_log(R):
+    """Rotation matrix (float32 poses: not exactly orthogonal) -> Rodrigues vector, through the quaternion (Shepperd's pivot)."""
+    m = np.asarray(R, np.float64).reshape(9)
+    tr = m[0] + m[4] + m[8]
+    if tr >= m[0] and tr >= m[4] and tr >= m[8]:
+        s = 2 * np.sqrt(1 + tr); q = [0.25 * s, (m[7] - m[5]) / s, (m[2] - m[6]) / s, (m[3] - m[1]) / s]
+    elif m[0] >= m[4] and m[0] >= m[8]:
+        s = 2 * np.sqrt(1 + m[0] - m[4] - m[8]); q = [(m[7] - m[5]) / s, 0.25 * s, (m[1] + m[3]) / s, (m[2] + m[6]) / s]
+    elif m[4] >= m[8]:
+        s = 2 * np.sqrt(1 + m[4] - m[0] - m[8]); q = [(m[2] - m[6]) / s, (m[1] + m[3]) / s, 0.25 * s, (m[5] + m[7]) / s]
+    else:
+        s = 2 * np.sqrt(1 + m[8] - m[0] - m[4]); q = [(m[3] - m[1]) / s, (m[2] + m[6]) / s, (m[5] + m[7]) / s, 0.25 * s]
+    q = np.asarray(q)
+    if q[0] < 0:
+        q = -q
+    q = q / np.sqrt(q @ q)
+    sv = np.sqrt(q[1:] @ q[1:])
+    f = 2 * np.arctan2(sv, q[0]) / sv if sv > 1e-8 else 2 / q[0]
+    return f * q[1:]
+
+
+def _rodrigues_jr(r):
+    th2 = float(r @ r)
+    th = np.sqrt(th2)
+    if th < 1e-2:
+        a, b = 0.5 - th2 / 24 + th2 * th2 / 720, 1 / 6 - th2 / 120 + th2 * th2 / 5040
+    else:
+        a, b = 2 * np.sin(0.5 * th) ** 2 / th2, (th - np.sin(th)) / (th2 * th)
+    S = _skew(r)
+    return np.eye(3) - a * S + b * (S @ S)
+
+
+def pnp_normal_equations(box, uv, K, x):
+    """At x = (Rodrigues vector, t): J^T J [6,6], J^T r [6] and the summed squared reprojection error of the corners."""
+    box, uv, K = np.asarray(box, np.float64), np.asarray(uv, np.float64), np.asarray(K, np.float64)
+    R, Jr = rodrigues(x[:3]), _rodrigues_jr(np.asarray(x[:3], np.float64))
+    q = (box @ R.T + x[3:]) @ K.T
+    proj = q[:, :2] / q[:, 2:3]
+    r = (proj - uv).reshape(-1)
+    J = np.zeros((2 * len(box), 6))
+    for i, X in enumerate(box):
+        d = (K[:2] - proj[i][:, None] * K[2][None]) / q[i, 2]            # d(u, v)/dc
+        J[2 * i:2 * i + 2, :3] = d @ (-R @ _skew(X) @ Jr)
+        J[2 * i:2 * i + 2, 3:] = d
+    return J.T @ J, J.T @ r, float(r @ r)
+
+
+def pnp(box, uv, K, pose_init):
+    """Pose from the 2-D corners: Levenberg-Marquardt on (Rodrigues vector, t) minimising the summed squared reprojection error — the
+    objective of cv2.solvePnP(SOLVEPNP_ITERATIVE), no distortion — started from pose_init (cv2 starts from a DLT estimate; on the
+    near-consistent corners of a smoothed track both reach the same minimum).  Marquardt's diagonal scaling, lam 1e-3 divided by 10
+    after a step that lowers the error and multiplied by 10 otherwise, at most 20 iterations or until |dx| <= 1e-10 (|x| + 1e-10)."""
+    pose_init = np.asarray(pose_init, np.float64)
+    x = np.concatenate([rotation_log(pose_init[:, :3]), pose_init[:, 3]])
+    A, g, err = pnp_normal_equations(box, uv, K, x)
+    lam = 1e-3
+    for _ in range(PNP_MAX_ITER):
+        M = A.copy()
+        M[np.diag_indices(6)] *= 1 + lam
+        try:
+            L = np.linalg.cholesky(M)
+        except np.linalg.LinAlgError:
+            lam = min(lam * 10, 1e16)
+            continue
+        dx = -np.linalg.solve(L.T, np.linalg.solve(L, g))
+        xn = x + dx
+        An, gn, errn = pnp_normal_equations(box, uv, K, xn)
+        if errn < err:
+            x, A, g, err = xn, An, gn, errn
+            lam = max(lam * 0.1, 1e-16)
+        else:
+            lam = min(lam * 10, 1e16)
+        if np.sqrt(dx @ dx) <= PNP_STEP_EPS * (np.sqrt(x @ x) + PNP_STEP_EPS):
+            break
+    return np.concatenate([rodrigues(x[:3]), x[3:, None]], 1)

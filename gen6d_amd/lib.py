@@ -112,6 +112,8 @@ SIGNATURES = {
     "g6d_chain_refine_update": [_P, _P, _P, _P, _I, _P, _P, _I, _P],
     "g6d_warp_batch": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _P],
     "g6d_warp_perspective": [_P, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _I, _I, _F, _P],
+    "g6d_track_gather": [_P, _P, _P, _P, _I, _P],
+    "g6d_track_commit": [_P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P, _I, _P],
 }
 
 _lib = None

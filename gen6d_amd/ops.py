@@ -1435,3 +1435,59 @@ def warp_batch(stack, single, idx, hinv, dh, dw, out=None):
     _lib.check(_lib.load().g6d_warp_batch(_ptr(stack), _ptr(single), _ptr(idx), B, sh, sw, ch, _ptr(hinv), _ptr(dst), dh, dw, _stream()),
                "g6d_warp_batch")
     return dst
+
+
+# ------------------------------------------------------------------------------------------------ multi-stream tracking
+def _track_same_device(what, *ts):
+    _need_gpu(*ts)
+    if len({t.device for t in ts}) != 1:
+        raise ValueError(f"{what}: operands must live on one device")
+
+
+def _track_map(what, slot_stream):
+    if slot_stream.dtype != torch.int32 or slot_stream.dim() != 1 or not slot_stream.is_contiguous():
+        raise ValueError(f"{what}: slot_stream must be a contiguous int32 [B] tensor")
+    return slot_stream.shape[0]
+
+
+def track_gather(pose_table, slot_stream, parking_pose):
+    """pose_table [S,12], slot_stream int32 [B] (stream id per slot, -1 = unused), parking_pose [12] -> input poses [B,3,4]: the stream's
+    last raw pose, the parking pose for an unused slot (g6d_track_gather)."""
+    _track_same_device("track_gather", pose_table, slot_stream, parking_pose)
+    _f32c(pose_table, parking_pose)
+    B = _track_map("track_gather", slot_stream)
+    if pose_table.dim() != 2 or pose_table.shape[1] != 12 or parking_pose.numel() != 12:
+        raise ValueError("track_gather: pose_table [S,12] and parking_pose [12] expected")
+    pose = torch.empty((B, 3, 4), dtype=torch.float32, device=pose_table.device)
+    _lib.check(_lib.load().g6d_track_gather(_ptr(pose_table), _ptr(slot_stream), _ptr(parking_pose), _ptr(pose), B, _stream()),
+               "g6d_track_gather")
+    return pose
+
+
+def track_commit(pose, K, slot_stream, reset, box, num, std, pose_table, hist, hist_count, smooth_table, out=None):
+    """Commit one refined frame per used slot (g6d_track_commit): pose [B,3,4] / [B,12], K [B,3,3] / [B,9], slot_stream int32 [B], reset
+    (restart the streams' corner history first), box [8,3], num / std (predict.py's smoothing window and width); per-stream tables
+    pose_table / smooth_table float32 [S,12], hist float64 [S,num,8,2], hist_count int32 [S] are updated in place.
+    -> out [B,2,3,4] = (raw, smoothed) pose per slot (`out`: optional destination; unused slots keep its content)."""
+    what = "track_commit"
+    _track_same_device(what, pose, K, slot_stream, box, pose_table, hist, hist_count, smooth_table)
+    _f32c(pose, K, box, pose_table, smooth_table)
+    B = _track_map(what, slot_stream)
+    num = int(num)
+    S = pose_table.shape[0]
+    if pose.numel() != 12 * B or K.numel() != 9 * B or box.numel() != 24:
+        raise ValueError("track_commit: pose [B,12], K [B,9] and box [8,3] expected")
+    if not 1 <= num <= 64 or not float(std) > 0:
+        raise ValueError("track_commit: 1 <= num <= 64 and std > 0 expected")
+    if (pose_table.shape != (S, 12) or smooth_table.shape != (S, 12) or hist.dtype != torch.float64 or not hist.is_contiguous() or
+            tuple(hist.shape) != (S, num, 8, 2) or hist_count.dtype != torch.int32 or not hist_count.is_contiguous() or
+            tuple(hist_count.shape) != (S,)):
+        raise ValueError("track_commit: tables pose / smooth float32 [S,12], hist float64 [S,num,8,2], hist_count int32 [S] expected")
+    if out is None:
+        out = torch.empty((B, 2, 3, 4), dtype=torch.float32, device=pose.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 24 * B or out.device != pose.device:
+        raise ValueError("track_commit: out must be a contiguous float32 [B,2,3,4] tensor")
+    _lib.check(_lib.load().g6d_track_commit(_ptr(pose), _ptr(K), _ptr(slot_stream), int(bool(reset)), _ptr(box), num, float(std),
+                                           _ptr(pose_table), _ptr(hist), _ptr(hist_count), _ptr(smooth_table), _ptr(out), B, _stream()),
+               "g6d_track_commit")
+    return out

@@ -1,0 +1,334 @@
+"""Batched multi-stream tracking (reference predict.py:49-72) on the device-resident chain.
+
+The reference's video loop runs the full pipeline on the first frame and one refinement step from the previous pose on every later
+frame, then smooths the result for display: the object's 3-D box is projected under each pose, the corners of the last frames are
+averaged with Gaussian weights (weighted_pts) and a pose is solved back from them (cv2.solvePnP).  `StreamTracker` runs that loop for
+many streams (cameras or clients watching one object) at once:
+
+  * stream s sits in slot s % batch of group s // batch; the group runs on lane (s // batch) % lanes, one HIP stream per lane, so a
+    stream's consecutive frames are ordered by its lane's stream with no events;
+  * a stream's first frame (after creation or `reset`) goes through detection, selection and cfg['refine_iter'] steps in
+    `DeviceChain.query_batch` (chunks of <= 8 queries) and is committed with its history restarted; every later frame is one of the
+    group's slots in a tick: gather (previous raw pose per slot) -> `track_iter` refinement steps -> commit (csrc/pose_chain.hip);
+  * each lane has one captured hipGraph of the tick (captured lazily, after warm-up runs on an all-unused slot map) with static image,
+    K and slot-map buffers that are filled on the lane's stream before each replay; unused slots (id -1) refine the parking pose
+    (DeviceChain.ref_poses[0]) and are not committed;
+  * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners.
+
+`track_streams` is the one-call form for whole sequences, with one synchronisation at the end and the networks' fp16 pair range guard.
+"""
+import numpy as np
+import torch
+
+from . import eval as EV
+from . import geometry as G
+from . import ops
+from .network import refiner as _refiner
+
+INIT_CHUNK = 8          # first frames per query_batch call: the batch size query_batch's detection + selection path is tested at
+
+
+class _Lane:
+    def __init__(self, stream):
+        self.stream, self.graph, self.img, self.K, self.map, self.out = stream, None, None, None, None, None
+
+
+class _Serial:
+    """The tracker's launches run on the lane's stream with whole ticks in flight: no intra-step stream forks (ops.SERIAL, as
+    DeviceChain.capture)."""
+
+    def __init__(self, stream):
+        self.stream = stream
+
+    def __enter__(self):
+        self.old, ops.SERIAL = ops.SERIAL, True
+        self.ctx = torch.cuda.stream(self.stream) if self.stream is not None else None
+        if self.ctx is not None:
+            self.ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self.ctx is not None:
+            self.ctx.__exit__(*exc)
+        ops.SERIAL = self.old
+        return False
+
+
+class StreamTracker:
+    def __init__(self, estimator, max_streams, batch=8, lanes=2, track_iter=1, smooth_num=5, smooth_std=2.5, object_pts=None,
+                 graphs=True):
+        if estimator.refiner is None:
+            raise ValueError("StreamTracker: the estimator has no refiner (tracking refines every frame)")
+        self.max_streams, self.batch, self.nlanes = int(max_streams), int(batch), int(lanes)
+        self.track_iter, self.num, self.std = int(track_iter), int(smooth_num), float(smooth_std)
+        if self.max_streams < 1 or self.nlanes < 1 or self.track_iter < 1:
+            raise ValueError("StreamTracker: max_streams, lanes and track_iter must be >= 1")
+        if not 1 <= self.batch <= _refiner.MAX_BATCH:
+            raise ValueError(f"StreamTracker: 1 <= batch <= {_refiner.MAX_BATCH} expected")
+        if not 1 <= self.num <= 64 or not self.std > 0:
+            raise ValueError("StreamTracker: 1 <= smooth_num <= 64 and smooth_std > 0 expected")
+        self.est = estimator
+        self.chain = estimator.device_chain()
+        self.dev = torch.device(estimator.device)
+        self.cuda = self.dev.type == "cuda"
+        if graphs and not self.cuda:
+            raise ValueError("StreamTracker: graphs=True needs the GPU (graphs=False runs the same ticks eagerly)")
+        self.graphs = bool(graphs)
+        pts = EV.get_ref_point_cloud(estimator.refiner.ref_database) if object_pts is None else object_pts
+        self.box_np = G.box_corners(pts)
+        self.box = torch.from_numpy(self.box_np.astype(np.float32)).to(self.dev)
+        S = self.max_streams
+        self.pose_table = torch.zeros((S, 12), dtype=torch.float32, device=self.dev)
+        self.smooth_table = torch.zeros((S, 12), dtype=torch.float32, device=self.dev)
+        self.hist = torch.zeros((S, self.num, 8, 2), dtype=torch.float64, device=self.dev)
+        self.hist_count = torch.zeros(S, dtype=torch.int32, device=self.dev)
+        self.parking = self.chain.ref_poses[0].contiguous()
+        self._lanes = [_Lane(torch.cuda.Stream(device=self.dev) if self.cuda else None) for _ in range(self.nlanes)]
+        if self.cuda:
+            for ln in self._lanes:             # the tables live as long as the tracker; their blocks outlive no lane's pending work
+                for t in (self.box, self.pose_table, self.smooth_table, self.hist, self.hist_count):
+                    t.record_stream(ln.stream)
+        self._started = [False] * S
+        self._frames = [0] * S                 # frames pushed per stream
+        self._shape = None
+        self._records = None                   # track_streams: [(rows [n,2,3,4] device, [(row, stream, frame)])]
+        for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
+            t = net.__dict__.get("_range")
+            if t is not None and t.names:
+                t.clear()
+
+    # ------------------------------------------------------------------ public API
+    def push(self, stream_ids, imgs, Ks=None):
+        """Enqueue one frame per listed stream: imgs uint8 [H,W,3] (numpy or device tensors; one shape per tracker), Ks [3,3] per stream
+        (None: predict.py's pseudo K).  Does not synchronise."""
+        ids = self._ids(stream_ids)
+        if len(imgs) != len(ids) or (Ks is not None and len(Ks) != len(ids)):
+            raise ValueError("StreamTracker.push: one image (and K) per stream id expected")
+        frames = [self._frame(im) for im in imgs]
+        h, w = self._shape[:2]
+        Ks = [EV.pseudo_K(h, w) if Ks is None else Ks[i] for i in range(len(ids))]
+        groups = {}
+        for i, s in enumerate(ids):
+            groups.setdefault(s // self.batch, []).append((s, frames[i], Ks[i]))
+        cur = torch.cuda.current_stream(self.dev) if self.cuda else None
+        for g in sorted(groups):
+            lane = self._lanes[g % self.nlanes]
+            if cur is not None:
+                lane.stream.wait_stream(cur)
+            with _Serial(lane.stream):
+                ents = [(s, self._upload(im, lane), self._upload(K.reshape(3, 3).float() if torch.is_tensor(K) else
+                                                             np.asarray(K, np.float32).reshape(3, 3), lane)) for s, im, K in groups[g]]
+                track = [e for e in ents if self._started[e[0]]]
+                init = [e for e in ents if not self._started[e[0]]]
+                if track:
+                    self._tick(lane, track)
+                for c0 in range(0, len(init), INIT_CHUNK):
+                    self._init(init[c0:c0 + INIT_CHUNK])
+        for s in ids:
+            self._started[s] = True
+            self._frames[s] += 1
+
+    def result(self, stream_ids=None):
+        """Synchronise -> {id: (pose [3,4], smoothed [3,4])} float32 numpy of each stream's latest frame (stream_ids None: every stream
+        that has one).  Raises RuntimeError if an fp16 pair map of the networks left the representable window since the last check:
+        the poses since then cannot be trusted (reset the streams; the maps' exponents are updated for the frames that follow)."""
+        if self.cuda:
+            torch.cuda.synchronize(self.dev)
+        self._check_range()
+        ids = [s for s in range(self.max_streams) if self._frames[s]] if stream_ids is None else self._ids(stream_ids)
+        for s in ids:
+            if not self._frames[s]:
+                raise ValueError(f"StreamTracker.result: stream {s} has no frame")
+        P, Sm = self.pose_table.cpu().numpy(), self.smooth_table.cpu().numpy()
+        return {s: (P[s].reshape(3, 4).copy(), Sm[s].reshape(3, 4).copy()) for s in ids}
+
+    def reset(self, stream_ids):
+        """The next frame of these streams starts over: detection, selection, full refinement, fresh smoothing history."""
+        for s in self._ids(stream_ids):
+            self._started[s] = False
+
+    # ------------------------------------------------------------------ internals
+    def _nets(self):
+        return [n for n in (self.est.detector, self.est.selector, self.est.refiner) if n is not None]
+
+    def _ids(self, stream_ids):
+        ids = [int(s) for s in stream_ids]
+        for s in ids:
+            if not 0 <= s < self.max_streams:
+                raise ValueError(f"StreamTracker: stream id {s} outside [0, {self.max_streams})")
+        if len(set(ids)) != len(ids):
+            raise ValueError("StreamTracker: a stream id is listed twice")
+        return ids
+
+    def _frame(self, im):
+        if not torch.is_tensor(im):
+            im = np.asarray(im)
+        shape, dtype = tuple(im.shape), im.dtype
+        if dtype not in (np.uint8, torch.uint8) or len(shape) != 3 or shape[2] != 3:
+            raise ValueError("StreamTracker: frames must be uint8 [H,W,3]")
+        if self._shape is None:
+            self._shape = shape
+        elif shape != self._shape:
+            raise ValueError(f"StreamTracker: frame shape {shape} differs from the tracker's {self._shape}")
+        return im
+
+    def _upload(self, a, lane=None):
+        """Host arrays -> device on the current (lane's) stream, through pinned memory: no host stall on the stream; device tensors are
+        recorded on the lane's stream."""
+        if torch.is_tensor(a):
+            if a.device.type == "cuda":
+                a.record_stream(lane.stream)
+                return a.contiguous()
+            t = a
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        if not self.cuda:
+            return t.to(self.dev)
+        return t.pin_memory().to(self.dev, non_blocking=True)
+
+    def _statics(self, lane):
+        if lane.img is None:
+            B, (h, w) = self.batch, self._shape[:2]
+            lane.img = torch.zeros((B, h, w, 3), dtype=torch.uint8, device=self.dev)
+            lane.K = torch.from_numpy(np.repeat(EV.pseudo_K(h, w)[None], B, 0)).to(self.dev)
+            lane.map = torch.full((B,), -1, dtype=torch.int32, device=self.dev)
+
+    def _tick_fn(self, lane):
+        """gather -> track_iter refinement steps (query_batch's refine loop) -> commit, on the lane's static buffers."""
+        pose0 = ops.track_gather(self.pose_table, lane.map, self.parking)
+        r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
+        return ops.track_commit(r["pose"], lane.K.reshape(self.batch, 9), lane.map, False, self.box, self.num, self.std, self.pose_table,
+                                self.hist, self.hist_count, self.smooth_table)
+
+    def _capture(self, lane, warmup=2):
+        lane.map.fill_(-1)
+        for _ in range(warmup):
+            self._tick_fn(lane)
+        graph = torch.cuda.CUDAGraph()
+        graph.capture_begin(capture_error_mode="thread_local")
+        try:
+            lane.out = self._tick_fn(lane)
+        finally:
+            graph.capture_end()
+        lane.graph = graph
+
+    def _tick(self, lane, ents):
+        self._statics(lane)
+        slots = [s % self.batch for s, _, _ in ents]
+        m = np.full(self.batch, -1, np.int32)
+        for (s, _, _), b in zip(ents, slots):
+            m[b] = s
+        if self.graphs and lane.graph is None:
+            self._capture(lane)
+        for (s, im, K), b in zip(ents, slots):
+            lane.img[b].copy_(im)
+            lane.K[b].copy_(K)
+        lane.map.copy_(self._upload(m))
+        if self.graphs:
+            lane.graph.replay()
+            out = lane.out
+        else:
+            out = self._tick_fn(lane)
+        if self._records is not None:
+            self._records.append((out.clone(), [(b, s, self._frames[s]) for (s, _, _), b in zip(ents, slots)]))
+
+    def _init(self, ents):
+        n = len(ents)
+        imgs = torch.stack([im for _, im, _ in ents], 0)
+        Ks = torch.stack([K for _, _, K in ents], 0)
+        r = self.chain.query_batch(imgs, Ks)
+        ids = self._upload(np.asarray([s for s, _, _ in ents], np.int32))
+        out = ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), ids, True, self.box, self.num, self.std, self.pose_table, self.hist,
+                               self.hist_count, self.smooth_table)
+        if self._records is not None:
+            self._records.append((out, [(i, s, self._frames[s]) for i, (s, _, _) in enumerate(ents)]))
+
+    def _check_range(self):
+        bad = []
+        for net in self._nets():
+            t = net.__dict__.get("_range")
+            if t is None or not t.names:
+                continue
+            a = t.read()
+            t.clear()
+            out = {n: v for n, v in a.items() if ops.pair_out_of_window(v, t.e[t.names[n]])}
+            if out:
+                t.set_exponents({n: ops.pair_exponent(v, t.e[t.names[n]]) for n, v in out.items()})
+                bad.append(f"{type(net).__name__}: " + ", ".join(f"{n} max |v| = {v:g}" for n, v in out.items()))
+        if bad:
+            raise RuntimeError("StreamTracker: fp16 pair maps left the representable window since the last check (" + "; ".join(bad) +
+                               "); the poses since then cannot be trusted — reset the streams")
+
+    def _collect(self, lengths):
+        """track_streams: one synchronisation, one read-back -> per stream (poses [T,3,4], smoothed [T,3,4])."""
+        if self.cuda:
+            torch.cuda.synchronize(self.dev)
+        rows = torch.cat([r.reshape(-1, 2, 12) for r, _ in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 2, 12))
+        res = [(np.zeros((T, 3, 4), np.float32), np.zeros((T, 3, 4), np.float32)) for T in lengths]
+        base = 0
+        for r, ents in self._records:
+            for row, s, f in ents:
+                res[s][0][f] = rows[base + row, 0].reshape(3, 4)
+                res[s][1][f] = rows[base + row, 1].reshape(3, 4)
+            base += r.shape[0]
+        return res
+
+
+def _stream_Ks(Ks, seqs):
+    out = []
+    for s, frames in enumerate(seqs):
+        k = None if Ks is None else Ks[s]
+        if k is None:
+            out.append([EV.pseudo_K(*np.asarray(f).shape[:2]) for f in frames])
+            continue
+        k = np.asarray(k, np.float32)
+        if k.shape == (3, 3):
+            out.append([k] * len(frames))
+        elif k.shape == (len(frames), 3, 3):
+            out.append(list(k))
+        else:
+            raise ValueError(f"track_streams: Ks of stream {s} must be [3,3] or [T,3,3]")
+    return out
+
+
+def host_track(estimator, frames, Ks, track_iter=1, smooth_num=5, smooth_std=2.5, box=None):
+    """One stream through the host-driven loop of predict.py:49-72: `estimator.predict` per frame (first frame: cfg['refine_iter'] steps,
+    later frames: `track_iter` steps from the previous pose) and the numpy box smoothing + PnP -> (poses [T,3,4], smoothed [T,3,4])."""
+    box = G.box_corners(EV.get_ref_point_cloud(estimator.refiner.ref_database)) if box is None else box
+    poses, smooth, hist, pose, it0 = [], [], [], None, estimator.cfg["refine_iter"]
+    try:
+        for im, K in zip(frames, Ks):
+            if pose is not None:
+                estimator.cfg["refine_iter"] = track_iter
+            pose, _ = estimator.predict(np.asarray(im), K, pose_init=pose)
+            K64, p64 = np.asarray(K, np.float64), np.asarray(pose, np.float32).astype(np.float64)
+            hist.append(G.project_points(box, p64, K64)[0])
+            poses.append(pose)
+            smooth.append(G.pnp(box, G.weighted_points(hist, smooth_num, smooth_std), K64, p64))
+    finally:
+        estimator.cfg["refine_iter"] = it0
+    return np.asarray(poses, np.float32).reshape(-1, 3, 4), np.asarray(smooth, np.float32).reshape(-1, 3, 4)
+
+
+def track_streams(estimator, streams, Ks=None, **tracker_kw):
+    """S frame sequences (possibly of different lengths; uint8 [H,W,3] frames of one shape) -> per stream (poses [T,3,4], smoothed
+    [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  Frame t of
+    every stream that has one is pushed in tick t; one synchronisation at the end.  Runs under the estimator's range guard: if an fp16
+    pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32."""
+    seqs = [list(s) for s in streams]
+    Kss = _stream_Ks(Ks, seqs)
+    kw = dict(tracker_kw)
+
+    def run():
+        tr = StreamTracker(estimator, len(seqs), **kw)
+        tr._records = []
+        for t in range(max((len(s) for s in seqs), default=0)):
+            ids = [s for s in range(len(seqs)) if t < len(seqs[s])]
+            tr.push(ids, [seqs[s][t] for s in ids], [Kss[s][t] for s in ids])
+        return tr._collect([len(s) for s in seqs])
+
+    def recompute():
+        box = None if kw.get("object_pts") is None else G.box_corners(kw["object_pts"])
+        return [host_track(estimator, frames, Kss[s], kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
+                for s, frames in enumerate(seqs)]
+    return estimator._range_guarded(run, recompute)

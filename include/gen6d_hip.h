@@ -541,6 +541,24 @@ int g6d_linear_gemv(const float* x, int B, int K, const float* W, const float* b
 int g6d_linear_gemv_batch(const float* x, int B, int K, const float* W, const float* bias, int O, int act, float* out, float* workspace,
                           size_t workspace_bytes, g6d_stream_t stream);
 
+/* Multi-stream tracking (gen6d_amd/tracking.py, reference predict.py:49-72); additive within ABI 12.  Per-stream state lives in tables
+ * indexed by stream id: pose_table / smooth_table [streams][12] (last raw / smoothed pose), hist [streams][num][8][2] float64 (ring of
+ * the projected box corners), hist_count [streams] (frames since the last reset).  slot_stream [batch]: the stream served by slot b, or
+ * -1 for an unused slot; ids must index the tables (the caller checks them).
+ * g6d_track_gather: pose_out[b][12] = the stream's last raw pose, or parking_pose[12] for an unused slot (a finite pose that looks at
+ * the object, so that the refinement step of an unused slot stays finite and inside the fp16 pair range records). */
+int g6d_track_gather(const float* pose_table, const int* slot_stream, const float* parking_pose, float* pose_out, int batch,
+                     g6d_stream_t stream);
+/* g6d_track_commit, one 64-thread block per used slot: pose [batch][12] (refined, unsmoothed), K [batch][9], box [8][3] (corner order
+ * of the reference's pts_range_to_bbox_pts).  Writes the raw pose into the stream's table row, projects the box under it and pushes the
+ * corners into the stream's ring (reset != 0: the count restarts first), averages the last min(count, num) frames with weights
+ * exp(-(i/std)^2) (i = frames older than the newest), solves PnP on the averaged corners by Levenberg-Marquardt on (Rodrigues vector, t)
+ * from the raw pose (<= 20 iterations), and writes the smoothed pose into smooth_table and out[b] = raw[12] | smoothed[12].
+ * Unused slots write nothing.  1 <= num <= G6D_TRACK_MAX_NUM, std > 0. */
+#define G6D_TRACK_MAX_NUM 64
+int g6d_track_commit(const float* pose, const float* K, const int* slot_stream, int reset, const float* box, int num, float std,
+                     float* pose_table, double* hist, int* hist_count, float* smooth_table, float* out, int batch, g6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
