@@ -1,0 +1,153 @@
+// Frame ingest (gen6d_amd/ingest.py; reference prepare.py:16-42 video2image): camera-native frames -> the RGB working-resolution images
+// of a batch, one launch for all frames.  The arithmetic is exact integer (include/gen6d_hip.h) and is restated in numpy
+// by tests/test_ingest_cpu.py.  Measured at 2.0 - 2.4 TB/s (a third of the HBM rate, bound by byte loads and the per-tap conversion)
+// and under half a percent of a tracker tick (profiles/r09_ingest_bench.md).
+//
+// Launch shape: the canvas is cut into 128 x 8 pixel tiles; block = one tile of one frame (flat list: blockIdx.x = frame * tiles + tile),
+// 256 threads, thread = 4 consecutive pixels of one canvas row.  The 64-bit divisions of the sampling rule are done once per tile and
+// canvas column / row (136 per 1024 pixels) into LDS as packed (index, step, weight) words.  A wave reads 2 canvas rows x 128 pixels: at
+// rotate 0 / 180 that is whole stretches of source rows; 12 output bytes per thread go out as three dwords when the canvas rows are
+// dword-aligned (W % 4 == 0).  Taps of weight 0 are not loaded (a same-size frame costs one tap per pixel), and the chroma terms of an
+// NV12 sample are computed once for the taps of its 2 x 2 block (at 2:1 all four taps of a pixel share one).
+#include "g6d_common.h"
+
+namespace {
+
+constexpr int TW = 128, TH = 8;
+
+// canvas coordinate t of an axis with `tgt` picture pixels over `src` source pixels -> i0 | (i1 - i0) << 13 | weight << 14
+__device__ __forceinline__ unsigned sample_word(int t, int tgt, int src) {
+  long long f = (long long)((unsigned long long)(2 * t + 1) * (unsigned)src * 1024ull / (unsigned)tgt) - 1024;
+  const long long hi = (long long)(src - 1) * 2048;
+  f = f < 0 ? 0 : (f > hi ? hi : f);
+  const unsigned i0 = (unsigned)(f >> 11), w = (unsigned)(f & 2047);
+  return i0 | ((i0 + 1 < (unsigned)src ? 1u : 0u) << 13) | (w << 14);
+}
+
+struct Src {
+  const unsigned char* p0; const unsigned char* p1;
+  int pitch0, pitch1, bpp, ro, nv12;
+  int cvr, cug, cvg, cub;
+};
+
+__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
+
+// NV12: the chroma terms of one UV sample (shared by the up to four luma taps of its 2 x 2 block), then one luma tap -> RGB
+struct Chroma { int r, g, b; };
+__device__ __forceinline__ Chroma chroma(const Src& s, int cx, int cy) {
+  const unsigned char* uv = s.p1 + (size_t)cy * s.pitch1 + 2 * cx;
+  const int d = (int)uv[0] - 128, e = (int)uv[1] - 128;
+  return Chroma{s.cvr * e + (1 << 19), -s.cug * d - s.cvg * e + (1 << 19), s.cub * d + (1 << 19)};
+}
+__device__ __forceinline__ void tap_nv12(const Src& s, const Chroma& k, int x, int y, int& r, int& g, int& b) {
+  const int c = max((int)s.p0[(size_t)y * s.pitch0 + x] - 16, 0) * 1220542;
+  r = sat8((c + k.r) >> 20); g = sat8((c + k.g) >> 20); b = sat8((c + k.b) >> 20);
+}
+__device__ __forceinline__ void tap_packed(const Src& s, int x, int y, int& r, int& g, int& b) {
+  const unsigned char* p = s.p0 + (size_t)y * s.pitch0 + (size_t)x * s.bpp;
+  r = p[s.ro]; g = p[1]; b = p[2 - s.ro];
+}
+
+__global__ void __launch_bounds__(256) frame_ingest_kernel(const G6dFrame* __restrict__ frames, unsigned char* __restrict__ out, int B, int H,
+                                                           int W, float* __restrict__ K_out, int tiles_x, int tiles) {
+  __shared__ unsigned cw[TW + TH];
+  const int fi = blockIdx.x / tiles, tile = blockIdx.x - fi * tiles;
+  const G6dFrame& f = frames[fi];
+  const int slot = f.slot;
+  if (slot < 0 || slot >= B) return;                      // (block-uniform)
+  const int t = threadIdx.x;
+  if (tile == 0 && t < 9) K_out[(size_t)9 * slot + t] = f.K[t];
+  const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
+  const int ws = f.width, hs = f.height, rot = f.rotate;
+  const int ow = min(f.out_w, W), oh = min(f.out_h, H);   // an empty or negative picture leaves a black canvas
+  const bool swap = rot == 90 || rot == 270;
+  if (t < TW + TH) {
+    unsigned v = 0;
+    if (t < TW) {
+      const int X = X0 + t;
+      if (X < ow) v = sample_word((rot == 90 || rot == 180) ? f.out_w - 1 - X : X, f.out_w, swap ? hs : ws);
+    } else {
+      const int Y = Y0 + t - TW;
+      if (Y < oh) v = sample_word((rot == 180 || rot == 270) ? f.out_h - 1 - Y : Y, f.out_h, swap ? ws : hs);
+    }
+    cw[t] = v;
+  }
+  __syncthreads();
+  const int ry = t >> 5, X = X0 + ((t & 31) << 2), Y = Y0 + ry;
+  if (Y >= H || X >= W) return;
+  Src s;
+  s.p0 = static_cast<const unsigned char*>(f.plane0); s.p1 = static_cast<const unsigned char*>(f.plane1);
+  s.pitch0 = f.pitch0; s.pitch1 = f.pitch1;
+  s.nv12 = f.format == G6D_FMT_NV12;
+  s.bpp = f.format >= G6D_FMT_RGBA32 ? 4 : 3;
+  s.ro = (f.format == G6D_FMT_BGR24 || f.format == G6D_FMT_BGRA32) ? 2 : 0;
+  const bool m709 = f.matrix == 1;
+  s.cvr = m709 ? 1880097 : 1673527; s.cug = m709 ? 223347 : 409993; s.cvg = m709 ? 558891 : 852492; s.cub = m709 ? 2214593 : 2116026;
+  const unsigned rw = cw[TW + ry];
+  unsigned char px[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int r = 0, g = 0, b = 0;
+    if (X + k < ow && Y < oh) {
+      const unsigned c = cw[(t & 31) * 4 + k];
+      const unsigned xw = swap ? rw : c, yw = swap ? c : rw;
+      const int x0 = xw & 8191, x1 = x0 + ((xw >> 13) & 1), y0 = yw & 8191, y1 = y0 + ((yw >> 13) & 1);
+      const unsigned wa = xw >> 14, wb = yw >> 14;
+      const unsigned w00 = (2048 - wa) * (2048 - wb), w01 = wa * (2048 - wb), w10 = (2048 - wa) * wb, w11 = wa * wb;
+      int r1, g1, b1;
+      unsigned ar = 1u << 21, ag = 1u << 21, ab = 1u << 21;
+#define G6D_ACC(w) { ar += (w) * r1; ag += (w) * g1; ab += (w) * b1; }
+      if (s.nv12) {                                       // (block-uniform) a UV sample is loaded once for the taps that share it
+        const bool sx = (x1 >> 1) == (x0 >> 1), sy = (y1 >> 1) == (y0 >> 1);
+        const Chroma k00 = chroma(s, x0 >> 1, y0 >> 1);
+        tap_nv12(s, k00, x0, y0, r1, g1, b1); G6D_ACC(w00)
+        Chroma k01 = k00;
+        if (wa) { if (!sx) k01 = chroma(s, x1 >> 1, y0 >> 1); tap_nv12(s, k01, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+        if (wb) {
+          const Chroma k10 = sy ? k00 : chroma(s, x0 >> 1, y1 >> 1);
+          tap_nv12(s, k10, x0, y1, r1, g1, b1); G6D_ACC(w10)
+          if (wa) {
+            const Chroma k11 = sx ? k10 : (sy ? k01 : chroma(s, x1 >> 1, y1 >> 1));
+            tap_nv12(s, k11, x1, y1, r1, g1, b1); G6D_ACC(w11)
+          }
+        }
+      } else {
+        tap_packed(s, x0, y0, r1, g1, b1); G6D_ACC(w00)
+        if (wa) { tap_packed(s, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+        if (wb) { tap_packed(s, x0, y1, r1, g1, b1); G6D_ACC(w10) }
+        if (wa && wb) { tap_packed(s, x1, y1, r1, g1, b1); G6D_ACC(w11) }
+      }
+#undef G6D_ACC
+      r = ar >> 22; g = ag >> 22; b = ab >> 22;
+    }
+    px[3 * k] = (unsigned char)r; px[3 * k + 1] = (unsigned char)g; px[3 * k + 2] = (unsigned char)b;
+  }
+  unsigned char* o = out + (((size_t)slot * H + Y) * W + X) * 3;
+  if (X + 4 <= W && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
+    unsigned* o32 = reinterpret_cast<unsigned*>(o);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      o32[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
+  } else {
+    const int nb = 3 * min(4, W - X);
+#pragma unroll
+    for (int j = 0; j < 12; ++j)
+      if (j < nb) o[j] = px[j];
+  }
+}
+
+}  // namespace
+
+extern "C" int g6d_sizeof_frame_desc(void) { return (int)sizeof(G6dFrame); }
+
+extern "C" int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int B, int H, int W, float* K_out, g6d_stream_t stream) {
+  if (!frames || n < 0 || !out || !K_out || B < 1 || H < 1 || W < 1) {
+    g6d_set_error("frame_ingest: bad args (null table / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
+  }
+  if (n == 0) return G6D_OK;
+  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest: too many tiles for one launch"); return G6D_EINVAL; }
+  hipLaunchKernelGGL(frame_ingest_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames, out, B, H,
+                     W, K_out, tiles_x, tiles);
+  return g6d_check_launch("frame_ingest");
+}

@@ -1,0 +1,255 @@
+"""Device-side frame ingest (reference prepare.py:16-42 `video2image` + predict.py:45,52-54): camera-native frames -> the uint8 RGB
+working-resolution images and intrinsics the networks take, in ONE launch of g6d_frame_ingest (csrc/ingest.hip) for any number of frames.
+
+A `Frame` describes one picture as a camera or a video decoder delivers it: packed rgb24 / bgr24 / rgba32 / bgra32 or NV12, any size up to
+8192, any row pitch, host or device memory, optionally turned by quarter turns.  `plan` places it in a canvas (scaled to fit, top-left
+corner) and maps its intrinsics; `ingest_frames` uploads what lives on the host through pinned memory without blocking and launches once.
+The reference's `--resolution R` is `canvas_for(R, h, w)`; its `--transpose` is rotate=180 with cv2 >= 4.5 (two flips) and
+rotate=90 with older versions (transpose + horizontal flip).  The scaling is the integer bilinear of DESIGN.md §4.17, not cv2's float one.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import eval as EV
+from . import lib as _lib
+from . import ops
+
+FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4}
+MATRICES = {"bt601": 0, "bt709": 1}
+BPP = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1}
+MAX_SIZE = 8192
+
+
+def _strides(a):
+    return tuple(a.stride()) if torch.is_tensor(a) else a.strides
+
+
+def _u8(a, what):
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+    if a.dtype not in (np.uint8, torch.uint8):
+        raise ValueError(f"Frame: {what} must be uint8")
+    if not 1 <= a.ndim <= 3:
+        raise ValueError(f"Frame: {what} must have 1 to 3 dimensions")
+    return a
+
+
+def _rows(a, inner):
+    """a ([rows, bytes] or [rows, w, c]) -> (a with unit-stride rows, pitch in bytes); copies only a layout a pitch cannot describe."""
+    st = _strides(a)
+    ok = st[-1] == 1 and (a.ndim == 2 or st[1] == inner) and (a.shape[0] == 1 or st[0] >= a.shape[1] * (inner if a.ndim == 3 else 1))
+    if not ok:
+        a = a.contiguous() if torch.is_tensor(a) else np.ascontiguousarray(a)
+        st = _strides(a)
+    return a, int(st[0])
+
+
+def _span(a, row_bytes, rows, pitch, offset=0):
+    """Flat view of `rows` rows of `row_bytes` bytes, `pitch` apart, inside a's memory (checked against a's extent)."""
+    need = (rows - 1) * pitch + row_bytes
+    st, sh = _strides(a), a.shape
+    extent = 1 + sum((n - 1) * s for n, s in zip(sh, st))
+    if offset + need > extent:
+        raise ValueError(f"Frame: the buffer holds {extent} bytes, {offset + need} are needed for {rows} rows of pitch {pitch}")
+    if torch.is_tensor(a):
+        return torch.as_strided(a, (need,), (1,), a.storage_offset() + offset)
+    base = np.lib.stride_tricks.as_strided(a, (extent,), (1,))
+    return base[offset:offset + need]
+
+
+class Frame:
+    """One source picture.  data: uint8 numpy array or torch tensor (host or device), [H,W,C] (C = 3 / 4 as the format says; sizes and
+    the pitch are taken from it), [rows, row bytes] or a flat buffer (give width / height / pitch).  NV12: either one [H*3/2, pitch] buffer
+    (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV plane ([H/2, bytes] or [H/2, W/2, 2]).
+    rotate: quarter turns clockwise applied after scaling (0 / 90 / 180 / 270).  K: the camera's intrinsics in SOURCE pixel coordinates, or
+    None for predict.py's pseudo intrinsics of the ingested picture.  matrix: "bt601" / "bt709" (limited range), NV12 only."""
+
+    def __init__(self, data, fmt="rgb24", width=None, height=None, pitch=None, rotate=0, K=None, uv=None, uv_pitch=None, matrix="bt601"):
+        if fmt not in FORMATS:
+            raise ValueError(f"Frame: unknown format {fmt!r} (one of {sorted(FORMATS)})")
+        if matrix not in MATRICES:
+            raise ValueError(f"Frame: unknown matrix {matrix!r} (bt601 or bt709)")
+        if rotate not in (0, 90, 180, 270):
+            raise ValueError(f"Frame: rotate must be 0, 90, 180 or 270, not {rotate!r}")
+        nv12, bpp = fmt == "nv12", BPP[fmt]
+        if uv is not None and not nv12:
+            raise ValueError("Frame: uv is the second plane of an nv12 frame")
+        d = _u8(data, "data")
+        if d.ndim == 3:
+            if nv12 or d.shape[2] != bpp:
+                raise ValueError(f"Frame: a {fmt} frame cannot be a {tuple(d.shape)} array")
+            d, p = _rows(d, bpp)
+            h, w = d.shape[:2]
+        elif d.ndim == 2:
+            d, p = _rows(d, 1)
+            if nv12 and uv is None:
+                if d.shape[0] % 3:
+                    raise ValueError("Frame: a one-buffer nv12 frame has H*3/2 rows")
+                h = d.shape[0] * 2 // 3
+            else:
+                h = d.shape[0]
+            w = width if width is not None else d.shape[1] // bpp
+        else:
+            if width is None or height is None:
+                raise ValueError("Frame: a flat buffer needs width and height")
+            if not (torch.is_tensor(d) or d.flags.c_contiguous) or _strides(d)[0] != 1:
+                d = d.contiguous() if torch.is_tensor(d) else np.ascontiguousarray(d)
+            h, w, p = height, width, (pitch if pitch is not None else int(width) * bpp)
+        if (width is not None and int(width) != w) or (height is not None and int(height) != h):
+            raise ValueError(f"Frame: width / height {width} x {height} given, the data says {w} x {h}")
+        if pitch is not None and d.ndim > 1 and int(pitch) != p and d.shape[0] > 1:
+            raise ValueError(f"Frame: pitch {pitch} given, the array's rows are {p} bytes apart")
+        w, h, p = int(w), int(h), int(p)
+        if not (1 <= w <= MAX_SIZE and 1 <= h <= MAX_SIZE):
+            raise ValueError(f"Frame: size {w} x {h} outside 1..{MAX_SIZE}")
+        if p < w * bpp:
+            raise ValueError(f"Frame: pitch {p} is smaller than a row of {w} {fmt} pixels")
+        self.fmt, self.width, self.height, self.pitch, self.rotate, self.matrix = fmt, w, h, p, int(rotate), matrix
+        self.K = None if K is None else np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float64).reshape(3, 3)
+        self.plane0 = _span(d, w * bpp, h, p)
+        self.plane1, self.uv_pitch = None, 0
+        if nv12:
+            if w % 2 or h % 2:
+                raise ValueError(f"Frame: an nv12 frame has even width and height, not {w} x {h}")
+            if uv is None:
+                if uv_pitch is not None and int(uv_pitch) != p:
+                    raise ValueError("Frame: a one-buffer nv12 frame has one pitch")
+                self.uv_pitch = p
+                self.plane1 = _span(d, w, h // 2, p, offset=p * h)
+            else:
+                u = _u8(uv, "uv")
+                if type(u) is not type(d) or (torch.is_tensor(u) and u.device != d.device):
+                    raise ValueError("Frame: data and uv must live in the same kind of memory")
+                if u.ndim == 1:
+                    up = int(uv_pitch) if uv_pitch is not None else w
+                else:
+                    u, up = _rows(u, 2)
+                    if u.shape[0] != h // 2 or (u.ndim == 3 and (u.shape[1] != w // 2 or u.shape[2] != 2)):
+                        raise ValueError(f"Frame: uv plane {tuple(u.shape)} does not belong to a {w} x {h} nv12 frame")
+                    if uv_pitch is not None and int(uv_pitch) != up and u.shape[0] > 1:
+                        raise ValueError(f"Frame: uv_pitch {uv_pitch} given, the array's rows are {up} bytes apart")
+                if up < w:
+                    raise ValueError(f"Frame: uv pitch {up} is smaller than a row of {w // 2} UV pairs")
+                self.uv_pitch = up
+                self.plane1 = _span(u, w, h // 2, up)
+
+    @property
+    def on_device(self):
+        return torch.is_tensor(self.plane0) and self.plane0.device.type != "cpu"
+
+    def rotated_size(self):
+        """(height, width) of the source after the rotation."""
+        return (self.width, self.height) if self.rotate in (90, 270) else (self.height, self.width)
+
+
+def canvas_for(resolution, h, w, rotate=0):
+    """(H, W) of the image the reference's video2image makes of an h x w frame at --resolution (prepare.py:27-29), turned by `rotate`."""
+    ratio = resolution / max(h, w)
+    H, W = int(ratio * h), int(ratio * w)
+    return (W, H) if rotate in (90, 270) else (H, W)
+
+
+def pixel_map(frame, out_h, out_w):
+    """3x3 affine map (float64) from SOURCE pixel coordinates to pixel coordinates of the ingested out_h x out_w picture: the half-pixel
+    centre scaling u' = (u + 0.5) * wt / ws - 0.5 followed by the rotation's pixel map (include/gen6d_hip.h)."""
+    wt, ht = (out_h, out_w) if frame.rotate in (90, 270) else (out_w, out_h)
+    sx, sy = wt / frame.width, ht / frame.height
+    S = np.array([[sx, 0, 0.5 * sx - 0.5], [0, sy, 0.5 * sy - 0.5], [0, 0, 1]], np.float64)
+    R = {0: [[1, 0, 0], [0, 1, 0], [0, 0, 1]], 90: [[0, -1, ht - 1], [1, 0, 0], [0, 0, 1]],
+         180: [[-1, 0, wt - 1], [0, -1, ht - 1], [0, 0, 1]], 270: [[0, 1, 0], [-1, 0, wt - 1], [0, 0, 1]]}[frame.rotate]
+    return np.asarray(R, np.float64) @ S
+
+
+def plan(frame, canvas_hw):
+    """-> (out_h, out_w, K'): the size of the scaled and rotated picture that fits the canvas with the source's aspect ratio (it sits at the
+    top-left corner) and its intrinsics, float64: A @ K for a frame with K, predict.py's pseudo K of the picture otherwise."""
+    H, W = int(canvas_hw[0]), int(canvas_hw[1])
+    if H < 1 or W < 1:
+        raise ValueError("plan: the canvas must be at least 1 x 1")
+    hs, ws = frame.rotated_size()
+    if H * ws <= W * hs:
+        out_h, out_w = H, max(1, H * ws // hs)
+    else:
+        out_w, out_h = W, max(1, W * hs // ws)
+    if frame.K is None:
+        return out_h, out_w, EV.pseudo_K(out_h, out_w).astype(np.float64)
+    return out_h, out_w, pixel_map(frame, out_h, out_w) @ frame.K
+
+
+def _host(p):
+    return p.numpy() if torch.is_tensor(p) else p
+
+
+def ingest_frames(frames, out, K_out, slots=None, stream=None):
+    """frames (Frame objects) -> out[slot] uint8 [B,H,W,3] and K_out[slot] float32 [B,3,3], slot i by default; one launch on `stream` (the
+    current stream if None).  Host-resident planes and the descriptor table are gathered in one pinned staging buffer and travel in one
+    non-blocking copy (copying planes that already are pinned one by one was measured slower); device-resident planes
+    are recorded on the stream.  Does not synchronise.  Slots no frame names keep their content."""
+    frames = list(frames)
+    n = len(frames)
+    if out.dim() != 4 or out.shape[3] != 3:
+        raise ValueError("ingest_frames: out must be a uint8 [B,H,W,3] tensor")
+    B, H, W = out.shape[:3]
+    slots = list(range(n)) if slots is None else [int(s) for s in slots]
+    if len(slots) != n or len(set(slots)) != n or any(not 0 <= s < B for s in slots):
+        raise ValueError(f"ingest_frames: one distinct slot in [0, {B}) per frame expected")
+    dev = out.device
+    cuda = dev.type == "cuda"
+    size = C.sizeof(_lib.G6dFrame)
+    table = (_lib.G6dFrame * max(n, 1))()
+    staged = []                                # host planes: (frame index, field, bytes)
+    for i, f in enumerate(frames):
+        if not isinstance(f, Frame):
+            raise ValueError("ingest_frames: Frame objects expected")
+        out_h, out_w, K = plan(f, (H, W))
+        e = table[i]
+        e.pitch0, e.pitch1, e.width, e.height = f.pitch, f.uv_pitch, f.width, f.height
+        e.format, e.rotate, e.matrix, e.slot, e.out_w, e.out_h = FORMATS[f.fmt], f.rotate, MATRICES[f.matrix], slots[i], out_w, out_h
+        e.K[:] = np.asarray(K, np.float64).astype(np.float32).reshape(9).tolist()
+        for field, p in (("plane0", f.plane0), ("plane1", f.plane1)):
+            if p is None:
+                continue
+            if f.on_device:
+                if p.device != dev:
+                    raise ValueError(f"ingest_frames: frame {i} lives on {p.device}, out on {dev}")
+                setattr(e, field, p.data_ptr())
+            else:
+                staged.append((i, field, _host(p)))
+    if n == 0:
+        return out
+    # layout of the upload (one pinned buffer, one copy): staged planes | table
+    offs, total = [], 0
+    for _, _, p in staged:
+        offs.append(total)
+        total += (p.shape[0] + 255) & ~255
+    toff = total
+    total = toff + n * size
+    ctx = torch.cuda.stream(stream) if (cuda and stream is not None) else None
+    if ctx is not None:
+        ctx.__enter__()
+    try:
+        if cuda:
+            cur = torch.cuda.current_stream(dev)
+            for f in frames:
+                if f.on_device:
+                    f.plane0.record_stream(cur)
+                    if f.plane1 is not None:
+                        f.plane1.record_stream(cur)
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        else:
+            host = buf = torch.empty(total, dtype=torch.uint8)
+        hn, base = host.numpy(), buf.data_ptr()
+        for (i, field, p), off in zip(staged, offs):
+            hn[off:off + p.shape[0]] = p
+            setattr(table[i], field, base + off)
+        hn[toff:] = np.frombuffer(table, np.uint8, n * size)
+        if cuda:
+            buf.copy_(host, non_blocking=True)
+        ops.frame_ingest(buf[toff:], n, out, K_out)
+    finally:
+        if ctx is not None:
+            ctx.__exit__(None, None, None)
+    return out

@@ -33,6 +33,13 @@ class G6dCorrSeg(C.Structure):
                 ("N", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class G6dFrame(C.Structure):
+    """include/gen6d_hip.h: one source frame of g6d_frame_ingest (the table lives in device memory)."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("pitch0", C.c_int32), ("pitch1", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("format", C.c_int32), ("rotate", C.c_int32), ("matrix", C.c_int32), ("slot", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("K", C.c_float * 9)]
+
+
 class G6dConv(C.Structure):
     _fields_ = [
         ("in_", C.c_void_p), ("mul", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p),
@@ -114,6 +121,8 @@ SIGNATURES = {
     "g6d_warp_perspective": [_P, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _I, _I, _F, _P],
     "g6d_track_gather": [_P, _P, _P, _P, _I, _P],
     "g6d_track_commit": [_P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P, _I, _P],
+    "g6d_frame_ingest": [_P, _I, _P, _I, _I, _I, _P, _P],
+    "g6d_sizeof_frame_desc": [],
 }
 
 _lib = None
@@ -139,6 +148,8 @@ def load():
     lib.g6d_sizeof_conv_desc.restype = C.c_int
     if lib.g6d_sizeof_conv_desc() != C.sizeof(G6dConv):
         raise RuntimeError("libgen6d_hip.so: G6dConv layout differs from the ctypes binding (stale build?)")
+    if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
+        raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
     lib.g6d_last_error.restype = C.c_char_p
     lib.g6d_set_knob.argtypes, lib.g6d_set_knob.restype = [C.c_char_p, C.c_double], C.c_int
     lib.g6d_get_knob.argtypes, lib.g6d_get_knob.restype = [C.c_char_p], C.c_double

@@ -1491,3 +1491,22 @@ def track_commit(pose, K, slot_stream, reset, box, num, std, pose_table, hist, h
                                            _ptr(pose_table), _ptr(hist), _ptr(hist_count), _ptr(smooth_table), _ptr(out), B, _stream()),
                "g6d_track_commit")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ frame ingest
+def frame_ingest(table, n, out, K_out):
+    """One launch of g6d_frame_ingest: `table` a contiguous uint8 device tensor holding n lib.G6dFrame records (8-byte aligned; built and
+    validated by gen6d_amd.ingest.ingest_frames), out uint8 [B,H,W,3], K_out float32 [B,3,3].  Every frame's picture is written into
+    out[slot] (the rest of that canvas 0) and its K into K_out[slot]; other slots are not touched."""
+    _track_same_device("frame_ingest", table, out, K_out)
+    n = int(n)
+    size = C.sizeof(_lib.G6dFrame)
+    if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or n < 0 or table.numel() < n * size or table.data_ptr() % 8:
+        raise ValueError(f"frame_ingest: table must be a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
+    if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[3] != 3 or not out.is_contiguous():
+        raise ValueError("frame_ingest: out must be a contiguous uint8 [B,H,W,3] tensor")
+    B, H, W = out.shape[:3]
+    if K_out.dtype != torch.float32 or tuple(K_out.shape) != (B, 3, 3) or not K_out.is_contiguous():
+        raise ValueError("frame_ingest: K_out must be a contiguous float32 [B,3,3] tensor")
+    _lib.check(_lib.load().g6d_frame_ingest(_ptr(table), n, _ptr(out), B, H, W, _ptr(K_out), _stream()), "g6d_frame_ingest")
+    return out

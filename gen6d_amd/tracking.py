@@ -13,7 +13,10 @@ many streams (cameras or clients watching one object) at once:
   * each lane has one captured hipGraph of the tick (captured lazily, after warm-up runs on an all-unused slot map) with static image,
     K and slot-map buffers that are filled on the lane's stream before each replay; unused slots (id -1) refine the parking pose
     (DeviceChain.ref_poses[0]) and are not committed;
-  * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners.
+  * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners;
+  * with `frame_size=(H, W)` the tracker takes camera-native frames (`gen6d_amd.ingest.Frame`: any size, packed RGB / BGR(A) or NV12,
+    pitched, rotated, mixed within one push): one g6d_frame_ingest launch per lane and tick scales them into the lane's static image
+    slots and writes their intrinsics, in place of the per-slot copies.
 
 `track_streams` is the one-call form for whole sequences, with one synchronisation at the end and the networks' fp16 pair range guard.
 """
@@ -22,6 +25,7 @@ import torch
 
 from . import eval as EV
 from . import geometry as G
+from . import ingest as I
 from . import ops
 from .network import refiner as _refiner
 
@@ -56,7 +60,7 @@ class _Serial:
 
 class StreamTracker:
     def __init__(self, estimator, max_streams, batch=8, lanes=2, track_iter=1, smooth_num=5, smooth_std=2.5, object_pts=None,
-                 graphs=True):
+                 graphs=True, frame_size=None):
         if estimator.refiner is None:
             raise ValueError("StreamTracker: the estimator has no refiner (tracking refines every frame)")
         self.max_streams, self.batch, self.nlanes = int(max_streams), int(batch), int(lanes)
@@ -91,6 +95,12 @@ class StreamTracker:
         self._started = [False] * S
         self._frames = [0] * S                 # frames pushed per stream
         self._shape = None
+        self.frame_size = None                 # (H, W): frames of any size and format are ingested into H x W images on the device
+        if frame_size is not None:
+            if len(frame_size) != 2 or min(int(v) for v in frame_size) < 1:
+                raise ValueError("StreamTracker: frame_size must be (H, W) with H, W >= 1")
+            self.frame_size = (int(frame_size[0]), int(frame_size[1]))
+            self._shape = self.frame_size + (3,)
         self._records = None                   # track_streams: [(rows [n,2,3,4] device, [(row, stream, frame)])]
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
             t = net.__dict__.get("_range")
@@ -100,13 +110,20 @@ class StreamTracker:
     # ------------------------------------------------------------------ public API
     def push(self, stream_ids, imgs, Ks=None):
         """Enqueue one frame per listed stream: imgs uint8 [H,W,3] (numpy or device tensors; one shape per tracker), Ks [3,3] per stream
-        (None: predict.py's pseudo K).  Does not synchronise."""
+        (None: predict.py's pseudo K).  A tracker with `frame_size` takes `ingest.Frame`s of any size and format instead (plain [h,w,3]
+        arrays count as rgb24 frames); their intrinsics travel in Frame.K, so Ks must be None.  Does not synchronise."""
         ids = self._ids(stream_ids)
         if len(imgs) != len(ids) or (Ks is not None and len(Ks) != len(ids)):
             raise ValueError("StreamTracker.push: one image (and K) per stream id expected")
-        frames = [self._frame(im) for im in imgs]
-        h, w = self._shape[:2]
-        Ks = [EV.pseudo_K(h, w) if Ks is None else Ks[i] for i in range(len(ids))]
+        if self.frame_size is not None:
+            if Ks is not None:
+                raise ValueError("StreamTracker.push: a tracker with frame_size takes the intrinsics in Frame.K, not in Ks")
+            frames = [im if isinstance(im, I.Frame) else I.Frame(self._rgb(im)) for im in imgs]
+            Ks = [None] * len(ids)
+        else:
+            frames = [self._frame(im) for im in imgs]
+            h, w = self._shape[:2]
+            Ks = [EV.pseudo_K(h, w) if Ks is None else Ks[i] for i in range(len(ids))]
         groups = {}
         for i, s in enumerate(ids):
             groups.setdefault(s // self.batch, []).append((s, frames[i], Ks[i]))
@@ -116,8 +133,11 @@ class StreamTracker:
             if cur is not None:
                 lane.stream.wait_stream(cur)
             with _Serial(lane.stream):
-                ents = [(s, self._upload(im, lane), self._upload(K.reshape(3, 3).float() if torch.is_tensor(K) else
-                                                             np.asarray(K, np.float32).reshape(3, 3), lane)) for s, im, K in groups[g]]
+                if self.frame_size is not None:
+                    ents = groups[g]           # (stream, Frame, None): uploaded and converted by the lane's ingest launch
+                else:
+                    ents = [(s, self._upload(im, lane), self._upload(K.reshape(3, 3).float() if torch.is_tensor(K) else
+                                                                 np.asarray(K, np.float32).reshape(3, 3), lane)) for s, im, K in groups[g]]
                 track = [e for e in ents if self._started[e[0]]]
                 init = [e for e in ents if not self._started[e[0]]]
                 if track:
@@ -160,12 +180,18 @@ class StreamTracker:
             raise ValueError("StreamTracker: a stream id is listed twice")
         return ids
 
-    def _frame(self, im):
+    @staticmethod
+    def _rgb(im):
         if not torch.is_tensor(im):
             im = np.asarray(im)
         shape, dtype = tuple(im.shape), im.dtype
         if dtype not in (np.uint8, torch.uint8) or len(shape) != 3 or shape[2] != 3:
             raise ValueError("StreamTracker: frames must be uint8 [H,W,3]")
+        return im
+
+    def _frame(self, im):
+        im = self._rgb(im)
+        shape = tuple(im.shape)
         if self._shape is None:
             self._shape = shape
         elif shape != self._shape:
@@ -220,9 +246,12 @@ class StreamTracker:
             m[b] = s
         if self.graphs and lane.graph is None:
             self._capture(lane)
-        for (s, im, K), b in zip(ents, slots):
-            lane.img[b].copy_(im)
-            lane.K[b].copy_(K)
+        if self.frame_size is not None:        # one launch fills the named slots of the static image and K buffers
+            I.ingest_frames([f for _, f, _ in ents], lane.img, lane.K, slots=slots)
+        else:
+            for (s, im, K), b in zip(ents, slots):
+                lane.img[b].copy_(im)
+                lane.K[b].copy_(K)
         lane.map.copy_(self._upload(m))
         if self.graphs:
             lane.graph.replay()
@@ -234,8 +263,13 @@ class StreamTracker:
 
     def _init(self, ents):
         n = len(ents)
-        imgs = torch.stack([im for _, im, _ in ents], 0)
-        Ks = torch.stack([K for _, _, K in ents], 0)
+        if self.frame_size is not None:
+            imgs = torch.empty((n,) + self._shape, dtype=torch.uint8, device=self.dev)
+            Ks = torch.empty((n, 3, 3), dtype=torch.float32, device=self.dev)
+            I.ingest_frames([f for _, f, _ in ents], imgs, Ks)
+        else:
+            imgs = torch.stack([im for _, im, _ in ents], 0)
+            Ks = torch.stack([K for _, _, K in ents], 0)
         r = self.chain.query_batch(imgs, Ks)
         ids = self._upload(np.asarray([s for s, _, _ in ents], np.int32))
         out = ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), ids, True, self.box, self.num, self.std, self.pose_table, self.hist,
@@ -291,6 +325,18 @@ def _stream_Ks(Ks, seqs):
     return out
 
 
+def _ingest_to_host(frames, frame_size, device):
+    """Frames of any format -> ([H,W,3] uint8 arrays, [3,3] float32 Ks) through the device ingest (track_streams' rare fallback path)."""
+    imgs, Ks = [], []
+    for f in frames:
+        img = torch.empty((1, int(frame_size[0]), int(frame_size[1]), 3), dtype=torch.uint8, device=device)
+        K = torch.empty((1, 3, 3), dtype=torch.float32, device=device)
+        I.ingest_frames([f if isinstance(f, I.Frame) else I.Frame(StreamTracker._rgb(f))], img, K)
+        imgs.append(img[0].cpu().numpy())
+        Ks.append(K[0].cpu().numpy())
+    return imgs, Ks
+
+
 def host_track(estimator, frames, Ks, track_iter=1, smooth_num=5, smooth_std=2.5, box=None):
     """One stream through the host-driven loop of predict.py:49-72: `estimator.predict` per frame (first frame: cfg['refine_iter'] steps,
     later frames: `track_iter` steps from the previous pose) and the numpy box smoothing + PnP -> (poses [T,3,4], smoothed [T,3,4])."""
@@ -312,23 +358,31 @@ def host_track(estimator, frames, Ks, track_iter=1, smooth_num=5, smooth_std=2.5
 
 def track_streams(estimator, streams, Ks=None, **tracker_kw):
     """S frame sequences (possibly of different lengths; uint8 [H,W,3] frames of one shape) -> per stream (poses [T,3,4], smoothed
-    [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  Frame t of
+    [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  With
+    `frame_size=(H, W)` the frames are `ingest.Frame`s (or [h,w,3] arrays) of any size and format, carry their own K, and Ks stays None.  Frame t of
     every stream that has one is pushed in tick t; one synchronisation at the end.  Runs under the estimator's range guard: if an fp16
     pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32."""
     seqs = [list(s) for s in streams]
-    Kss = _stream_Ks(Ks, seqs)
     kw = dict(tracker_kw)
+    native = kw.get("frame_size") is not None
+    if native and Ks is not None:
+        raise ValueError("track_streams: with frame_size the intrinsics travel in Frame.K, not in Ks")
+    Kss = None if native else _stream_Ks(Ks, seqs)
 
     def run():
         tr = StreamTracker(estimator, len(seqs), **kw)
         tr._records = []
         for t in range(max((len(s) for s in seqs), default=0)):
             ids = [s for s in range(len(seqs)) if t < len(seqs[s])]
-            tr.push(ids, [seqs[s][t] for s in ids], [Kss[s][t] for s in ids])
+            tr.push(ids, [seqs[s][t] for s in ids], None if native else [Kss[s][t] for s in ids])
         return tr._collect([len(s) for s in seqs])
 
     def recompute():
         box = None if kw.get("object_pts") is None else G.box_corners(kw["object_pts"])
+        if native:                             # the host loop takes plain arrays: ingest each frame on the device and read it back
+            host = [_ingest_to_host(frames, kw["frame_size"], estimator.device) for frames in seqs]
+            return [host_track(estimator, fr, Kh, kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
+                    for fr, Kh in host]
         return [host_track(estimator, frames, Kss[s], kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
                 for s, frames in enumerate(seqs)]
     return estimator._range_guarded(run, recompute)

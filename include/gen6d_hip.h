@@ -559,6 +559,37 @@ int g6d_track_gather(const float* pose_table, const int* slot_stream, const floa
 int g6d_track_commit(const float* pose, const float* K, const int* slot_stream, int reset, const float* box, int num, float std,
                      float* pose_table, double* hist, int* hist_count, float* smooth_table, float* out, int batch, g6d_stream_t stream);
 
+/* Frame ingest (gen6d_amd/ingest.py; reference prepare.py:16-42 video2image + predict.py:45,52-54); additive within ABI 12.  ONE launch
+ * reads n camera-native frames (packed RGB / BGR / RGBA / BGRA or NV12, any size, row pitch and quarter-turn rotation), scales each to
+ * out_w x out_h with the integer bilinear below, and writes the RGB picture into the top-left corner of image `slot` of
+ * out [B][H][W][3] uint8 (canvas pixels outside the picture are written as 0) and the frame's K into K_out [B][3][3].  Slots that no frame
+ * names are not touched; a frame whose slot lies outside [0, B) is skipped; two frames must not name the same slot.
+ * The table lives in DEVICE memory (it changes with every call, so the launch stays outside captured graphs); the caller validates its
+ * contents: planes cover height rows of pitch bytes, 1 <= width, height <= 8192, even sizes for NV12, out_w <= W, out_h <= H.
+ * Arithmetic (exact integers, the numpy restatement in tests/test_ingest_cpu.py is bit-identical): with wt x ht the scaled
+ * picture before rotation ((out_w, out_h) for rotate 0 / 180, (out_h, out_w) for 90 / 270) and ws x hs the source,
+ *   fx = clamp(floor((2x+1) * ws * 1024 / wt) - 1024, 0, (ws-1) * 2048), x0 = fx >> 11, a = fx & 2047, x1 = min(x0+1, ws-1), y likewise (b);
+ *   each tap is converted to RGB, then per channel v = ((2048-a)(2048-b) p00 + a(2048-b) p01 + (2048-a) b p10 + a b p11 + 2^21) >> 22;
+ *   NV12 tap: chroma UV[y>>1][x>>1], c = max(Y-16, 0), d = U-128, e = V-128, R = sat8((CY c + CVR e + 2^19) >> 20),
+ *   G = sat8((CY c - CUG d - CVG e + 2^19) >> 20), B = sat8((CY c + CUB d + 2^19) >> 20) with round(k * 2^20) constants of BT.601 / BT.709
+ *   limited range; canvas pixel (X, Y) of a picture turned clockwise by 90 is the unrotated (Y, ht-1-X), 180: (wt-1-X, ht-1-Y),
+ *   270: (wt-1-Y, X). */
+enum { G6D_FMT_RGB24 = 0, G6D_FMT_BGR24 = 1, G6D_FMT_RGBA32 = 2, G6D_FMT_BGRA32 = 3, G6D_FMT_NV12 = 4 };
+typedef struct G6dFrame {          /* one per frame */
+  const void* plane0;              /* packed pixels, or the Y plane of NV12 */
+  const void* plane1;              /* NV12: interleaved UV plane; else NULL */
+  int32_t pitch0, pitch1;          /* bytes per source row */
+  int32_t width, height;           /* source size in pixels, 1..8192 */
+  int32_t format;                  /* G6D_FMT_* */
+  int32_t rotate;                  /* 0 / 90 / 180 / 270 degrees clockwise */
+  int32_t matrix;                  /* NV12 only: 0 BT.601 limited range, 1 BT.709 limited range */
+  int32_t slot;                    /* destination image index in `out`; outside [0, B): frame skipped */
+  int32_t out_w, out_h;            /* size of the scaled AND rotated picture inside the canvas */
+  float   K[9];                    /* intrinsics of the canvas picture, written to K_out[slot] */
+} G6dFrame;
+int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int B, int H, int W, float* K_out, g6d_stream_t stream);
+int g6d_sizeof_frame_desc(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,93 @@
+"""The frame-ingest kernel alone (csrc/ingest.hip): 32 device-resident frames per launch, two cases:
+
+  nv12-1080p   32 x (1080x1920 NV12 -> 540x960 canvas)
+  rgb-same     32 x (480x640 rgb24 -> 480x640 canvas)
+
+Bytes are counted from shapes: the source rows a launch touches (every row of every plane, pixel bytes only) plus the canvas bytes it
+writes.  Timing: device events around `--launches` back-to-back launches (includes the table upload of each call), or, under the profiler,
+the kernel's own durations:
+
+  python tools/ingest_bench.py [--launches 50]
+  rocprofv3 --kernel-trace -d DIR -o ingest --output-format csv -- python tools/ingest_bench.py
+  python tools/ingest_bench.py --trace-csv DIR/.../ingest_kernel_trace.csv [--tick-ms T] [--out FILE.md]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_BPS = 6.3e12          # achievable HBM rate the shares are quoted against
+CASES = {"nv12-1080p": dict(src=(1080, 1920), fmt="nv12", canvas=(540, 960)), "rgb-same": dict(src=(480, 640), fmt="rgb24", canvas=(480, 640))}
+N = 32
+
+
+def case_bytes(c):
+    (h, w), (H, W) = c["src"], c["canvas"]
+    src = h * w * 3 // 2 if c["fmt"] == "nv12" else h * w * 3
+    return N * (src + H * W * 3)
+
+
+def trace_table(path, launches, tick_ms):
+    import csv
+    rows = [r for r in csv.DictReader(open(path)) if "frame_ingest" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    warm = 3
+    out = ["| case | launches | kernel us (median) | min | max | bytes per launch | TB/s (median) | share of 6.3 TB/s | share of a tick |",
+           "|---|---:|---:|---:|---:|---:|---:|---:|---:|"]
+    per = warm + launches
+    for i, (name, c) in enumerate(CASES.items()):
+        d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[i * per + warm:(i + 1) * per]])
+        if not len(d):
+            continue
+        b, med = case_bytes(c), float(np.median(d))
+        tick = f"{med / (tick_ms * 1e3):.2%}" if tick_ms else "-"
+        out.append(f"| {name} | {len(d)} | {med:.1f} | {d.min():.1f} | {d.max():.1f} | {b / 1e6:.1f} MB | {b / med / 1e6:.2f} | "
+                   f"{b / med / 1e6 / (HBM_BPS / 1e12):.1%} | {tick} |")
+    return "\n".join(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--trace-csv", default=None)
+    ap.add_argument("--tick-ms", type=float, default=0.0, help="tick time of the 32-stream tracker the kernel time is set against")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.trace_csv:
+        txt = trace_table(args.trace_csv, args.launches, args.tick_ms)
+        print(txt)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write("\n## The ingest kernel (rocprofv3 --kernel-trace, tools/ingest_bench.py)\n\n32 device-resident frames per launch; bytes = "
+                        "source rows touched + canvas bytes, from shapes.\n\n" + txt + "\n")
+        return
+    import torch
+    from gen6d_amd.ingest import Frame, ingest_frames
+    if not torch.cuda.is_available():
+        sys.exit("ingest_bench: needs the GPU (the kernel has no CPU fallback)")
+    rng = np.random.RandomState(0)
+    for name, c in CASES.items():
+        (h, w), (H, W) = c["src"], c["canvas"]
+        shape = (h * 3 // 2, w) if c["fmt"] == "nv12" else (h, w, 3)
+        frames = [Frame(torch.from_numpy(rng.randint(0, 256, shape).astype(np.uint8)).cuda(), c["fmt"]) for _ in range(N)]
+        out = torch.zeros((N, H, W, 3), dtype=torch.uint8, device="cuda")
+        K = torch.zeros((N, 3, 3), device="cuda")
+        for _ in range(3):
+            ingest_frames(frames, out, K)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            ingest_frames(frames, out, K)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / args.launches
+        b = case_bytes(c)
+        print(f"{name}: {us:.1f} us per call (events, table upload included), {b / 1e6:.1f} MB -> {b / us / 1e6:.2f} TB/s", flush=True)
+
+
+if __name__ == "__main__":
+    main()

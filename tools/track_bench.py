@@ -7,6 +7,7 @@ clock starts (the upload of a user's numpy frames is not part of the tick).  Gra
 each; the table gives the median and the spread (max - min) / median.
 
   python tools/track_bench.py [--streams 1,8,32] [--frames 30] [--repeats 3] [--out profiles/r08_track_bench.md]
+  python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p        (graphs only, the variants alternated)
   rocprofv3 --kernel-trace --stats -d DIR -o track -- python tools/track_bench.py --profile 32      (one configuration, graphs)
   python tools/track_bench.py --stats-csv DIR/.../track_kernel_stats.csv --ticks N --tick-ms T --out profiles/r08_track_kernel_stats.md
 """
@@ -42,13 +43,41 @@ def build(dev):
     return est, frames, K
 
 
-def run(est, frames, K, S, F, batch, graphs):
-    """-> (seconds of the timed ticks, timed ticks)."""
+def native_frames(frames, K, mode):
+    """The frames a tracker with frame_size is fed -> (Frame list, canvas).
+    same: the device-resident 480x640 RGB frames with their K, through the ingest launch (the computation of the plain path).
+    nv12-1080p: host-resident 1080x1920 NV12 frames (numpy) into a 540x960 canvas: each synthetic
+    frame enlarged 2.25x (nearest) into the left 1440 columns of a grey full-HD picture, BT.601; intrinsics: predict.py's pseudo K."""
+    import torch
+    from gen6d_amd.ingest import Frame
+    if mode == "same":
+        return [Frame(f, K=K) for f in frames], tuple(frames[0].shape[:2])
+    out = []
+    yi, xi = (np.arange(1080) / 2.25).astype(int), (np.arange(1440) / 2.25).astype(int)
+    for f in frames[:8]:
+        g = f.cpu().numpy()[yi][:, xi].astype(np.int64)
+        buf = np.full((1620, 1920), 128, np.uint8)
+        buf[:1080, :1440] = ((66 * g[..., 0] + 129 * g[..., 1] + 25 * g[..., 2] + 128) >> 8) + 16
+        c = g[::2, ::2]
+        buf[1080:, 0:1440:2] = ((-38 * c[..., 0] - 74 * c[..., 1] + 112 * c[..., 2] + 128) >> 8) + 128
+        buf[1080:, 1:1440:2] = ((112 * c[..., 0] - 94 * c[..., 1] - 18 * c[..., 2] + 128) >> 8) + 128
+        out.append(Frame(buf, "nv12"))
+    return out, (540, 960)
+
+
+def run(est, frames, K, S, F, batch, graphs, ingest=None):
+    """-> (seconds of the timed ticks, timed ticks).  ingest: None (plain frames, the tracker without frame_size) or a mode of
+    native_frames."""
     import torch
     from gen6d_amd.tracking import StreamTracker
-    tr = StreamTracker(est, S, batch=batch, graphs=graphs)
     ids = list(range(S))
-    Ks = [K] * S
+    if ingest in (None, "none"):
+        tr = StreamTracker(est, S, batch=batch, graphs=graphs)
+        Ks = [K] * S
+    else:
+        frames, canvas = native_frames(frames, K, ingest)
+        tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas)
+        Ks = None
     frame = lambda s, t: frames[(7 * s + t) % len(frames)]
     for t in range(2):                                  # first frames, then the tick that captures the lanes' graphs
         tr.push(ids, [frame(s, t) for s in ids], Ks)
@@ -84,6 +113,9 @@ def main():
     ap.add_argument("--profile", type=int, default=0, help="one graphs run of this many streams (for a rocprofv3 trace)")
     ap.add_argument("--stats-csv", default=None)
     ap.add_argument("--ticks", type=int, default=0)
+    ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p: graphs runs of these frame "
+                    "sources, alternated (with --profile: the one source of the profiled run)")
+    ap.add_argument("--batch", type=int, default=0, help="--profile: slots per lane (default min(streams, 8))")
     ap.add_argument("--tick-ms", type=float, default=0.0)
     args = ap.parse_args()
     if args.stats_csv:
@@ -100,12 +132,35 @@ def main():
     est, frames, K = build(dev)
     if args.profile:
         S = args.profile
-        dt, n = run(est, frames, K, S, args.frames, min(S, 8), True)
-        print(f"profile S={S}: {n} ticks, {dt / n * 1e3:.3f} ms/tick")
+        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest)
+        print(f"profile S={S} ingest={args.ingest}: {n} ticks, {dt / n * 1e3:.3f} ms/tick")
         return
     configs = [(int(s), min(int(s), 8)) for s in args.streams.split(",")]
     if 32 in [c[0] for c in configs]:
         configs.append((32, 32))
+    if args.ingest:
+        modes = args.ingest.split(",")
+        lines = ["| streams | batch | frames | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
+        for S, B in configs:
+            res = {m: [] for m in modes}
+            for _ in range(args.repeats):
+                for m in modes:                       # alternated
+                    dt, n = run(est, frames, K, S, args.frames, B, True, m)
+                    res[m].append((S * n / dt, dt / n * 1e3))
+            for m in modes:
+                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
+                med = float(np.median(fps))
+                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
+                             f"{', '.join(f'{v:.1f}' for v in fps)} |")
+                print(lines[-1], flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("# Tracked frames/s by frame source (tools/track_bench.py --ingest)\n\n"
+                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
+                        "of each source, alternated.  none: plain 480x640 device frames (tracker without frame_size); same: the same frames "
+                        "through the ingest launch; nv12-1080p: host-resident 1080x1920 NV12 frames into a 540x960 canvas, upload "
+                        "included.\n\n" + "\n".join(lines) + "\n")
+        return
     lines = ["| streams | batch | lanes | mode | tracked frames/s (median) | ms per tick | spread |", "|---:|---:|---:|---|---:|---:|---:|"]
     for S, B in configs:
         res = {True: [], False: []}
