@@ -40,6 +40,14 @@ class G6dFrame(C.Structure):
                 ("out_w", C.c_int32), ("out_h", C.c_int32), ("K", C.c_float * 9)]
 
 
+class G6dSink(C.Structure):
+    """include/gen6d_hip.h: one destination of g6d_frame_emit (the table lives in device memory)."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("pitch0", C.c_int32), ("pitch1", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("format", C.c_int32), ("matrix", C.c_int32), ("slot", C.c_int32), ("pic_w", C.c_int32),
+                ("pic_h", C.c_int32), ("thickness", C.c_int32), ("dot_radius", C.c_int32), ("line_rgb", C.c_int32), ("dot_rgb", C.c_int32),
+                ("box", C.c_int32)]
+
+
 class G6dConv(C.Structure):
     _fields_ = [
         ("in_", C.c_void_p), ("mul", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p),
@@ -123,6 +131,9 @@ SIGNATURES = {
     "g6d_track_commit": [_P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P, _I, _P],
     "g6d_frame_ingest": [_P, _I, _P, _I, _I, _I, _P, _P],
     "g6d_sizeof_frame_desc": [],
+    "g6d_track_corners": [_P, _P, _P, _P, _P, _P, _I, _P],
+    "g6d_frame_emit": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "g6d_sizeof_sink_desc": [],
 }
 
 _lib = None
@@ -150,6 +161,8 @@ def load():
         raise RuntimeError("libgen6d_hip.so: G6dConv layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
         raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
+    if lib.g6d_sizeof_sink_desc() != C.sizeof(G6dSink):
+        raise RuntimeError("libgen6d_hip.so: G6dSink layout differs from the ctypes binding (stale build?)")
     lib.g6d_last_error.restype = C.c_char_p
     lib.g6d_set_knob.argtypes, lib.g6d_set_knob.restype = [C.c_char_p, C.c_double], C.c_int
     lib.g6d_get_knob.argtypes, lib.g6d_get_knob.restype = [C.c_char_p], C.c_double

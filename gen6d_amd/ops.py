@@ -1510,3 +1510,44 @@ def frame_ingest(table, n, out, K_out):
         raise ValueError("frame_ingest: K_out must be a contiguous float32 [B,3,3] tensor")
     _lib.check(_lib.load().g6d_frame_ingest(_ptr(table), n, _ptr(out), B, H, W, _ptr(K_out), _stream()), "g6d_frame_ingest")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ annotated frame output
+def track_corners(table, K, slot_stream, box, pts=None, valid=None):
+    """The box (box [8,3]) projected under row slot_stream[b] of `table` (pose_table or smooth_table, float32 [S,12]) and K [B,3,3] / [B,9],
+    rounded floor(v + 0.5) -> (pts int32 [B,8,2], valid int32 [B]) (g6d_track_corners; `pts` / `valid`: optional destinations).  valid is 0
+    for an unused slot, a corner behind the camera or outside [-8192, 16383]."""
+    what = "track_corners"
+    _track_same_device(what, table, K, slot_stream, box)
+    _f32c(table, K, box)
+    B = _track_map(what, slot_stream)
+    if table.dim() != 2 or table.shape[1] != 12 or K.numel() != 9 * B or box.numel() != 24:
+        raise ValueError("track_corners: table [S,12], K [B,9] and box [8,3] expected")
+    if pts is None:
+        pts = torch.empty((B, 8, 2), dtype=torch.int32, device=table.device)
+    if valid is None:
+        valid = torch.empty((B,), dtype=torch.int32, device=table.device)
+    if (pts.dtype != torch.int32 or valid.dtype != torch.int32 or not pts.is_contiguous() or not valid.is_contiguous() or
+            tuple(pts.shape) != (B, 8, 2) or tuple(valid.shape) != (B,) or pts.device != table.device or valid.device != table.device):
+        raise ValueError("track_corners: pts must be a contiguous int32 [B,8,2] tensor and valid a contiguous int32 [B] tensor")
+    _lib.check(_lib.load().g6d_track_corners(_ptr(table), _ptr(K), _ptr(slot_stream), _ptr(box), _ptr(pts), _ptr(valid), B, _stream()),
+               "g6d_track_corners")
+    return pts, valid
+
+
+def frame_emit(table, n, imgs, pts, valid):
+    """One launch of g6d_frame_emit: `table` a contiguous uint8 device tensor holding n lib.G6dSink records (8-byte aligned; built and
+    validated by gen6d_amd.emit.emit_frames), imgs uint8 [B,H,W,3], pts int32 [sets,B,8,2] and valid int32 [sets,B] with 1 or 2 corner
+    sets.  Every sink receives image `slot` with the box of its corner set drawn on it, in its own format."""
+    _track_same_device("frame_emit", table, imgs, pts, valid)
+    n = int(n)
+    size = C.sizeof(_lib.G6dSink)
+    if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or n < 0 or table.numel() < n * size or table.data_ptr() % 8:
+        raise ValueError(f"frame_emit: table must be a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
+    if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or not imgs.is_contiguous():
+        raise ValueError("frame_emit: imgs must be a contiguous uint8 [B,H,W,3] tensor")
+    B, H, W = imgs.shape[:3]
+    if (pts.dtype != torch.int32 or valid.dtype != torch.int32 or not pts.is_contiguous() or not valid.is_contiguous() or pts.dim() != 4 or
+            pts.shape[0] not in (1, 2) or tuple(pts.shape[1:]) != (B, 8, 2) or tuple(valid.shape) != (pts.shape[0], B)):
+        raise ValueError("frame_emit: pts must be a contiguous int32 [sets,B,8,2] tensor and valid int32 [sets,B], sets 1 or 2")
+    _lib.check(_lib.load().g6d_frame_emit(_ptr(table), n, _ptr(imgs), B, H, W, _ptr(pts), _ptr(valid), _stream()), "g6d_frame_emit")

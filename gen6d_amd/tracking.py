@@ -16,13 +16,19 @@ many streams (cameras or clients watching one object) at once:
   * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners;
   * with `frame_size=(H, W)` the tracker takes camera-native frames (`gen6d_amd.ingest.Frame`: any size, packed RGB / BGR(A) or NV12,
     pitched, rotated, mixed within one push): one g6d_frame_ingest launch per lane and tick scales them into the lane's static image
-    slots and writes their intrinsics, in place of the per-slot copies.
+    slots and writes their intrinsics, in place of the per-slot copies (DESIGN.md §4.17);
+  * with `sinks` a push also writes what predict.py writes per frame: the working-resolution picture with the projected box drawn on it
+    (raw and / or smoothed pose), in an encoder's or a display's format, into device or pinned host buffers the caller names
+    (`gen6d_amd.emit.Sink`).  After the lane's tick (or the commit of an init chunk) the corners are projected on the device and ONE
+    g6d_frame_emit launch per lane and tick fills that lane's sinks, stream-ordered on the lane's stream, outside the captured graph
+    (DESIGN.md §4.18).  A tracker used without sinks launches nothing of this.
 
 `track_streams` is the one-call form for whole sequences, with one synchronisation at the end and the networks' fp16 pair range guard.
 """
 import numpy as np
 import torch
 
+from . import emit as E
 from . import eval as EV
 from . import geometry as G
 from . import ingest as I
@@ -35,6 +41,7 @@ INIT_CHUNK = 8          # first frames per query_batch call: the batch size quer
 class _Lane:
     def __init__(self, stream):
         self.stream, self.graph, self.img, self.K, self.map, self.out = stream, None, None, None, None, None
+        self.emitted = None                    # event recorded after the lane's last emit (wait_emitted)
 
 
 class _Serial:
@@ -102,19 +109,25 @@ class StreamTracker:
             self.frame_size = (int(frame_size[0]), int(frame_size[1]))
             self._shape = self.frame_size + (3,)
         self._records = None                   # track_streams: [(rows [n,2,3,4] device, [(row, stream, frame)])]
+        self._sinks = {}                       # the running push: stream id -> [Sink, ...]
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
             t = net.__dict__.get("_range")
             if t is not None and t.names:
                 t.clear()
 
     # ------------------------------------------------------------------ public API
-    def push(self, stream_ids, imgs, Ks=None):
+    def push(self, stream_ids, imgs, Ks=None, sinks=None):
         """Enqueue one frame per listed stream: imgs uint8 [H,W,3] (numpy or device tensors; one shape per tracker), Ks [3,3] per stream
         (None: predict.py's pseudo K).  A tracker with `frame_size` takes `ingest.Frame`s of any size and format instead (plain [h,w,3]
-        arrays count as rgb24 frames); their intrinsics travel in Frame.K, so Ks must be None.  Does not synchronise."""
+        arrays count as rgb24 frames); their intrinsics travel in Frame.K, so Ks must be None.
+        sinks: None, or one entry per stream id: an `emit.Sink`, a list of them (predict.py writes the raw and the smoothed picture of a
+        frame) or None.  Each sink receives the stream's working-resolution frame with the box of this frame's pose drawn on it; the
+        picture's size is the frame's `ingest.plan` with `frame_size`, the whole image otherwise.  Device sinks are written on the lane's
+        stream; host sinks are valid after `wait_emitted` or `result`.  Does not synchronise."""
         ids = self._ids(stream_ids)
         if len(imgs) != len(ids) or (Ks is not None and len(Ks) != len(ids)):
             raise ValueError("StreamTracker.push: one image (and K) per stream id expected")
+        per_stream = self._sink_lists(ids, sinks)
         if self.frame_size is not None:
             if Ks is not None:
                 raise ValueError("StreamTracker.push: a tracker with frame_size takes the intrinsics in Frame.K, not in Ks")
@@ -128,6 +141,7 @@ class StreamTracker:
         for i, s in enumerate(ids):
             groups.setdefault(s // self.batch, []).append((s, frames[i], Ks[i]))
         cur = torch.cuda.current_stream(self.dev) if self.cuda else None
+        self._sinks = per_stream
         for g in sorted(groups):
             lane = self._lanes[g % self.nlanes]
             if cur is not None:
@@ -144,6 +158,10 @@ class StreamTracker:
                     self._tick(lane, track)
                 for c0 in range(0, len(init), INIT_CHUNK):
                     self._init(init[c0:c0 + INIT_CHUNK])
+                if self.cuda and any(s in self._sinks for s, _, _ in ents):
+                    lane.emitted = torch.cuda.Event()
+                    lane.emitted.record(lane.stream)
+        self._sinks = {}
         for s in ids:
             self._started[s] = True
             self._frames[s] += 1
@@ -151,7 +169,8 @@ class StreamTracker:
     def result(self, stream_ids=None):
         """Synchronise -> {id: (pose [3,4], smoothed [3,4])} float32 numpy of each stream's latest frame (stream_ids None: every stream
         that has one).  Raises RuntimeError if an fp16 pair map of the networks left the representable window since the last check:
-        the poses since then cannot be trusted (reset the streams; the maps' exponents are updated for the frames that follow)."""
+        the poses since then cannot be trusted (reset the streams; the maps' exponents are updated for the frames that follow).  The
+        error covers the frames emitted into sinks since the last check as well: their boxes were drawn from those poses."""
         if self.cuda:
             torch.cuda.synchronize(self.dev)
         self._check_range()
@@ -161,6 +180,14 @@ class StreamTracker:
                 raise ValueError(f"StreamTracker.result: stream {s} has no frame")
         P, Sm = self.pose_table.cpu().numpy(), self.smooth_table.cpu().numpy()
         return {s: (P[s].reshape(3, 4).copy(), Sm[s].reshape(3, 4).copy()) for s in ids}
+
+    def wait_emitted(self, stream_ids=None):
+        """Block the host until the sinks of the listed streams' pushes (None: of every stream) are filled: waits on the events of the
+        lanes involved, not on the device.  Host sinks are valid after it (or after `result`); it does not run the range check."""
+        lanes = self._lanes if stream_ids is None else [self._lanes[(s // self.batch) % self.nlanes] for s in self._ids(stream_ids)]
+        for ln in lanes:
+            if ln.emitted is not None:
+                ln.emitted.synchronize()
 
     def reset(self, stream_ids):
         """The next frame of these streams starts over: detection, selection, full refinement, fresh smoothing history."""
@@ -179,6 +206,39 @@ class StreamTracker:
         if len(set(ids)) != len(ids):
             raise ValueError("StreamTracker: a stream id is listed twice")
         return ids
+
+    @staticmethod
+    def _sink_lists(ids, sinks):
+        """push's `sinks` -> {stream id: [Sink, ...]} for the streams that have any."""
+        if sinks is None:
+            return {}
+        sinks = list(sinks)
+        if len(sinks) != len(ids):
+            raise ValueError("StreamTracker.push: sinks must be None or hold one entry (Sink, list of Sinks or None) per stream id")
+        out = {}
+        for s, ent in zip(ids, sinks):
+            lst = [] if ent is None else ([ent] if isinstance(ent, E.Sink) else list(ent))
+            if any(not isinstance(k, E.Sink) for k in lst):
+                raise ValueError("StreamTracker.push: a sinks entry is an emit.Sink, a list of them or None")
+            if lst:
+                out[s] = lst
+        return out
+
+    def _emit(self, imgs, K9, slot_map, ents, slots):
+        """Project the box under the raw / smoothed poses just committed and fill the sinks of these streams: at most two
+        g6d_track_corners launches and one g6d_frame_emit launch on the current (lane's) stream."""
+        todo = [(b, f, k) for (s, f, _), b in zip(ents, slots) for k in self._sinks.get(s, ())]
+        if not todo:
+            return
+        n = slot_map.shape[0]                  # a corner set is read only by sinks that name it, so only those sets are computed
+        pts = torch.empty((2, n, 8, 2), dtype=torch.int32, device=self.dev)
+        valid = torch.empty((2, n), dtype=torch.int32, device=self.dev)
+        for name, table in (("raw", self.pose_table), ("smooth", self.smooth_table)):
+            if any(k.box and k.pose == name for _, _, k in todo):
+                ops.track_corners(table, K9, slot_map, self.box, pts[E.POSES[name]], valid[E.POSES[name]])
+        H, W = imgs.shape[1:3]
+        sizes = [I.plan(f, (H, W))[:2] if self.frame_size is not None else (H, W) for _, f, _ in todo]
+        E.emit_frames(imgs, pts, valid, [k for _, _, k in todo], slots=[b for b, _, _ in todo], pic_sizes=sizes)
 
     @staticmethod
     def _rgb(im):
@@ -260,6 +320,8 @@ class StreamTracker:
             out = self._tick_fn(lane)
         if self._records is not None:
             self._records.append((out.clone(), [(b, s, self._frames[s]) for (s, _, _), b in zip(ents, slots)]))
+        if self._sinks:
+            self._emit(lane.img, lane.K.reshape(self.batch, 9), lane.map, ents, slots)
 
     def _init(self, ents):
         n = len(ents)
@@ -276,6 +338,8 @@ class StreamTracker:
                                self.hist_count, self.smooth_table)
         if self._records is not None:
             self._records.append((out, [(i, s, self._frames[s]) for i, (s, _, _) in enumerate(ents)]))
+        if self._sinks:
+            self._emit(imgs, Ks.reshape(n, 9), ids, ents, list(range(n)))
 
     def _check_range(self):
         bad = []

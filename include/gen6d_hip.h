@@ -590,6 +590,56 @@ typedef struct G6dFrame {          /* one per frame */
 int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int B, int H, int W, float* K_out, g6d_stream_t stream);
 int g6d_sizeof_frame_desc(void);
 
+/* Annotated frame output (gen6d_amd/emit.py; reference predict.py:60-72 + utils/draw_utils.py draw_bbox_3d); additive within ABI 12.
+ * g6d_track_corners, one 64-thread block per slot: the box (box[8][3], corner order of pts_range_to_bbox_pts) projected in float64 (the
+ * projection of g6d_track_commit) under row slot_stream[b] of `table` (pose_table or smooth_table, [streams][12]) and K[b][9]; every
+ * coordinate rounded as floor(v + 0.5) -> pts[b][8][2] int32, valid[b] int32.  valid[b] = 0 (and pts[b] = 0) when the slot is unused
+ * (slot_stream[b] < 0), when a corner's depth is <= 0 or a rounded coordinate lies outside [-8192, 16383] (NaN included); else 1. */
+int g6d_track_corners(const float* table, const float* K, const int* slot_stream, const float* box, int32_t* pts, int32_t* valid,
+                      int batch, g6d_stream_t stream);
+/* g6d_frame_emit, the counterpart of g6d_frame_ingest: ONE launch writes n sinks.  Sink i shows image `slot` of imgs [B][H][W][3] uint8
+ * RGB with the box of pts[box][slot] drawn on it, in the sink's format, into memory the caller names.  pts [sets][B][8][2] int32 and
+ * valid [sets][B] int32 hold one or two corner sets (predict.py writes the raw and the smoothed picture of a frame); `box` names the set.
+ * The table lives in DEVICE memory (it changes with every call, so the launch stays outside captured graphs); the caller validates its
+ * contents: planes cover `height` rows of `pitch` bytes, 1 <= width, height <= 8192 (even for NV12), 0 <= pic_w <= W, 0 <= pic_h <= H,
+ * 0 <= thickness, dot_radius <= 255, box < sets.  A sink whose slot lies outside [0, B) is skipped; sinks may share a slot but must not
+ * overlap in memory.  No scaling, no rotation.
+ * Exact integer rules (the numpy restatement in tests/test_emit_cpu.py is bit-identical).
+ * Annotated RGB at picture pixel (x, y), corners q_j = pts[box][slot][j]; priority: edges, then discs, then the picture (draw_bbox_3d
+ * draws its lines over its discs).  Nothing is drawn when box is not 0 or 1, valid[box][slot] == 0 or a corner lies outside
+ * [-8192, 16383].
+ *   disc j covers the pixel iff dot_radius >= 0 and (x-qx)^2 + (y-qy)^2 <= dot_radius^2                          -> dot_rgb
+ *   edge (a, b) of 0-1 1-2 2-3 3-0 4-5 5-6 6-7 7-4 0-4 1-5 2-6 3-7, thickness > 0: d = q_b - q_a, p = (x, y) - q_a, L = d.d, s = p.d,
+ *     t = min(max(s, 0), L), E = L |p|^2 - 2 t s + t^2; covered iff E <= floor(thickness^2 L / 4) (L > 0) or 4 |p|^2 <= thickness^2
+ *     (L == 0): the pixel centre lies within thickness / 2 of the segment                                        -> line_rgb
+ *     (64-bit: with 0 <= x, y < 8192 and corners in [-8192, 16383], |p| components <= 16383 and |d| components <= 24575, so
+ *      L <= 1.21e9, L |p|^2 <= 6.5e17, |2 t s| <= 2.0e18, t^2 <= 1.5e18, thickness^2 L <= 7.9e13: every term and sum < 2^63)
+ * Sink pixel (x, y) = the annotated picture pixel when x < pic_w and y < pic_h, else RGB (0, 0, 0) (a sink larger than the picture pads
+ * black, a smaller one crops).  Packed formats: channel order as in the ingest, alpha 255.
+ * NV12, limited range, round(k * 2^20) constants of the forward matrix (Y row 219/255 (Kr, Kg, Kb); Cb row 224/255 (-Kr/(2(1-Kb)),
+ * -Kg/(2(1-Kb)), 1/2); Cr row 224/255 (1/2, -Kg/(2(1-Kr)), -Kb/(2(1-Kr)))):
+ *   Y  = sat8((CYR R + CYG G + CYB B + 2^19 + 16 * 2^20) >> 20) per pixel;
+ *   Cb = sat8((CBR sR + CBG sG + CBB sB + 2^21 + 128 * 2^22) >> 22), Cr likewise, once per 2 x 2 block from the channel sums sR, sG, sB of
+ *   its four annotated sink pixels (the division by 4 is folded into the shift);
+ *   BT.601 (Kr, Kb) = (0.299, 0.114):   CY = (269262, 528618, 102662), CB = (-155423, -305128, 460551), CR = (460551, -385654, -74897)
+ *   BT.709 (Kr, Kb) = (0.2126, 0.0722): CY = (191455, 644067, 65019),  CB = (-105533, -355018, 460551), CR = (460551, -418321, -42230) */
+typedef struct G6dSink {           /* one per destination */
+  void* plane0;                    /* packed pixels, or the Y plane of NV12 */
+  void* plane1;                    /* NV12: interleaved UV plane; else NULL */
+  int32_t pitch0, pitch1;          /* bytes per sink row */
+  int32_t width, height;           /* sink size in pixels, 1..8192 (even for NV12) */
+  int32_t format;                  /* G6D_FMT_* */
+  int32_t matrix;                  /* NV12 only: 0 BT.601 limited range, 1 BT.709 limited range */
+  int32_t slot;                    /* source image index in `imgs`; outside [0, B): sink skipped */
+  int32_t pic_w, pic_h;            /* the picture inside the canvas (top-left corner), <= W, H */
+  int32_t thickness, dot_radius;   /* draw_bbox_3d: 2, 2 */
+  int32_t line_rgb, dot_rgb;       /* 0xRRGGBB; draw_bbox_3d: 0x0000FF, 0xFF0000 */
+  int32_t box;                     /* corner set drawn: 0 or 1; anything else: no box */
+} G6dSink;
+int g6d_frame_emit(const G6dSink* sinks, int n, const uint8_t* imgs, int B, int H, int W, const int32_t* pts, const int32_t* valid,
+                   g6d_stream_t stream);
+int g6d_sizeof_sink_desc(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,94 @@
+"""The frame-emit kernel alone (csrc/emit.hip): 32 device-resident images per launch into 32 device sinks of the same size, with a valid
+box on every image, four cases:
+
+  540p-nv12  / 540p-rgb24     32 x (540x960 RGB  -> NV12 / rgb24)
+  1080p-nv12 / 1080p-rgb24    32 x (1080x1920 RGB -> NV12 / rgb24)
+
+Bytes are counted from shapes: the image bytes a launch reads plus the sink bytes it writes (pixel bytes only).  Timing: device events
+around `--launches` back-to-back calls (includes the table upload of each call), or, under the profiler, the kernel's own durations:
+
+  python tools/emit_bench.py [--launches 50]
+  rocprofv3 --kernel-trace -d DIR -o emit --output-format csv -- python tools/emit_bench.py
+  python tools/emit_bench.py --trace-csv DIR/.../emit_kernel_trace.csv [--tick-ms T] [--out FILE.md]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_BPS = 6.3e12          # achievable HBM rate the shares are quoted against
+CASES = {"540p-nv12": ((540, 960), "nv12"), "540p-rgb24": ((540, 960), "rgb24"), "1080p-nv12": ((1080, 1920), "nv12"),
+         "1080p-rgb24": ((1080, 1920), "rgb24")}
+N = 32
+WARM = 3
+
+
+def case_bytes(c):
+    (h, w), fmt = c
+    return N * (h * w * 3 + (h * w * 3 // 2 if fmt == "nv12" else h * w * 3))
+
+
+def trace_table(path, launches, tick_ms):
+    import csv
+    rows = [r for r in csv.DictReader(open(path)) if "frame_emit" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    out = ["| case | launches | kernel us (median) | min | max | bytes per launch | TB/s (median) | share of 6.3 TB/s | share of a tick |",
+           "|---|---:|---:|---:|---:|---:|---:|---:|---:|"]
+    per = WARM + launches
+    for i, (name, c) in enumerate(CASES.items()):
+        d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[i * per + WARM:(i + 1) * per]])
+        if not len(d):
+            continue
+        b, med = case_bytes(c), float(np.median(d))
+        tick = f"{med / (tick_ms * 1e3):.2%}" if tick_ms else "-"
+        out.append(f"| {name} | {len(d)} | {med:.1f} | {d.min():.1f} | {d.max():.1f} | {b / 1e6:.1f} MB | {b / med / 1e6:.2f} | "
+                   f"{b / med / 1e6 / (HBM_BPS / 1e12):.1%} | {tick} |")
+    return "\n".join(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--trace-csv", default=None)
+    ap.add_argument("--tick-ms", type=float, default=0.0, help="tick time of the 32-stream tracker the kernel time is set against")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.trace_csv:
+        txt = trace_table(args.trace_csv, args.launches, args.tick_ms)
+        print(txt)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write("\n## The emit kernel (rocprofv3 --kernel-trace, tools/emit_bench.py)\n\n32 device-resident images and sinks per launch, a "
+                        "box on every image; bytes = image bytes read + sink bytes written, from shapes.\n\n" + txt + "\n")
+        return
+    import torch
+    from gen6d_amd.emit import Sink, emit_frames
+    if not torch.cuda.is_available():
+        sys.exit("emit_bench: needs the GPU (the kernel has no CPU fallback)")
+    rng = np.random.RandomState(0)
+    for name, ((h, w), fmt) in CASES.items():
+        imgs = torch.from_numpy(rng.randint(0, 256, (N, h, w, 3)).astype(np.uint8)).cuda()
+        shape = (h * 3 // 2, w) if fmt == "nv12" else (h, w, 3)
+        sinks = [Sink(torch.zeros(shape, dtype=torch.uint8, device="cuda"), fmt) for _ in range(N)]
+        q = np.stack([rng.randint(w // 8, w - w // 8, (N, 8)), rng.randint(h // 8, h - h // 8, (N, 8))], -1).astype(np.int32)
+        pts, valid = torch.from_numpy(q).cuda(), torch.ones(N, dtype=torch.int32, device="cuda")
+        for _ in range(WARM):
+            emit_frames(imgs, pts, valid, sinks)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            emit_frames(imgs, pts, valid, sinks)
+        e1.record()
+        torch.cuda.synchronize()
+        us = e0.elapsed_time(e1) * 1e3 / args.launches
+        b = case_bytes(CASES[name])
+        print(f"{name}: {us:.1f} us per call (events, table upload included), {b / 1e6:.1f} MB -> {b / us / 1e6:.2f} TB/s", flush=True)
+        del imgs, sinks
+
+
+if __name__ == "__main__":
+    main()

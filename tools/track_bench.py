@@ -8,6 +8,8 @@ each; the table gives the median and the spread (max - min) / median.
 
   python tools/track_bench.py [--streams 1,8,32] [--frames 30] [--repeats 3] [--out profiles/r08_track_bench.md]
   python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p        (graphs only, the variants alternated)
+  python tools/track_bench.py --streams 32 --emit nv12 [--emit-host]            (graphs only: no sinks / device sinks / pinned host sinks
+                                                                                 of the working-resolution picture, alternated)
   rocprofv3 --kernel-trace --stats -d DIR -o track -- python tools/track_bench.py --profile 32      (one configuration, graphs)
   python tools/track_bench.py --stats-csv DIR/.../track_kernel_stats.csv --ticks N --tick-ms T --out profiles/r08_track_kernel_stats.md
 """
@@ -65,26 +67,39 @@ def native_frames(frames, K, mode):
     return out, (540, 960)
 
 
-def run(est, frames, K, S, F, batch, graphs, ingest=None):
+def make_sinks(S, hw, fmt, host):
+    """One sink per stream for the smoothed picture at working resolution, in device memory or in pinned host memory; reused every tick
+    (a lane's emits are ordered on its stream)."""
+    import torch
+    from gen6d_amd.emit import Sink
+    h, w = hw
+    shape = (h * 3 // 2, w) if fmt == "nv12" else (h, w, 3)
+    mk = (lambda: torch.zeros(shape, dtype=torch.uint8).pin_memory()) if host else (lambda: torch.zeros(shape, dtype=torch.uint8, device="cuda"))
+    return [Sink(mk(), fmt) for _ in range(S)]
+
+
+def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=False):
     """-> (seconds of the timed ticks, timed ticks).  ingest: None (plain frames, the tracker without frame_size) or a mode of
-    native_frames."""
+    native_frames.  emit: None, or the format of one sink per stream filled on every push (emit_host: pinned host sinks)."""
     import torch
     from gen6d_amd.tracking import StreamTracker
     ids = list(range(S))
     if ingest in (None, "none"):
         tr = StreamTracker(est, S, batch=batch, graphs=graphs)
         Ks = [K] * S
+        canvas = tuple(frames[0].shape[:2])
     else:
         frames, canvas = native_frames(frames, K, ingest)
         tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas)
         Ks = None
     frame = lambda s, t: frames[(7 * s + t) % len(frames)]
+    kw = {"sinks": make_sinks(S, canvas, emit, emit_host)} if emit else {}
     for t in range(2):                                  # first frames, then the tick that captures the lanes' graphs
-        tr.push(ids, [frame(s, t) for s in ids], Ks)
+        tr.push(ids, [frame(s, t) for s in ids], Ks, **kw)
     tr.result()
     t0 = time.perf_counter()
     for t in range(2, F):
-        tr.push(ids, [frame(s, t) for s in ids], Ks)
+        tr.push(ids, [frame(s, t) for s in ids], Ks, **kw)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     tr.result()
@@ -116,6 +131,9 @@ def main():
     ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p: graphs runs of these frame "
                     "sources, alternated (with --profile: the one source of the profiled run)")
     ap.add_argument("--batch", type=int, default=0, help="--profile: slots per lane (default min(streams, 8))")
+    ap.add_argument("--emit", default=None, choices=["nv12", "rgb24"], help="graphs runs without sinks and with one device sink of this "
+                    "format per stream, alternated (with --profile: the profiled run emits)")
+    ap.add_argument("--emit-host", action="store_true", help="--emit: pinned host sinks as a third variant (--profile: instead of device sinks)")
     ap.add_argument("--tick-ms", type=float, default=0.0)
     args = ap.parse_args()
     if args.stats_csv:
@@ -132,12 +150,35 @@ def main():
     est, frames, K = build(dev)
     if args.profile:
         S = args.profile
-        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest)
-        print(f"profile S={S} ingest={args.ingest}: {n} ticks, {dt / n * 1e3:.3f} ms/tick")
+        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest, args.emit, args.emit_host)
+        print(f"profile S={S} ingest={args.ingest} emit={args.emit}{' (host)' if args.emit and args.emit_host else ''}: {n} ticks, "
+              f"{dt / n * 1e3:.3f} ms/tick")
         return
     configs = [(int(s), min(int(s), 8)) for s in args.streams.split(",")]
     if 32 in [c[0] for c in configs]:
         configs.append((32, 32))
+    if args.emit:
+        modes = ["none", "device"] + (["host"] if args.emit_host else [])
+        lines = ["| streams | batch | sinks | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
+        for S, B in configs:
+            res = {m: [] for m in modes}
+            for _ in range(args.repeats):
+                for m in modes:                       # alternated
+                    dt, n = run(est, frames, K, S, args.frames, B, True, args.ingest, None if m == "none" else args.emit, m == "host")
+                    res[m].append((S * n / dt, dt / n * 1e3))
+            for m in modes:
+                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
+                med = float(np.median(fps))
+                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
+                             f"{', '.join(f'{v:.1f}' for v in fps)} |")
+                print(lines[-1], flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(f"# Tracked frames/s with annotated frame output (tools/track_bench.py --emit {args.emit})\n\n"
+                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
+                        f"of each variant, alternated.  none: no sinks; device: one {args.emit} device sink per stream and frame (the smoothed "
+                        "picture at working resolution); host: the same into pinned host memory, copy included.\n\n" + "\n".join(lines) + "\n")
+        return
     if args.ingest:
         modes = args.ingest.split(",")
         lines = ["| streams | batch | frames | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
