@@ -198,9 +198,9 @@ __global__ void resize_pyramid_kernel(const PyrArgs a) {
 extern "C" int g6d_detector_assemble(const float* s0, const float* s1, const float* s2, int hc, int wc, int rfn,
                                      const float* mu_sigma, float clip, int hs, int ws, int scale_idx, int nch,
                                      float* stacked, int batch, g6d_stream_t stream) {
-  if (!s0 || !s1 || !s2 || !mu_sigma || !stacked || hc <= 0 || wc <= 0 || (hc & 3) || (wc & 3) || rfn <= 0 ||
+  if (!s0 || !s1 || !s2 || !mu_sigma || !stacked || hc <= 0 || wc <= 0 || (hc & 3) || (wc & 3) || rfn <= 0 || hs <= 0 || ws <= 0 ||
       scale_idx < 0 || 3 * scale_idx + 3 > nch || batch < 1 || batch > 65535) {
-    g6d_set_error("detector_assemble: bad args (level-0 map must be a multiple of 4)"); return G6D_EINVAL;
+    g6d_set_error("detector_assemble: bad args (level-0 map must be a multiple of 4, hs and ws positive)"); return G6D_EINVAL;
   }
   LevelStats st;
   for (int l = 0; l < 3; ++l) { st.mu[l] = mu_sigma[2 * l]; st.sigma[l] = mu_sigma[2 * l + 1]; }

@@ -628,7 +628,7 @@ extern "C" int g6d_affine_act_pool(const float* in, int ld_in, const float* scal
 
 extern "C" int g6d_upsample_bilinear(const float* in, int ld_in, const float* scale, const float* shift, int per_n,
                                      int N, int H, int W, int C, int factor, float* out, int ld_out, g6d_stream_t stream) {
-  if (!in || !out || (C & 3) || (ld_in & 3) || (ld_out & 3) || factor < 1 || N <= 0 || !g6d_aligned16(in) ||
+  if (!in || !out || (C & 3) || (ld_in & 3) || (ld_out & 3) || factor < 1 || N <= 0 || H <= 0 || W <= 0 || !g6d_aligned16(in) ||
       !g6d_aligned16(out) || (scale && (!shift || !g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("upsample_bilinear: bad args"); return G6D_EINVAL;
   }
@@ -696,7 +696,9 @@ extern "C" int g6d_max_an_add(const float* in, int ld_in, int rfn, int an, int C
 
 extern "C" int g6d_attention(const float* q, const float* k, const float* v, int ld, int n, int C, int heads, float* out,
                              int ld_out, int batch, g6d_stream_t stream) {
-  if (!q || !k || !v || !out || n <= 0 || heads <= 0 || C % heads || batch < 1 || batch > 65535) { g6d_set_error("attention: bad args"); return G6D_EINVAL; }
+  if (!q || !k || !v || !out || n <= 0 || heads <= 0 || C <= 0 || C % heads || ld < C || ld_out < C || batch < 1 || batch > 65535) {
+    g6d_set_error("attention: bad args (ld >= C, ld_out >= C)"); return G6D_EINVAL;
+  }
   size_t lds = (size_t)(C / heads + n) * sizeof(float);
   if (lds > 60000) { g6d_set_error("attention: n too large"); return G6D_EINVAL; }
   if (n <= ATT_N && C / heads <= ATT_N)

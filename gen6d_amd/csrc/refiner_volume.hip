@@ -58,11 +58,12 @@ __device__ __forceinline__ Taps taps_from(const Taps& t, int src) {
 }
 
 // unconditional, clamped loads (branches around loads serialise them); out-of-range taps carry weight 0
-__device__ __forceinline__ f32x4 gather_view(const float* __restrict__ fmap, const Taps& t, int c) {
-  const f32x4 v00 = *reinterpret_cast<const f32x4*>(fmap + t.o00 + c);
-  const f32x4 v01 = *reinterpret_cast<const f32x4*>(fmap + t.o01 + c);
-  const f32x4 v10 = *reinterpret_cast<const f32x4*>(fmap + t.o10 + c);
-  const f32x4 v11 = *reinterpret_cast<const f32x4*>(fmap + t.o11 + c);
+// (fmap_c: the view's map advanced to the lane's channels — one 64-bit address sum per view, then one per tap)
+__device__ __forceinline__ f32x4 gather_view(const float* __restrict__ fmap_c, const Taps& t) {
+  const f32x4 v00 = *reinterpret_cast<const f32x4*>(fmap_c + t.o00);
+  const f32x4 v01 = *reinterpret_cast<const f32x4*>(fmap_c + t.o01);
+  const f32x4 v10 = *reinterpret_cast<const f32x4*>(fmap_c + t.o10);
+  const f32x4 v11 = *reinterpret_cast<const f32x4*>(fmap_c + t.o11);
   f32x4 acc = t.w00 * v00;
   acc += t.w01 * v01;
   acc += t.w10 * v10;
@@ -114,12 +115,18 @@ __global__ void __launch_bounds__(256, 4) refiner_volume_kernel(const float* __r
       for (int c = 0; c < 4; ++c) P[r * 4 + c] = K[r * 3] * T[c] + K[r * 3 + 1] * T[4 + c] + K[r * 3 + 2] * T[8 + c];
   }
   const Taps mine = project_view(fh, fw, C, P, vx, vy, vz, h_in, w_in);
-  for (int c = l32 * 4; c < C; c += 128) {           // (uniform trip count per half-wave pair: C is a kernel argument)
+  // Every lane of the half-wave walks every 128-channel chunk: taps_from() below reads lanes 0..rfn, which must be active in the
+  // loop whatever C is (with a per-lane bound they are not once C <= 4 * rfn).  Lanes whose channels lie beyond C gather the last
+  // four channels again (in range) and store nothing.
+  for (int c0 = 0; c0 < C; c0 += 128) {
+    const int c_mine = c0 + l32 * 4;
+    const bool c_in = c_mine < C;
+    const int c = c_in ? c_mine : C - 4;
     f32x4 s[MAX_RFN];
     f32x4 sum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < MAX_RFN; ++r)
-      if (r < rfn) { s[r] = gather_view(feats + r * fsz, taps_from(mine, r), c); sum += s[r]; }
+      if (r < rfn) { s[r] = gather_view(feats + r * fsz + c, taps_from(mine, r)); sum += s[r]; }
     const f32x4 mean = sum * inv_n;
     f32x4 var = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -127,8 +134,8 @@ __global__ void __launch_bounds__(256, 4) refiner_volume_kernel(const float* __r
       if (r < rfn) { f32x4 d = s[r] - mean; var += d * d; }
     var = var * inv_n1;
     f32x4 sd = {sqrtf(var[0]), sqrtf(var[1]), sqrtf(var[2]), sqrtf(var[3])};
-    const f32x4 q = gather_view(feats + rfn * fsz, taps_from(mine, rfn), c);
-    if (!live) continue;
+    const f32x4 q = gather_view(feats + rfn * fsz + c, taps_from(mine, rfn));
+    if (!live || !c_in) continue;
     *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + c) = mean;
     *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + C + c) = q;
     *reinterpret_cast<f32x4*>(stdv + (size_t)half * C + c) = sd;
@@ -140,9 +147,10 @@ __global__ void __launch_bounds__(256, 4) refiner_volume_kernel(const float* __r
 extern "C" int g6d_refiner_volume(const float* feats, const float* projs, const float* rot_in,
                                   const float* lin, int rfn, int fh, int fw, int C, int h_in, int w_in, int sn,
                                   float* mean_in, float* stdv, g6d_stream_t stream) {
-  if (!feats || !projs || !rot_in || !lin || !mean_in || !stdv || rfn < 1 || rfn > MAX_RFN || (C & 3) ||
-      sn < 1 || sn > 256 || !g6d_aligned16(feats) || !g6d_aligned16(mean_in) || !g6d_aligned16(stdv)) {
-    g6d_set_error("refiner_volume: bad args (1 <= rfn <= 8, C % 4 == 0)"); return G6D_EINVAL;
+  if (!feats || !projs || !rot_in || !lin || !mean_in || !stdv || rfn < 1 || rfn > MAX_RFN || C < 4 || (C & 3) ||
+      fh <= 0 || fw <= 0 || h_in <= 0 || w_in <= 0 || sn < 1 || sn > 256 || !g6d_aligned16(feats) || !g6d_aligned16(mean_in) ||
+      !g6d_aligned16(stdv)) {
+    g6d_set_error("refiner_volume: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
   }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {projs, nullptr, nullptr, nullptr, nullptr, rot_in, 3};
@@ -158,9 +166,10 @@ extern "C" int g6d_refiner_volume(const float* feats, const float* projs, const 
 extern "C" int g6d_refiner_volume_kp(const float* feats, const float* ref_Ks, const float* ref_poses, const float* K_in,
                                      const float* pose_in, const float* lin, int rfn, int fh, int fw, int C, int h_in, int w_in, int sn,
                                      float* mean_in, float* stdv, int batch, g6d_stream_t stream) {
-  if (!feats || !ref_Ks || !ref_poses || !K_in || !pose_in || !lin || !mean_in || !stdv || rfn < 1 || rfn > MAX_RFN || (C & 3) ||
-      sn < 1 || sn > 256 || batch < 1 || batch > 65535 || !g6d_aligned16(feats) || !g6d_aligned16(mean_in) || !g6d_aligned16(stdv)) {
-    g6d_set_error("refiner_volume_kp: bad args (1 <= rfn <= 8, C % 4 == 0)"); return G6D_EINVAL;
+  if (!feats || !ref_Ks || !ref_poses || !K_in || !pose_in || !lin || !mean_in || !stdv || rfn < 1 || rfn > MAX_RFN || C < 4 || (C & 3) ||
+      fh <= 0 || fw <= 0 || h_in <= 0 || w_in <= 0 || sn < 1 || sn > 256 || batch < 1 || batch > 65535 || !g6d_aligned16(feats) ||
+      !g6d_aligned16(mean_in) || !g6d_aligned16(stdv)) {
+    g6d_set_error("refiner_volume_kp: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
   }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {nullptr, ref_Ks, ref_poses, K_in, pose_in, pose_in, 4};

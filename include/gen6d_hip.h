@@ -202,7 +202,7 @@ int g6d_affine_act_pool(const float* in, int ld_in, const float* scale, const fl
                         int pool, int N, int H, int W, int C, float* out, int ld_out, g6d_stream_t stream);
 
 /* Bilinear up-sampling by an integer factor (align_corners=False, F.interpolate in network/refiner.py:74-75) of
- * relu?(x*scale+shift) on [N][H][W][C] -> [N][H*f][W*f][C] written with channel stride ld_out. */
+ * relu?(x*scale+shift) on [N][H][W][C] -> [N][H*f][W*f][C] written with channel stride ld_out.  N, H, W > 0, factor >= 1. */
 int g6d_upsample_bilinear(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n,
                           int N, int H, int W, int C, int factor, float* out, int ld_out, g6d_stream_t stream);
 
@@ -412,6 +412,8 @@ int g6d_selector_levels(int nlev, int qn, const float* const* que, const float* 
  *   lin       [sn]                torch.linspace(-1,1,sn)
  *   mean_in   [sn^3][2C]          cat[mean over refs, query sample]   (input of mean_embed)
  *   std       [sn^3][C]           1 <= rfn <= 8
+ * C is any positive multiple of 4 (also below 4 * (rfn + 1) and off the 128-channel trips of a half-wave: every lane walks every
+ * trip, lanes beyond C store nothing); fh, fw, h_in, w_in > 0, sn <= 256.  Anything else is refused with G6D_EINVAL.
  * ---------------------------------------------------------------------------------------------------------------- */
 int g6d_refiner_volume(const float* feats, const float* projs, const float* rot_in, const float* lin, int rfn, int fh,
                        int fw, int C, int h_in, int w_in, int sn, float* mean_in, float* std, g6d_stream_t stream);
@@ -428,7 +430,7 @@ int g6d_refiner_volume_kp(const float* feats, const float* ref_Ks, const float* 
  * correlation maps (level l at 1/(8*2^l) resolution, channels-last [h_l*w_l][rfn]), nearest-upsample levels 1,2 to
  * level-0 size, normalise ((x-mu_l)/sigma_l), clip to +-clip, bilinear-resize (align_corners=False) to (hs,ws) and
  * write channels [3*scale_idx .. 3*scale_idx+2] of stacked [hs*ws][rfn][nch].  batch >= 1 queries (network/detector.py:291-304
- * takes [qn,H,W,3]): s_l [batch][h_l*w_l][rfn], stacked [batch][hs*ws][rfn][nch].
+ * takes [qn,H,W,3]): s_l [batch][h_l*w_l][rfn], stacked [batch][hs*ws][rfn][nch].  hc, wc multiples of 4; hs, ws > 0.
  * ---------------------------------------------------------------------------------------------------------------- */
 int g6d_detector_assemble(const float* s0, const float* s1, const float* s2, int hc, int wc, int rfn,
                           const float* mu_sigma /* HOST pointer: {mu0,sigma0,mu1,sigma1,mu2,sigma2} */, float clip, int hs, int ws,
@@ -463,8 +465,8 @@ int g6d_vps_norm(const float* vps, int D, float* feats, int ld, int c_off, int b
 int g6d_max_an_add(const float* in, int ld_in, int rfn, int an, int C, const float* embed, float* out, int ld_out, int batch,
                    g6d_stream_t stream);
 /* multi-head attention over n tokens with the reference's head split c -> (d=c/heads, head=c%heads), scale
- * 1/sqrt(C/heads): q,k,v [batch*n][ld] -> out [batch*n][ld_out], attention among the n tokens of one query
- * (attention.py:4-17,60-64) */
+ * 1/sqrt(C/heads): q,k,v [batch*n][ld] -> out [batch*n][ld_out] (ld >= C, ld_out >= C), attention among the n tokens of one
+ * query (attention.py:4-17,60-64) */
 int g6d_attention(const float* q, const float* k, const float* v, int ld, int n, int C, int heads, float* out,
                   int ld_out, int batch, g6d_stream_t stream);
 /* LayerNorm over C per token with affine (attention.py:19-26): out may alias in */

@@ -383,6 +383,9 @@ def vps_norm(vps, feats, c_off):
         for b in range(vps.shape[0]):
             vps_norm(vps[b], feats[b * D:(b + 1) * D], c_off)
         return feats
+    if vps.shape[-1] == 1:                                          # (F.instance_norm refuses a single value per channel: the same formula)
+        feats[:, c_off:c_off + 3] = ((vps - vps.mean(1, keepdim=True)) / torch.sqrt(vps.var(1, unbiased=False, keepdim=True) + 1e-5)).T
+        return feats
     feats[:, c_off:c_off + 3] = F.instance_norm(vps[None], eps=1e-5)[0].T
     return feats
 
@@ -431,18 +434,18 @@ def linear_gemv(x, W, bias, act=0):
     return _act(F.linear(x, W, bias), act)
 
 
-def warp_perspective(src_u8, H, dh, dw, out_float=False):
-    """Plain bilinear inverse warp with zero border (float weights)."""
+def warp_perspective(src_u8, H, dh, dw, out_float=False, dtype=torch.float32):
+    """Plain bilinear inverse warp with zero border (float weights); dtype: the precision of the coordinates and the blend."""
     import numpy as np
     H = np.asarray(H, dtype=np.float64)
     if H.shape == (2, 3): H = np.concatenate([H, [[0.0, 0.0, 1.0]]], 0)
-    hinv = torch.from_numpy(np.linalg.inv(H).astype(np.float32))
+    hinv = torch.from_numpy(np.linalg.inv(H)).to(dtype)
     sh, sw, ch = src_u8.shape
-    ys, xs = torch.meshgrid(torch.arange(dh, dtype=torch.float32), torch.arange(dw, dtype=torch.float32), indexing="ij")
+    ys, xs = torch.meshgrid(torch.arange(dh, dtype=dtype), torch.arange(dw, dtype=dtype), indexing="ij")
     p = torch.stack([xs, ys, torch.ones_like(xs)], -1) @ hinv.T
     fx, fy = p[..., 0] / p[..., 2], p[..., 1] / p[..., 2]
     gx, gy = (fx + 0.5) / sw * 2 - 1, (fy + 0.5) / sh * 2 - 1
-    img = src_u8.float().permute(2, 0, 1)[None].cpu()
+    img = src_u8.to(dtype).permute(2, 0, 1)[None].cpu()
     out = F.grid_sample(img, torch.stack([gx, gy], -1)[None], mode="bilinear", padding_mode="zeros", align_corners=False)[0]
     out = out.permute(1, 2, 0)
     out = (out / 255.0) if out_float else out.round().clamp(0, 255).to(torch.uint8)
@@ -522,7 +525,7 @@ def chain_refine_update(rot, off, scl, geo, norm):
     return torch.from_numpy(G.denormalize_pose(pr, nm[0], nm[1:]).astype(np.float32))
 
 
-def warp_batch(stack, single, idx, hinv, dh, dw, out=None):
+def warp_batch(stack, single, idx, hinv, dh, dw, out=None, dtype=torch.float32):
     import numpy as np
     B = hinv.shape[0]
     res = []
@@ -530,7 +533,7 @@ def warp_batch(stack, single, idx, hinv, dh, dw, out=None):
         sel = -1 if idx is None else int(idx[b])
         src = single if sel < 0 else stack[sel]
         H = np.linalg.inv(_np(hinv[b]).reshape(3, 3))
-        res.append(warp_perspective(src, H, dh, dw).float().div(255).permute(2, 0, 1))
+        res.append(warp_perspective(src, H, dh, dw, dtype=dtype).to(dtype).div(255).permute(2, 0, 1))
     r = torch.stack(res, 0)
     if out is not None:
         out.copy_(r)
