@@ -114,6 +114,15 @@ class DeviceChain:
         return {"pose": pose, "det": det5, "sel": sel, "logits": logits[0], "refine_poses": poses, "crop": crop}
 
     # ------------------------------------------------------------------ a batch of queries, no host synchronisation
+    def detect_batch(self, que_imgs):
+        """The detection half of `query_batch`: que_imgs uint8 [B,H,W,3] on the device -> det [B,5] = (x, y, 2^scale, cell).  det[:, 2]
+        is the reference-to-query size ratio that `pose_from_similarity` takes.  The tracker's health check calls it on a lane's image
+        batch (gen6d_amd/tracking.py)."""
+        with torch.no_grad():
+            x = que_imgs.permute(0, 3, 1, 2).float().div_(255)
+            det = self.est.detector.detect_impl(x.contiguous())
+            return torch.cat([det["positions"], det["scales"][:, None], det["que_select_id"].float()], 1).contiguous()
+
     def query_batch(self, que_imgs, que_Ks, pose_init=None, refine_iter=None):
         """que_imgs uint8 [B,H,W,3], que_Ks float32 [B,3,3] on the device (B <= 8) -> dict of device tensors: 'pose' [B,3,4], 'det'
         [B,5], 'sel' [B,2], 'logits' [B,rfn], 'refine_poses' (list of [B,3,4]).  The B queries share every launch (round 3): the
@@ -128,9 +137,7 @@ class DeviceChain:
             ar = torch.arange(B, dtype=torch.int32, device=self.dev)
             K9 = que_Ks.reshape(B, 9).contiguous()
             if pose_init is None:
-                x = que_imgs.permute(0, 3, 1, 2).float().div_(255)
-                det = est.detector.detect_impl(x.contiguous())
-                det5 = torch.cat([det["positions"], det["scales"][:, None], det["que_select_id"].float()], 1).contiguous()
+                det5 = self.detect_batch(que_imgs)
                 crop = ops.warp_batch(que_imgs, None, ar, ops.chain_crop_from_detection(det5, size), size, size)
                 logits, angles = est.selector.compute_view_point_feats(crop)
                 pose, sel = ops.chain_pose_from_selection(det5, logits.contiguous(), angles.contiguous(), self.ref_poses, self.ref_Ks, K9,

@@ -439,4 +439,89 @@ PA_HD int pnp_lm(const double* box, const double* uv, int c0, int c1, const M3& 
 }
 struct NoReduce { PA_HD void operator()(double*) const {} };
 
+// ---- track health (gen6d_amd/tracking.py HealthPolicy): is a refined pose a plausible continuation of its stream?
+//      Every comparison is written !(x <= thr), so that a NaN fails its gate; an infinite threshold disables it.
+enum { TH_NONE = 0, TH_TRACKING = 1, TH_SUSPECT = 2, TH_LOST = 3 };                                   // health[s][0]
+enum { THF_NONFINITE = 1, THF_BEHIND = 2, THF_SMALL = 4, THF_LARGE = 8, THF_OUTSIDE = 16, THF_ROT = 32, THF_SHIFT = 64, THF_SCALE = 128,
+       THF_VERIFY_POS = 256, THF_VERIFY_SCALE = 512, THF_FRAME_BITS = 255, THF_VERIFY_BITS = 768 };   // health[s][3]
+struct HealthGates { double min_px, max_px, margin, max_rot_deg, max_shift, max_log2_scale; };
+PA_HD bool pose_finite(const P34& p) {
+  bool ok = true;
+  for (int i = 0; i < 12; ++i) ok = ok && isfinite(p.m[i]);
+  return ok;
+}
+// The object centre under a pose: X = R c + t, z = X.z, (u, v) = (K X).xy / z, d_px = f diameter / z with f = (K00 + K11) / 2
+PA_HD void health_centre(const P34& p, const M3& K, const V3& c, double diameter, double& u, double& v, double& z, double& d_px) {
+  const V3 X = pose_apply(p, c), q = mulv(K, X);
+  z = X.z; u = q.x / z; v = q.y / z;
+  d_px = 0.5 * (K.m[0] + K.m[4]) * diameter / z;
+}
+// The gates of one candidate pose -> flag bits 0..7; m[7] = (u, v, z, d_px, rot_deg, shift, log2_scale).  prev == nullptr (an
+// acquisition) skips the motion gates.  The two hard failures end the evaluation: a non-finite pose leaves every measure 0, a centre
+// that is not in front of the camera leaves all but z 0 (nothing past them is defined).  A previous centre that is not in front of the
+// camera fails SCALE and leaves shift and log2_scale 0.
+PA_HD int health_gates(const P34* prev, const P34& cur, const M3& K, double w, double h, const V3& c, double diameter,
+                       const HealthGates& g, double* m) {
+  for (int i = 0; i < 7; ++i) m[i] = 0.0;
+  if (!pose_finite(cur)) return THF_NONFINITE;
+  double u, v, z, d;
+  health_centre(cur, K, c, diameter, u, v, z, d);
+  m[2] = z;
+  if (!(z > 0.0)) return THF_BEHIND;
+  m[0] = u; m[1] = v; m[3] = d;
+  int f = 0;
+  if (!(d >= g.min_px)) f |= THF_SMALL;
+  if (!(d <= g.max_px * fmax(w, h))) f |= THF_LARGE;
+  const double mg = g.margin * d;
+  if (!(u >= -mg) || !(u <= w + mg) || !(v >= -mg) || !(v <= h + mg)) f |= THF_OUTSIDE;
+  if (prev) {
+    double tr = 0.0;                                             // tr(R_new R_prev^T)
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) tr += cur.m[4 * i + j] * prev->m[4 * i + j];
+    m[4] = acos(fmin(fmax(0.5 * (tr - 1.0), -1.0), 1.0)) * (180.0 / 3.14159265358979323846);
+    if (!(m[4] <= g.max_rot_deg)) f |= THF_ROT;
+    double up, vp, zp, dp;
+    health_centre(*prev, K, c, diameter, up, vp, zp, dp);
+    if (!(zp > 0.0)) {
+      f |= THF_SCALE;
+    } else {
+      m[5] = hypot(u - up, v - vp) / d;
+      m[6] = fabs(log2(zp / z));
+      if (!(m[5] <= g.max_shift)) f |= THF_SHIFT;
+      if (!(m[6] <= g.max_log2_scale)) f |= THF_SCALE;
+    }
+  }
+  return f;
+}
+// State update of one evaluated frame on row = (status, bad, vbad, flags): replaces flag bits 0..7, keeps 8..9.  commit: the frame
+// passed and is committed; draw: the stream is not LOST after this frame.
+PA_HD void health_update(int f, bool reset, int patience, int* row, bool& commit, bool& draw) {
+  int status, bad = row[1], vbad = row[2];
+  if (reset) { status = f ? TH_LOST : TH_TRACKING; bad = 0; vbad = 0; }
+  else if (f & (THF_NONFINITE | THF_BEHIND)) status = TH_LOST;
+  else if (f) { bad += 1; status = bad >= patience ? TH_LOST : TH_SUSPECT; }
+  else { bad = 0; status = TH_TRACKING; }
+  row[0] = status; row[1] = bad; row[2] = vbad; row[3] = (row[3] & THF_VERIFY_BITS) | f;
+  commit = f == 0; draw = status != TH_LOST;
+}
+// The detector's check of a committed pose: det = (x, y, reference-to-query size ratio); ref_px: the object's mean projected diameter
+// in the reference views -> flag bits 8..9; m[2] = (verify_shift, verify_log2_scale)
+PA_HD int verify_gates(double dx, double dy, double ds, const P34& pose, const M3& K, const V3& c, double diameter, double ref_px,
+                       double max_shift, double max_log2_scale, double* m) {
+  double u, v, z, d;
+  health_centre(pose, K, c, diameter, u, v, z, d);
+  m[0] = hypot(dx - u, dy - v) / d;
+  m[1] = fabs(log2(ds * ref_px / d));
+  int f = 0;
+  if (!(m[0] <= max_shift)) f |= THF_VERIFY_POS;
+  if (!(m[1] <= max_log2_scale)) f |= THF_VERIFY_SCALE;
+  return f;
+}
+// ... and its state update: a failed check counts towards LOST, a passed one clears the count; bits 0..7 are kept
+PA_HD void verify_update(int f, int patience, int* row) {
+  if (f) { row[2] += 1; if (row[2] >= patience) row[0] = TH_LOST; }
+  else row[2] = 0;
+  row[3] = (row[3] & THF_FRAME_BITS) | f;
+}
+
 }  // namespace pa

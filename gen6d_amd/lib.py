@@ -129,6 +129,9 @@ SIGNATURES = {
     "g6d_warp_perspective": [_P, _I, _I, _I, C.POINTER(C.c_float), _P, _I, _I, _I, _F, _P],
     "g6d_track_gather": [_P, _P, _P, _P, _I, _P],
     "g6d_track_commit": [_P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P, _I, _P],
+    "g6d_track_gate": [_P, _P, _P, _P, _I, _P],
+    "g6d_track_health": [_P, _P, _P, _P, _I, _I, _P, _I, _P, _D, _I, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _I, _P],
+    "g6d_track_verify": [_P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P, _P, _I, _P],
     "g6d_frame_ingest": [_P, _I, _P, _I, _I, _I, _P, _P],
     "g6d_sizeof_frame_desc": [],
     "g6d_track_corners": [_P, _P, _P, _P, _P, _P, _I, _P],

@@ -1493,6 +1493,90 @@ def track_commit(pose, K, slot_stream, reset, box, num, std, pose_table, hist, h
     return out
 
 
+# ------------------------------------------------------------------------------------------------ track health
+def _track_health_tables(what, health, measures):
+    if (health.dtype != torch.int32 or health.dim() != 2 or health.shape[1] != 4 or not health.is_contiguous() or
+            (measures is not None and (measures.dtype != torch.float32 or tuple(measures.shape) != (health.shape[0], 12) or
+                                       not measures.is_contiguous()))):
+        raise ValueError(f"{what}: tables health int32 [S,4] and measures float32 [S,12] expected")
+
+
+def _track_slot_out(what, t, B, device):
+    if t is None:
+        return torch.empty((B,), dtype=torch.int32, device=device)
+    if t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{what}: a slot map destination must be a contiguous int32 [B] tensor")
+    return t
+
+
+def track_gate(pose_table, health, slot_stream, slot_eff=None):
+    """Before the gather (g6d_track_gate): pose_table [S,12], health int32 [S,4], slot_stream int32 [B] -> slot_eff int32 [B]: the stream
+    id of a used slot whose stream is not LOST and whose table row is finite, else -1.  A non-finite row of a stream that is not LOST
+    sets its status to LOST with flags NONFINITE (in place)."""
+    what = "track_gate"
+    _track_same_device(what, pose_table, health, slot_stream)
+    _f32c(pose_table)
+    B = _track_map(what, slot_stream)
+    _track_health_tables(what, health, None)
+    if pose_table.dim() != 2 or pose_table.shape[1] != 12 or pose_table.shape[0] != health.shape[0]:
+        raise ValueError("track_gate: pose_table [S,12] beside health [S,4] expected")
+    slot_eff = _track_slot_out(what, slot_eff, B, pose_table.device)
+    _lib.check(_lib.load().g6d_track_gate(_ptr(pose_table), _ptr(health), _ptr(slot_stream), _ptr(slot_eff), B, _stream()), "g6d_track_gate")
+    return slot_eff
+
+
+def track_health(pose_prev, pose_new, K, pic, size, slot_eff, reset, center, diameter, policy, health, measures, slot_commit=None,
+                 slot_draw=None):
+    """After the refinement, before the commit (g6d_track_health): pose_prev [B,12] (the gathered poses; None with reset), pose_new [B,12],
+    K [B,9], pic int32 [B,2] picture (w, h) per slot or None for size = (W, H), slot_eff int32 [B], center [3], diameter (the box diagonal),
+    policy: the thresholds (tracking.HealthPolicy: patience, min_px, max_px, margin, max_rot_deg, max_shift, max_log2_scale), passed by
+    value.  Updates health int32 [S,4] and measures float32 [S,12] in place -> (slot_commit, slot_draw) int32 [B]."""
+    what = "track_health"
+    ts = [t for t in (pose_prev, pose_new, K, pic, slot_eff, center, health, measures) if t is not None]
+    _track_same_device(what, *ts)
+    _f32c(*[t for t in (pose_prev, pose_new, K, center) if t is not None])
+    B = _track_map(what, slot_eff)
+    _track_health_tables(what, health, measures)
+    if (pose_prev is None) != bool(reset):
+        raise ValueError("track_health: pose_prev is given exactly when reset is false")
+    if pose_new.numel() != 12 * B or K.numel() != 9 * B or center.numel() != 3 or (pose_prev is not None and pose_prev.numel() != 12 * B):
+        raise ValueError("track_health: pose_prev / pose_new [B,12], K [B,9] and center [3] expected")
+    if pic is not None and (pic.dtype != torch.int32 or tuple(pic.shape) != (B, 2) or not pic.is_contiguous()):
+        raise ValueError("track_health: pic must be a contiguous int32 [B,2] tensor")
+    W, H = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    if pic is None and (W < 1 or H < 1):
+        raise ValueError("track_health: pic or size = (W, H) with W, H >= 1 expected")
+    if not float(diameter) > 0 or int(policy.patience) < 1:
+        raise ValueError("track_health: diameter > 0 and patience >= 1 expected")
+    slot_commit = _track_slot_out(what, slot_commit, B, pose_new.device)
+    slot_draw = _track_slot_out(what, slot_draw, B, pose_new.device)
+    _lib.check(_lib.load().g6d_track_health(_ptr(pose_prev), _ptr(pose_new), _ptr(K), _ptr(pic), W, H, _ptr(slot_eff), int(bool(reset)),
+                                           _ptr(center), float(diameter), int(policy.patience), float(policy.min_px), float(policy.max_px),
+                                           float(policy.margin), float(policy.max_rot_deg), float(policy.max_shift),
+                                           float(policy.max_log2_scale), _ptr(health), _ptr(measures), _ptr(slot_commit), _ptr(slot_draw), B,
+                                           _stream()), "g6d_track_health")
+    return slot_commit, slot_draw
+
+
+def track_verify(det, pose_table, K, slot_commit, center, diameter, ref_px, policy, health, measures):
+    """The detector's check of the slots committed in this tick (g6d_track_verify): det [B,5] as DeviceChain.detect_batch forms it,
+    pose_table [S,12], K [B,9], slot_commit int32 [B], ref_px (the object's mean projected diameter in the reference views), policy:
+    verify_shift, verify_log2_scale, verify_patience by value.  Updates health and measures (columns 7, 8) in place."""
+    what = "track_verify"
+    _track_same_device(what, det, pose_table, K, slot_commit, center, health, measures)
+    _f32c(det, pose_table, K, center)
+    B = _track_map(what, slot_commit)
+    _track_health_tables(what, health, measures)
+    if (tuple(det.shape) != (B, 5) or K.numel() != 9 * B or center.numel() != 3 or pose_table.dim() != 2 or
+            tuple(pose_table.shape) != (health.shape[0], 12)):
+        raise ValueError("track_verify: det [B,5], K [B,9], center [3] and pose_table [S,12] expected")
+    if not float(diameter) > 0 or not float(ref_px) > 0 or int(policy.verify_patience) < 1:
+        raise ValueError("track_verify: diameter > 0, ref_px > 0 and verify_patience >= 1 expected")
+    _lib.check(_lib.load().g6d_track_verify(_ptr(det), _ptr(pose_table), _ptr(K), _ptr(slot_commit), _ptr(center), float(diameter),
+                                           float(ref_px), float(policy.verify_shift), float(policy.verify_log2_scale),
+                                           int(policy.verify_patience), _ptr(health), _ptr(measures), B, _stream()), "g6d_track_verify")
+
+
 # ------------------------------------------------------------------------------------------------ frame ingest
 def frame_ingest(table, n, out, K_out):
     """One launch of g6d_frame_ingest: `table` a contiguous uint8 device tensor holding n lib.G6dFrame records (8-byte aligned; built and

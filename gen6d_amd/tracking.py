@@ -21,10 +21,18 @@ many streams (cameras or clients watching one object) at once:
     (raw and / or smoothed pose), in an encoder's or a display's format, into device or pinned host buffers the caller names
     (`gen6d_amd.emit.Sink`).  After the lane's tick (or the commit of an init chunk) the corners are projected on the device and ONE
     g6d_frame_emit launch per lane and tick fills that lane's sinks, stream-ordered on the lane's stream, outside the captured graph
-    (DESIGN.md §4.18).  A tracker used without sinks launches nothing of this.
+    (DESIGN.md §4.18).  A tracker used without sinks launches nothing of this;
+  * with `health=HealthPolicy(...)` every stream carries a status (TRACKING / SUSPECT / LOST) that the device keeps: a gate parks lost
+    streams and non-finite table rows before the gather, a health launch judges every refined pose before the commit (a bad frame is
+    not committed), the detector can check the committed poses every n-th tick, and the host, which sees the status with a fixed lag,
+    sends lost streams through the acquisition path again.  A tracker without a policy launches nothing of this.
 
 `track_streams` is the one-call form for whole sequences, with one synchronisation at the end and the networks' fp16 pair range guard.
 """
+import collections
+import dataclasses
+import math
+
 import numpy as np
 import torch
 
@@ -38,10 +46,73 @@ from .network import refiner as _refiner
 INIT_CHUNK = 8          # first frames per query_batch call: the batch size query_batch's detection + selection path is tested at
 
 
+# health[s] = (status, bad, vbad, flags), include/gen6d_hip.h
+NONE, TRACKING, SUSPECT, LOST = 0, 1, 2, 3
+NONFINITE, BEHIND, SMALL, LARGE, OUTSIDE, ROT, SHIFT, SCALE, VERIFY_POS, VERIFY_SCALE = (1 << i for i in range(10))
+
+Health = collections.namedtuple("Health", "status bad vbad flags measures")
+
+
+@dataclasses.dataclass(frozen=True)
+class HealthPolicy:
+    """When is a stream still tracking its object, and what happens when it is not.
+
+    The defaults are policy, not measurements: nobody has run real sequences through this tracker, only the synthetic database, so
+    treat them as a starting point for your cameras.  A threshold of inf disables its gate; a negative motion threshold never passes.
+
+    patience: consecutive bad frames before a stream is LOST.  min_px / max_px: smallest projected object diameter in picture pixels /
+    largest in units of the longer picture side.  margin: how far the projected centre may lie outside the picture, in projected
+    diameters.  max_rot_deg, max_shift (projected diameters), max_log2_scale (|log2(z_prev / z_new)|): the motion between the last
+    committed pose and the refined one.  verify_every: 0 is off; otherwise on every n-th tick of a group of slots the detector checks the poses
+    that tick committed: its position within verify_shift projected diameters of the projected centre and its size within verify_log2_scale octaves
+    of the projected one, LOST after verify_patience consecutive failed checks.  reacquire_every: pushes of a LOST stream between
+    acquisition attempts.  lag: the host acts on the status of a lane's tick t at push t + lag: push p waits for tick p - lag, so at
+    most `lag` ticks of a lane are in flight, the one being enqueued included (0 behaves as 1: a tick's status cannot be known before
+    the tick is enqueued)."""
+    patience: int = 3
+    min_px: float = 8.0
+    max_px: float = 4.0
+    margin: float = 0.5
+    max_rot_deg: float = 45.0
+    max_shift: float = 1.0
+    max_log2_scale: float = 1.0
+    verify_every: int = 0
+    verify_shift: float = 1.0
+    verify_log2_scale: float = 1.5
+    verify_patience: int = 2
+    reacquire_every: int = 1
+    lag: int = 2
+
+    def __post_init__(self):
+        for name in ("patience", "verify_patience", "reacquire_every", "lag", "verify_every"):
+            if not isinstance(getattr(self, name), (int, np.integer)) or isinstance(getattr(self, name), bool):
+                raise ValueError(f"HealthPolicy: {name} must be an integer")
+        if self.patience < 1 or self.verify_patience < 1 or self.reacquire_every < 1:
+            raise ValueError("HealthPolicy: patience, verify_patience and reacquire_every must be >= 1")
+        if self.lag < 0 or self.verify_every < 0:
+            raise ValueError("HealthPolicy: lag and verify_every must be >= 0")
+        for name in ("min_px", "max_px", "margin", "max_rot_deg", "max_shift", "max_log2_scale", "verify_shift", "verify_log2_scale"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or math.isnan(float(v)):
+                raise ValueError(f"HealthPolicy: {name} must be a number (inf disables the gate), not NaN")
+
+    @classmethod
+    def lax(cls, **kw):
+        """Every soft gate infinite: only a non-finite pose or an object centre behind the camera loses a stream."""
+        inf = float("inf")
+        soft = dict(min_px=-inf, max_px=inf, margin=inf, max_rot_deg=inf, max_shift=inf, max_log2_scale=inf, verify_shift=inf,
+                    verify_log2_scale=inf)
+        soft.update(kw)
+        return cls(**soft)
+
+
 class _Lane:
     def __init__(self, stream):
         self.stream, self.graph, self.img, self.K, self.map, self.out = stream, None, None, None, None, None
         self.emitted = None                    # event recorded after the lane's last emit (wait_emitted)
+        # health: slot maps and picture sizes of the tick (static), the status mirror's ring, the pushes this lane worked in / consumed
+        self.eff = self.commit = self.draw = self.pic = self.rows = None
+        self.snap, self.snap_ev, self.n, self.consumed, self.ticks = [], [], 0, 0, {}
 
 
 class _Serial:
@@ -67,7 +138,7 @@ class _Serial:
 
 class StreamTracker:
     def __init__(self, estimator, max_streams, batch=8, lanes=2, track_iter=1, smooth_num=5, smooth_std=2.5, object_pts=None,
-                 graphs=True, frame_size=None):
+                 graphs=True, frame_size=None, health=None):
         if estimator.refiner is None:
             raise ValueError("StreamTracker: the estimator has no refiner (tracking refines every frame)")
         self.max_streams, self.batch, self.nlanes = int(max_streams), int(batch), int(lanes)
@@ -78,6 +149,9 @@ class StreamTracker:
             raise ValueError(f"StreamTracker: 1 <= batch <= {_refiner.MAX_BATCH} expected")
         if not 1 <= self.num <= 64 or not self.std > 0:
             raise ValueError("StreamTracker: 1 <= smooth_num <= 64 and smooth_std > 0 expected")
+        if health is not None and not isinstance(health, HealthPolicy):
+            raise ValueError("StreamTracker: health must be a HealthPolicy or None")
+        self.policy = health
         self.est = estimator
         self.chain = estimator.device_chain()
         self.dev = torch.device(estimator.device)
@@ -110,6 +184,8 @@ class StreamTracker:
             self._shape = self.frame_size + (3,)
         self._records = None                   # track_streams: [(rows [n,2,3,4] device, [(row, stream, frame)])]
         self._sinks = {}                       # the running push: stream id -> [Sink, ...]
+        if self.policy is not None:
+            self._health_state()
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
             t = net.__dict__.get("_range")
             if t is not None and t.names:
@@ -142,6 +218,9 @@ class StreamTracker:
             groups.setdefault(s // self.batch, []).append((s, frames[i], Ks[i]))
         cur = torch.cuda.current_stream(self.dev) if self.cuda else None
         self._sinks = per_stream
+        if self.policy is not None:
+            self._consume()                    # before any lane work: the wait stays clear of a capture
+        worked = []
         for g in sorted(groups):
             lane = self._lanes[g % self.nlanes]
             if cur is not None:
@@ -152,8 +231,14 @@ class StreamTracker:
                 else:
                     ents = [(s, self._upload(im, lane), self._upload(K.reshape(3, 3).float() if torch.is_tensor(K) else
                                                                  np.asarray(K, np.float32).reshape(3, 3), lane)) for s, im, K in groups[g]]
-                track = [e for e in ents if self._started[e[0]]]
-                init = [e for e in ents if not self._started[e[0]]]
+                fresh = {e[0] for e in ents if not self._started[e[0]] or self._due(e[0])}
+                track = [e for e in ents if e[0] not in fresh]
+                init = [e for e in ents if e[0] in fresh]
+                if self.policy is not None:
+                    if lane not in worked:
+                        worked.append(lane)
+                    for s, _, _ in init:       # an acquisition: what the mirror held about the stream is history
+                        self._mirror[s], self._fresh[s], self._attempt[s], self._seen_ok[s] = 0, lane.n, self._frames[s], False
                 if track:
                     self._tick(lane, track)
                 for c0 in range(0, len(init), INIT_CHUNK):
@@ -161,10 +246,28 @@ class StreamTracker:
                 if self.cuda and any(s in self._sinks for s, _, _ in ents):
                     lane.emitted = torch.cuda.Event()
                     lane.emitted.record(lane.stream)
+        for lane in worked:
+            self._snapshot(lane)
         self._sinks = {}
         for s in ids:
             self._started[s] = True
             self._frames[s] += 1
+
+    def health(self, stream_ids=None):
+        """Synchronise and refresh the host's status mirror -> {id: Health(status, bad, vbad, flags, measures [12] float32)} of each
+        stream (stream_ids None: every stream that has a frame).  Needs a tracker with a HealthPolicy."""
+        if self.policy is None:
+            raise ValueError("StreamTracker.health: the tracker has no HealthPolicy")
+        ids = [s for s in range(self.max_streams) if self._frames[s]] if stream_ids is None else self._ids(stream_ids)
+        if self.cuda:
+            torch.cuda.synchronize(self.dev)
+        Hh, M = self.health_table.cpu().numpy(), self.measures.cpu().numpy()
+        self._mirror[:] = Hh
+        for s in range(self.max_streams):
+            self._seen_ok[s] = self._seen_ok[s] or int(Hh[s, 0]) in (TRACKING, SUSPECT)
+        for ln in self._lanes:                 # every snapshot in flight is older than what was just read
+            ln.consumed = ln.n
+        return {s: Health(int(Hh[s, 0]), int(Hh[s, 1]), int(Hh[s, 2]), int(Hh[s, 3]), M[s].copy()) for s in ids}
 
     def result(self, stream_ids=None):
         """Synchronise -> {id: (pose [3,4], smoothed [3,4])} float32 numpy of each stream's latest frame (stream_ids None: every stream
@@ -193,8 +296,65 @@ class StreamTracker:
         """The next frame of these streams starts over: detection, selection, full refinement, fresh smoothing history."""
         for s in self._ids(stream_ids):
             self._started[s] = False
+            if self.policy is not None:
+                self._mirror[s], self._seen_ok[s] = 0, False
 
     # ------------------------------------------------------------------ internals
+    def _health_state(self):
+        S, pol = self.max_streams, self.policy
+        self.health_table = torch.zeros((S, 4), dtype=torch.int32, device=self.dev)
+        self.measures = torch.zeros((S, 12), dtype=torch.float32, device=self.dev)
+        self.diameter = float(np.linalg.norm(np.asarray(self.box_np[6], np.float64) - np.asarray(self.box_np[0], np.float64)))
+        info = self.est.ref_info               # the object's mean projected diameter in the reference views, float64
+        P, Kr = np.asarray(info["poses"], np.float64).reshape(-1, 3, 4), np.asarray(info["Ks"], np.float64).reshape(-1, 3, 3)
+        z = P[:, 2, :3] @ np.asarray(info["center"], np.float64).reshape(3) + P[:, 2, 3]
+        self.ref_px = float(np.mean(0.5 * (Kr[:, 0, 0] + Kr[:, 1, 1]) * self.diameter / z))
+        self._mirror = np.zeros((S, 4), np.int32)              # the status the host routes on (fixed lag behind the device)
+        self._fresh = [0] * S                  # the lane push index of the stream's last acquisition: older snapshots do not count
+        self._attempt = [0] * S                # the stream's own push index of its last acquisition
+        self._seen_ok = [False] * S            # the mirror has shown the stream alive since that acquisition
+        for li, ln in enumerate(self._lanes):
+            ln.rows = [s for s in range(S) if (s // self.batch) % self.nlanes == li]
+            for _ in range(pol.lag + 1):
+                buf = torch.zeros((S, 4), dtype=torch.int32)
+                ln.snap.append(buf.pin_memory() if self.cuda else buf)
+                ln.snap_ev.append(None)
+            if self.cuda:
+                for t in (self.health_table, self.measures):
+                    t.record_stream(ln.stream)
+
+    def _due(self, s):
+        """A stream the mirror shows LOST takes the acquisition path at the first push after the host learnt of the loss, and after a
+        failed attempt at every reacquire_every-th push of the stream."""
+        if self.policy is None or self._mirror[s, 0] != LOST:
+            return False
+        return self._seen_ok[s] or self._frames[s] - self._attempt[s] >= self.policy.reacquire_every
+
+    def _consume(self):
+        """Top of a push (the lane's push number n): wait for the snapshot of the lane's push n - lag and take its rows into the mirror."""
+        lag = self.policy.lag
+        for ln in self._lanes:
+            while ln.consumed <= ln.n - max(lag, 1):
+                i, k = ln.consumed, ln.consumed % (lag + 1)
+                if ln.snap_ev[k] is not None:
+                    ln.snap_ev[k].synchronize()
+                snap = ln.snap[k].numpy()
+                for s in ln.rows:
+                    if self._fresh[s] <= i:
+                        self._mirror[s] = snap[s]
+                        self._seen_ok[s] = self._seen_ok[s] or int(snap[s, 0]) in (TRACKING, SUSPECT)
+                ln.consumed += 1
+
+    def _snapshot(self, lane):
+        """End of a lane's work in a push: the health table travels to the next pinned buffer of the lane's ring, stream-ordered."""
+        k = lane.n % (self.policy.lag + 1)
+        with _Serial(lane.stream):
+            lane.snap[k].copy_(self.health_table, non_blocking=True)
+            if self.cuda:
+                lane.snap_ev[k] = torch.cuda.Event()
+                lane.snap_ev[k].record(lane.stream)
+        lane.n += 1
+
     def _nets(self):
         return [n for n in (self.est.detector, self.est.selector, self.est.refiner) if n is not None]
 
@@ -278,9 +438,23 @@ class StreamTracker:
             lane.img = torch.zeros((B, h, w, 3), dtype=torch.uint8, device=self.dev)
             lane.K = torch.from_numpy(np.repeat(EV.pseudo_K(h, w)[None], B, 0)).to(self.dev)
             lane.map = torch.full((B,), -1, dtype=torch.int32, device=self.dev)
+            if self.policy is not None:
+                lane.eff, lane.commit, lane.draw = (torch.full((B,), -1, dtype=torch.int32, device=self.dev) for _ in range(3))
+                lane.pic = torch.tensor([[w, h]] * B, dtype=torch.int32, device=self.dev)
 
     def _tick_fn(self, lane):
-        """gather -> track_iter refinement steps (query_batch's refine loop) -> commit, on the lane's static buffers."""
+        """gather -> track_iter refinement steps (query_batch's refine loop) -> commit, on the lane's static buffers.  With a health
+        policy: gate -> gather of the gated map -> steps -> health -> commit of the frames that passed."""
+        if self.policy is not None:
+            B = self.batch
+            ops.track_gate(self.pose_table, self.health_table, lane.map, lane.eff)
+            pose0 = ops.track_gather(self.pose_table, lane.eff, self.parking)
+            r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
+            K9 = lane.K.reshape(B, 9)
+            ops.track_health(pose0.reshape(B, 12), r["pose"].reshape(B, 12), K9, lane.pic, None, lane.eff, False, self.chain.center,
+                             self.diameter, self.policy, self.health_table, self.measures, lane.commit, lane.draw)
+            return ops.track_commit(r["pose"], K9, lane.commit, False, self.box, self.num, self.std, self.pose_table, self.hist,
+                                    self.hist_count, self.smooth_table)
         pose0 = ops.track_gather(self.pose_table, lane.map, self.parking)
         r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
         return ops.track_commit(r["pose"], lane.K.reshape(self.batch, 9), lane.map, False, self.box, self.num, self.std, self.pose_table,
@@ -313,15 +487,42 @@ class StreamTracker:
                 lane.img[b].copy_(im)
                 lane.K[b].copy_(K)
         lane.map.copy_(self._upload(m))
+        if self.policy is not None:            # the picture inside each slot's canvas, (w, h)
+            h, w = self._shape[:2]
+            pic = np.tile(np.asarray([w, h], np.int32), (self.batch, 1))
+            if self.frame_size is not None:
+                for (s, f, _), b in zip(ents, slots):
+                    pic[b] = I.plan(f, (h, w))[1::-1]
+            lane.pic.copy_(self._upload(pic))
         if self.graphs:
             lane.graph.replay()
             out = lane.out
         else:
             out = self._tick_fn(lane)
-        if self._records is not None:
-            self._records.append((out.clone(), [(b, s, self._frames[s]) for (s, _, _), b in zip(ents, slots)]))
+        rows = [(b, s, self._frames[s]) for (s, _, _), b in zip(ents, slots)]
+        if self.policy is not None:
+            g = ents[0][0] // self.batch           # groups that share a lane count their own ticks: each is checked every n-th time
+            lane.ticks[g] = lane.ticks.get(g, 0) + 1
+            if self.policy.verify_every and lane.ticks[g] % self.policy.verify_every == 0:
+                self._verify(lane)
+            if self._records is not None:
+                self._records.append((out.clone(), rows, lane.commit.clone(), self.health_table[:, 0].clone()))
+        elif self._records is not None:
+            self._records.append((out.clone(), rows))
         if self._sinks:
-            self._emit(lane.img, lane.K.reshape(self.batch, 9), lane.map, ents, slots)
+            self._emit(lane.img, lane.K.reshape(self.batch, 9), lane.map if self.policy is None else lane.draw, ents, slots)
+
+    def _verify(self, lane):
+        """The detector's check of the poses this tick committed: the detection half of query_batch on the lane's image batch in chunks
+        of <= INIT_CHUNK images and one g6d_track_verify launch per chunk, eager on the lane's stream after the tick's graph.  The
+        tick's slot_draw is not recomputed: a stream this check has just lost still shows this frame's (committed) box and loses it
+        from the next frame on."""
+        K9 = lane.K.reshape(self.batch, 9)
+        for c0 in range(0, self.batch, INIT_CHUNK):
+            c1 = min(c0 + INIT_CHUNK, self.batch)
+            det = self.chain.detect_batch(lane.img[c0:c1])
+            ops.track_verify(det, self.pose_table, K9[c0:c1], lane.commit[c0:c1], self.chain.center, self.diameter, self.ref_px,
+                             self.policy, self.health_table, self.measures)
 
     def _init(self, ents):
         n = len(ents)
@@ -334,10 +535,25 @@ class StreamTracker:
             Ks = torch.stack([K for _, _, K in ents], 0)
         r = self.chain.query_batch(imgs, Ks)
         ids = self._upload(np.asarray([s for s, _, _ in ents], np.int32))
-        out = ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), ids, True, self.box, self.num, self.std, self.pose_table, self.hist,
-                               self.hist_count, self.smooth_table)
-        if self._records is not None:
-            self._records.append((out, [(i, s, self._frames[s]) for i, (s, _, _) in enumerate(ents)]))
+        rows = [(i, s, self._frames[s]) for i, (s, _, _) in enumerate(ents)]
+        if self.policy is not None:            # an acquisition that fails its gates is not committed: the stream stays LOST
+            H, W = self._shape[:2]
+            pic = None
+            if self.frame_size is not None:
+                pic = self._upload(np.asarray([I.plan(f, (H, W))[1::-1] for _, f, _ in ents], np.int32))
+            commit, draw = ops.track_health(None, r["pose"].reshape(n, 12), Ks.reshape(n, 9), pic, (W, H), ids, True, self.chain.center,
+                                            self.diameter, self.policy, self.health_table, self.measures)
+            out = torch.zeros((n, 2, 3, 4), dtype=torch.float32, device=self.dev)
+            ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), commit, True, self.box, self.num, self.std, self.pose_table,
+                             self.hist, self.hist_count, self.smooth_table, out=out)
+            if self._records is not None:
+                self._records.append((out, rows, commit, self.health_table[:, 0].clone()))
+            ids = draw
+        else:
+            out = ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), ids, True, self.box, self.num, self.std, self.pose_table,
+                                   self.hist, self.hist_count, self.smooth_table)
+            if self._records is not None:
+                self._records.append((out, rows))
         if self._sinks:
             self._emit(imgs, Ks.reshape(n, 9), ids, ents, list(range(n)))
 
@@ -361,14 +577,24 @@ class StreamTracker:
         """track_streams: one synchronisation, one read-back -> per stream (poses [T,3,4], smoothed [T,3,4])."""
         if self.cuda:
             torch.cuda.synchronize(self.dev)
-        rows = torch.cat([r.reshape(-1, 2, 12) for r, _ in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 2, 12))
+        rows = torch.cat([r[0].reshape(-1, 2, 12) for r in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 2, 12))
         res = [(np.zeros((T, 3, 4), np.float32), np.zeros((T, 3, 4), np.float32)) for T in lengths]
+        if self.policy is not None:            # ... and status [T]; a frame that was not committed repeats the previous frame's poses
+            res = [r + (np.zeros(len(r[0]), np.int32),) for r in res]
+            commits = torch.cat([r[2] for r in self._records], 0).cpu().numpy() if self._records else np.zeros(0, np.int32)
+            status = torch.stack([r[3] for r in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 0), np.int32)
         base = 0
-        for r, ents in self._records:
-            for row, s, f in ents:
+        for i, rec in enumerate(self._records):
+            for row, s, f in rec[1]:
+                if self.policy is not None:
+                    res[s][2][f] = status[i, s]
+                    if commits[base + row] < 0:
+                        if f:
+                            res[s][0][f], res[s][1][f] = res[s][0][f - 1], res[s][1][f - 1]
+                        continue
                 res[s][0][f] = rows[base + row, 0].reshape(3, 4)
                 res[s][1][f] = rows[base + row, 1].reshape(3, 4)
-            base += r.shape[0]
+            base += rec[0].shape[0]
         return res
 
 
@@ -425,7 +651,10 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
     [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  With
     `frame_size=(H, W)` the frames are `ingest.Frame`s (or [h,w,3] arrays) of any size and format, carry their own K, and Ks stays None.  Frame t of
     every stream that has one is pushed in tick t; one synchronisation at the end.  Runs under the estimator's range guard: if an fp16
-    pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32."""
+    pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32.
+    With `health=HealthPolicy(...)` every stream's tuple is (poses, smoothed, status [T] int32): the status after each frame; a frame
+    that was not committed repeats the previous frame's poses (all zero before the first commit).  The host-driven recomputation has
+    no health notion: it reports every frame as TRACKING."""
     seqs = [list(s) for s in streams]
     kw = dict(tracker_kw)
     native = kw.get("frame_size") is not None
@@ -449,4 +678,6 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
                     for fr, Kh in host]
         return [host_track(estimator, frames, Kss[s], kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
                 for s, frames in enumerate(seqs)]
-    return estimator._range_guarded(run, recompute)
+    if kw.get("health") is None:
+        return estimator._range_guarded(run, recompute)
+    return estimator._range_guarded(run, lambda: [r + (np.full(len(r[0]), TRACKING, np.int32),) for r in recompute()])

@@ -561,6 +561,44 @@ int g6d_track_gather(const float* pose_table, const int* slot_stream, const floa
 int g6d_track_commit(const float* pose, const float* K, const int* slot_stream, int reset, const float* box, int num, float std,
                      float* pose_table, double* hist, int* hist_count, float* smooth_table, float* out, int batch, g6d_stream_t stream);
 
+/* Track health (gen6d_amd/tracking.py HealthPolicy; the reference's predict.py loop has no counterpart: it feeds every
+ * frame's pose into the next frame unconditionally); additive within ABI 12.  Two more per-stream tables: health [streams][4] int32 =
+ * (status, bad, vbad, flags) and measures [streams][12] float32 = (u, v, z, d_px, rot_deg, shift, log2_scale, verify_shift,
+ * verify_log2_scale, 0, 0, 0), the measures of the last evaluated candidate pose.  One thread per slot, float64 on the float32 inputs;
+ * every comparison is !(x <= thr): a NaN fails, an infinite threshold disables its gate.  The policy travels by value, so a captured
+ * graph holds it.
+ * g6d_track_gate, before the gather: slot_eff[b] = slot_stream[b] when the slot is used, its stream is not LOST and the 12 floats of
+ * its pose_table row are finite, else -1 (the gather then parks the slot like an unused one, so nothing non-finite reaches the networks).
+ * A non-finite row of a stream that is not LOST sets status = LOST, flags = NONFINITE. */
+enum { G6D_TRACK_NONE = 0, G6D_TRACK_TRACKING = 1, G6D_TRACK_SUSPECT = 2, G6D_TRACK_LOST = 3 };
+enum { G6D_TRACK_NONFINITE = 1, G6D_TRACK_BEHIND = 2, G6D_TRACK_SMALL = 4, G6D_TRACK_LARGE = 8, G6D_TRACK_OUTSIDE = 16, G6D_TRACK_ROT = 32,
+       G6D_TRACK_SHIFT = 64, G6D_TRACK_SCALE = 128, G6D_TRACK_VERIFY_POS = 256, G6D_TRACK_VERIFY_SCALE = 512 };
+int g6d_track_gate(const float* pose_table, int32_t* health, const int* slot_stream, int* slot_eff, int batch, g6d_stream_t stream);
+/* g6d_track_health, after the refinement and before the commit.  pose_prev [batch][12] (the gathered poses; NULL with reset != 0, an
+ * acquisition), pose_new [batch][12], K [batch][9], pic [batch][2] int32 (picture (w, h) per slot; NULL: (W, H)), center [3], diameter
+ * (the box diagonal).  Per used slot of slot_eff, with X = R center + t, z = X.z, f = (K00 + K11) / 2, (u, v) = (K X).xy / z,
+ * d_px = f diameter / z:
+ *   NONFINITE an entry of pose_new is not finite (ends the evaluation, measures 0);  BEHIND !(z > 0) (ends it too, only z is recorded);
+ *   SMALL !(d_px >= min_px);  LARGE !(d_px <= max_px max(w, h));  OUTSIDE u outside [-margin d_px, w + margin d_px] or v likewise with h;
+ *   without reset: ROT rot_deg = acos(clamp((tr(R_new R_prev^T) - 1) / 2, -1, 1)) 180 / pi, !(rot_deg <= max_rot_deg);
+ *   SHIFT shift = hypot(u - u_prev, v - v_prev) / d_px under pose_prev and the same K;  SCALE log2_scale = |log2(z_prev / z)|, which also
+ *   fails when !(z_prev > 0) (shift and log2_scale are then 0 and SHIFT is not evaluated).
+ * State: NONFINITE or BEHIND -> LOST; any other bit -> bad += 1, LOST if bad >= patience else SUSPECT; no bit -> bad = 0, TRACKING; with
+ * reset: any bit -> LOST else TRACKING, bad = vbad = 0.  flags bits 0..7 are replaced, 8..9 kept.  slot_commit[b] = the stream id when
+ * the frame passed, slot_draw[b] = the stream id unless the stream is LOST after this frame, else -1 (also for unused slots). */
+int g6d_track_health(const float* pose_prev, const float* pose_new, const float* K, const int32_t* pic, int W, int H, const int* slot_eff,
+                     int reset, const float* center, double diameter, int patience, double min_px, double max_px, double margin,
+                     double max_rot_deg, double max_shift, double max_log2_scale, int32_t* health, float* measures, int* slot_commit,
+                     int* slot_draw, int batch, g6d_stream_t stream);
+/* g6d_track_verify, the detector's independent check of the slots committed in this tick: det [batch][5] = (x, y, 2^scale, cell) as the
+ * chain forms it (det[2] is the reference-to-query size ratio), the stream's committed raw pose from pose_table, ref_px = the object's
+ * mean projected diameter over the reference views.  verify_shift = hypot(det.x - u, det.y - v) / d_px, verify_log2_scale =
+ * |log2(det[2] ref_px / d_px)|; a failed check sets VERIFY_POS / VERIFY_SCALE and vbad += 1, LOST at vbad >= verify_patience; a passed
+ * one clears both bits and vbad.  flags bits 0..7 are kept. */
+int g6d_track_verify(const float* det, const float* pose_table, const float* K, const int* slot_commit, const float* center,
+                     double diameter, double ref_px, double verify_shift, double verify_log2_scale, int verify_patience, int32_t* health,
+                     float* measures, int batch, g6d_stream_t stream);
+
 /* Frame ingest (gen6d_amd/ingest.py; reference prepare.py:16-42 video2image + predict.py:45,52-54); additive within ABI 12.  ONE launch
  * reads n camera-native frames (packed RGB / BGR / RGBA / BGRA or NV12, any size, row pitch and quarter-turn rotation), scales each to
  * out_w x out_h with the integer bilinear below, and writes the RGB picture into the top-left corner of image `slot` of

@@ -10,6 +10,8 @@ each; the table gives the median and the spread (max - min) / median.
   python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p        (graphs only, the variants alternated)
   python tools/track_bench.py --streams 32 --emit nv12 [--emit-host]            (graphs only: no sinks / device sinks / pinned host sinks
                                                                                  of the working-resolution picture, alternated)
+  python tools/track_bench.py --streams 32 --health off,lax,verify10 [--lens 10000]   (graphs only: no HealthPolicy / every soft
+                                                     gate off / the same with the detector's check every 10th tick; --lens: see health_policy)
   rocprofv3 --kernel-trace --stats -d DIR -o track -- python tools/track_bench.py --profile 32      (one configuration, graphs)
   python tools/track_bench.py --stats-csv DIR/.../track_kernel_stats.csv --ticks N --tick-ms T --out profiles/r08_track_kernel_stats.md
 """
@@ -78,19 +80,34 @@ def make_sinks(S, hw, fmt, host):
     return [Sink(mk(), fmt) for _ in range(S)]
 
 
-def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=False):
-    """-> (seconds of the timed ticks, timed ticks).  ingest: None (plain frames, the tracker without frame_size) or a mode of
-    native_frames.  emit: None, or the format of one sink per stream filled on every push (emit_host: pinned host sinks)."""
+def health_policy(mode):
+    """off: no policy.  lax: the health launches with every soft gate off.  verify10: the same plus the detector's check on every 10th
+    tick.  The synthetic weights put the object centre at a depth of ~3e-5 focal lengths, i.e. ~0 with the database's intrinsics, where
+    about a third of all frames fall behind the camera, which no policy forgives: every such loss of a live stream costs one acquisition
+    (detection, selection, refine_iter steps) at the push where the host learns of it, and the run measures those.  `--lens MUL` feeds
+    every variant of a --health run (off included) intrinsics of MUL times the focal length, which keeps the centre in front: the
+    table's `lost` column counts the streams that are LOST at the end of a run."""
+    from gen6d_amd.tracking import HealthPolicy
+    if mode in (None, "off"):
+        return {}
+    return {"health": HealthPolicy.lax(verify_every={"lax": 0, "verify10": 10}[mode])}
+
+
+def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=False, health=None, lost=None):
+    """-> (seconds of the timed ticks, timed ticks).  lost: a list that receives the number of LOST streams at the end of a health run.  ingest: None (plain frames, the tracker without frame_size) or a mode of
+    native_frames.  emit: None, or the format of one sink per stream filled on every push (emit_host: pinned host sinks).  health: a
+    mode of health_policy."""
     import torch
     from gen6d_amd.tracking import StreamTracker
     ids = list(range(S))
+    hk = health_policy(health)
     if ingest in (None, "none"):
-        tr = StreamTracker(est, S, batch=batch, graphs=graphs)
+        tr = StreamTracker(est, S, batch=batch, graphs=graphs, **hk)
         Ks = [K] * S
         canvas = tuple(frames[0].shape[:2])
     else:
         frames, canvas = native_frames(frames, K, ingest)
-        tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas)
+        tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas, **hk)
         Ks = None
     frame = lambda s, t: frames[(7 * s + t) % len(frames)]
     kw = {"sinks": make_sinks(S, canvas, emit, emit_host)} if emit else {}
@@ -103,6 +120,8 @@ def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=F
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     tr.result()
+    if hk and lost is not None:
+        lost.append(sum(h.status == 3 for h in tr.health().values()))
     return dt, F - 2
 
 
@@ -135,6 +154,9 @@ def main():
                     "format per stream, alternated (with --profile: the profiled run emits)")
     ap.add_argument("--emit-host", action="store_true", help="--emit: pinned host sinks as a third variant (--profile: instead of device sinks)")
     ap.add_argument("--tick-ms", type=float, default=0.0)
+    ap.add_argument("--health", default=None, help="comma list of off / lax / verify10: graphs runs "
+                    "with these health policies, alternated (with --profile: the one policy of the profiled run)")
+    ap.add_argument("--lens", type=float, default=1.0, help="--health: every variant runs behind intrinsics of this many focal lengths")
     args = ap.parse_args()
     if args.stats_csv:
         txt = stats_table(args.stats_csv, args.ticks, args.tick_ms)
@@ -148,15 +170,42 @@ def main():
     import torch
     dev = torch.device("cuda", 0)
     est, frames, K = build(dev)
+    if args.health and args.lens != 1.0:
+        K = (np.asarray(K, np.float32) * np.array([[args.lens, 1, 1], [1, args.lens, 1], [1, 1, 1]])).astype(np.float32)
     if args.profile:
         S = args.profile
-        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest, args.emit, args.emit_host)
-        print(f"profile S={S} ingest={args.ingest} emit={args.emit}{' (host)' if args.emit and args.emit_host else ''}: {n} ticks, "
+        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest, args.emit, args.emit_host, args.health)
+        print(f"profile S={S} ingest={args.ingest} emit={args.emit}{' (host)' if args.emit and args.emit_host else ''} "
+              f"health={args.health}: {n} ticks, "
               f"{dt / n * 1e3:.3f} ms/tick")
         return
     configs = [(int(s), min(int(s), 8)) for s in args.streams.split(",")]
     if 32 in [c[0] for c in configs]:
         configs.append((32, 32))
+    if args.health:
+        modes = args.health.split(",")
+        lines = ["| streams | batch | health | tracked frames/s (median) | ms per tick | spread | runs (frames/s) | lost |",
+                 "|---:|---:|---|---:|---:|---:|---|---|"]
+        for S, B in configs:
+            res, lost = {m: [] for m in modes}, {m: [] for m in modes}
+            for _ in range(args.repeats):
+                for m in modes:                       # alternated
+                    dt, n = run(est, frames, K, S, args.frames, B, True, args.ingest, health=m, lost=lost[m])
+                    res[m].append((S * n / dt, dt / n * 1e3))
+            for m in modes:
+                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
+                med = float(np.median(fps))
+                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
+                             f"{', '.join(f'{v:.1f}' for v in fps)} | {', '.join(str(v) for v in lost[m]) or '-'} |")
+                print(lines[-1], flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("# Tracked frames/s by health policy (tools/track_bench.py --health)\n\n"
+                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
+                        f"of each policy, alternated, intrinsics of {args.lens:g} x the database's focal length.  off: no HealthPolicy; lax: gate, "
+                        "health, the status mirror and the host's routing with every soft gate off; verify10: the same with the detector's "
+                        "check on every 10th tick; lost: streams LOST at the end of each run.\n\n" + "\n".join(lines) + "\n")
+        return
     if args.emit:
         modes = ["none", "device"] + (["host"] if args.emit_host else [])
         lines = ["| streams | batch | sinks | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
