@@ -30,6 +30,7 @@ many streams (cameras or clients watching one object) at once:
 `track_streams` is the one-call form for whole sequences, with one synchronisation at the end and the networks' fp16 pair range guard.
 """
 import collections
+import contextlib
 import dataclasses
 import math
 
@@ -106,34 +107,93 @@ class HealthPolicy:
         return cls(**soft)
 
 
-class _Lane:
+# A frame on its way through a lane: frame is the ingest.Frame (K None) with frame_size, else the uploaded image beside its uploaded K;
+# slot is stream % batch in a tick and the index in its chunk in an init.
+_Entry = collections.namedtuple("_Entry", "stream slot frame K")
+# track_streams: out [n,2,3,4] of a tick or an init chunk, rows [(row, stream, frame)]; with a policy the committed map and the status
+_Record = collections.namedtuple("_Record", "out rows commit status")
+
+
+class _Lane:                                   # what a tick touches
     def __init__(self, stream):
         self.stream, self.graph, self.img, self.K, self.map, self.out = stream, None, None, None, None, None
         self.emitted = None                    # event recorded after the lane's last emit (wait_emitted)
-        # health: slot maps and picture sizes of the tick (static), the status mirror's ring, the pushes this lane worked in / consumed
-        self.eff = self.commit = self.draw = self.pic = self.rows = None
-        self.snap, self.snap_ev, self.n, self.consumed, self.ticks = [], [], 0, 0, {}
+        self.eff = self.commit = self.draw = self.pic = None   # health: slot maps and picture sizes of the tick (static)
+        self.ticks = {}                        # health: ticks per group of slots (the detector's check runs on every n-th)
 
 
-class _Serial:
+@contextlib.contextmanager
+def _Serial(stream):
     """The tracker's launches run on the lane's stream with whole ticks in flight: no intra-step stream forks (ops.SERIAL, as
     DeviceChain.capture)."""
+    old, ops.SERIAL = ops.SERIAL, True
+    try:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            yield
+    finally:
+        ops.SERIAL = old
 
-    def __init__(self, stream):
-        self.stream = stream
 
-    def __enter__(self):
-        self.old, ops.SERIAL = ops.SERIAL, True
-        self.ctx = torch.cuda.stream(self.stream) if self.stream is not None else None
-        if self.ctx is not None:
-            self.ctx.__enter__()
-        return self
+class _HealthMirror:
+    """The host's view of the device's health table, a fixed lag behind it: the status the host routes on.  rows: per
+    lane the streams whose groups run on it; pinned: the lanes' rings of snapshot buffers are pinned host memory (a GPU tracker)."""
 
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        ops.SERIAL = self.old
-        return False
+    def __init__(self, policy, rows, pinned):
+        S, ring = sum(len(r) for r in rows), policy.lag + 1
+        self.policy, self.rows = policy, rows
+        self.status = np.zeros((S, 4), np.int32)               # (status, bad, vbad, flags) per stream as the host last saw them
+        self._fresh = [0] * S                  # the lane push index of the stream's last acquisition: older snapshots do not count
+        self._attempt = [0] * S                # the stream's own push index of its last acquisition
+        self._seen_ok = [False] * S            # the view has shown the stream alive since that acquisition
+        self.n, self.consumed = [0] * len(rows), [0] * len(rows)       # pushes each lane worked in / whose snapshots are consumed
+        buf = lambda: torch.zeros((S, 4), dtype=torch.int32).pin_memory() if pinned else torch.zeros((S, 4), dtype=torch.int32)
+        self.snap = [[buf() for _ in range(ring)] for _ in rows]
+        self.events = [[None] * ring for _ in rows]
+
+    def _take(self, s, row):
+        self.status[s] = row
+        self._seen_ok[s] = self._seen_ok[s] or int(row[0]) in (TRACKING, SUSPECT)
+
+    def due(self, s, frame):
+        """A stream the view shows LOST takes the acquisition path at the first push (its own push index: `frame`) after the host learnt
+        of the loss, and after a failed attempt at every reacquire_every-th push of the stream."""
+        return self.status[s, 0] == LOST and (self._seen_ok[s] or frame - self._attempt[s] >= self.policy.reacquire_every)
+
+    def acquired(self, s, lane, frame):        # an acquisition on this lane: what the view held about the stream is history
+        self.status[s], self._fresh[s], self._attempt[s], self._seen_ok[s] = 0, self.n[lane], frame, False
+
+    def forget(self, s):                       # reset
+        self.status[s], self._seen_ok[s] = 0, False
+
+    def consume(self):
+        """Top of a push (a lane's push number n): wait for the snapshot of the lane's push n - lag and take its rows."""
+        lag = self.policy.lag
+        for li, rows in enumerate(self.rows):
+            while self.consumed[li] <= self.n[li] - max(lag, 1):
+                i, k = self.consumed[li], self.consumed[li] % (lag + 1)
+                if self.events[li][k] is not None:
+                    self.events[li][k].synchronize()
+                snap = self.snap[li][k].numpy()
+                for s in rows:
+                    if self._fresh[s] <= i:
+                        self._take(s, snap[s])
+                self.consumed[li] += 1
+
+    def snapshot(self, lane, table, stream):
+        """End of a lane's work in a push: the health table travels to the next buffer of the lane's ring, ordered on its stream."""
+        k = self.n[lane] % len(self.snap[lane])
+        with _Serial(stream):
+            self.snap[lane][k].copy_(table, non_blocking=True)
+            if stream is not None:
+                self.events[lane][k] = torch.cuda.Event()
+                self.events[lane][k].record(stream)
+        self.n[lane] += 1
+
+    def refresh(self, table):
+        """health(): the table as read after a synchronisation; every snapshot in flight is older."""
+        for s, row in enumerate(table):
+            self._take(s, row)
+        self.consumed = list(self.n)
 
 
 class StreamTracker:
@@ -151,9 +211,7 @@ class StreamTracker:
             raise ValueError("StreamTracker: 1 <= smooth_num <= 64 and smooth_std > 0 expected")
         if health is not None and not isinstance(health, HealthPolicy):
             raise ValueError("StreamTracker: health must be a HealthPolicy or None")
-        self.policy = health
-        self.est = estimator
-        self.chain = estimator.device_chain()
+        self.policy, self.est, self.chain = health, estimator, estimator.device_chain()
         self.dev = torch.device(estimator.device)
         self.cuda = self.dev.type == "cuda"
         if graphs and not self.cuda:
@@ -163,29 +221,29 @@ class StreamTracker:
         self.box_np = G.box_corners(pts)
         self.box = torch.from_numpy(self.box_np.astype(np.float32)).to(self.dev)
         S = self.max_streams
-        self.pose_table = torch.zeros((S, 12), dtype=torch.float32, device=self.dev)
-        self.smooth_table = torch.zeros((S, 12), dtype=torch.float32, device=self.dev)
+        self.pose_table, self.smooth_table = (torch.zeros((S, 12), dtype=torch.float32, device=self.dev) for _ in range(2))
         self.hist = torch.zeros((S, self.num, 8, 2), dtype=torch.float64, device=self.dev)
         self.hist_count = torch.zeros(S, dtype=torch.int32, device=self.dev)
         self.parking = self.chain.ref_poses[0].contiguous()
         self._lanes = [_Lane(torch.cuda.Stream(device=self.dev) if self.cuda else None) for _ in range(self.nlanes)]
+        self._mirror = None                    # the host's lagged view of the health table (_HealthMirror), with a policy
+        tables = [self.box, self.pose_table, self.smooth_table, self.hist, self.hist_count]
+        if health is not None:
+            tables += self._health_state()
         if self.cuda:
             for ln in self._lanes:             # the tables live as long as the tracker; their blocks outlive no lane's pending work
-                for t in (self.box, self.pose_table, self.smooth_table, self.hist, self.hist_count):
+                for t in tables:
                     t.record_stream(ln.stream)
-        self._started = [False] * S
+        self._started, self._shape = [False] * S, None
         self._frames = [0] * S                 # frames pushed per stream
-        self._shape = None
         self.frame_size = None                 # (H, W): frames of any size and format are ingested into H x W images on the device
         if frame_size is not None:
             if len(frame_size) != 2 or min(int(v) for v in frame_size) < 1:
                 raise ValueError("StreamTracker: frame_size must be (H, W) with H, W >= 1")
             self.frame_size = (int(frame_size[0]), int(frame_size[1]))
             self._shape = self.frame_size + (3,)
-        self._records = None                   # track_streams: [(rows [n,2,3,4] device, [(row, stream, frame)])]
+        self._records = None                   # track_streams: [_Record]
         self._sinks = {}                       # the running push: stream id -> [Sink, ...]
-        if self.policy is not None:
-            self._health_state()
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
             t = net.__dict__.get("_range")
             if t is not None and t.names:
@@ -203,7 +261,7 @@ class StreamTracker:
         ids = self._ids(stream_ids)
         if len(imgs) != len(ids) or (Ks is not None and len(Ks) != len(ids)):
             raise ValueError("StreamTracker.push: one image (and K) per stream id expected")
-        per_stream = self._sink_lists(ids, sinks)
+        self._sinks = self._sink_lists(ids, sinks)
         if self.frame_size is not None:
             if Ks is not None:
                 raise ValueError("StreamTracker.push: a tracker with frame_size takes the intrinsics in Frame.K, not in Ks")
@@ -211,43 +269,38 @@ class StreamTracker:
             Ks = [None] * len(ids)
         else:
             frames = [self._frame(im) for im in imgs]
-            h, w = self._shape[:2]
-            Ks = [EV.pseudo_K(h, w) if Ks is None else Ks[i] for i in range(len(ids))]
+            Ks = [EV.pseudo_K(*self._shape[:2])] * len(ids) if Ks is None else Ks
         groups = {}
-        for i, s in enumerate(ids):
-            groups.setdefault(s // self.batch, []).append((s, frames[i], Ks[i]))
+        for s, f, K in zip(ids, frames, Ks):
+            groups.setdefault(s // self.batch, []).append((s, f, K))
         cur = torch.cuda.current_stream(self.dev) if self.cuda else None
-        self._sinks = per_stream
-        if self.policy is not None:
-            self._consume()                    # before any lane work: the wait stays clear of a capture
-        worked = []
+        mirror = self._mirror
+        if mirror is not None:
+            mirror.consume()                   # before any lane work: the wait stays clear of a capture
+        worked = {}
         for g in sorted(groups):
-            lane = self._lanes[g % self.nlanes]
+            li, lane = g % self.nlanes, self._lanes[g % self.nlanes]
             if cur is not None:
                 lane.stream.wait_stream(cur)
             with _Serial(lane.stream):
-                if self.frame_size is not None:
-                    ents = groups[g]           # (stream, Frame, None): uploaded and converted by the lane's ingest launch
-                else:
-                    ents = [(s, self._upload(im, lane), self._upload(K.reshape(3, 3).float() if torch.is_tensor(K) else
-                                                                 np.asarray(K, np.float32).reshape(3, 3), lane)) for s, im, K in groups[g]]
-                fresh = {e[0] for e in ents if not self._started[e[0]] or self._due(e[0])}
-                track = [e for e in ents if e[0] not in fresh]
-                init = [e for e in ents if e[0] in fresh]
-                if self.policy is not None:
-                    if lane not in worked:
-                        worked.append(lane)
-                    for s, _, _ in init:       # an acquisition: what the mirror held about the stream is history
-                        self._mirror[s], self._fresh[s], self._attempt[s], self._seen_ok[s] = 0, lane.n, self._frames[s], False
+                ents = [self._entry(s, f, K, lane) for s, f, K in groups[g]]
+                fresh = {e.stream for e in ents if not self._started[e.stream] or
+                         (mirror is not None and mirror.due(e.stream, self._frames[e.stream]))}
+                track = [e for e in ents if e.stream not in fresh]
+                init = [e for e in ents if e.stream in fresh]
+                if mirror is not None:
+                    worked[li] = lane
+                    for e in init:
+                        mirror.acquired(e.stream, li, self._frames[e.stream])
                 if track:
                     self._tick(lane, track)
                 for c0 in range(0, len(init), INIT_CHUNK):
                     self._init(init[c0:c0 + INIT_CHUNK])
-                if self.cuda and any(s in self._sinks for s, _, _ in ents):
+                if self.cuda and any(e.stream in self._sinks for e in ents):
                     lane.emitted = torch.cuda.Event()
                     lane.emitted.record(lane.stream)
-        for lane in worked:
-            self._snapshot(lane)
+        for li, lane in worked.items():        # the last thing on the lane's stream in this push
+            mirror.snapshot(li, self.health_table, lane.stream)
         self._sinks = {}
         for s in ids:
             self._started[s] = True
@@ -256,17 +309,13 @@ class StreamTracker:
     def health(self, stream_ids=None):
         """Synchronise and refresh the host's status mirror -> {id: Health(status, bad, vbad, flags, measures [12] float32)} of each
         stream (stream_ids None: every stream that has a frame).  Needs a tracker with a HealthPolicy."""
-        if self.policy is None:
+        if self._mirror is None:
             raise ValueError("StreamTracker.health: the tracker has no HealthPolicy")
         ids = [s for s in range(self.max_streams) if self._frames[s]] if stream_ids is None else self._ids(stream_ids)
         if self.cuda:
             torch.cuda.synchronize(self.dev)
         Hh, M = self.health_table.cpu().numpy(), self.measures.cpu().numpy()
-        self._mirror[:] = Hh
-        for s in range(self.max_streams):
-            self._seen_ok[s] = self._seen_ok[s] or int(Hh[s, 0]) in (TRACKING, SUSPECT)
-        for ln in self._lanes:                 # every snapshot in flight is older than what was just read
-            ln.consumed = ln.n
+        self._mirror.refresh(Hh)
         return {s: Health(int(Hh[s, 0]), int(Hh[s, 1]), int(Hh[s, 2]), int(Hh[s, 3]), M[s].copy()) for s in ids}
 
     def result(self, stream_ids=None):
@@ -296,8 +345,8 @@ class StreamTracker:
         """The next frame of these streams starts over: detection, selection, full refinement, fresh smoothing history."""
         for s in self._ids(stream_ids):
             self._started[s] = False
-            if self.policy is not None:
-                self._mirror[s], self._seen_ok[s] = 0, False
+            if self._mirror is not None:
+                self._mirror.forget(s)
 
     # ------------------------------------------------------------------ internals
     def _health_state(self):
@@ -309,51 +358,9 @@ class StreamTracker:
         P, Kr = np.asarray(info["poses"], np.float64).reshape(-1, 3, 4), np.asarray(info["Ks"], np.float64).reshape(-1, 3, 3)
         z = P[:, 2, :3] @ np.asarray(info["center"], np.float64).reshape(3) + P[:, 2, 3]
         self.ref_px = float(np.mean(0.5 * (Kr[:, 0, 0] + Kr[:, 1, 1]) * self.diameter / z))
-        self._mirror = np.zeros((S, 4), np.int32)              # the status the host routes on (fixed lag behind the device)
-        self._fresh = [0] * S                  # the lane push index of the stream's last acquisition: older snapshots do not count
-        self._attempt = [0] * S                # the stream's own push index of its last acquisition
-        self._seen_ok = [False] * S            # the mirror has shown the stream alive since that acquisition
-        for li, ln in enumerate(self._lanes):
-            ln.rows = [s for s in range(S) if (s // self.batch) % self.nlanes == li]
-            for _ in range(pol.lag + 1):
-                buf = torch.zeros((S, 4), dtype=torch.int32)
-                ln.snap.append(buf.pin_memory() if self.cuda else buf)
-                ln.snap_ev.append(None)
-            if self.cuda:
-                for t in (self.health_table, self.measures):
-                    t.record_stream(ln.stream)
-
-    def _due(self, s):
-        """A stream the mirror shows LOST takes the acquisition path at the first push after the host learnt of the loss, and after a
-        failed attempt at every reacquire_every-th push of the stream."""
-        if self.policy is None or self._mirror[s, 0] != LOST:
-            return False
-        return self._seen_ok[s] or self._frames[s] - self._attempt[s] >= self.policy.reacquire_every
-
-    def _consume(self):
-        """Top of a push (the lane's push number n): wait for the snapshot of the lane's push n - lag and take its rows into the mirror."""
-        lag = self.policy.lag
-        for ln in self._lanes:
-            while ln.consumed <= ln.n - max(lag, 1):
-                i, k = ln.consumed, ln.consumed % (lag + 1)
-                if ln.snap_ev[k] is not None:
-                    ln.snap_ev[k].synchronize()
-                snap = ln.snap[k].numpy()
-                for s in ln.rows:
-                    if self._fresh[s] <= i:
-                        self._mirror[s] = snap[s]
-                        self._seen_ok[s] = self._seen_ok[s] or int(snap[s, 0]) in (TRACKING, SUSPECT)
-                ln.consumed += 1
-
-    def _snapshot(self, lane):
-        """End of a lane's work in a push: the health table travels to the next pinned buffer of the lane's ring, stream-ordered."""
-        k = lane.n % (self.policy.lag + 1)
-        with _Serial(lane.stream):
-            lane.snap[k].copy_(self.health_table, non_blocking=True)
-            if self.cuda:
-                lane.snap_ev[k] = torch.cuda.Event()
-                lane.snap_ev[k].record(lane.stream)
-        lane.n += 1
+        self._mirror = _HealthMirror(pol, [[s for s in range(S) if (s // self.batch) % self.nlanes == li] for li in range(self.nlanes)],
+                                     self.cuda)
+        return [self.health_table, self.measures]              # (recorded on the lanes' streams with the other tables)
 
     def _nets(self):
         return [n for n in (self.est.detector, self.est.selector, self.est.refiner) if n is not None]
@@ -384,53 +391,61 @@ class StreamTracker:
                 out[s] = lst
         return out
 
-    def _emit(self, imgs, K9, slot_map, ents, slots):
+    def _entry(self, s, frame, K, lane):
+        if K is None:                          # an ingest.Frame: uploaded and converted by the lane's ingest launch
+            return _Entry(s, None, frame, None)
+        K = K.reshape(3, 3).float() if torch.is_tensor(K) else np.asarray(K, np.float32).reshape(3, 3)
+        return _Entry(s, None, self._upload(frame, lane), self._upload(K, lane))
+
+    def _picture(self, e):
+        """The picture (h, w) of an entry inside its canvas: what the ingest plans for a Frame, a plain image fills the canvas."""
+        return I.plan(e.frame, self._shape[:2])[:2] if isinstance(e.frame, I.Frame) else tuple(e.frame.shape[:2])
+
+    def _pic(self, ents, n):
+        """int32 [n,2]: the picture (w, h) in each entry's slot, the whole canvas in a slot without an entry (g6d_track_health's pic)."""
+        h, w = self._shape[:2]
+        pic = np.tile(np.asarray([w, h], np.int32), (n, 1))
+        for e in ents:
+            pic[e.slot] = self._picture(e)[::-1]
+        return pic
+
+    def _emit(self, imgs, K9, slot_map, ents):
         """Project the box under the raw / smoothed poses just committed and fill the sinks of these streams: at most two
         g6d_track_corners launches and one g6d_frame_emit launch on the current (lane's) stream."""
-        todo = [(b, f, k) for (s, f, _), b in zip(ents, slots) for k in self._sinks.get(s, ())]
+        todo = [(e, k) for e in ents for k in self._sinks.get(e.stream, ())]
         if not todo:
             return
         n = slot_map.shape[0]                  # a corner set is read only by sinks that name it, so only those sets are computed
         pts = torch.empty((2, n, 8, 2), dtype=torch.int32, device=self.dev)
         valid = torch.empty((2, n), dtype=torch.int32, device=self.dev)
         for name, table in (("raw", self.pose_table), ("smooth", self.smooth_table)):
-            if any(k.box and k.pose == name for _, _, k in todo):
+            if any(k.box and k.pose == name for _, k in todo):
                 ops.track_corners(table, K9, slot_map, self.box, pts[E.POSES[name]], valid[E.POSES[name]])
-        H, W = imgs.shape[1:3]
-        sizes = [I.plan(f, (H, W))[:2] if self.frame_size is not None else (H, W) for _, f, _ in todo]
-        E.emit_frames(imgs, pts, valid, [k for _, _, k in todo], slots=[b for b, _, _ in todo], pic_sizes=sizes)
+        sizes = [self._picture(e) for e, _ in todo]
+        E.emit_frames(imgs, pts, valid, [k for _, k in todo], slots=[e.slot for e, _ in todo], pic_sizes=sizes)
 
     @staticmethod
     def _rgb(im):
-        if not torch.is_tensor(im):
-            im = np.asarray(im)
-        shape, dtype = tuple(im.shape), im.dtype
-        if dtype not in (np.uint8, torch.uint8) or len(shape) != 3 or shape[2] != 3:
+        im = im if torch.is_tensor(im) else np.asarray(im)
+        if im.dtype not in (np.uint8, torch.uint8) or len(im.shape) != 3 or im.shape[2] != 3:
             raise ValueError("StreamTracker: frames must be uint8 [H,W,3]")
         return im
 
     def _frame(self, im):
         im = self._rgb(im)
-        shape = tuple(im.shape)
-        if self._shape is None:
-            self._shape = shape
-        elif shape != self._shape:
-            raise ValueError(f"StreamTracker: frame shape {shape} differs from the tracker's {self._shape}")
+        self._shape = self._shape or tuple(im.shape)       # the first frame sets the tracker's shape
+        if tuple(im.shape) != self._shape:
+            raise ValueError(f"StreamTracker: frame shape {tuple(im.shape)} differs from the tracker's {self._shape}")
         return im
 
     def _upload(self, a, lane=None):
         """Host arrays -> device on the current (lane's) stream, through pinned memory: no host stall on the stream; device tensors are
         recorded on the lane's stream."""
-        if torch.is_tensor(a):
-            if a.device.type == "cuda":
-                a.record_stream(lane.stream)
-                return a.contiguous()
-            t = a
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(a))
-        if not self.cuda:
-            return t.to(self.dev)
-        return t.pin_memory().to(self.dev, non_blocking=True)
+        if torch.is_tensor(a) and a.device.type == "cuda":
+            a.record_stream(lane.stream)
+            return a.contiguous()
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.pin_memory().to(self.dev, non_blocking=True) if self.cuda else t.to(self.dev)
 
     def _statics(self, lane):
         if lane.img is None:
@@ -442,23 +457,26 @@ class StreamTracker:
                 lane.eff, lane.commit, lane.draw = (torch.full((B,), -1, dtype=torch.int32, device=self.dev) for _ in range(3))
                 lane.pic = torch.tensor([[w, h]] * B, dtype=torch.int32, device=self.dev)
 
+    def _judge(self, prev, pose, K9, pic, size, slot_map, commit=None, draw=None):
+        """The health step between a refinement from the gathered poses `prev` (None: an acquisition) and its commit -> (slot_commit,
+        slot_draw): a frame that fails its gates is not committed, a LOST stream is not drawn.  Without a policy: the slot map itself."""
+        if self.policy is None:
+            return slot_map, slot_map
+        n = slot_map.shape[0]
+        return ops.track_health(None if prev is None else prev.reshape(n, 12), pose.reshape(n, 12), K9, pic, size, slot_map, prev is None,
+                                self.chain.center, self.diameter, self.policy, self.health_table, self.measures, commit, draw)
+
     def _tick_fn(self, lane):
-        """gather -> track_iter refinement steps (query_batch's refine loop) -> commit, on the lane's static buffers.  With a health
-        policy: gate -> gather of the gated map -> steps -> health -> commit of the frames that passed."""
+        """(gate ->) gather -> track_iter refinement steps (query_batch's refine loop) (-> health) -> commit of the frames that passed,
+        on the lane's static buffers -> (out, slot_commit, slot_draw).  The gate parks lost streams and non-finite rows."""
+        eff, K9 = lane.map, lane.K.reshape(self.batch, 9)
         if self.policy is not None:
-            B = self.batch
-            ops.track_gate(self.pose_table, self.health_table, lane.map, lane.eff)
-            pose0 = ops.track_gather(self.pose_table, lane.eff, self.parking)
-            r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
-            K9 = lane.K.reshape(B, 9)
-            ops.track_health(pose0.reshape(B, 12), r["pose"].reshape(B, 12), K9, lane.pic, None, lane.eff, False, self.chain.center,
-                             self.diameter, self.policy, self.health_table, self.measures, lane.commit, lane.draw)
-            return ops.track_commit(r["pose"], K9, lane.commit, False, self.box, self.num, self.std, self.pose_table, self.hist,
-                                    self.hist_count, self.smooth_table)
-        pose0 = ops.track_gather(self.pose_table, lane.map, self.parking)
+            eff = ops.track_gate(self.pose_table, self.health_table, lane.map, lane.eff)
+        pose0 = ops.track_gather(self.pose_table, eff, self.parking)
         r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
-        return ops.track_commit(r["pose"], lane.K.reshape(self.batch, 9), lane.map, False, self.box, self.num, self.std, self.pose_table,
-                                self.hist, self.hist_count, self.smooth_table)
+        commit, draw = self._judge(pose0, r["pose"], K9, lane.pic, None, eff, lane.commit, lane.draw)
+        return ops.track_commit(r["pose"], K9, commit, False, self.box, self.num, self.std, self.pose_table, self.hist, self.hist_count,
+                                self.smooth_table), commit, draw
 
     def _capture(self, lane, warmup=2):
         lane.map.fill_(-1)
@@ -474,43 +492,34 @@ class StreamTracker:
 
     def _tick(self, lane, ents):
         self._statics(lane)
-        slots = [s % self.batch for s, _, _ in ents]
+        ents = [e._replace(slot=e.stream % self.batch) for e in ents]
         m = np.full(self.batch, -1, np.int32)
-        for (s, _, _), b in zip(ents, slots):
-            m[b] = s
+        m[[e.slot for e in ents]] = [e.stream for e in ents]
         if self.graphs and lane.graph is None:
             self._capture(lane)
         if self.frame_size is not None:        # one launch fills the named slots of the static image and K buffers
-            I.ingest_frames([f for _, f, _ in ents], lane.img, lane.K, slots=slots)
+            I.ingest_frames([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
         else:
-            for (s, im, K), b in zip(ents, slots):
-                lane.img[b].copy_(im)
-                lane.K[b].copy_(K)
+            for e in ents:
+                lane.img[e.slot].copy_(e.frame)
+                lane.K[e.slot].copy_(e.K)
         lane.map.copy_(self._upload(m))
-        if self.policy is not None:            # the picture inside each slot's canvas, (w, h)
-            h, w = self._shape[:2]
-            pic = np.tile(np.asarray([w, h], np.int32), (self.batch, 1))
-            if self.frame_size is not None:
-                for (s, f, _), b in zip(ents, slots):
-                    pic[b] = I.plan(f, (h, w))[1::-1]
-            lane.pic.copy_(self._upload(pic))
+        if lane.pic is not None:               # (a policy's static buffer)
+            lane.pic.copy_(self._upload(self._pic(ents, self.batch)))
         if self.graphs:
             lane.graph.replay()
-            out = lane.out
-        else:
-            out = self._tick_fn(lane)
-        rows = [(b, s, self._frames[s]) for (s, _, _), b in zip(ents, slots)]
-        if self.policy is not None:
-            g = ents[0][0] // self.batch           # groups that share a lane count their own ticks: each is checked every n-th time
+        out, commit, draw = lane.out if self.graphs else self._tick_fn(lane)
+        judged = commit is not lane.map        # (_judge hands the map itself back when there is no policy)
+        if judged:
+            g = ents[0].stream // self.batch   # groups that share a lane count their own ticks: each is checked every n-th time
             lane.ticks[g] = lane.ticks.get(g, 0) + 1
             if self.policy.verify_every and lane.ticks[g] % self.policy.verify_every == 0:
                 self._verify(lane)
-            if self._records is not None:
-                self._records.append((out.clone(), rows, lane.commit.clone(), self.health_table[:, 0].clone()))
-        elif self._records is not None:
-            self._records.append((out.clone(), rows))
+        if self._records is not None:
+            self._records.append(_Record(out.clone(), [(e.slot, e.stream, self._frames[e.stream]) for e in ents],
+                                         commit.clone() if judged else None, self.health_table[:, 0].clone() if judged else None))
         if self._sinks:
-            self._emit(lane.img, lane.K.reshape(self.batch, 9), lane.map if self.policy is None else lane.draw, ents, slots)
+            self._emit(lane.img, lane.K.reshape(self.batch, 9), draw, ents)
 
     def _verify(self, lane):
         """The detector's check of the poses this tick committed: the detection half of query_batch on the lane's image batch in chunks
@@ -525,37 +534,29 @@ class StreamTracker:
                              self.policy, self.health_table, self.measures)
 
     def _init(self, ents):
-        n = len(ents)
-        if self.frame_size is not None:
+        n, (H, W) = len(ents), self._shape[:2]
+        ents = [e._replace(slot=i) for i, e in enumerate(ents)]
+        native = self.frame_size is not None
+        if native:
             imgs = torch.empty((n,) + self._shape, dtype=torch.uint8, device=self.dev)
             Ks = torch.empty((n, 3, 3), dtype=torch.float32, device=self.dev)
-            I.ingest_frames([f for _, f, _ in ents], imgs, Ks)
+            I.ingest_frames([e.frame for e in ents], imgs, Ks)
         else:
-            imgs = torch.stack([im for _, im, _ in ents], 0)
-            Ks = torch.stack([K for _, _, K in ents], 0)
+            imgs = torch.stack([e.frame for e in ents], 0)
+            Ks = torch.stack([e.K for e in ents], 0)
         r = self.chain.query_batch(imgs, Ks)
-        ids = self._upload(np.asarray([s for s, _, _ in ents], np.int32))
-        rows = [(i, s, self._frames[s]) for i, (s, _, _) in enumerate(ents)]
-        if self.policy is not None:            # an acquisition that fails its gates is not committed: the stream stays LOST
-            H, W = self._shape[:2]
-            pic = None
-            if self.frame_size is not None:
-                pic = self._upload(np.asarray([I.plan(f, (H, W))[1::-1] for _, f, _ in ents], np.int32))
-            commit, draw = ops.track_health(None, r["pose"].reshape(n, 12), Ks.reshape(n, 9), pic, (W, H), ids, True, self.chain.center,
-                                            self.diameter, self.policy, self.health_table, self.measures)
-            out = torch.zeros((n, 2, 3, 4), dtype=torch.float32, device=self.dev)
-            ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), commit, True, self.box, self.num, self.std, self.pose_table,
-                             self.hist, self.hist_count, self.smooth_table, out=out)
-            if self._records is not None:
-                self._records.append((out, rows, commit, self.health_table[:, 0].clone()))
-            ids = draw
-        else:
-            out = ops.track_commit(r["pose"].reshape(n, 12), Ks.reshape(n, 9), ids, True, self.box, self.num, self.std, self.pose_table,
-                                   self.hist, self.hist_count, self.smooth_table)
-            if self._records is not None:
-                self._records.append((out, rows))
+        pose, K9 = r["pose"].reshape(n, 12), Ks.reshape(n, 9)
+        ids = self._upload(np.asarray([e.stream for e in ents], np.int32))
+        pic = self._upload(self._pic(ents, n)) if native and self.policy is not None else None
+        commit, draw = self._judge(None, pose, K9, pic, (W, H), ids)
+        judged = commit is not ids             # an acquisition that fails its gates is not committed (its rows of out stay 0): still LOST
+        out = ops.track_commit(pose, K9, commit, True, self.box, self.num, self.std, self.pose_table, self.hist, self.hist_count,
+                               self.smooth_table, out=torch.zeros((n, 2, 3, 4), dtype=torch.float32, device=self.dev) if judged else None)
+        if self._records is not None:
+            self._records.append(_Record(out, [(e.slot, e.stream, self._frames[e.stream]) for e in ents], commit if judged else None,
+                                         self.health_table[:, 0].clone() if judged else None))
         if self._sinks:
-            self._emit(imgs, Ks.reshape(n, 9), ids, ents, list(range(n)))
+            self._emit(imgs, K9, draw, ents)
 
     def _check_range(self):
         bad = []
@@ -577,24 +578,25 @@ class StreamTracker:
         """track_streams: one synchronisation, one read-back -> per stream (poses [T,3,4], smoothed [T,3,4])."""
         if self.cuda:
             torch.cuda.synchronize(self.dev)
-        rows = torch.cat([r[0].reshape(-1, 2, 12) for r in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 2, 12))
+        recs = self._records
+        rows = torch.cat([r.out.reshape(-1, 2, 12) for r in recs], 0).cpu().numpy() if recs else np.zeros((0, 2, 12))
         res = [(np.zeros((T, 3, 4), np.float32), np.zeros((T, 3, 4), np.float32)) for T in lengths]
         if self.policy is not None:            # ... and status [T]; a frame that was not committed repeats the previous frame's poses
             res = [r + (np.zeros(len(r[0]), np.int32),) for r in res]
-            commits = torch.cat([r[2] for r in self._records], 0).cpu().numpy() if self._records else np.zeros(0, np.int32)
-            status = torch.stack([r[3] for r in self._records], 0).cpu().numpy() if self._records else np.zeros((0, 0), np.int32)
+        judged = bool(recs) and recs[0].commit is not None
+        commits = torch.cat([r.commit for r in recs], 0).cpu().numpy() if judged else None
+        status = torch.stack([r.status for r in recs], 0).cpu().numpy() if judged else None
         base = 0
-        for i, rec in enumerate(self._records):
-            for row, s, f in rec[1]:
-                if self.policy is not None:
+        for i, rec in enumerate(recs):
+            for row, s, f in rec.rows:
+                if judged:
                     res[s][2][f] = status[i, s]
                     if commits[base + row] < 0:
-                        if f:
-                            res[s][0][f], res[s][1][f] = res[s][0][f - 1], res[s][1][f - 1]
+                        res[s][0][f], res[s][1][f] = (res[s][0][f - 1], res[s][1][f - 1]) if f else (0, 0)
                         continue
                 res[s][0][f] = rows[base + row, 0].reshape(3, 4)
                 res[s][1][f] = rows[base + row, 1].reshape(3, 4)
-            base += rec[0].shape[0]
+            base += rec.out.shape[0]
         return res
 
 
@@ -672,12 +674,10 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
 
     def recompute():
         box = None if kw.get("object_pts") is None else G.box_corners(kw["object_pts"])
-        if native:                             # the host loop takes plain arrays: ingest each frame on the device and read it back
-            host = [_ingest_to_host(frames, kw["frame_size"], estimator.device) for frames in seqs]
-            return [host_track(estimator, fr, Kh, kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
-                    for fr, Kh in host]
-        return [host_track(estimator, frames, Kss[s], kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
-                for s, frames in enumerate(seqs)]
+        # the host loop takes plain arrays: native frames are ingested on the device one by one and read back
+        host = [_ingest_to_host(frames, kw["frame_size"], estimator.device) for frames in seqs] if native else zip(seqs, Kss)
+        return [host_track(estimator, fr, Kh, kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
+                for fr, Kh in host]
     if kw.get("health") is None:
         return estimator._range_guarded(run, recompute)
     return estimator._range_guarded(run, lambda: [r + (np.full(len(r[0]), TRACKING, np.int32),) for r in recompute()])

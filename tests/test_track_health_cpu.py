@@ -472,9 +472,9 @@ def test_forced_loss_and_reacquisition_schedule(scene, patched, monkeypatch):
     assert not tr.result([0])[0][0].any()
     # reset clears the mirror entry and the next push starts over whatever the lag
     tr.health()
-    assert tr._mirror[0, 0] == Lo
+    assert tr._mirror.status[0, 0] == Lo
     tr.reset([0])
-    assert tr._mirror[0, 0] == T.NONE
+    assert tr._mirror.status[0, 0] == T.NONE
     tr.push([0], [frames[2]], [Ks[2]])
     assert log[-1][0] == 10
     # lag 2 (the default) acts one push later, lag 0 behaves as lag 1

@@ -125,6 +125,33 @@ def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=F
     return dt, F - 2
 
 
+def sweep(est, frames, K, args, configs, variants, label, title, text, lanes=False):
+    """Every (streams, batch) configuration x every variant [(name, keywords of `run`)] (graphs unless a variant says otherwise),
+    `--repeats` times, alternated -> one table row each, printed as it is known; `--out` receives the table under `title` and `text`.
+    label: the heading of the variants' column.  lanes: the plain table, with a lanes column and without the list of runs.  Variants with
+    a health policy add the `lost` column."""
+    health = any("health" in kw for _, kw in variants)
+    cols = ["streams", "batch"] + ["lanes"] * lanes + [label, "tracked frames/s (median)", "ms per tick", "spread"]
+    cols += ["runs (frames/s)"] * (not lanes) + ["lost"] * health
+    lines = ["| " + " | ".join(cols) + " |", "|" + "|".join("---" if c in (label, "runs (frames/s)", "lost") else "---:" for c in cols) + "|"]
+    for S, B in configs:
+        res, lost = {name: [] for name, _ in variants}, {name: [] for name, _ in variants}
+        for _ in range(args.repeats):
+            for name, kw in variants:                 # alternated
+                dt, n = run(est, frames, K, S, args.frames, B, **{"graphs": True, "lost": lost[name], **kw})
+                res[name].append((S * n / dt, dt / n * 1e3))
+        for name, _ in variants:
+            fps, ms = np.array([r[0] for r in res[name]]), np.array([r[1] for r in res[name]])
+            med = float(np.median(fps))
+            cells = [str(S), str(B)] + ["2"] * lanes + [name, f"{med:.1f}", f"{float(np.median(ms)):.3f}", f"{(fps.max() - fps.min()) / med:.1%}"]
+            cells += [", ".join(f"{v:.1f}" for v in fps)] * (not lanes) + [", ".join(str(v) for v in lost[name]) or "-"] * health
+            lines.append("| " + " | ".join(cells) + " |")
+            print(lines[-1], flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(f"# {title}\n\n{text}\n\n" + "\n".join(lines) + "\n")
+
+
 def stats_table(csv_path, ticks, tick_ms):
     """rocprofv3 kernel stats CSV -> markdown rows (name, calls, total ms, per tick us, share of a tick)."""
     import csv
@@ -182,97 +209,31 @@ def main():
     configs = [(int(s), min(int(s), 8)) for s in args.streams.split(",")]
     if 32 in [c[0] for c in configs]:
         configs.append((32, 32))
+    graphs = "Synthetic database and weights, graphs, "
+    each = f"{args.frames} frames per stream, the first two excluded, {args.repeats} repeats of each "
     if args.health:
-        modes = args.health.split(",")
-        lines = ["| streams | batch | health | tracked frames/s (median) | ms per tick | spread | runs (frames/s) | lost |",
-                 "|---:|---:|---|---:|---:|---:|---|---|"]
-        for S, B in configs:
-            res, lost = {m: [] for m in modes}, {m: [] for m in modes}
-            for _ in range(args.repeats):
-                for m in modes:                       # alternated
-                    dt, n = run(est, frames, K, S, args.frames, B, True, args.ingest, health=m, lost=lost[m])
-                    res[m].append((S * n / dt, dt / n * 1e3))
-            for m in modes:
-                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
-                med = float(np.median(fps))
-                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
-                             f"{', '.join(f'{v:.1f}' for v in fps)} | {', '.join(str(v) for v in lost[m]) or '-'} |")
-                print(lines[-1], flush=True)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write("# Tracked frames/s by health policy (tools/track_bench.py --health)\n\n"
-                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
-                        f"of each policy, alternated, intrinsics of {args.lens:g} x the database's focal length.  off: no HealthPolicy; lax: gate, "
-                        "health, the status mirror and the host's routing with every soft gate off; verify10: the same with the detector's "
-                        "check on every 10th tick; lost: streams LOST at the end of each run.\n\n" + "\n".join(lines) + "\n")
-        return
-    if args.emit:
-        modes = ["none", "device"] + (["host"] if args.emit_host else [])
-        lines = ["| streams | batch | sinks | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
-        for S, B in configs:
-            res = {m: [] for m in modes}
-            for _ in range(args.repeats):
-                for m in modes:                       # alternated
-                    dt, n = run(est, frames, K, S, args.frames, B, True, args.ingest, None if m == "none" else args.emit, m == "host")
-                    res[m].append((S * n / dt, dt / n * 1e3))
-            for m in modes:
-                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
-                med = float(np.median(fps))
-                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
-                             f"{', '.join(f'{v:.1f}' for v in fps)} |")
-                print(lines[-1], flush=True)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write(f"# Tracked frames/s with annotated frame output (tools/track_bench.py --emit {args.emit})\n\n"
-                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
-                        f"of each variant, alternated.  none: no sinks; device: one {args.emit} device sink per stream and frame (the smoothed "
-                        "picture at working resolution); host: the same into pinned host memory, copy included.\n\n" + "\n".join(lines) + "\n")
-        return
-    if args.ingest:
-        modes = args.ingest.split(",")
-        lines = ["| streams | batch | frames | tracked frames/s (median) | ms per tick | spread | runs (frames/s) |", "|---:|---:|---|---:|---:|---:|---|"]
-        for S, B in configs:
-            res = {m: [] for m in modes}
-            for _ in range(args.repeats):
-                for m in modes:                       # alternated
-                    dt, n = run(est, frames, K, S, args.frames, B, True, m)
-                    res[m].append((S * n / dt, dt / n * 1e3))
-            for m in modes:
-                fps, ms = np.array([r[0] for r in res[m]]), np.array([r[1] for r in res[m]])
-                med = float(np.median(fps))
-                lines.append(f"| {S} | {B} | {m} | {med:.1f} | {float(np.median(ms)):.3f} | {(fps.max() - fps.min()) / med:.1%} | "
-                             f"{', '.join(f'{v:.1f}' for v in fps)} |")
-                print(lines[-1], flush=True)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write("# Tracked frames/s by frame source (tools/track_bench.py --ingest)\n\n"
-                        f"Synthetic database and weights, graphs, {args.frames} frames per stream, the first two excluded, {args.repeats} repeats "
-                        "of each source, alternated.  none: plain 480x640 device frames (tracker without frame_size); same: the same frames "
-                        "through the ingest launch; nv12-1080p: host-resident 1080x1920 NV12 frames into a 540x960 canvas, upload "
-                        "included.\n\n" + "\n".join(lines) + "\n")
-        return
-    lines = ["| streams | batch | lanes | mode | tracked frames/s (median) | ms per tick | spread |", "|---:|---:|---:|---|---:|---:|---:|"]
-    for S, B in configs:
-        res = {True: [], False: []}
-        for _ in range(args.repeats):
-            for g in (True, False):                   # alternated
-                dt, n = run(est, frames, K, S, args.frames, B, g)
-                res[g].append((S * n / dt, dt / n * 1e3))
-        for g in (True, False):
-            fps = np.array([r[0] for r in res[g]])
-            ms = np.array([r[1] for r in res[g]])
-            med = float(np.median(fps))
-            lines.append(f"| {S} | {B} | 2 | {'graphs' if g else 'eager'} | {med:.1f} | {float(np.median(ms)):.3f} | "
-                         f"{(fps.max() - fps.min()) / med:.1%} |")
-            print(lines[-1], flush=True)
-    txt = "\n".join(lines)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("# Tracked frames/s (tools/track_bench.py)\n\n"
-                    f"Synthetic database and weights, 480x640 frames, {args.frames} frames per stream, the first two excluded (first frames "
-                    f"and the graph-capturing tick), {args.repeats} repeats of each mode, alternated.  One tracked frame = one refinement "
-                    "step from the stream's previous pose + the box smoothing.\n\n" + txt + "\n")
-
+        sweep(est, frames, K, args, configs, [(m, {"ingest": args.ingest, "health": m}) for m in args.health.split(",")], "health",
+              "Tracked frames/s by health policy (tools/track_bench.py --health)",
+              graphs + each + f"policy, alternated, intrinsics of {args.lens:g} x the database's focal length.  off: no HealthPolicy; lax: "
+              "gate, health, the status mirror and the host's routing with every soft gate off; verify10: the same with the detector's "
+              "check on every 10th tick; lost: streams LOST at the end of each run.")
+    elif args.emit:
+        dev = {"ingest": args.ingest, "emit": args.emit}
+        sweep(est, frames, K, args, configs,
+              [("none", {"ingest": args.ingest}), ("device", dev)] + ([("host", dict(dev, emit_host=True))] if args.emit_host else []), "sinks",
+              f"Tracked frames/s with annotated frame output (tools/track_bench.py --emit {args.emit})",
+              graphs + each + f"variant, alternated.  none: no sinks; device: one {args.emit} device sink per stream and frame (the smoothed "
+              "picture at working resolution); host: the same into pinned host memory, copy included.")
+    elif args.ingest:
+        sweep(est, frames, K, args, configs, [(m, {"ingest": m}) for m in args.ingest.split(",")], "frames",
+              "Tracked frames/s by frame source (tools/track_bench.py --ingest)",
+              graphs + each + "source, alternated.  none: plain 480x640 device frames (tracker without frame_size); same: the same frames "
+              "through the ingest launch; nv12-1080p: host-resident 1080x1920 NV12 frames into a 540x960 canvas, upload included.")
+    else:
+        sweep(est, frames, K, args, configs, [("graphs", {}), ("eager", {"graphs": False})], "mode", "Tracked frames/s (tools/track_bench.py)",
+              f"Synthetic database and weights, 480x640 frames, {args.frames} frames per stream, the first two excluded (first frames "
+              f"and the graph-capturing tick), {args.repeats} repeats of each mode, alternated.  One tracked frame = one refinement "
+              "step from the stream's previous pose + the box smoothing.", lanes=True)
 
 if __name__ == "__main__":
     main()
