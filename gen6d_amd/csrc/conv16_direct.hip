@@ -18,6 +18,8 @@
 //     optionally per-(image group, channel) sum / sum of squares in fp64 for the InstanceNorm that follows (volume net).
 // K order: input-channel slice outermost, taps innermost — the nine shifted reads of a 16 KB slice hit L1 / L2.
 #include "g6d_common.h"
+#include "conv16w_geom.h"
+#include <type_traits>
 
 namespace {
 
@@ -27,7 +29,7 @@ constexpr int C16_LDS = 2 * C16_STAGE;                         // 64 KB
 constexpr int C16_EP_LD = 68;                                  // floats per pixel row of the epilogue tile (64 channels + 4: conflict-free b128 reads)
 constexpr unsigned C16_OOB = 0x80000000u;
 
-struct C16Seg {
+struct C16Seg : c16g::Tiling {     // (the base: the halo-patch kernel's own tiling of the same segment, the h_* fields)
   const char* in; char* full; char* pool;
   int H, W, DH;            // map height / width, rows per image group (D * H)
   int rows;                // N * D * H rows of the tall image
@@ -35,10 +37,6 @@ struct C16Seg {
   int tw_log2, tiles_x, tile0;
   unsigned in_bytes;       // extent of the input buffer as the descriptor sees it (incl. the back-shift)
   int back;                // bytes the descriptor base lies BEFORE the tensor (offset of tap (0,0,0) from the centre, negated)
-  // halo-patch kernel (conv16h_kernel): its own tiling of the same segment
-  int h_tw_log2, h_tiles_x, h_tile0, h_tpi;      // tile width, tiles per row, first tile, tiles per image (0: tiles of whole small images)
-  int h_segh, h_bands;                            // rows per band (min(H, TH)), bands per tile (TH / h_segh: > 1 when a tile holds several images)
-  int h_swa, h_swd;                               // LDS slot swizzle: ((pcol >> h_swa) + prow * h_swd) & (slots - 1)
 };
 struct C16Params {
   C16Seg seg[4];
@@ -65,43 +63,53 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t c16_rsrc(const void* p, unsign
 // Output element types (full_type / pool_type): 1 = the 16-bit type T, 2 = fp32, 3 = fp16 hi / lo PAIR [pixel][2][Cout] (hi = rn16(v),
 // lo = rn16(v - hi): the input format of the MM = 3 kernels; ld counts 16-bit elements and holds both planes).
 // NT = threads that share the pass (256: the whole block, NPX = 128; 64: one wave, tid = lane, no block-wide synchronisation inside).
-template <int MM, int NT, int NPX, int CH = 64>
+// FT / PT / ST >= 0: full_type / pool_type / (statistics on) known at compile time — the halo-patch kernel picks the variant of its
+// launch with one block-uniform branch; -1: read from p.
+// Addresses: one block-uniform 64-bit base per output (the tile's first pixel) + a 32-bit lane part (the launcher bounds a tile's extent
+// in an output to 2^32 bytes); a pixel (py, px) of the tile is stored iff py < yl and px < xl, two block-uniform limits.
+// wst (NT = 64): the lane's fp64 sums of the wave's passes, see c16_stats_flush.
+template <int MM, int NT, int NPX, int CH = 64, int FT = -1, int PT = -1, int ST = -1>
 __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16Seg& sg, const float* ep, double* red, int tid, int cbase, int g0, int x0,
-                                                  int tw_log2, int ylim, int px0, unsigned& amax) {
+                                                  int tw_log2, int ylim, int px0, unsigned& amax, double (&wst)[2]) {
   typedef typename C16T<MM>::T T;
   typedef typename C16T<MM>::V V8;
   static_assert(NT == 64 || (NPX == 128 && CH == 64), "the block-wide form handles whole tiles of 64 channels");
   constexpr int C8 = CH / 8, C4 = CH / 4;                                           // 16-byte items per pixel: 16-bit / fp32 output
+  const int full_type = FT >= 0 ? FT : p.full_type, pool_type = PT >= 0 ? PT : p.pool_type;
+  const bool stats_on = ST >= 0 ? ST != 0 : p.stats != nullptr;
   const int TW = 1 << tw_log2, W = sg.W;
-  const int TW2 = TW >> 1, py0 = px0 >> tw_log2, PR2 = (NPX >> tw_log2) >> 1;      // first tile row of the pass, pooled rows of the pass
-  auto inside = [&](int lp, int& g, int& x) {                                       // lp: pixel of the pass = row of ep
-    const int px = px0 + lp, py = px >> tw_log2;
-    g = g0 + py; x = x0 + (px & (TW - 1));
-    return py < ylim && g < sg.rows && x < W;
+  const int py0 = px0 >> tw_log2;                                                   // first tile row of the pass
+  const int yl = min(ylim, sg.rows - g0), xl = W - x0;
+  auto inside = [&](int lp, unsigned& pix) {                                        // lp: pixel of the pass = row of ep; pix: its index from the tile's first pixel
+    const int px = px0 + lp, py = px >> tw_log2, xx = px & (TW - 1);
+    pix = (unsigned)(py * W + xx);
+    return py < yl && xx < xl;
   };
   // pair outputs hold split16(v * 2^-eo); amax: max bits(|v|) of the stored unscaled values, recorded by the caller once per wave
   // after its last pass (G6dRange16)
-  const bool pairs = p.full_type == 3 || p.pool_type == 3;
+  const bool pairs = full_type == 3 || pool_type == 3;
   const int eo = pairs ? g6d_exp_out(p.rng) : 0;
-  if (p.full_type == 1) {
+  if (full_type == 1) {
+    char* fb = sg.full + (((long)g0 * W + x0) * sg.ld_full + cbase) * 2;
 #pragma unroll
     for (int j = 0; j < NPX * C8 / NT; ++j) {
       const int lp = tid / C8 + (NT / C8) * j, ch = (tid % C8) * 8;
-      int g, x;
-      if (inside(lp, g, x)) {
+      unsigned pix;
+      if (inside(lp, pix)) {
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch), v1 = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch + 4);
         V8 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { o[e] = (T)v0[e]; o[4 + e] = (T)v1[e]; }
-        *reinterpret_cast<V8*>(sg.full + (((long)g * W + x) * sg.ld_full + cbase + ch) * 2) = o;
+        *reinterpret_cast<V8*>(fb + (pix * (unsigned)sg.ld_full + ch) * 2u) = o;
       }
     }
-  } else if (p.full_type == 3) {
+  } else if (full_type == 3) {
+    char* fb = sg.full + (((long)g0 * W + x0) * sg.ld_full + cbase) * 2;
 #pragma unroll
     for (int j = 0; j < NPX * C8 / NT; ++j) {
       const int lp = tid / C8 + (NT / C8) * j, ch = (tid % C8) * 8;
-      int g, x;
-      if (inside(lp, g, x)) {
+      unsigned pix;
+      if (inside(lp, pix)) {
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch), v1 = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch + 4);
         V8 hi, lo;
 #pragma unroll
@@ -111,71 +119,93 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
           hi[e] = (T)u0; lo[e] = (T)(u0 - (float)hi[e]);
           hi[4 + e] = (T)u1; lo[4 + e] = (T)(u1 - (float)hi[4 + e]);
         }
-        char* o = sg.full + (((long)g * W + x) * sg.ld_full + cbase + ch) * 2;
+        char* o = fb + (pix * (unsigned)sg.ld_full + ch) * 2u;
         *reinterpret_cast<V8*>(o) = hi;
         *reinterpret_cast<V8*>(o + p.Cout * 2) = lo;
       }
     }
-  } else if (p.full_type == 2) {
+  } else if (full_type == 2) {
+    char* fb = sg.full + (((long)g0 * W + x0) * sg.ld_full + cbase) * 4;
 #pragma unroll
     for (int j = 0; j < NPX * C4 / NT; ++j) {
       const int lp = tid / C4 + (NT / C4) * j, ch = (tid % C4) * 4;
-      int g, x;
-      if (inside(lp, g, x))
-        *reinterpret_cast<f32x4*>(sg.full + (((long)g * W + x) * sg.ld_full + cbase + ch) * 4) = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch);
+      unsigned pix;
+      if (inside(lp, pix))
+        *reinterpret_cast<f32x4*>(fb + (pix * (unsigned)sg.ld_full + ch) * 4u) = *reinterpret_cast<const f32x4*>(ep + lp * C16_EP_LD + ch);
     }
   }
-  if (p.pool_type) {
-    const int per = p.pool_type == 2 ? 4 : 8, chunks = CH / per;      // channels per item, items per pooled pixel
-    for (int it = tid; it < (NPX / 4) * chunks; it += NT) {
-      const int pp = it / chunks, ch = (it - pp * chunks) * per;
-      const int pry = pp / TW2, prx = pp - pry * TW2;
-      const int r00 = ((2 * pry) << tw_log2) + 2 * prx;
-      const int g = g0 + py0 + 2 * pry, x = x0 + 2 * prx;
-      if (pry < PR2 && py0 + 2 * pry < ylim && g < sg.rows && x < W) {
-        float m[8];
+  if (pool_type) {
+    // pooled maps have even H and W and tiles start on even rows and columns: pooled pixel (g0 / 2 + qy, x0 / 2 + qx) is stored iff the
+    // window's first pixel is
+    const int W2 = W >> 1;
+    const long pb = ((long)(g0 >> 1) * W2 + (x0 >> 1)) * sg.ld_pool + cbase;
+    auto pooled = [&](auto per_c) {
+      constexpr int per = decltype(per_c)::value, chunks = CH / per;               // channels per item, items per pooled pixel (powers of two)
+      static_assert((NPX / 4) * chunks % NT == 0, "whole rounds of items");
 #pragma unroll
-        for (int e = 0; e < 8; e += 4) {
-          if (e < per) {
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(ep + r00 * C16_EP_LD + ch + e), q1 = *reinterpret_cast<const f32x4*>(ep + (r00 + 1) * C16_EP_LD + ch + e);
-            const f32x4 q2 = *reinterpret_cast<const f32x4*>(ep + (r00 + TW) * C16_EP_LD + ch + e), q3 = *reinterpret_cast<const f32x4*>(ep + (r00 + TW + 1) * C16_EP_LD + ch + e);
+      for (int j = 0; j < (NPX / 4) * chunks / NT; ++j) {
+        const int it = tid + NT * j, pp = it / chunks, ch = (it % chunks) * per;
+        const int pry = pp >> (tw_log2 - 1), prx = pp & ((TW >> 1) - 1);
+        const int r00 = ((2 * pry) << tw_log2) + 2 * prx;
+        if (py0 + 2 * pry < yl && 2 * prx < xl) {
+          float m[8];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) m[e + u] = fmaxf(fmaxf(q0[u], q1[u]), fmaxf(q2[u], q3[u]));
+          for (int e = 0; e < 8; e += 4) {
+            if (e < per) {
+              const f32x4 q0 = *reinterpret_cast<const f32x4*>(ep + r00 * C16_EP_LD + ch + e), q1 = *reinterpret_cast<const f32x4*>(ep + (r00 + 1) * C16_EP_LD + ch + e);
+              const f32x4 q2 = *reinterpret_cast<const f32x4*>(ep + (r00 + TW) * C16_EP_LD + ch + e), q3 = *reinterpret_cast<const f32x4*>(ep + (r00 + TW + 1) * C16_EP_LD + ch + e);
+#pragma unroll
+              for (int u = 0; u < 4; ++u) m[e + u] = fmaxf(fmaxf(q0[u], q1[u]), fmaxf(q2[u], q3[u]));
+            }
           }
-        }
-        const long o = ((long)(g >> 1) * (W >> 1) + (x >> 1)) * sg.ld_pool + cbase + ch;
-        if (p.pool_type == 1) {
-          V8 ov;
+          const unsigned o = (unsigned)(((py0 >> 1) + pry) * W2 + prx) * (unsigned)sg.ld_pool + ch;
+          if constexpr (per == 4) {
+            f32x4 ov = {m[0], m[1], m[2], m[3]};
+            *reinterpret_cast<f32x4*>(sg.pool + pb * 4 + o * 4u) = ov;
+          } else if (pool_type == 1) {
+            V8 ov;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) ov[e] = (T)m[e];
-          *reinterpret_cast<V8*>(sg.pool + o * 2) = ov;
-        } else if (p.pool_type == 3) {
-          V8 hi, lo;
+            for (int e = 0; e < 8; ++e) ov[e] = (T)m[e];
+            *reinterpret_cast<V8*>(sg.pool + pb * 2 + o * 2u) = ov;
+          } else {
+            V8 hi, lo;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            amax = max(amax, g6d_abs_bits(m[e]));
-            const float u = ldexpf(m[e], -eo);
-            hi[e] = (T)u; lo[e] = (T)(u - (float)hi[e]);
+            for (int e = 0; e < 8; ++e) {
+              amax = max(amax, g6d_abs_bits(m[e]));
+              const float u = ldexpf(m[e], -eo);
+              hi[e] = (T)u; lo[e] = (T)(u - (float)hi[e]);
+            }
+            char* d = sg.pool + pb * 2 + o * 2u;
+            *reinterpret_cast<V8*>(d) = hi;
+            *reinterpret_cast<V8*>(d + p.Cout * 2) = lo;
           }
-          *reinterpret_cast<V8*>(sg.pool + o * 2) = hi;
-          *reinterpret_cast<V8*>(sg.pool + (o + p.Cout) * 2) = lo;
-        } else {
-          f32x4 ov = {m[0], m[1], m[2], m[3]};
-          *reinterpret_cast<f32x4*>(sg.pool + o * 4) = ov;
         }
       }
-    }
+    };
+    if (pool_type == 2) pooled(std::integral_constant<int, 4>{});
+    else pooled(std::integral_constant<int, 8>{});
   }
-  if (p.stats) {
-    // per-(group, channel) sum / sum of squares of the fp32 results of the tile's VALID pixels (a tile never straddles groups)
-    const int grp = p.stat_rows_per_group > 0 ? (int)(((long)g0 * W) / p.stat_rows_per_group) : 0;
+  if (stats_on) {
+    // per-(group, channel) sum / sum of squares of the fp32 results of the tile's VALID pixels (a tile never straddles groups):
+    // fp32 partial sums of 32 pixels each, in pixel order, combined in fp64
+    auto sum32 = [&](int lp0, int c, float& s1, float& s2) {
+      s1 = 0.f; s2 = 0.f;
+      // (block-uniform) every pixel of the pass is valid: no test per pixel
+      if (py0 + (NPX >> tw_log2) <= yl && TW <= xl) {
+#pragma unroll 8
+        for (int lp = lp0; lp < lp0 + 32; ++lp) { const float v = ep[lp * C16_EP_LD + c]; s1 += v; s2 += v * v; }
+      } else {
+        for (int lp = lp0; lp < lp0 + 32; ++lp) {
+          unsigned pix;
+          if (inside(lp, pix)) { const float v = ep[lp * C16_EP_LD + c]; s1 += v; s2 += v * v; }
+        }
+      }
+    };
     if constexpr (NT == 256) {
+      const int grp = p.stat_rows_per_group > 0 ? (int)(((long)g0 * W) / p.stat_rows_per_group) : 0;
       const int c = tid & 63, q = tid >> 6;
-      float s1 = 0.f, s2 = 0.f;
-      for (int lp = 32 * q; lp < 32 * q + 32; ++lp) {
-        int g, x;
-        if (inside(lp, g, x)) { const float v = ep[lp * C16_EP_LD + c]; s1 += v; s2 += v * v; }
-      }
+      float s1, s2;
+      sum32(32 * q, c, s1, s2);
       red[(q * 64 + c) * 2] = (double)s1; red[(q * 64 + c) * 2 + 1] = (double)s2;
       __syncthreads();
       if (tid < 128) {
@@ -184,21 +214,29 @@ __device__ __forceinline__ void c16_epilogue_pass(const C16Params& p, const C16S
         atomicAdd(p.stats + ((long)grp * p.Cout + cbase + cc) * 2 + w, v);
       }
     } else {
-      // one wave: lane = channel; fp32 partial sums of 32 pixels each, combined in fp64
-      if (tid < CH) {                  // (no early return: the caller's range record needs every lane)
-        double d1 = 0.0, d2 = 0.0;
-        for (int q = 0; q < NPX / 32; ++q) {
-          float s1 = 0.f, s2 = 0.f;
-          for (int lp = 32 * q; lp < 32 * q + 32; ++lp) {
-            int g, x;
-            if (inside(lp, g, x)) { const float v = ep[lp * C16_EP_LD + tid]; s1 += v; s2 += v * v; }
-          }
-          d1 += (double)s1; d2 += (double)s2;
-        }
-        atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2, d1);
-        atomicAdd(p.stats + ((long)grp * p.Cout + cbase + tid) * 2 + 1, d2);
+      // one wave: lane = channel lane % CH of pixel group lane / CH (CH = 32: the two halves of the pass, every lane at work)
+      constexpr int PPG = NPX * CH / 64;                                            // pixels per group
+#pragma unroll
+      for (int q = 0; q < PPG / 32; ++q) {
+        float s1, s2;
+        sum32(PPG * (tid / CH) + 32 * q, tid % CH, s1, s2);
+        wst[0] += (double)s1; wst[1] += (double)s2;
       }
     }
+  }
+}
+
+// The wave-private statistics after a wave's last pass: the pixel groups of a channel are added across lanes, then ONE pair of fp64
+// atomics per (wave, channel).  (Every lane takes part: no early return before it.)
+template <int CH>
+__device__ __forceinline__ void c16_stats_flush(const C16Params& p, const C16Seg& sg, int lane, int cbase, int g0, double (&wst)[2]) {
+  static_assert(CH == 32 || CH == 64, "one or two pixel groups per channel");
+  if constexpr (CH == 32) { wst[0] += __shfl_xor(wst[0], 32); wst[1] += __shfl_xor(wst[1], 32); }
+  const unsigned grp = p.stat_rows_per_group > 0 ? (unsigned)(g0 * sg.W) / (unsigned)p.stat_rows_per_group : 0u;   // (pixels of a segment < 2^31)
+  if (lane < CH) {
+    double* d = p.stats + ((long)grp * p.Cout + cbase + lane) * 2;
+    atomicAdd(d, wst[0]);
+    atomicAdd(d + 1, wst[1]);
   }
 }
 
@@ -211,12 +249,13 @@ __device__ __forceinline__ void c16_epilogue(const C16Params& p, const C16Seg& s
   float* ep = reinterpret_cast<float*>(lds);
   double* red = reinterpret_cast<double*>(lds + C16_BM * C16_EP_LD * 4);       // [4 quarters][64 ch][2] statistics partials
   unsigned amax = 0;
+  double wst[2] = {0.0, 0.0};                                                   // (the wave-private form's)
 #pragma unroll 1
   for (int h = 0; h < 2; ++h) {
     const int cbase = nt * C16_BN + 64 * h;
     write_tile(h, ep, cbase);
     __syncthreads();
-    c16_epilogue_pass<MM, 256, 128>(p, sg, ep, red, tid, cbase, g0, x0, tw_log2, ylim, 0, amax);
+    c16_epilogue_pass<MM, 256, 128>(p, sg, ep, red, tid, cbase, g0, x0, tw_log2, ylim, 0, amax, wst);
     __syncthreads();
   }
   if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
@@ -577,8 +616,9 @@ template <int MM> struct C16W {
   static constexpr int EPW = NPX * C16_EP_LD * 4;                               // a wave's epilogue tile
 };
 
-struct C16Geom {      // one 128-pixel tile of the halo tiling (block-uniform)
-  int si, g0, x0, y0, ylim, tw_log2, PW, segh, bandr, P, swa, swd, ni;
+struct C16Geom {      // one 128-pixel tile of the halo tiling (block-uniform: scalar registers): its segment, position, pieces per plane
+  int si, ni;
+  c16g::Tile t;
 };
 __device__ __forceinline__ C16Geom c16w_geom(const C16Params& p, int ptile) {
   C16Geom o;
@@ -586,20 +626,8 @@ __device__ __forceinline__ C16Geom c16w_geom(const C16Params& p, int ptile) {
 #pragma unroll
   for (int i = 1; i < 4; ++i) if (i < p.nseg && ptile >= p.seg[i].h_tile0) si = i;
   const C16Seg& sg = p.seg[si];
-  const int t = ptile - sg.h_tile0;
-  o.si = si; o.tw_log2 = sg.h_tw_log2;
-  const int TW = 1 << o.tw_log2, TH = C16_BM >> o.tw_log2;
-  o.PW = TW + 2;
-  if (sg.h_tpi > 0) {                                          // tiles inside one image
-    const int n = t / sg.h_tpi, r = t - n * sg.h_tpi;
-    const int ty = r / sg.h_tiles_x, tx = r - ty * sg.h_tiles_x;
-    o.y0 = ty * TH; o.x0 = tx * TW; o.g0 = n * sg.H + o.y0; o.ylim = min(TH, sg.H - o.y0);
-  } else {                                                     // tiles of TH / H whole images
-    const int ty = t / sg.h_tiles_x, tx = t - ty * sg.h_tiles_x;
-    o.y0 = 0; o.x0 = tx * TW; o.g0 = ty * TH; o.ylim = TH;
-  }
-  o.segh = sg.h_segh; o.bandr = sg.h_segh + 2; o.P = sg.h_bands * o.bandr * o.PW;
-  o.swa = sg.h_swa; o.swd = sg.h_swd; o.ni = (o.P + 15) >> 4;
+  o.si = si; o.ni = (sg.h_P + 15) >> 4;
+  o.t = c16g::tile_of(sg, sg.H, sg.W, ptile - sg.h_tile0);
   return o;
 }
 
@@ -621,7 +649,6 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   constexpr int WN = 4 / WM, NP = R::NP, KS = R::KS, NBL = KS * NP * NT2, CW = 32 * NT2;   // (NT2 = 1 in a 16-bit mode: 32-channel waves for Cout = 64)
   constexpr bool SINGLE = MM == 3 && WM == 2;                  // one patch stage instead of two (see the slice hand-over below)
   constexpr int TILE_B = NP * R::PLANE, STAGE = WM * TILE_B;
-  constexpr int NPIT = (NP * R::NI_MAX + 3) / 4;               // DMA wave-instructions per wave, tile and slice at most
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // block id -> (tile group, channel block): the channel blocks of a tile group run back to back on ONE XCD (ids = xcd mod 8)
@@ -632,61 +659,75 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   const int nchunk = p.Cin >> 5;
   typedef __attribute__((address_space(3))) void* lds_ptr;
 
-  // ---- the patch pieces this lane requests per slice: tile tl, piece k = wv + 4 i of its NP * ni pieces (plane k / ni, rows 16 (k % ni) + lane / 4)
-  // A piece none of whose lanes lies inside the map (halo pixels outside the image, the tail of the last piece) is not requested: its LDS
-  // rows are zeroed here, once, in both stages (the geometry is the same for every slice).
-  unsigned poff[WM][NPIT], pmask[WM];
-  int t_ni[WM], t_si[WM];
+  // ---- the patch pieces this lane requests per slice: tile tl, pieces ii = wv + 4 j of its ni pieces per plane (rows 16 ii + lane / 4),
+  // the same piece of every plane (the lo plane of a pixel follows its hi plane: one offset serves both).  The geometry
+  // (conv16w_geom.h) is computed once per tile; an INTERIOR tile — its whole patch inside one image — needs no validity test.
+  // A piece none of whose lanes lies inside the map (halo pixels outside the image) is not requested: its LDS rows are zeroed here,
+  // once, in both stages (the geometry is the same for every slice).
+  constexpr int NPJ = (R::NI_MAX + 3) / 4;                     // pieces per wave, tile and plane at most
+  unsigned poff[WM][NPJ], pmask[WM];
+  C16Geom gms[WM];
 #pragma unroll
   for (int tl = 0; tl < WM; ++tl) {
-    const C16Geom gm = c16w_geom(p, min(tg * WM + tl, p.ptiles - 1));
+    gms[tl] = c16w_geom(p, min(tg * WM + tl, p.ptiles - 1));
+    const C16Geom& gm = gms[tl];
     const C16Seg& sg = p.seg[gm.si];
-    const int npt = NP * gm.ni;
-    t_ni[tl] = gm.ni; t_si[tl] = gm.si;
-    pmask[tl] = 0;
+    const unsigned base = c16g::tile_base(sg.W, sg.ld_in, gm.t);
+    unsigned pm = 0;
+    if (gm.t.interior) {
 #pragma unroll
-    for (int i = 0; i < NPIT; ++i) {
-      const int k = wv + 4 * i;
-      const int pl = k >= gm.ni ? 1 : 0, ii = k - pl * gm.ni;
-      const int q = ii * 16 + (lane >> 2);
-      const int prow = q / gm.PW, pcol = q - prow * gm.PW;
-      const int b = prow / gm.bandr, lr = prow - b * gm.bandr - 1;   // band, row inside the band's image rows (-1 .. segh)
-      const int g = gm.g0 + b * gm.segh + lr, x = gm.x0 + pcol - 1;
-      const int yimg = gm.y0 + lr;                                    // (whole-image tiles: y0 = 0, lr = the image row)
-      const bool ok = k < npt && q < gm.P && yimg >= 0 && yimg < sg.H && g < sg.rows && x >= 0 && x < sg.W;
-      const int slot = (lane & 3) ^ (((pcol >> gm.swa) + prow * gm.swd) & 3);
-      poff[tl][i] = ok ? (unsigned)((((long)g * sg.W + x) * sg.ld_in + pl * p.Cin) * 2 + slot * 16) : C16_OOB;
-      if (k < npt) {
-        if (__builtin_amdgcn_ballot_w64(ok) != 0) pmask[tl] |= 1u << i;
-        else {
-          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-          char* dst = lds + tl * TILE_B + pl * R::PLANE + ii * 1024 + lane * 16;
-          *reinterpret_cast<f32x4*>(dst) = z;
-          if constexpr (!SINGLE) *reinterpret_cast<f32x4*>(dst + STAGE) = z;
+      for (int j = 0; j < NPJ; ++j) {
+        const c16g::Piece pc = c16g::piece_of(sg, wv + 4 * j, lane);
+        poff[tl][j] = pc.in_patch ? c16g::piece_offset(sg, sg.W, sg.ld_in, base, pc) : C16_OOB;     // (the tail of the last piece)
+        if (wv + 4 * j < gm.ni) pm |= 1u << j;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NPJ; ++j) {
+        const int ii = wv + 4 * j;
+        const c16g::Piece pc = c16g::piece_of(sg, ii, lane);
+        const bool ok = c16g::piece_valid(sg, sg.H, sg.W, sg.rows, gm.t, pc);
+        poff[tl][j] = ok ? c16g::piece_offset(sg, sg.W, sg.ld_in, base, pc) : C16_OOB;
+        if (ii < gm.ni) {
+          if (__builtin_amdgcn_ballot_w64(ok) != 0) pm |= 1u << j;
+          else {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) {
+              char* dst = lds + tl * TILE_B + pl * R::PLANE + ii * 1024 + lane * 16;
+              *reinterpret_cast<f32x4*>(dst) = z;
+              if constexpr (!SINGLE) *reinterpret_cast<f32x4*>(dst + STAGE) = z;
+            }
+          }
         }
       }
     }
-    pmask[tl] = __builtin_amdgcn_readfirstlane(pmask[tl]);
+    pmask[tl] = __builtin_amdgcn_readfirstlane(pm);
   }
+  const unsigned plane_b = (unsigned)(p.Cin * 2);
   auto issue_patch = [&](int c, int stage) {
     if (c >= nchunk) return;                                           // (no request past the last slice: the waits count 0 pieces there)
     const unsigned ck = (unsigned)(c * 64);
 #pragma unroll
     for (int tl = 0; tl < WM; ++tl) {
-      const C16Seg& sg = p.seg[t_si[tl]];
+      const C16Seg& sg = p.seg[gms[tl].si];
       const __amdgpu_buffer_rsrc_t rs_in = c16_rsrc(sg.in, sg.in_bytes - sg.back);
-      const int ni = t_ni[tl];
 #pragma unroll
-      for (int i = 0; i < NPIT; ++i) {
-        const int k = wv + 4 * i;
-        if (pmask[tl] >> i & 1) {
-          const int pl = k >= ni ? 1 : 0, ii = k - pl * ni;
-          const unsigned vo = poff[tl][i] == C16_OOB ? C16_OOB : poff[tl][i] + ck;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr)(lds + stage * STAGE + tl * TILE_B + pl * R::PLANE + ii * 1024), 16, vo, 0, 0, 0);
+      for (int j = 0; j < NPJ; ++j) {
+        if (pmask[tl] >> j & 1) {
+          const unsigned vo = poff[tl][j] == C16_OOB ? C16_OOB : poff[tl][j] + ck;      // (C16_OOB + a plane stays beyond the buffer)
+#pragma unroll
+          for (int pl = 0; pl < NP; ++pl)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr)(lds + stage * STAGE + tl * TILE_B + pl * R::PLANE + (wv + 4 * j) * 1024), 16,
+                                                     vo + pl * plane_b, 0, 0, 0);
         }
       }
     }
   };
+  // this wave's tile (fragment geometry, epilogue)
+  const C16Geom gm = WM == 1 ? gms[0] : gms[wm ? WM - 1 : 0];
+  const C16Seg& sgw = p.seg[gm.si];
+  const int f_tw_log2 = sgw.h_tw_log2, f_PW = (1 << f_tw_log2) + 2;
 
   // ---- filter fragments of (slice c, tap t): KS x NP x 2 pieces of 16 bytes per lane of THIS wave's 64 channels, hand-issued (see
   // conv16r_kernel).  Packed K steps hold 64 channels (pairs: 32): slice c is half (c & 1) of packed step (c >> 1) * 9 + t.
@@ -729,17 +770,12 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     // feeds one MFMA per (16-channel n-tile, term).  The pair tilings have swd = 0 and swa <= 2 (c16_halo_tiling): the slot swizzle
     // (column >> swa) & 3 of tap column kx is then the same for the eight m-tiles (their columns differ by multiples of 16) — xs[kx],
     // the logical slot folded in — and a fragment address is qb[mt] + the tap's offset: one VALU per two reads (hi and lo plane).
-    const C16Geom gm = c16w_geom(p, min(tg * WM + wm, p.ptiles - 1));
     int qb[8], xs[3];
 #pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-      const int r = 16 * mt + (lane & 15), py = r >> gm.tw_log2, px = r & ((1 << gm.tw_log2) - 1);
-      const int b = py / gm.segh, ly = py - b * gm.segh;
-      qb[mt] = ((b * gm.bandr + ly) * gm.PW + px) * 64 + wm * TILE_B;
-    }
+    for (int mt = 0; mt < 8; ++mt) qb[mt] = c16g::frag_pixel(sgw, 16 * mt + (lane & 15)) * 64 + wm * TILE_B;
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) xs[kx] = ((lane >> 4) ^ ((((lane & 15 & ((1 << gm.tw_log2) - 1)) + kx) >> gm.swa) & 3)) << 4;
-    const int PW64 = gm.PW * 64;
+    for (int kx = 0; kx < 3; ++kx) xs[kx] = ((lane >> 4) ^ ((((lane & 15 & ((1 << f_tw_log2) - 1)) + kx) >> sgw.h_swa) & 3)) << 4;
+    const int PW64 = f_PW * 64;
     auto tap_off = [&](int t, int stg) { return xs[t % 3] + (stg * STAGE + (t / 3) * PW64 + (t % 3) * 64); };
     auto read_pair = [&](int mp, int off, V8 (&a)[2][NP]) {      // the fragments of m-tiles 2 mp, 2 mp + 1
 #pragma unroll
@@ -841,37 +877,48 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     constexpr int MTP = R::NPX / 16;                              // m-tiles per pass
     const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
     unsigned amax = 0;
+    double wst[2] = {0.0, 0.0};
+    // the passes, specialised on the launch's output format (full_type, pool_type, statistics: -1 = read from p in the pass)
+    auto passes = [&](auto ftc, auto ptc, auto stc) {
 #pragma unroll
-    for (int ps = 0; ps < 8 / MTP; ++ps) {
+      for (int ps = 0; ps < 8 / MTP; ++ps) {
 #pragma unroll
-      for (int m = 0; m < MTP; ++m)
+        for (int m = 0; m < MTP; ++m)
 #pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2)
+          for (int n2 = 0; n2 < 2; ++n2)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int px = 16 * m + 4 * (lane >> 4) + r;
-            float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
-            if (p.relu) v = fmaxf(v, 0.f);
-            ep[px * C16_EP_LD + 16 * n2 + (lane & 15)] = v;
-          }
-      c16_epilogue_pass<2, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
-    }
+            for (int r = 0; r < 4; ++r) {
+              const int px = 16 * m + 4 * (lane >> 4) + r;
+              float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
+              if (p.relu) v = fmaxf(v, 0.f);
+              ep[px * C16_EP_LD + 16 * n2 + (lane & 15)] = v;
+            }
+        c16_epilogue_pass<2, 64, R::NPX, CW, decltype(ftc)::value, decltype(ptc)::value, decltype(stc)::value>(
+            p, sg, ep, nullptr, lane, chan0, gm.t.g0, gm.t.x0, f_tw_log2, gm.t.ylim, ps * R::NPX, amax, wst);
+      }
+    };
+    typedef std::integral_constant<int, -1> any_;
+    typedef std::integral_constant<int, 0> c0_;
+    // the trunks' forms (pair outputs, no statistics) and the selector's (fp32 map and statistics); anything else: the general form
+    if (!p.stats && p.full_type == 3 && p.pool_type == 0) passes(std::integral_constant<int, 3>{}, c0_{}, c0_{});
+    else if (!p.stats && p.full_type == 0 && p.pool_type == 3) passes(c0_{}, std::integral_constant<int, 3>{}, c0_{});
+    else if (!p.stats && p.full_type == 3 && p.pool_type == 3) passes(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, c0_{});
+    else if (p.stats && p.full_type == 2 && p.pool_type == 0) passes(std::integral_constant<int, 2>{}, c0_{}, std::integral_constant<int, 1>{});
+    else passes(any_{}, any_{}, any_{});
+    if (p.stats) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
     g6d_range_record(p.rng, amax);
   } else {
     // ---- fragment geometry of this wave's tile: m-tile mt = tile pixels 32 mt + (lane & 31) -> patch row of tap (0, 0)
-    const C16Geom gm = c16w_geom(p, min(tg * WM + wm, p.ptiles - 1));
     const int fhalf = lane >> 5;
     // slot swizzle of patch (row, column): ((column >> swa) + row * swd) & 3, and swd != 0 only with swa == 0 (c16_halo_tiling): with
     // fe = column + row * swd (swa == 0) or column (swd == 0) the swizzle of tap (ky, kx) is ((fe + kx) >> swa) + ky * swd
     int qb[4], fe[4];
+    const int PW64 = f_PW * 64, swa = sgw.h_swa, swd = sgw.h_swd;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-      const int r = 32 * mt + (lane & 31), py = r >> gm.tw_log2, px = r & ((1 << gm.tw_log2) - 1);
-      const int b = py / gm.segh, ly = py - b * gm.segh;
-      const int frow = b * gm.bandr + ly;
-      qb[mt] = (frow * gm.PW + px) * 64 + wm * TILE_B; fe[mt] = px + frow * gm.swd;
+      const int r = 32 * mt + (lane & 31);
+      qb[mt] = c16g::frag_pixel(sgw, r) * 64 + wm * TILE_B; fe[mt] = (r & ((1 << f_tw_log2) - 1)) + c16g::frag_row(sgw, r) * swd;
     }
-    const int PW64 = gm.PW * 64, swa = gm.swa, swd = gm.swd;
     auto tap_addr = [&](int ky, int kx, int stage, int (&tb)[4]) {
       const int so = stage * STAGE + (ky * PW64 + kx * 64);
 #pragma unroll
@@ -974,21 +1021,33 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     constexpr int MTP = R::NPX / 32;                              // m-tiles per pass
     const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
     unsigned amax = 0;
+    double wst[2] = {0.0, 0.0};
+    auto passes = [&](auto ftc, auto ptc, auto stc) {              // (specialised on the output format as in the pair branch)
 #pragma unroll
-    for (int ps = 0; ps < 4 / MTP; ++ps) {
+      for (int ps = 0; ps < 4 / MTP; ++ps) {
 #pragma unroll
-      for (int m = 0; m < MTP; ++m)
+        for (int m = 0; m < MTP; ++m)
 #pragma unroll
-        for (int n2 = 0; n2 < NT2; ++n2)
+          for (int n2 = 0; n2 < NT2; ++n2)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int px = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
-            if (p.relu) v = fmaxf(v, 0.f);
-            ep[px * C16_EP_LD + 32 * n2 + (lane & 31)] = v;
-          }
-      c16_epilogue_pass<MM, 64, R::NPX, CW>(p, sg, ep, nullptr, lane, chan0, gm.g0, gm.x0, gm.tw_log2, gm.ylim, ps * R::NPX, amax);
-    }
+            for (int r = 0; r < 16; ++r) {
+              const int px = 32 * m + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+              float v = fmaf(acc[ps * MTP + m][n2][r], as, bv[n2]);
+              if (p.relu) v = fmaxf(v, 0.f);
+              ep[px * C16_EP_LD + 32 * n2 + (lane & 31)] = v;
+            }
+        c16_epilogue_pass<MM, 64, R::NPX, CW, decltype(ftc)::value, decltype(ptc)::value, decltype(stc)::value>(
+            p, sg, ep, nullptr, lane, chan0, gm.t.g0, gm.t.x0, f_tw_log2, gm.t.ylim, ps * R::NPX, amax, wst);
+      }
+    };
+    typedef std::integral_constant<int, -1> any_;
+    typedef std::integral_constant<int, 0> c0_;
+    typedef std::integral_constant<int, 1> c1_;
+    if (!p.stats && p.full_type == 1 && p.pool_type == 0) passes(c1_{}, c0_{}, c0_{});
+    else if (!p.stats && p.full_type == 0 && p.pool_type == 1) passes(c0_{}, c1_{}, c0_{});
+    else if (!p.stats && p.full_type == 1 && p.pool_type == 1) passes(c1_{}, c1_{}, c0_{});
+    else passes(any_{}, any_{}, any_{});
+    if (p.stats) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
     if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
   }
 }
@@ -1374,7 +1433,8 @@ bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs) {
     if (waste < best - 1e-9) {
       best = waste; found = true;
       int l2 = 0; while ((1 << l2) < tw) ++l2;
-      o.h_tw_log2 = l2; o.h_tiles_x = tx; o.h_tpi = tpi; o.h_segh = segh; o.h_bands = bands;
+      int sl2 = 0; while ((1 << sl2) < segh) ++sl2;           // (segh = TH or a divisor of it: a power of two)
+      o.h_tw_log2 = l2; o.h_tiles_x = tx; o.h_tpi = tpi; o.h_segh_log2 = sl2; o.h_bands = bands;
       tiles = (int)nt;
       // conflict-free slot swizzles found by tools/ubench/conv16_swizzle.py: ((pcol >> a) + prow * d) & (slots - 1)  (64-byte patch rows:
       // 4 slots).  The pair kernel reads 16 pixels x 4 slots per 16 lanes (16x16x32 fragments), the 16-bit modes 32 pixels x 2 slots;
@@ -1383,7 +1443,8 @@ bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs) {
       else { o.h_swa = tw == 32 ? 2 : (tw == 16 ? 1 : 0); o.h_swd = tw <= 8 ? 1 : 0; }
     }
   }
-  return found;
+  // patch size and the reciprocals that replace the kernel's divisions (exact for every tile index of the segment, or no halo tiling)
+  return found && c16g::finish(o, tiles);
 }
 
 int c16_pick_tw(int W, int pool) {
@@ -1435,6 +1496,8 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
     if (!g6d_aligned16(s.in) || (s.ld_in & 7) || (full_type && (!g6d_aligned16(s.out_full) || (s.ld_full & 7))) || (pool_type && (!g6d_aligned16(s.out_pool) || (s.ld_pool & 7)))) {
       g6d_set_error("conv16_direct: 16-byte aligned rows expected"); return G6D_EINVAL;
     }
+    // (the epilogues address an output from the tile's first pixel with 32-bit offsets: at most 32 rows of W pixels)
+    if (32L * s.W * (s.ld_full > s.ld_pool ? s.ld_full : s.ld_pool) * 4 >= (1L << 32)) { g6d_set_error("conv16_direct: 32 output rows beyond 4 GB"); return G6D_EINVAL; }
     o.in = static_cast<const char*>(s.in); o.full = static_cast<char*>(s.out_full); o.pool = static_cast<char*>(s.out_pool);
     o.H = s.H; o.W = s.W; o.DH = s.D * s.H; o.rows = s.N * s.D * s.H;
     o.ld_in = s.ld_in; o.ld_full = s.ld_full; o.ld_pool = s.ld_pool;
