@@ -9,6 +9,8 @@
 // rotate 0 / 180 that is whole stretches of source rows; 12 output bytes per thread go out as three dwords when the canvas rows are
 // dword-aligned (W % 4 == 0).  Taps of weight 0 are not loaded (a same-size frame costs one tap per pixel), and the chroma terms of an
 // NV12 sample are computed once for the taps of its 2 x 2 block (at 2:1 all four taps of a pixel share one).
+// g6d_frame_ingest_mesh (second half of the file) is the same launch with a lens per frame: blocks of a frame with a mesh take their
+// source coordinates from it (nodes in LDS, 64-bit integer interpolation), blocks of a frame without one run the plain tile.
 #include "g6d_common.h"
 
 namespace {
@@ -136,6 +138,177 @@ __global__ void __launch_bounds__(256) frame_ingest_kernel(const G6dFrame* __res
   }
 }
 
+// ---- g6d_frame_ingest_mesh: the same launch with a lens per frame (a coarse mesh of source coordinates instead of the scaling rule) ----
+// frame_ingest_kernel above stays as it was measured (§4.17); the pieces of its body are restated here as functions so that the plain and
+// the mesh tile of this kernel share them (pulling them out of frame_ingest_kernel changes its register allocation and schedule).
+
+// the four taps of one pixel (weights wa, wb in 1/2048), blended per channel
+__device__ __forceinline__ void gather(const Src& s, int x0, int x1, int y0, int y1, unsigned wa, unsigned wb, int& r, int& g, int& b) {
+  const unsigned w00 = (2048 - wa) * (2048 - wb), w01 = wa * (2048 - wb), w10 = (2048 - wa) * wb, w11 = wa * wb;
+  int r1, g1, b1;
+  unsigned ar = 1u << 21, ag = 1u << 21, ab = 1u << 21;
+#define G6D_ACC(w) { ar += (w) * r1; ag += (w) * g1; ab += (w) * b1; }
+  if (s.nv12) {                                           // (block-uniform) a UV sample is loaded once for the taps that share it
+    const bool sx = (x1 >> 1) == (x0 >> 1), sy = (y1 >> 1) == (y0 >> 1);
+    const Chroma k00 = chroma(s, x0 >> 1, y0 >> 1);
+    tap_nv12(s, k00, x0, y0, r1, g1, b1); G6D_ACC(w00)
+    Chroma k01 = k00;
+    if (wa) { if (!sx) k01 = chroma(s, x1 >> 1, y0 >> 1); tap_nv12(s, k01, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+    if (wb) {
+      const Chroma k10 = sy ? k00 : chroma(s, x0 >> 1, y1 >> 1);
+      tap_nv12(s, k10, x0, y1, r1, g1, b1); G6D_ACC(w10)
+      if (wa) {
+        const Chroma k11 = sx ? k10 : (sy ? k01 : chroma(s, x1 >> 1, y1 >> 1));
+        tap_nv12(s, k11, x1, y1, r1, g1, b1); G6D_ACC(w11)
+      }
+    }
+  } else {
+    tap_packed(s, x0, y0, r1, g1, b1); G6D_ACC(w00)
+    if (wa) { tap_packed(s, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+    if (wb) { tap_packed(s, x0, y1, r1, g1, b1); G6D_ACC(w10) }
+    if (wa && wb) { tap_packed(s, x1, y1, r1, g1, b1); G6D_ACC(w11) }
+  }
+#undef G6D_ACC
+  r = ar >> 22; g = ag >> 22; b = ab >> 22;
+}
+
+__device__ __forceinline__ Src source_of(const G6dFrame& f) {
+  Src s;
+  s.p0 = static_cast<const unsigned char*>(f.plane0); s.p1 = static_cast<const unsigned char*>(f.plane1);
+  s.pitch0 = f.pitch0; s.pitch1 = f.pitch1;
+  s.nv12 = f.format == G6D_FMT_NV12;
+  s.bpp = f.format >= G6D_FMT_RGBA32 ? 4 : 3;
+  s.ro = (f.format == G6D_FMT_BGR24 || f.format == G6D_FMT_BGRA32) ? 2 : 0;
+  const bool m709 = f.matrix == 1;
+  s.cvr = m709 ? 1880097 : 1673527; s.cug = m709 ? 223347 : 409993; s.cvg = m709 ? 558891 : 852492; s.cub = m709 ? 2214593 : 2116026;
+  return s;
+}
+
+// a thread's 4 pixels -> canvas row Y of image `slot` from column X on
+__device__ __forceinline__ void store4(unsigned char* __restrict__ out, const unsigned char (&px)[12], int slot, int H, int W, int X, int Y) {
+  unsigned char* o = out + (((size_t)slot * H + Y) * W + X) * 3;
+  if (X + 4 <= W && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
+    unsigned* o32 = reinterpret_cast<unsigned*>(o);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      o32[j] = (unsigned)px[4 * j] | ((unsigned)px[4 * j + 1] << 8) | ((unsigned)px[4 * j + 2] << 16) | ((unsigned)px[4 * j + 3] << 24);
+  } else {
+    const int nb = 3 * min(4, W - X);
+#pragma unroll
+    for (int j = 0; j < 12; ++j)
+      if (j < nb) o[j] = px[j];
+  }
+}
+
+// one tile of a frame by the plain rule (scaling + quarter turn); cw: TW + TH words of LDS
+__device__ __forceinline__ void plain_tile(const G6dFrame& f, unsigned* cw, unsigned char* __restrict__ out, int slot, int H, int W, int X0,
+                                           int Y0) {
+  const int t = threadIdx.x;
+  const int ws = f.width, hs = f.height, rot = f.rotate;
+  const int ow = min(f.out_w, W), oh = min(f.out_h, H);   // an empty or negative picture leaves a black canvas
+  const bool swap = rot == 90 || rot == 270;
+  if (t < TW + TH) {
+    unsigned v = 0;
+    if (t < TW) {
+      const int X = X0 + t;
+      if (X < ow) v = sample_word((rot == 90 || rot == 180) ? f.out_w - 1 - X : X, f.out_w, swap ? hs : ws);
+    } else {
+      const int Y = Y0 + t - TW;
+      if (Y < oh) v = sample_word((rot == 180 || rot == 270) ? f.out_h - 1 - Y : Y, f.out_h, swap ? ws : hs);
+    }
+    cw[t] = v;
+  }
+  __syncthreads();
+  const int ry = t >> 5, X = X0 + ((t & 31) << 2), Y = Y0 + ry;
+  if (Y >= H || X >= W) return;
+  const Src s = source_of(f);
+  const unsigned rw = cw[TW + ry];
+  unsigned char px[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int r = 0, g = 0, b = 0;
+    if (X + k < ow && Y < oh) {
+      const unsigned c = cw[(t & 31) * 4 + k];
+      const unsigned xw = swap ? rw : c, yw = swap ? c : rw;
+      const int x0 = xw & 8191, x1 = x0 + ((xw >> 13) & 1), y0 = yw & 8191, y1 = y0 + ((yw >> 13) & 1);
+      gather(s, x0, x1, y0, y1, xw >> 14, yw >> 14, r, g, b);
+    }
+    px[3 * k] = (unsigned char)r; px[3 * k + 1] = (unsigned char)g; px[3 * k + 2] = (unsigned char)b;
+  }
+  store4(out, px, slot, H, W, X, Y);
+}
+
+constexpr int MESH_NX = TW / 2 + 1, MESH_NY = TH / 2 + 1;  // a tile's nodes at the finest step, 2
+
+// v = (g - j) * m0 + j * m1 of one node column (x and y parts), 64-bit: |m| <= 2^30, g <= 16
+struct Col { long long x, y; };
+__device__ __forceinline__ Col column(const int2* nd, int at, int below, int g, int j) {
+  const int2 m0 = nd[at], m1 = nd[at + below];
+  return Col{(long long)(g - j) * m0.x + (long long)j * m1.x, (long long)(g - j) * m0.y + (long long)j * m1.y};
+}
+
+// one tile of a lens frame.  The canvas coordinates are those AFTER the quarter turn (the host undid it when it built the mesh), so there
+// is no rotation here.  nd: MESH_NX * MESH_NY nodes of LDS
+__device__ __forceinline__ void mesh_tile(const G6dFrame& f, const G6dMesh& m, int2* nd, unsigned char* __restrict__ out, int slot, int H, int W,
+                                          int X0, int Y0) {
+  const int t = threadIdx.x;
+  const int lg = min(max(m.step_log2, 1), 4), g = 1 << lg, sh = 2 * lg + 5;
+  const int tnx = (TW >> lg) + 1, tny = max(TH >> lg, 1) + 1;   // nodes of this tile (a tile lies inside one row of cells at step 16)
+  const int c0 = X0 >> lg, r0 = Y0 >> lg;
+  for (int k = t; k < tnx * tny; k += 256) {              // columns / rows past the mesh's edge are read only by pixels outside the picture
+    const int r = k / tnx, c = k - r * tnx;
+    const int* p = m.nodes + 2 * ((size_t)max(min(r0 + r, m.ny - 1), 0) * m.nx + max(min(c0 + c, m.nx - 1), 0));
+    nd[k] = make_int2(p[0], p[1]);
+  }
+  __syncthreads();
+  const int ry = t >> 5, X = X0 + ((t & 31) << 2), Y = Y0 + ry;
+  if (Y >= H || X >= W) return;
+  const int ws = f.width, hs = f.height;
+  const int ow = min(f.out_w, W), oh = min(f.out_h, H);
+  const Src s = source_of(f);
+  // a thread's 4 pixels lie in one cell (two at step 2): the node columns they use, blended down the cell once
+  const int j = Y & (g - 1), at = ((Y >> lg) - r0) * tnx + (X >> lg) - c0;
+  const Col q0 = column(nd, at, tnx, g, j), q1 = column(nd, at + 1, tnx, g, j);
+  const Col q2 = lg == 1 ? column(nd, at + 2, tnx, g, j) : q1;
+  const long long half = 1ll << (sh - 1);
+  const int xhi = (ws - 1) * 2048, yhi = (hs - 1) * 2048;
+  unsigned char px[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int r = 0, gr = 0, b = 0;
+    if (X + k < ow && Y < oh) {
+      const bool second = lg == 1 && k >= 2;
+      const Col& l = second ? q1 : q0;
+      const Col& h = second ? q2 : q1;
+      const int i = (X + k) & (g - 1);
+      int fx = (int)(((g - i) * l.x + i * h.x + half) >> sh), fy = (int)(((g - i) * l.y + i * h.y + half) >> sh);
+      if (fx >= -1024 && fx <= xhi + 1024 && fy >= -1024 && fy <= yhi + 1024) {   // else: the constant border, black
+        fx = min(max(fx, 0), xhi); fy = min(max(fy, 0), yhi);
+        const int x0 = fx >> 11, y0 = fy >> 11;
+        gather(s, x0, min(x0 + 1, ws - 1), y0, min(y0 + 1, hs - 1), fx & 2047, fy & 2047, r, gr, b);
+      }
+    }
+    px[3 * k] = (unsigned char)r; px[3 * k + 1] = (unsigned char)gr; px[3 * k + 2] = (unsigned char)b;
+  }
+  store4(out, px, slot, H, W, X, Y);
+}
+
+__global__ void __launch_bounds__(256) frame_ingest_lens_kernel(const G6dFrame* __restrict__ frames, const G6dMesh* __restrict__ meshes,
+                                                                unsigned char* __restrict__ out, int B, int H, int W,
+                                                                float* __restrict__ K_out, int tiles_x, int tiles) {
+  __shared__ unsigned cw[TW + TH];
+  __shared__ int2 nd[MESH_NX * MESH_NY];
+  const int fi = blockIdx.x / tiles, tile = blockIdx.x - fi * tiles;
+  const G6dFrame& f = frames[fi];
+  const int slot = f.slot;
+  if (slot < 0 || slot >= B) return;                      // (block-uniform)
+  if (tile == 0 && threadIdx.x < 9) K_out[(size_t)9 * slot + threadIdx.x] = f.K[threadIdx.x];
+  const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
+  const G6dMesh& m = meshes[fi];
+  if (m.nodes) mesh_tile(f, m, nd, out, slot, H, W, X0, Y0);     // (block-uniform)
+  else plain_tile(f, cw, out, slot, H, W, X0, Y0);
+}
+
 }  // namespace
 
 extern "C" int g6d_sizeof_frame_desc(void) { return (int)sizeof(G6dFrame); }
@@ -150,4 +323,19 @@ extern "C" int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int
   hipLaunchKernelGGL(frame_ingest_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames, out, B, H,
                      W, K_out, tiles_x, tiles);
   return g6d_check_launch("frame_ingest");
+}
+
+extern "C" int g6d_sizeof_mesh_desc(void) { return (int)sizeof(G6dMesh); }
+
+extern "C" int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* meshes, int n, uint8_t* out, int B, int H, int W, float* K_out,
+                                     g6d_stream_t stream) {
+  if (!frames || !meshes || n < 0 || !out || !K_out || B < 1 || H < 1 || W < 1) {
+    g6d_set_error("frame_ingest_mesh: bad args (null table / meshes / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
+  }
+  if (n == 0) return G6D_OK;
+  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_mesh: too many tiles for one launch"); return G6D_EINVAL; }
+  hipLaunchKernelGGL(frame_ingest_lens_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
+                     meshes, out, B, H, W, K_out, tiles_x, tiles);
+  return g6d_check_launch("frame_ingest_mesh");
 }

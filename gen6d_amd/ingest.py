@@ -4,10 +4,14 @@ working-resolution images and intrinsics the networks take, in ONE launch of g6d
 A `Frame` describes one picture as a camera or a video decoder delivers it: packed rgb24 / bgr24 / rgba32 / bgra32 or NV12, any size up to
 8192, any row pitch, host or device memory, optionally turned by quarter turns.  `plan` places it in a canvas (scaled to fit, top-left
 corner) and maps its intrinsics; `ingest_frames` uploads what lives on the host through pinned memory without blocking and launches once.
+A Frame with a `Lens` (a calibrated distortion model beside its K) is undistorted in the same launch (g6d_frame_ingest_mesh): the host
+evaluates the model once per camera into a coarse mesh of fixed-point source coordinates, the kernel interpolates it with integers.
 The reference's `--resolution R` is `canvas_for(R, h, w)`; its `--transpose` is rotate=180 with cv2 >= 4.5 (two flips) and
 rotate=90 with older versions (transpose + horizontal flip).  The scaling is the integer bilinear of DESIGN.md §4.17, not cv2's float one.
 """
+import collections
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -20,6 +24,9 @@ FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4}
 MATRICES = {"bt601": 0, "bt709": 1}
 BPP = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1}
 MAX_SIZE = 8192
+LENS_MODELS = {"brown": (4, 5, 8), "fisheye": (4,)}      # model -> admissible numbers of coefficients
+MESH_STEPS = (16, 8, 4, 2)
+MESH_CACHE = 64                                          # device meshes kept per process (one per camera, plan and device)
 
 
 def _strides(a):
@@ -59,20 +66,109 @@ def _span(a, row_bytes, rows, pitch, offset=0):
     return base[offset:offset + need]
 
 
+@dataclasses.dataclass(frozen=True)
+class Lens:
+    """A lens distortion model in OpenCV's conventions, immutable and hashable; goes with a Frame's K: Frame(..., K=K, lens=Lens(...)).
+    With (x, y) normalised undistorted coordinates and r2 = x^2 + y^2:
+      "brown", coeffs k1 k2 p1 p2 [k3 [k4 k5 k6]]: rad = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+        xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2), yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y;
+      "fisheye", coeffs k1 k2 k3 k4: t = atan(r), td = t (1 + k1 t^2 + k2 t^4 + k3 t^6 + k4 t^8), (xd, yd) = (td / r) (x, y) (factor 1 at r = 0).
+    The ingested picture is the scaled virtual pinhole picture of the source's size with intrinsics new_K (default: the frame's K, as
+    cv2.undistort); pixels that look past the source's edge are black.  tol: the mesh's largest distance to the model in canvas pixels."""
+    model: str
+    coeffs: tuple
+    new_K: tuple = None
+    tol: float = 1 / 16
+
+    def __post_init__(self):
+        if self.model not in LENS_MODELS:
+            raise ValueError(f"Lens: unknown model {self.model!r} (one of {sorted(LENS_MODELS)})")
+        c = tuple(float(v) for v in np.asarray(self.coeffs, np.float64).reshape(-1))
+        if len(c) not in LENS_MODELS[self.model]:
+            raise ValueError(f"Lens: a {self.model} lens takes {' / '.join(map(str, LENS_MODELS[self.model]))} coefficients, not {len(c)}")
+        if not np.isfinite(c).all() or not (np.isfinite(self.tol) and self.tol > 0):
+            raise ValueError("Lens: finite coefficients and a positive tol expected")
+        K = self.new_K
+        if K is not None:
+            K = tuple(float(v) for v in np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float64).reshape(9))
+        for name, v in (("coeffs", c), ("new_K", K), ("tol", float(self.tol))):       # normalised: equal lenses compare and hash equal
+            object.__setattr__(self, name, v)
+
+    def distort(self, x, y):
+        """Normalised undistorted (x, y) -> normalised distorted (xd, yd), float64."""
+        x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+        r2 = x * x + y * y
+        if self.model == "fisheye":
+            k1, k2, k3, k4 = self.coeffs
+            r = np.sqrt(r2)
+            t = np.arctan(r)
+            t2 = t * t
+            td = t * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+            s = np.where(r > 0, td / np.where(r > 0, r, 1.0), 1.0)
+            return x * s, y * s
+        k1, k2, p1, p2, k3, k4, k5, k6 = self.coeffs + (0.0,) * (8 - len(self.coeffs))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rad = (1 + r2 * (k1 + r2 * (k2 + r2 * k3))) / (1 + r2 * (k4 + r2 * (k5 + r2 * k6)))
+            return x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x), y * rad + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+
+    def source_coords(self, K, ws, hs, rotate, out_w, out_h, X, Y):
+        """Canvas pixel coordinates (X, Y) of the out_w x out_h picture of a ws x hs source -> the source coordinates (ud, vd) the lens
+        puts them at, float64: undo the quarter turn, the scaling u = (x + 0.5) ws / wt - 0.5, new_K^-1, the model, K."""
+        wt, ht = (out_h, out_w) if rotate in (90, 270) else (out_w, out_h)
+        X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)
+        x, y = {0: (X, Y), 90: (Y, ht - 1 - X), 180: (wt - 1 - X, ht - 1 - Y), 270: (wt - 1 - Y, X)}[rotate]
+        u, v = (x + 0.5) * ws / wt - 0.5, (y + 0.5) * hs / ht - 0.5
+        K = np.asarray(K, np.float64).reshape(3, 3)
+        Ni = np.linalg.inv(K if self.new_K is None else np.asarray(self.new_K, np.float64).reshape(3, 3))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = Ni[2, 0] * u + Ni[2, 1] * v + Ni[2, 2]
+            xd, yd = self.distort((Ni[0, 0] * u + Ni[0, 1] * v + Ni[0, 2]) / w, (Ni[1, 0] * u + Ni[1, 1] * v + Ni[1, 2]) / w)
+            w = K[2, 0] * xd + K[2, 1] * yd + K[2, 2]
+            return (K[0, 0] * xd + K[0, 1] * yd + K[0, 2]) / w, (K[1, 0] * xd + K[1, 1] * yd + K[1, 2]) / w
+
+    def mesh(self, K, ws, hs, rotate, out_w, out_h):
+        """-> (nodes int32 [ny, nx, 2], step_log2): source coordinates in 1/65536 pixels at the canvas pixels (g c, g r), c = 0 ..
+        ceil(out_w / g), r likewise, clamped to +-2^30 (a coordinate that is not finite counts as far outside).  g = 2^step_log2 is the
+        largest of 16, 8, 4, 2 at which the bilinear interpolation of the nodes stays within tol * max(ws / wt, hs / ht) source pixels
+        (tol canvas pixels) of the model at every cell's centre and edge midpoints."""
+        wt, ht = (out_h, out_w) if rotate in (90, 270) else (out_w, out_h)
+        at = lambda X, Y: np.stack(self.source_coords(K, ws, hs, rotate, out_w, out_h, X, Y), -1)
+        bound = self.tol * max(ws / wt, hs / ht)
+        for g in MESH_STEPS:
+            xs, ys = np.arange(-(-out_w // g) + 1, dtype=np.float64) * g, np.arange(-(-out_h // g) + 1, dtype=np.float64) * g
+            m = at(*np.meshgrid(xs, ys))
+            xc, yc = xs[:-1] + g / 2, ys[:-1] + g / 2
+            with np.errstate(invalid="ignore"):
+                miss = max(np.abs(at(*np.meshgrid(xc, ys)) - (m[:, :-1] + m[:, 1:]) / 2).max(),                 # horizontal edges
+                           np.abs(at(*np.meshgrid(xs, yc)) - (m[:-1] + m[1:]) / 2).max(),                       # vertical edges
+                           np.abs(at(*np.meshgrid(xc, yc)) - (m[:-1, :-1] + m[:-1, 1:] + m[1:, :-1] + m[1:, 1:]) / 4).max())
+            if miss <= bound:                                        # (a NaN fails this)
+                fixed = np.clip(np.rint(np.nan_to_num(m, nan=np.inf) * 65536.0), -2.0 ** 30, 2.0 ** 30)
+                return np.ascontiguousarray(fixed.astype(np.int32)), g.bit_length() - 1
+        raise ValueError(f"{self!r}: a mesh of step 2 misses the model by {miss:.3g} source pixels at a {ws} x {hs} source in a {out_w} x "
+                         f"{out_h} picture, more than tol allows ({bound:.3g})")
+
+
 class Frame:
     """One source picture.  data: uint8 numpy array or torch tensor (host or device), [H,W,C] (C = 3 / 4 as the format says; sizes and
     the pitch are taken from it), [rows, row bytes] or a flat buffer (give width / height / pitch).  NV12: either one [H*3/2, pitch] buffer
     (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV plane ([H/2, bytes] or [H/2, W/2, 2]).
     rotate: quarter turns clockwise applied after scaling (0 / 90 / 180 / 270).  K: the camera's intrinsics in SOURCE pixel coordinates, or
-    None for predict.py's pseudo intrinsics of the ingested picture.  matrix: "bt601" / "bt709" (limited range), NV12 only."""
+    None for predict.py's pseudo intrinsics of the ingested picture.  matrix: "bt601" / "bt709" (limited range), NV12 only.  lens: the
+    camera's `Lens` (needs K): the ingested picture is the undistorted one, and its intrinsics come from the lens's new_K."""
 
-    def __init__(self, data, fmt="rgb24", width=None, height=None, pitch=None, rotate=0, K=None, uv=None, uv_pitch=None, matrix="bt601"):
+    def __init__(self, data, fmt="rgb24", width=None, height=None, pitch=None, rotate=0, K=None, uv=None, uv_pitch=None, matrix="bt601",
+                 lens=None):
         if fmt not in FORMATS:
             raise ValueError(f"Frame: unknown format {fmt!r} (one of {sorted(FORMATS)})")
         if matrix not in MATRICES:
             raise ValueError(f"Frame: unknown matrix {matrix!r} (bt601 or bt709)")
         if rotate not in (0, 90, 180, 270):
             raise ValueError(f"Frame: rotate must be 0, 90, 180 or 270, not {rotate!r}")
+        if lens is not None and not isinstance(lens, Lens):
+            raise ValueError("Frame: lens must be an ingest.Lens")
+        if lens is not None and K is None:
+            raise ValueError("Frame: a frame with a lens must carry the camera's K")
         nv12, bpp = fmt == "nv12", BPP[fmt]
         if uv is not None and not nv12:
             raise ValueError("Frame: uv is the second plane of an nv12 frame")
@@ -108,6 +204,7 @@ class Frame:
             raise ValueError(f"Frame: pitch {p} is smaller than a row of {w} {fmt} pixels")
         self.fmt, self.width, self.height, self.pitch, self.rotate, self.matrix = fmt, w, h, p, int(rotate), matrix
         self.K = None if K is None else np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float64).reshape(3, 3)
+        self.lens = lens
         self.plane0 = _span(d, w * bpp, h, p)
         self.plane1, self.uv_pitch = None, 0
         if nv12:
@@ -164,7 +261,8 @@ def pixel_map(frame, out_h, out_w):
 
 def plan(frame, canvas_hw):
     """-> (out_h, out_w, K'): the size of the scaled and rotated picture that fits the canvas with the source's aspect ratio (it sits at the
-    top-left corner) and its intrinsics, float64: A @ K for a frame with K, predict.py's pseudo K of the picture otherwise."""
+    top-left corner) and its intrinsics, float64: A @ K for a frame with K (A @ new_K of its lens), predict.py's pseudo K of the picture
+    otherwise."""
     H, W = int(canvas_hw[0]), int(canvas_hw[1])
     if H < 1 or W < 1:
         raise ValueError("plan: the canvas must be at least 1 x 1")
@@ -175,18 +273,35 @@ def plan(frame, canvas_hw):
         out_w, out_h = W, max(1, W * hs // ws)
     if frame.K is None:
         return out_h, out_w, EV.pseudo_K(out_h, out_w).astype(np.float64)
-    return out_h, out_w, pixel_map(frame, out_h, out_w) @ frame.K
+    K = frame.K if frame.lens is None or frame.lens.new_K is None else np.asarray(frame.lens.new_K, np.float64).reshape(3, 3)
+    return out_h, out_w, pixel_map(frame, out_h, out_w) @ K
 
 
 def _host(p):
     return p.numpy() if torch.is_tensor(p) else p
 
 
+_meshes = collections.OrderedDict()     # (device, lens, K, ws, hs, rotate, out_w, out_h) -> _Mesh, least recently used first
+
+
+class _Mesh:
+    """A lens mesh on its way to / in device memory: host (int32 [ny, nx, 2], until uploaded), nodes (the device tensor), step_log2, and
+    the stream and event of the upload (a launch on another stream waits for the event on the device)."""
+
+    def __init__(self, host, step_log2):
+        self.host, self.step_log2, self.nodes, self.stream, self.event = host, step_log2, None, None, None
+
+
+def _mesh_key(frame, out_h, out_w, dev):
+    return (dev, frame.lens, frame.K.tobytes(), frame.width, frame.height, frame.rotate, out_w, out_h)
+
+
 def ingest_frames(frames, out, K_out, slots=None, stream=None):
     """frames (Frame objects) -> out[slot] uint8 [B,H,W,3] and K_out[slot] float32 [B,3,3], slot i by default; one launch on `stream` (the
     current stream if None).  Host-resident planes and the descriptor table are gathered in one pinned staging buffer and travel in one
     non-blocking copy (copying planes that already are pinned one by one was measured slower); device-resident planes
-    are recorded on the stream.  Does not synchronise.  Slots no frame names keep their content."""
+    are recorded on the stream.  Frames with a lens make it one launch of g6d_frame_ingest_mesh instead: a camera's mesh is built on its
+    first frame, travels in the same copy and stays on the device.  Does not synchronise.  Slots no frame names keep their content."""
     frames = list(frames)
     n = len(frames)
     if out.dim() != 4 or out.shape[3] != 3:
@@ -199,7 +314,9 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
     cuda = dev.type == "cuda"
     size = C.sizeof(_lib.G6dFrame)
     table = (_lib.G6dFrame * max(n, 1))()
+    mtable = (_lib.G6dMesh * max(n, 1))()      # used when some frame has a lens
     staged = []                                # host planes: (frame index, field, bytes)
+    meshes, fresh = {}, {}                     # frame index -> _Mesh; key -> _Mesh built in this call (cached once it is uploaded)
     for i, f in enumerate(frames):
         if not isinstance(f, Frame):
             raise ValueError("ingest_frames: Frame objects expected")
@@ -217,15 +334,24 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
                 setattr(e, field, p.data_ptr())
             else:
                 staged.append((i, field, _host(p)))
+        if f.lens is not None:
+            key = _mesh_key(f, out_h, out_w, dev)
+            m = _meshes.get(key) or fresh.get(key)
+            if m is None:
+                m = fresh[key] = _Mesh(*f.lens.mesh(f.K, f.width, f.height, f.rotate, out_w, out_h))
+            elif key in _meshes:
+                _meshes.move_to_end(key)                             # most recently used
+            meshes[i] = m
     if n == 0:
         return out
-    # layout of the upload (one pinned buffer, one copy): staged planes | table
+    # layout of the upload (one pinned buffer, one copy): staged planes | new meshes | table | mesh table
     offs, total = [], 0
-    for _, _, p in staged:
+    for p in [p for _, _, p in staged] + [m.host.reshape(-1).view(np.uint8) for m in fresh.values()]:
         offs.append(total)
         total += (p.shape[0] + 255) & ~255
     toff = total
-    total = toff + n * size
+    moff = toff + n * size
+    total = moff + (n * C.sizeof(_lib.G6dMesh) if meshes else 0)
     ctx = torch.cuda.stream(stream) if (cuda and stream is not None) else None
     if ctx is not None:
         ctx.__enter__()
@@ -245,10 +371,34 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
         for (i, field, p), off in zip(staged, offs):
             hn[off:off + p.shape[0]] = p
             setattr(table[i], field, base + off)
-        hn[toff:] = np.frombuffer(table, np.uint8, n * size)
+        for m, off in zip(fresh.values(), offs[len(staged):]):
+            hn[off:off + m.host.nbytes] = m.host.reshape(-1).view(np.uint8)
+            m.nodes = torch.empty(m.host.shape, dtype=torch.int32, device=dev)
+        for i, m in meshes.items():
+            mtable[i].nodes, mtable[i].ny, mtable[i].nx, mtable[i].step_log2 = m.nodes.data_ptr(), m.nodes.shape[0], m.nodes.shape[1], m.step_log2
+        hn[toff:moff] = np.frombuffer(table, np.uint8, n * size)
+        if meshes:
+            hn[moff:] = np.frombuffer(mtable, np.uint8, total - moff)
         if cuda:
             buf.copy_(host, non_blocking=True)
-        ops.frame_ingest(buf[toff:], n, out, K_out)
+        for (key, m), off in zip(fresh.items(), offs[len(staged):]):  # out of the staging buffer into the mesh's own memory, on this stream
+            m.nodes.view(-1).copy_(buf[off:off + m.host.nbytes].view(torch.int32))
+            m.host = None
+            if cuda:
+                m.stream, m.event = cur, torch.cuda.Event()
+                m.event.record(cur)
+            _meshes[key] = m
+        while len(_meshes) > MESH_CACHE:
+            _meshes.popitem(last=False)
+        if cuda:
+            for m in meshes.values():
+                if m.stream != cur:                                   # uploaded on another lane's stream: this launch waits for it on the device
+                    cur.wait_event(m.event)
+                    m.nodes.record_stream(cur)
+        if meshes:
+            ops.frame_ingest_mesh(buf[toff:moff], buf[moff:], n, out, K_out)
+        else:
+            ops.frame_ingest(buf[toff:], n, out, K_out)
     finally:
         if ctx is not None:
             ctx.__exit__(None, None, None)

@@ -40,6 +40,11 @@ class G6dFrame(C.Structure):
                 ("out_w", C.c_int32), ("out_h", C.c_int32), ("K", C.c_float * 9)]
 
 
+class G6dMesh(C.Structure):
+    """include/gen6d_hip.h: the lens mesh of one frame of g6d_frame_ingest_mesh (nodes None: the plain rule; the table lives in device memory)."""
+    _fields_ = [("nodes", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("step_log2", C.c_int32), ("reserved", C.c_int32)]
+
+
 class G6dSink(C.Structure):
     """include/gen6d_hip.h: one destination of g6d_frame_emit (the table lives in device memory)."""
     _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("pitch0", C.c_int32), ("pitch1", C.c_int32), ("width", C.c_int32),
@@ -134,6 +139,8 @@ SIGNATURES = {
     "g6d_track_verify": [_P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P, _P, _I, _P],
     "g6d_frame_ingest": [_P, _I, _P, _I, _I, _I, _P, _P],
     "g6d_sizeof_frame_desc": [],
+    "g6d_frame_ingest_mesh": [_P, _P, _I, _P, _I, _I, _I, _P, _P],
+    "g6d_sizeof_mesh_desc": [],
     "g6d_track_corners": [_P, _P, _P, _P, _P, _P, _I, _P],
     "g6d_frame_emit": [_P, _I, _P, _I, _I, _I, _P, _P, _P],
     "g6d_sizeof_sink_desc": [],
@@ -164,6 +171,8 @@ def load():
         raise RuntimeError("libgen6d_hip.so: G6dConv layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
         raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
+    if lib.g6d_sizeof_mesh_desc() != C.sizeof(G6dMesh):
+        raise RuntimeError("libgen6d_hip.so: G6dMesh layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_sink_desc() != C.sizeof(G6dSink):
         raise RuntimeError("libgen6d_hip.so: G6dSink layout differs from the ctypes binding (stale build?)")
     lib.g6d_last_error.restype = C.c_char_p

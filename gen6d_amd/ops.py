@@ -1578,21 +1578,39 @@ def track_verify(det, pose_table, K, slot_commit, center, diameter, ref_px, poli
 
 
 # ------------------------------------------------------------------------------------------------ frame ingest
+def _frame_ingest_args(what, table, n, out, K_out):
+    n = int(n)
+    size = C.sizeof(_lib.G6dFrame)
+    if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or n < 0 or table.numel() < n * size or table.data_ptr() % 8:
+        raise ValueError(f"{what}: table must be a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
+    if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[3] != 3 or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous uint8 [B,H,W,3] tensor")
+    B, H, W = out.shape[:3]
+    if K_out.dtype != torch.float32 or tuple(K_out.shape) != (B, 3, 3) or not K_out.is_contiguous():
+        raise ValueError(f"{what}: K_out must be a contiguous float32 [B,3,3] tensor")
+    return n, B, H, W
+
+
 def frame_ingest(table, n, out, K_out):
     """One launch of g6d_frame_ingest: `table` a contiguous uint8 device tensor holding n lib.G6dFrame records (8-byte aligned; built and
     validated by gen6d_amd.ingest.ingest_frames), out uint8 [B,H,W,3], K_out float32 [B,3,3].  Every frame's picture is written into
     out[slot] (the rest of that canvas 0) and its K into K_out[slot]; other slots are not touched."""
     _track_same_device("frame_ingest", table, out, K_out)
-    n = int(n)
-    size = C.sizeof(_lib.G6dFrame)
-    if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or n < 0 or table.numel() < n * size or table.data_ptr() % 8:
-        raise ValueError(f"frame_ingest: table must be a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
-    if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[3] != 3 or not out.is_contiguous():
-        raise ValueError("frame_ingest: out must be a contiguous uint8 [B,H,W,3] tensor")
-    B, H, W = out.shape[:3]
-    if K_out.dtype != torch.float32 or tuple(K_out.shape) != (B, 3, 3) or not K_out.is_contiguous():
-        raise ValueError("frame_ingest: K_out must be a contiguous float32 [B,3,3] tensor")
+    n, B, H, W = _frame_ingest_args("frame_ingest", table, n, out, K_out)
     _lib.check(_lib.load().g6d_frame_ingest(_ptr(table), n, _ptr(out), B, H, W, _ptr(K_out), _stream()), "g6d_frame_ingest")
+    return out
+
+
+def frame_ingest_mesh(table, meshes, n, out, K_out):
+    """One launch of g6d_frame_ingest_mesh: frame_ingest with `meshes`, a contiguous uint8 device tensor holding n lib.G6dMesh records
+    (8-byte aligned), record i the lens mesh of frame i (nodes in device memory) or nodes 0 for the plain rule."""
+    _track_same_device("frame_ingest_mesh", table, meshes, out, K_out)
+    n, B, H, W = _frame_ingest_args("frame_ingest_mesh", table, n, out, K_out)
+    size = C.sizeof(_lib.G6dMesh)
+    if meshes.dtype != torch.uint8 or meshes.dim() != 1 or not meshes.is_contiguous() or meshes.numel() < n * size or meshes.data_ptr() % 8:
+        raise ValueError(f"frame_ingest_mesh: meshes must be a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
+    _lib.check(_lib.load().g6d_frame_ingest_mesh(_ptr(table), _ptr(meshes), n, _ptr(out), B, H, W, _ptr(K_out), _stream()),
+               "g6d_frame_ingest_mesh")
     return out
 
 

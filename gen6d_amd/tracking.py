@@ -15,7 +15,8 @@ many streams (cameras or clients watching one object) at once:
     (DeviceChain.ref_poses[0]) and are not committed;
   * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners;
   * with `frame_size=(H, W)` the tracker takes camera-native frames (`gen6d_amd.ingest.Frame`: any size, packed RGB / BGR(A) or NV12,
-    pitched, rotated, mixed within one push): one g6d_frame_ingest launch per lane and tick scales them into the lane's static image
+    pitched, rotated, with or without a calibrated `ingest.Lens`, mixed within one push): one g6d_frame_ingest launch per lane and tick
+    (g6d_frame_ingest_mesh when a frame has a lens: it is undistorted on the way) scales them into the lane's static image
     slots and writes their intrinsics, in place of the per-slot copies (DESIGN.md §4.17);
   * with `sinks` a push also writes what predict.py writes per frame: the working-resolution picture with the projected box drawn on it
     (raw and / or smoothed pose), in an encoder's or a display's format, into device or pinned host buffers the caller names

@@ -630,6 +630,29 @@ typedef struct G6dFrame {          /* one per frame */
 int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int B, int H, int W, float* K_out, g6d_stream_t stream);
 int g6d_sizeof_frame_desc(void);
 
+/* Lens undistortion inside the ingest launch (gen6d_amd/ingest.py `Lens`); additive within ABI 12.  g6d_frame_ingest_mesh is
+ * g6d_frame_ingest with one G6dMesh per frame (meshes[i] belongs to frames[i]; the table lives in device memory, 8-byte aligned).  A frame
+ * whose mesh has nodes == NULL takes the plain rule above, bit for bit; a tick that mixes plain and lens frames is one launch.
+ * A mesh gives the SOURCE coordinate of every canvas pixel of the picture (the quarter turn already undone by whoever built it: the
+ * frame's `rotate` is not used): node (c, r) sits at canvas pixel (g c, g r), g = 2^step_log2 in {2, 4, 8, 16}, and holds (x, y) in
+ * 1/65536 source pixels, |value| <= 2^30; nx >= ceil(out_w / g) + 1, ny >= ceil(out_h / g) + 1.  Canvas pixel (X, Y) of the picture,
+ * exact integers (the numpy restatement in tests/test_ingest_lens_cpu.py is bit-identical): i = X mod g, j = Y mod g,
+ * m00 m01 / m10 m11 the nodes of its cell (m01 to the right, m10 below),
+ *   S = (g-i)(g-j) m00 + i (g-j) m01 + (g-i) j m10 + i j m11 (64-bit), f = (S + 2^(s-1)) >> s (arithmetic) with s = 2 step_log2 + 5:
+ *   fx from the x parts, fy from the y parts, in 1/2048 source pixels;
+ *   fx < -1024, fx > (ws-1) 2048 + 1024, or the same for fy against hs: the pixel is (0, 0, 0) (a constant black border);
+ *   else fx = clamp(fx, 0, (ws-1) 2048), x0 = fx >> 11, a = fx & 2047, x1 = min(x0+1, ws-1), y likewise; taps, NV12 conversion and
+ *   blend as above. */
+typedef struct G6dMesh {           /* one per frame */
+  const int32_t* nodes;            /* [ny][nx][2] (x, y), device memory; NULL: the plain rule */
+  int32_t nx, ny;                  /* nodes per row, rows */
+  int32_t step_log2;               /* 1..4 */
+  int32_t reserved;
+} G6dMesh;
+int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* meshes, int n, uint8_t* out, int B, int H, int W, float* K_out,
+                          g6d_stream_t stream);
+int g6d_sizeof_mesh_desc(void);
+
 /* Annotated frame output (gen6d_amd/emit.py; reference predict.py:60-72 + utils/draw_utils.py draw_bbox_3d); additive within ABI 12.
  * g6d_track_corners, one 64-thread block per slot: the box (box[8][3], corner order of pts_range_to_bbox_pts) projected in float64 (the
  * projection of g6d_track_commit) under row slot_stream[b] of `table` (pose_table or smooth_table, [streams][12]) and K[b][9]; every

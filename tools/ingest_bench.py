@@ -1,27 +1,37 @@
-"""The frame-ingest kernel alone (csrc/ingest.hip): 32 device-resident frames per launch, two cases:
+"""The frame-ingest kernels alone (csrc/ingest.hip): 32 device-resident frames per launch, two cases:
 
   nv12-1080p   32 x (1080x1920 NV12 -> 540x960 canvas)
   rgb-same     32 x (480x640 rgb24 -> 480x640 canvas)
+
+and with --lens two more, the same frames with a strong lens (brown -0.35 0.12 0.001 -0.0005 -0.02, f = 1000 / 333) through the mesh path
+of g6d_frame_ingest_mesh (nv12-1080p-lens, rgb-same-lens), and nv12-1080p-mixed: 31 plain frames and one lens frame, so that the plain
+frames take the plain tile of the lens kernel.  --rounds R runs the cases R times in turn (variants alternate; the table gives the
+spread of the rounds' medians).
 
 Bytes are counted from shapes: the source rows a launch touches (every row of every plane, pixel bytes only) plus the canvas bytes it
 writes.  Timing: device events around `--launches` back-to-back launches (includes the table upload of each call), or, under the profiler,
 the kernel's own durations:
 
-  python tools/ingest_bench.py [--launches 50]
-  rocprofv3 --kernel-trace -d DIR -o ingest --output-format csv -- python tools/ingest_bench.py
-  python tools/ingest_bench.py --trace-csv DIR/.../ingest_kernel_trace.csv [--tick-ms T] [--out FILE.md]
+  python tools/ingest_bench.py [--launches 50] [--lens] [--rounds 3]
+  rocprofv3 --kernel-trace -d DIR -o ingest --output-format csv -- python tools/ingest_bench.py [--lens] [--rounds 3]
+  python tools/ingest_bench.py --trace-csv DIR/.../ingest_kernel_trace.csv [--lens] [--rounds 3] [--tick-ms T] [--out FILE.md]
 """
 import argparse
 import os
+import re
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+N = 32
 HBM_BPS = 6.3e12          # achievable HBM rate the shares are quoted against
 CASES = {"nv12-1080p": dict(src=(1080, 1920), fmt="nv12", canvas=(540, 960)), "rgb-same": dict(src=(480, 640), fmt="rgb24", canvas=(480, 640))}
-N = 32
+LENS_CASES = {"nv12-1080p-lens": dict(CASES["nv12-1080p"], lens=N), "rgb-same-lens": dict(CASES["rgb-same"], lens=N),
+              "nv12-1080p-mixed": dict(CASES["nv12-1080p"], lens=1)}
+BROWN = (-0.35, 0.12, 0.001, -0.0005, -0.02)
+WARM = 3
 
 
 def case_bytes(c):
@@ -30,21 +40,24 @@ def case_bytes(c):
     return N * (src + H * W * 3)
 
 
-def trace_table(path, launches, tick_ms):
+def trace_table(path, cases, launches, rounds, tick_ms):
     import csv
     rows = [r for r in csv.DictReader(open(path)) if "frame_ingest" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    warm = 3
-    out = ["| case | launches | kernel us (median) | min | max | bytes per launch | TB/s (median) | share of 6.3 TB/s | share of a tick |",
-           "|---|---:|---:|---:|---:|---:|---:|---:|---:|"]
-    per = warm + launches
-    for i, (name, c) in enumerate(CASES.items()):
-        d = np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[i * per + warm:(i + 1) * per]])
-        if not len(d):
+    out = ["| case | kernel | launches | kernel us (median) | min | max | medians of the rounds | bytes per launch | TB/s (median) | share of 6.3 TB/s | share of a tick |",
+           "|---|---|---:|---:|---:|---:|---|---:|---:|---:|---:|"]
+    per = WARM + launches
+    for i, (name, c) in enumerate(cases.items()):
+        mine = [rows[(r * len(cases) + i) * per + WARM:(r * len(cases) + i + 1) * per] for r in range(rounds)]
+        if not all(len(m) == launches for m in mine):
             continue
-        b, med = case_bytes(c), float(np.median(d))
+        d = [np.array([(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in m]) for m in mine]
+        kernels = sorted({re.search(r"frame_ingest\w*", r["Kernel_Name"]).group(0) for m in mine for r in m})
+        alld = np.concatenate(d)
+        b, med = case_bytes(c), float(np.median(alld))
         tick = f"{med / (tick_ms * 1e3):.2%}" if tick_ms else "-"
-        out.append(f"| {name} | {len(d)} | {med:.1f} | {d.min():.1f} | {d.max():.1f} | {b / 1e6:.1f} MB | {b / med / 1e6:.2f} | "
+        out.append(f"| {name} | {' '.join(kernels)} | {len(alld)} | {med:.1f} | {alld.min():.1f} | {alld.max():.1f} | "
+                   f"{' '.join(f'{np.median(x):.1f}' for x in d)} | {b / 1e6:.1f} MB | {b / med / 1e6:.2f} | "
                    f"{b / med / 1e6 / (HBM_BPS / 1e12):.1%} | {tick} |")
     return "\n".join(out)
 
@@ -52,12 +65,15 @@ def trace_table(path, launches, tick_ms):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--lens", action="store_true", help="add the lens cases (g6d_frame_ingest_mesh)")
+    ap.add_argument("--rounds", type=int, default=1, help="run the cases this many times in turn")
     ap.add_argument("--trace-csv", default=None)
     ap.add_argument("--tick-ms", type=float, default=0.0, help="tick time of the 32-stream tracker the kernel time is set against")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    cases = dict(CASES, **LENS_CASES) if args.lens else CASES
     if args.trace_csv:
-        txt = trace_table(args.trace_csv, args.launches, args.tick_ms)
+        txt = trace_table(args.trace_csv, cases, args.launches, args.rounds, args.tick_ms)
         print(txt)
         if args.out:
             with open(args.out, "a") as f:
@@ -65,28 +81,33 @@ def main():
                         "source rows touched + canvas bytes, from shapes.\n\n" + txt + "\n")
         return
     import torch
-    from gen6d_amd.ingest import Frame, ingest_frames
+    from gen6d_amd.ingest import Frame, Lens, ingest_frames
     if not torch.cuda.is_available():
         sys.exit("ingest_bench: needs the GPU (the kernel has no CPU fallback)")
     rng = np.random.RandomState(0)
-    for name, c in CASES.items():
+    work = {}
+    for name, c in cases.items():
         (h, w), (H, W) = c["src"], c["canvas"]
         shape = (h * 3 // 2, w) if c["fmt"] == "nv12" else (h, w, 3)
-        frames = [Frame(torch.from_numpy(rng.randint(0, 256, shape).astype(np.uint8)).cuda(), c["fmt"]) for _ in range(N)]
-        out = torch.zeros((N, H, W, 3), dtype=torch.uint8, device="cuda")
-        K = torch.zeros((N, 3, 3), device="cuda")
-        for _ in range(3):
-            ingest_frames(frames, out, K)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launches):
-            ingest_frames(frames, out, K)
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) * 1e3 / args.launches
-        b = case_bytes(c)
-        print(f"{name}: {us:.1f} us per call (events, table upload included), {b / 1e6:.1f} MB -> {b / us / 1e6:.2f} TB/s", flush=True)
+        f = 1000.0 * w / 1920
+        K = np.array([[f, 0, w / 2 - 0.5], [0, f, h / 2 - 0.5], [0, 0, 1]])
+        frames = [Frame(torch.from_numpy(rng.randint(0, 256, shape).astype(np.uint8)).cuda(), c["fmt"],
+                        **(dict(K=K, lens=Lens("brown", BROWN)) if i < c.get("lens", 0) else {})) for i in range(N)]
+        work[name] = (frames, torch.zeros((N, H, W, 3), dtype=torch.uint8, device="cuda"), torch.zeros((N, 3, 3), device="cuda"))
+    for _ in range(args.rounds):
+        for name, (frames, out, K) in work.items():
+            for _ in range(WARM):
+                ingest_frames(frames, out, K)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                ingest_frames(frames, out, K)
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / args.launches
+            b = case_bytes(cases[name])
+            print(f"{name}: {us:.1f} us per call (events, table upload included), {b / 1e6:.1f} MB -> {b / us / 1e6:.2f} TB/s", flush=True)
 
 
 if __name__ == "__main__":

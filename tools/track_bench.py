@@ -7,7 +7,7 @@ clock starts (the upload of a user's numpy frames is not part of the tick).  Gra
 each; the table gives the median and the spread (max - min) / median.
 
   python tools/track_bench.py [--streams 1,8,32] [--frames 30] [--repeats 3] [--out profiles/r08_track_bench.md]
-  python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p        (graphs only, the variants alternated)
+  python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p[,nv12-1080p-lens]   (graphs only, the variants alternated)
   python tools/track_bench.py --streams 32 --emit nv12 [--emit-host]            (graphs only: no sinks / device sinks / pinned host sinks
                                                                                  of the working-resolution picture, alternated)
   python tools/track_bench.py --streams 32 --health off,lax,verify10 [--lens 10000]   (graphs only: no HealthPolicy / every soft
@@ -51,9 +51,14 @@ def native_frames(frames, K, mode):
     """The frames a tracker with frame_size is fed -> (Frame list, canvas).
     same: the device-resident 480x640 RGB frames with their K, through the ingest launch (the computation of the plain path).
     nv12-1080p: host-resident 1080x1920 NV12 frames (numpy) into a 540x960 canvas: each synthetic
-    frame enlarged 2.25x (nearest) into the left 1440 columns of a grey full-HD picture, BT.601; intrinsics: predict.py's pseudo K."""
+    frame enlarged 2.25x (nearest) into the left 1440 columns of a grey full-HD picture, BT.601; intrinsics: predict.py's pseudo K.
+    nv12-1080p-lens: the same frames as pictures of a camera with f = 1000 and the lens brown (-0.35, 0.12, 0.001, -0.0005, -0.02),
+    undistorted by the ingest launch (one mesh for all streams, built and uploaded in the first tick)."""
     import torch
-    from gen6d_amd.ingest import Frame
+    from gen6d_amd.ingest import Frame, Lens
+    cam = {}
+    if mode == "nv12-1080p-lens":
+        cam = dict(K=np.array([[1000.0, 0, 959.5], [0, 1000.0, 539.5], [0, 0, 1]]), lens=Lens("brown", (-0.35, 0.12, 0.001, -0.0005, -0.02)))
     if mode == "same":
         return [Frame(f, K=K) for f in frames], tuple(frames[0].shape[:2])
     out = []
@@ -65,7 +70,7 @@ def native_frames(frames, K, mode):
         c = g[::2, ::2]
         buf[1080:, 0:1440:2] = ((-38 * c[..., 0] - 74 * c[..., 1] + 112 * c[..., 2] + 128) >> 8) + 128
         buf[1080:, 1:1440:2] = ((112 * c[..., 0] - 94 * c[..., 1] - 18 * c[..., 2] + 128) >> 8) + 128
-        out.append(Frame(buf, "nv12"))
+        out.append(Frame(buf, "nv12", **cam))
     return out, (540, 960)
 
 
@@ -174,7 +179,7 @@ def main():
     ap.add_argument("--profile", type=int, default=0, help="one graphs run of this many streams (for a rocprofv3 trace)")
     ap.add_argument("--stats-csv", default=None)
     ap.add_argument("--ticks", type=int, default=0)
-    ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p: graphs runs of these frame "
+    ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p / nv12-1080p-lens: graphs runs of these frame "
                     "sources, alternated (with --profile: the one source of the profiled run)")
     ap.add_argument("--batch", type=int, default=0, help="--profile: slots per lane (default min(streams, 8))")
     ap.add_argument("--emit", default=None, choices=["nv12", "rgb24"], help="graphs runs without sinks and with one device sink of this "
@@ -228,7 +233,8 @@ def main():
         sweep(est, frames, K, args, configs, [(m, {"ingest": m}) for m in args.ingest.split(",")], "frames",
               "Tracked frames/s by frame source (tools/track_bench.py --ingest)",
               graphs + each + "source, alternated.  none: plain 480x640 device frames (tracker without frame_size); same: the same frames "
-              "through the ingest launch; nv12-1080p: host-resident 1080x1920 NV12 frames into a 540x960 canvas, upload included.")
+              "through the ingest launch; nv12-1080p: host-resident 1080x1920 NV12 frames into a 540x960 canvas, upload included; "
+              "nv12-1080p-lens: those frames with a strong brown lens, undistorted in the same launch.")
     else:
         sweep(est, frames, K, args, configs, [("graphs", {}), ("eager", {"graphs": False})], "mode", "Tracked frames/s (tools/track_bench.py)",
               f"Synthetic database and weights, 480x640 frames, {args.frames} frames per stream, the first two excluded (first frames "
