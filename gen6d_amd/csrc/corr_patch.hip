@@ -12,6 +12,7 @@
 //            [32 co][36] double-buffered; 16 MFMAs (v_mfma_f32_32x32x2_f32) per wave per kx
 //   split  = units are split across gridDim.z; partial tiles go to a workspace, the last block of a tile adds them (g6d_common.h).
 #include "g6d_common.h"
+#include "seg_table.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -452,6 +453,17 @@ int corr_run(const float* in_base, float* out_base, CorrArgs& sa, int Cin, const
   return g6d_check_launch("corr2d_patch");
 }
 
+// The map list of a multi-map launch from its validated table (seg_table.h)
+CorrArgs corr_segments(const G6dSegTable& t) {
+  CorrArgs sa = {};
+  sa.nseg = t.nseg;
+  for (int k = 0; k < t.nseg; ++k) {
+    const G6dSeg& g = t.seg[k];
+    sa.seg[k] = CorrSeg{0, g.H, g.W, 0, g.in_off, g.full_off, g.ld_in, g.ld_full, g.N, 0};
+  }
+  return sa;
+}
+
 }  // namespace
 
 // Stride-1 2-D cross-correlation without bias for Cout <= 32 (the detector's reference-as-filter correlation).
@@ -480,26 +492,10 @@ extern "C" int g6d_corr2d_patch_multi(const G6dCorrSeg* segs, int nseg, int Cin,
       kw > 31 || !g6d_aligned16(wgt) || (long long)Cout * kh * kw * Cin >= (1ll << 30) || math_mode < 0 || math_mode > 2) {
     g6d_set_error("corr2d_patch_multi: bad args (1..4 maps, Cout <= 32, odd kernel <= 31, Cin % 4 == 0)"); return G6D_EINVAL;
   }
-  const float* in0 = segs[0].in; float* out0 = segs[0].out;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    if (!g.in || !g.out || g.H <= 0 || g.W <= 0 || g.N <= 0 || (g.ld_in & 3) || g.ld_in < Cin || g.ld_out < Cout || !g6d_aligned16(g.in)) {
-      g6d_set_error("corr2d_patch_multi: bad map"); return G6D_EINVAL;
-    }
-    if (g.in < in0) in0 = g.in;
-    if (g.out < out0) out0 = g.out;
-  }
-  CorrArgs sa = {};
-  sa.nseg = nseg;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    const long long io = g.in - in0, oo = g.out - out0;
-    if (io + (long long)g.N * g.H * g.W * g.ld_in >= (1ll << 30) || oo + (long long)g.N * g.H * g.W * g.ld_out >= (1ll << 31)) {
-      g6d_set_error("corr2d_patch_multi: maps must lie within 2^30 floats of each other (allocate them from one buffer)"); return G6D_EINVAL;
-    }
-    sa.seg[k] = CorrSeg{0, g.H, g.W, 0, (int)io, (int)oo, g.ld_in, g.ld_out, g.N, 0};
-  }
-  return corr_run(in0, out0, sa, Cin, wgt, Cout, kh, kw, workspace, workspace_bytes, math_mode, reinterpret_cast<hipStream_t>(stream_));
+  G6dSegTable t;
+  if (int rc = g6d_seg_table("corr2d_patch_multi", "map", "", segs, nseg, Cin, Cout, G6D_REACH_CORR_PATCH, t)) return rc;
+  CorrArgs sa = corr_segments(t);
+  return corr_run(t.in, t.full, sa, Cin, wgt, Cout, kh, kw, workspace, workspace_bytes, math_mode, reinterpret_cast<hipStream_t>(stream_));
 }
 
 // g6d_corr2d_patch_multi with 16-bit matrix-core operands on its own kernel (corr16_patch_kernel): w16 = the filters rounded to the
@@ -511,24 +507,8 @@ extern "C" int g6d_corr2d_patch16_multi(const G6dCorrSeg* segs, int nseg, int Ci
       kw > 15 || !g6d_aligned16(w16) || (math_mode != 1 && math_mode != 2)) {
     g6d_set_error("corr2d_patch16_multi: bad args (1..4 maps, Cin % 32 == 0, Cout <= 32, odd kernel <= 15, math_mode 1 or 2)"); return G6D_EINVAL;
   }
-  const float* in0 = segs[0].in; float* out0 = segs[0].out;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    if (!g.in || !g.out || g.H <= 0 || g.W <= 0 || g.N <= 0 || (g.ld_in & 3) || g.ld_in < Cin || g.ld_out < Cout || !g6d_aligned16(g.in)) {
-      g6d_set_error("corr2d_patch16_multi: bad map"); return G6D_EINVAL;
-    }
-    if (g.in < in0) in0 = g.in;
-    if (g.out < out0) out0 = g.out;
-  }
-  CorrArgs sa = {};
-  sa.nseg = nseg;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    const long long io = g.in - in0, oo = g.out - out0;
-    if (io + (long long)g.N * g.H * g.W * g.ld_in >= (1ll << 30) || oo + (long long)g.N * g.H * g.W * g.ld_out >= (1ll << 31)) {
-      g6d_set_error("corr2d_patch16_multi: maps must lie within 2^30 floats of each other (allocate them from one buffer)"); return G6D_EINVAL;
-    }
-    sa.seg[k] = CorrSeg{0, g.H, g.W, 0, (int)io, (int)oo, g.ld_in, g.ld_out, g.N, 0};
-  }
-  return corr_run(in0, out0, sa, Cin, nullptr, Cout, kh, kw, workspace, workspace_bytes, math_mode, reinterpret_cast<hipStream_t>(stream_), w16);
+  G6dSegTable t;
+  if (int rc = g6d_seg_table("corr2d_patch16_multi", "map", "", segs, nseg, Cin, Cout, G6D_REACH_CORR_PATCH, t)) return rc;
+  CorrArgs sa = corr_segments(t);
+  return corr_run(t.in, t.full, sa, Cin, nullptr, Cout, kh, kw, workspace, workspace_bytes, math_mode, reinterpret_cast<hipStream_t>(stream_), w16);
 }

@@ -39,6 +39,7 @@
 //             rows 2hh, 2hh+1), then bias / ReLU / stores / 2x2 max-pool / statistics per lane.  Chunk split with the in-kernel
 //             hand-off of g6d_common.h as in the other kernels.
 #include "g6d_common.h"
+#include "seg_table.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <algorithm>
@@ -795,6 +796,15 @@ int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_byt
   return w43_launch_t<0, 1, 4>(a, blocks, stream);
 }
 
+// The segment list and bases of a multi-map launch from its validated table (seg_table.h)
+void w43_segments(W43Args& a, const G6dSegTable& t) {
+  a.in = t.in; a.out_full = t.full; a.out_pool = t.pool; a.nseg = t.nseg;
+  for (int k = 0; k < t.nseg; ++k) {
+    const G6dSeg& g = t.seg[k];
+    a.seg[k] = W43Seg{0, g.N, g.H, g.W, 0, 0, g.in_off, g.full_off, g.pool_off, g.ld_in, g.ld_full, g.ld_pool};
+  }
+}
+
 }  // namespace
 
 #ifdef W43_TIMING
@@ -814,32 +824,11 @@ extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Ci
   if (!segs || nseg < 1 || nseg > W43_MAX_SEG || !U43 || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U43)) {
     g6d_set_error("wino43_conv3x3_multi: bad args (1..4 segments, Cin % 8 == 0, Cout % 64 == 0)"); return G6D_EINVAL;
   }
+  G6dSegTable t;
+  if (int rc = g6d_seg_table("wino43_conv3x3_multi", "segment", G6D_SAME_KINDS, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
   W43Args a = {};
-  const bool want_full = segs[0].out_full != nullptr, want_pool = segs[0].out_pool != nullptr;
-  if (!want_full && !want_pool) { g6d_set_error("wino43_conv3x3_multi: no output"); return G6D_EINVAL; }
-  const float* in0 = segs[0].in; float* f0 = segs[0].out_full; float* p0 = segs[0].out_pool;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dWinoSeg& g = segs[k];
-    if (!g.in || (g.out_full != nullptr) != want_full || (g.out_pool != nullptr) != want_pool || g.N <= 0 || g.H <= 0 || g.W <= 0 ||
-        (g.ld_in & 3) || g.ld_in < Cin || (want_full && g.ld_full < Cout) || (want_pool && (g.ld_pool < Cout || g.H < 2 || g.W < 2)) ||
-        !g6d_aligned16(g.in)) {
-      g6d_set_error("wino43_conv3x3_multi: bad segment (all segments give the same kinds of output)"); return G6D_EINVAL;
-    }
-    if (g.in < in0) in0 = g.in;
-    if (want_full && g.out_full < f0) f0 = g.out_full;
-    if (want_pool && g.out_pool < p0) p0 = g.out_pool;
-  }
-  a.in = in0; a.U = U43; a.bias = bias; a.out_full = f0; a.out_pool = p0;
-  a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1; a.nseg = nseg;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dWinoSeg& g = segs[k];
-    const long long io = g.in - in0, fo = want_full ? g.out_full - f0 : 0, po = want_pool ? g.out_pool - p0 : 0;
-    if (io + (long long)g.N * g.H * g.W * g.ld_in >= (1ll << 29) || fo + (long long)g.N * g.H * g.W * g.ld_full >= (1ll << 31) ||
-        po + (long long)g.N * g.H * g.W * g.ld_pool >= (1ll << 31)) {
-      g6d_set_error("wino43_conv3x3_multi: segments must lie within 2^29 floats of each other (allocate them from one buffer)"); return G6D_EINVAL;
-    }
-    a.seg[k] = W43Seg{0, g.N, g.H, g.W, 0, 0, (int)io, (int)fo, (int)po, g.ld_in, g.ld_full, g.ld_pool};
-  }
+  a.U = U43; a.bias = bias; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1;
+  w43_segments(a, t);
   return w43_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -853,27 +842,13 @@ extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin
   if (!segs || nseg < 1 || nseg > W43_MAX_SEG || !U43 || (kblocks != 5 && kblocks != 3) || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 31) || !g6d_aligned16(U43)) {
     g6d_set_error("corr2d_wino43_multi: bad args (1..4 map sizes, 15x15 = 5 blocks or 9x9 = 3 blocks, Cin % 8 == 0, Cout % 32 == 0)"); return G6D_EINVAL;
   }
+  for (int k = 1; k < nseg; ++k)
+    if (segs[k].ld_in != segs[0].ld_in) return g6d_bad_seg("corr2d_wino43_multi", "map", G6D_SHARED_LD_IN);
+  G6dSegTable t;
+  if (int rc = g6d_seg_table("corr2d_wino43_multi", "map", G6D_SHARED_LD_IN, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
   W43Args a = {};
-  const float* in0 = segs[0].in; float* f0 = segs[0].out;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    if (!g.in || !g.out || g.N <= 0 || g.H <= 0 || g.W <= 0 || (g.ld_in & 3) || g.ld_in < Cin || g.ld_in != segs[0].ld_in || g.ld_out < Cout ||
-        !g6d_aligned16(g.in)) {
-      g6d_set_error("corr2d_wino43_multi: bad map (all maps share ld_in)"); return G6D_EINVAL;
-    }
-    if (g.in < in0) in0 = g.in;
-    if (g.out < f0) f0 = g.out;
-  }
-  a.in = in0; a.U = U43; a.bias = nullptr; a.out_full = f0; a.out_pool = nullptr;
-  a.Cin = Cin; a.Cout = Cout; a.relu = 0; a.D = 1; a.nseg = nseg;
-  for (int k = 0; k < nseg; ++k) {
-    const G6dCorrSeg& g = segs[k];
-    const long long io = g.in - in0, fo = g.out - f0;
-    if (io + (long long)g.N * g.H * g.W * g.ld_in >= (1ll << 29) || fo + (long long)g.N * g.H * g.W * g.ld_out >= (1ll << 31)) {
-      g6d_set_error("corr2d_wino43_multi: maps must lie within 2^29 floats of each other (allocate them from one buffer)"); return G6D_EINVAL;
-    }
-    a.seg[k] = W43Seg{0, g.N, g.H, g.W, 0, 0, (int)io, (int)fo, 0, g.ld_in, g.ld_out, 0};
-  }
+  a.U = U43; a.bias = nullptr; a.Cin = Cin; a.Cout = Cout; a.relu = 0; a.D = 1;
+  w43_segments(a, t);
   return w43_run(a, 0, kblocks * kblocks, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 

@@ -50,14 +50,23 @@ PROFILE = None
 PROFILE_HBM = None
 
 
-def _timed_hbm(name, nbytes, launch):
-    if PROFILE_HBM is None:
+_T16 = {1: torch.bfloat16, 2: torch.float16, 3: torch.float16}       # math / filter mode -> the 16-bit operand type
+
+
+def _timed(on, launch, book):
+    """launch() — with profiling `on`, between two HIP events recorded on the launch stream, which book(e0, e1) then files in PROFILE /
+    PROFILE_HBM.  Labels and byte counts are built inside `book`, so a launch that is not profiled pays for none of them."""
+    if not on:
         return launch()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     launch()
     e1.record()
-    PROFILE_HBM.setdefault(name, []).append((float(nbytes), e0, e1))
+    book(e0, e1)
+
+
+def _timed_hbm(name, nbytes, launch):
+    _timed(PROFILE_HBM is not None, launch, lambda e0, e1: PROFILE_HBM.setdefault(name, []).append((float(nbytes), e0, e1)))
 
 
 def _stream():
@@ -179,7 +188,7 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         cache = w_wino.__dict__.setdefault("_g6d_u16", {})
         if MATH_MODE not in cache:
             from .network.backbone import winograd_filters16_taps
-            cache[MATH_MODE] = winograd_filters16_taps(w, kd, {1: torch.bfloat16, 2: torch.float16}[MATH_MODE])
+            cache[MATH_MODE] = winograd_filters16_taps(w, kd, _T16[MATH_MODE])
         u16 = cache[MATH_MODE]
     ws = workspace(x.device)
     d = _lib.G6dConv(
@@ -205,11 +214,8 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
             cnt = new_counter(x.device)
             d.fin_scale, d.fin_shift, d.fin_counter = fin[0].data_ptr(), fin[1].data_ptr(), cnt.data_ptr()
             d.fin_count, d.fin_eps, d.fin_groups = float(finalize), float(eps), G
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm")
-        e1.record()
+
+    def book(e0, e1):
         fam = _lib.load().g6d_conv_plan(C.byref(d))
         fl = 2.0 * N * Do * Ho * Wo * Cout * kd * kh * kw * Cin
         if fam == 4:          # narrow-output layer on the vector ALUs: bound by reading its input, booked with the HBM-bound kernels
@@ -221,8 +227,7 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
                         f"{' mul' if mul is not None else ''}{' aff' if in_scale is not None else ''}{' stats' if stats is not None else ''}",
                         # algorithmic bytes: every operand once (input images, multiplier maps, filters, output)
                         4.0 * ((in_mod or N) * Di * Hi * Wi * Cin + (mul.numel() if mul is not None else 0) + w.numel() + N * Do * Ho * Wo * Cout), fl))
-    else:
-        _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm")
+    _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm"), book)
     if finalize is not None:
         return fin if fin is not None else stats_finalize(stats, finalize, eps)
     return out
@@ -236,15 +241,11 @@ def corr2d_patch(x, w, out, k):
     if N * D != 1 or (Ho, Wo) != (H, W) or tuple(w.shape) != (Cout, k * k, Cin) or not w.is_contiguous():
         raise ValueError("corr2d_patch: shape mismatch")
     ws = workspace(x.device)
-    flops = 2.0 * H * W * Cout * k * k * Cin
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().g6d_corr2d_patch(_ptr(x), H, W, Cin, ld_in, _ptr(w), Cout, k, k, _ptr(out), ld_out, _ptr(ws),
-                                           ws.numel() * 4, int(MATH_MODE), _stream()), "g6d_corr2d_patch")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((flops, e0, e1, f"corr2d_patch in={H}x{W}x{Cin} out={Cout} k={k}x{k}", 4.0 * (H * W * (Cin + Cout) + w.numel())))
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_corr2d_patch(_ptr(x), H, W, Cin, ld_in, _ptr(w), Cout, k, k, _ptr(out), ld_out, _ptr(ws),
+                                                          ws.numel() * 4, int(MATH_MODE), _stream()), "g6d_corr2d_patch"),
+           lambda e0, e1: PROFILE.append((2.0 * H * W * Cout * k * k * Cin, e0, e1, f"corr2d_patch in={H}x{W}x{Cin} out={Cout} k={k}x{k}",
+                                          4.0 * (H * W * (Cin + Cout) + w.numel()))))
     return out
 
 
@@ -260,6 +261,27 @@ def corr_filters16(w, k, dtype):
     return torch.cat([out.reshape(-1), torch.zeros(512, dtype=dtype, device=w.device)]).contiguous()
 
 
+def _corr_table(name, what, xs, outs, Cin, Cout, k, strided_single=False):
+    """The G6dCorrSeg table of a correlation launch over the maps xs[i] -> outs[i] ([N,1,H_i,W_i,C] views; dense, except that a single
+    map may be strided where `strided_single`) -> (table, direct-form FLOPs, size string)."""
+    segs = (_lib.G6dCorrSeg * len(xs))()
+    flops, sizes = 0.0, []
+    for i, (x, o) in enumerate(zip(xs, outs)):
+        N, D, H, W, Cx, ld_in = _cl5(x, f"{what}.x")
+        No, _, Ho, Wo, Co, ld_out = _cl5(o, f"{what}.out")
+        dense = x.is_contiguous() and o.is_contiguous()
+        if D != 1 or No != N or (Ho, Wo) != (H, W) or Cx != Cin or Co != Cout or not (dense or (strided_single and N == 1)):
+            raise ValueError(f"{name}: shape mismatch ({'batched ' if strided_single else ''}maps must be dense)")
+        segs[i] = _lib.G6dCorrSeg(in_=x.data_ptr(), out=o.data_ptr(), H=H, W=W, ld_in=ld_in, ld_out=ld_out, N=N)
+        flops += 2.0 * N * H * W * Cout * k * k * Cin
+        sizes.append(f"{N}x{H}x{W}" if N > 1 else f"{H}x{W}")
+    return segs, flops, "+".join(sizes)
+
+
+def _numel(*lists):
+    return sum(t.numel() for ts in lists for t in ts)
+
+
 def corr2d_patch_multi(xs, w, outs, k):
     """corr2d_patch for several map sizes in ONE launch (the scales of the detector's pyramid against the same reference filters):
     xs[i] [N,1,H_i,W_i,Cin] and outs[i] [N,1,H_i,W_i,Cout] dense tensors (N = queries of the batch at that scale), each list cut
@@ -268,40 +290,23 @@ def corr2d_patch_multi(xs, w, outs, k):
     if not 1 <= len(xs) <= 4 or len(outs) != len(xs):
         raise ValueError("corr2d_patch_multi: 1..4 maps")
     Cout, _, Cin = w.shape
-    segs = (_lib.G6dCorrSeg * len(xs))()
-    flops, sizes = 0.0, []
-    for i, (x, o) in enumerate(zip(xs, outs)):
-        N, D, H, W, Cx, ld_in = _cl5(x, "corr2d_multi.x")
-        No, _, Ho, Wo, Co, ld_out = _cl5(o, "corr2d_multi.out")
-        if D != 1 or No != N or (Ho, Wo) != (H, W) or Cx != Cin or Co != Cout or (N > 1 and not (x.is_contiguous() and o.is_contiguous())):
-            raise ValueError("corr2d_patch_multi: shape mismatch (batched maps must be dense)")
-        segs[i] = _lib.G6dCorrSeg(in_=x.data_ptr(), out=o.data_ptr(), H=H, W=W, ld_in=ld_in, ld_out=ld_out, N=N)
-        flops += 2.0 * N * H * W * Cout * k * k * Cin
-        sizes.append(f"{N}x{H}x{W}" if N > 1 else f"{H}x{W}")
+    segs, flops, sizes = _corr_table("corr2d_patch_multi", "corr2d_multi", xs, outs, Cin, Cout, k, strided_single=True)
     if tuple(w.shape) != (Cout, k * k, Cin) or not w.is_contiguous():
         raise ValueError("corr2d_patch_multi: filter shape mismatch")
     ws = workspace(w.device)
     # reduced-precision mode: the 16-bit kernel with all kw weight tiles of a unit staged at once (g6d_corr2d_patch16_multi); its
     # host-rounded, unit-major filters are built once per (filter tensor, type) and kept on the fp32 tensor
-    w16 = None
+    wk, sfx = w, ""
     if MATH_MODE and Cin % 32 == 0 and k <= 15:
         cache = w.__dict__.setdefault("_g6d_c16", {})
         if MATH_MODE not in cache:
-            cache[MATH_MODE] = corr_filters16(w, k, {1: torch.bfloat16, 2: torch.float16}[MATH_MODE])
-        w16 = cache[MATH_MODE]
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if w16 is not None:
-        _lib.check(_lib.load().g6d_corr2d_patch16_multi(segs, len(xs), Cin, _ptr(w16), Cout, k, k, _ptr(ws), ws.numel() * 4, int(MATH_MODE),
-                                                       _stream()), "g6d_corr2d_patch16_multi")
-    else:
-        _lib.check(_lib.load().g6d_corr2d_patch_multi(segs, len(xs), Cin, _ptr(w), Cout, k, k, _ptr(ws), ws.numel() * 4, int(MATH_MODE),
-                                                     _stream()), "g6d_corr2d_patch_multi")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((flops, e0, e1, f"corr2d_patch{'16' if w16 is not None else ''} multi in={'+'.join(sizes)}x{Cin} out={Cout} k={k}x{k}",
-                        4.0 * (sum(x.numel() for x in xs) + sum(o.numel() for o in outs) + w.numel())))
+            cache[MATH_MODE] = corr_filters16(w, k, _T16[MATH_MODE])
+        wk, sfx = cache[MATH_MODE], "16"
+    entry = f"g6d_corr2d_patch{sfx}_multi"
+    _timed(PROFILE is not None,
+           lambda: _lib.check(getattr(_lib.load(), entry)(segs, len(xs), Cin, _ptr(wk), Cout, k, k, _ptr(ws), ws.numel() * 4, int(MATH_MODE), _stream()), entry),
+           lambda e0, e1: PROFILE.append((flops, e0, e1, f"corr2d_patch{sfx} multi in={sizes}x{Cin} out={Cout} k={k}x{k}",
+                                          4.0 * (_numel(xs, outs) + w.numel()))))
     return outs
 
 
@@ -314,28 +319,15 @@ def corr2d_wino_multi(xs, U, outs, kblocks=5):
     Cin, Cout = xs[0].shape[4], U.shape[2]
     if tuple(U.shape) != (kblocks * kblocks * (Cin // 8), 16, Cout, 8) or not U.is_contiguous():
         raise ValueError(f"corr2d_wino_multi: U must be contiguous {(kblocks * kblocks * (Cin // 8), 16, Cout, 8)}")
-    segs = (_lib.G6dCorrSeg * len(xs))()
-    flops, sizes = 0.0, []
     k = 3 * kblocks
-    for i, (x, o) in enumerate(zip(xs, outs)):
-        N, D, H, W, Cx, ld_in = _cl5(x, "corr2d_wino.x")
-        No, _, Ho, Wo, Co, ld_out = _cl5(o, "corr2d_wino.out")
-        if D != 1 or No != N or (Ho, Wo) != (H, W) or Cx != Cin or Co != Cout or not (x.is_contiguous() and o.is_contiguous()):
-            raise ValueError("corr2d_wino_multi: shape mismatch (maps must be dense)")
-        segs[i] = _lib.G6dCorrSeg(in_=x.data_ptr(), out=o.data_ptr(), H=H, W=W, ld_in=ld_in, ld_out=ld_out, N=N)
-        flops += 2.0 * N * H * W * Cout * k * k * Cin
-        sizes.append(f"{N}x{H}x{W}" if N > 1 else f"{H}x{W}")
+    segs, flops, sizes = _corr_table("corr2d_wino_multi", "corr2d_wino", xs, outs, Cin, Cout, k)
     ws = workspace(U.device)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().g6d_corr2d_wino_multi(segs, len(xs), Cin, _ptr(U), Cout, int(kblocks), _ptr(ws), ws.numel() * 4, _stream()),
-               "g6d_corr2d_wino_multi")
-    if PROFILE is not None:
-        e1.record()
-        # FLOPs executed in the Winograd domain = direct form / 2.25 (booked in the Winograd family)
-        PROFILE.append((flops / 2.25, e0, e1, f"wino3x3 corr multi in={'+'.join(sizes)}x{Cin} out={Cout} k={k}x{k} ({kblocks}x{kblocks} blocks of 3x3)",
-                        4.0 * (sum(x.numel() for x in xs) + sum(o.numel() for o in outs) + U.numel())))
+    # FLOPs executed in the Winograd domain = direct form / 2.25 (booked in the Winograd family)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_corr2d_wino_multi(segs, len(xs), Cin, _ptr(U), Cout, int(kblocks), _ptr(ws), ws.numel() * 4, _stream()),
+                              "g6d_corr2d_wino_multi"),
+           lambda e0, e1: PROFILE.append((flops / 2.25, e0, e1, f"wino3x3 corr multi in={sizes}x{Cin} out={Cout} k={k}x{k} ({kblocks}x{kblocks} blocks of 3x3)",
+                                          4.0 * (_numel(xs, outs) + U.numel()))))
     return outs
 
 
@@ -489,18 +481,14 @@ def wino_conv3x3(x, U, bias, relu=True, full=True, pool=False):
         raise ValueError(f"wino_conv3x3: U must be contiguous {(Cin // 8, 16, Cout, 8)}")
     y = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x.device) if full else None
     yp = torch.empty((N, H // 2, W // 2, Cout), dtype=torch.float32, device=x.device) if pool else None
-    flops = 2.0 * N * H * W * Cout * 9 * Cin
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     ws = workspace(x.device)
-    _lib.check(_lib.load().g6d_wino_conv3x3(_ptr(x), N, H, W, Cin, ld_in, _ptr(U), _ptr(bias), Cout, int(relu), _ptr(y), Cout,
-                                           _ptr(yp), Cout, _ptr(ws), ws.numel() * 4, _stream()), "g6d_wino_conv3x3")
-    if PROFILE is not None:
-        e1.record()
-        # direct-form FLOPs / 2.25 = multiplications actually executed in the Winograd domain (what the matrix cores do)
-        PROFILE.append((flops / 2.25, e0, e1, f"wino3x3 N={N} in={H}x{W}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}",
-                        4.0 * (x.numel() + U.numel() + (y.numel() if full else 0) + (yp.numel() if pool else 0))))
+    # direct-form FLOPs / 2.25 = multiplications actually executed in the Winograd domain (what the matrix cores do)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_wino_conv3x3(_ptr(x), N, H, W, Cin, ld_in, _ptr(U), _ptr(bias), Cout, int(relu), _ptr(y), Cout,
+                                                          _ptr(yp), Cout, _ptr(ws), ws.numel() * 4, _stream()), "g6d_wino_conv3x3"),
+           lambda e0, e1: PROFILE.append((2.0 * N * H * W * Cout * 9 * Cin / 2.25, e0, e1,
+                                          f"wino3x3 N={N} in={H}x{W}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}",
+                                          4.0 * (x.numel() + U.numel() + (y.numel() if full else 0) + (yp.numel() if pool else 0)))))
     return y, yp
 
 
@@ -516,19 +504,16 @@ def alloc_like_segments(shapes, device):
     return [buf[st:st + n].view(sh) for st, n, sh in zip(starts, sizes, shapes)]
 
 
-def wino_conv3x3_multi(xs, U, bias, relu=True, full=True, pool=False):
-    """One trunk layer over several map sizes in ONE launch (the scales of the detector's image pyramid): xs = dense
-    channels-last [N_i,H_i,W_i,Cin] tensors cut from one buffer (alloc_like_segments / the outputs of the previous layer).
-    Returns (list of y_i or None, list of maxpool2x2(y_i) or None)."""
-    _need_gpu(U, bias, *xs)
+def _wino_table(name, xs, Cout, full, pool):
+    """The G6dWinoSeg table of a Winograd trunk launch over the segments xs ([N_i,H_i,W_i,Cin], dense) with its outputs allocated, one
+    buffer per kind -> (table, Cin, ys or None, yps or None, direct-form FLOPs, describe); describe() -> (the label's "in=... out=..."
+    part, activation floats moved), for the profile."""
     if not 1 <= len(xs) <= 4:
-        raise ValueError("wino_conv3x3_multi: 1..4 segments")
-    Cin, Cout = xs[0].shape[3], U.shape[2]
-    if tuple(U.shape) != (Cin // 8, 16, Cout, 8) or not U.is_contiguous() or bias.numel() != Cout:
-        raise ValueError(f"wino_conv3x3_multi: U must be contiguous {(Cin // 8, 16, Cout, 8)}")
+        raise ValueError(f"{name}: 1..4 segments")
+    Cin = xs[0].shape[3]
     for x in xs:
         if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[3] != Cin:
-            raise ValueError("wino_conv3x3_multi: segments must be contiguous float32 [N,H,W,Cin]")
+            raise ValueError(f"{name}: segments must be contiguous float32 [N,H,W,Cin]")
     dev = xs[0].device
     ys = alloc_like_segments([(x.shape[0], x.shape[1], x.shape[2], Cout) for x in xs], dev) if full else None
     yps = alloc_like_segments([(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, Cout) for x in xs], dev) if pool else None
@@ -539,17 +524,36 @@ def wino_conv3x3_multi(xs, U, bias, relu=True, full=True, pool=False):
         segs[i] = _lib.G6dWinoSeg(in_=x.data_ptr(), out_full=ys[i].data_ptr() if full else None,
                                   out_pool=yps[i].data_ptr() if pool else None, N=N, H=H, W=W, ld_in=Cin, ld_full=Cout, ld_pool=Cout)
         flops += 2.0 * N * H * W * Cout * 9 * Cin
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(dev)
-    _lib.check(_lib.load().g6d_wino_conv3x3_multi(segs, len(xs), Cin, _ptr(U), _ptr(bias), Cout, int(relu), _ptr(ws), ws.numel() * 4,
-                                                 _stream()), "g6d_wino_conv3x3_multi")
-    if PROFILE is not None:
-        e1.record()
+
+    def describe():
         sizes = "+".join(f"{x.shape[0]}x{x.shape[1]}x{x.shape[2]}" for x in xs)
-        PROFILE.append((flops / 2.25, e0, e1, f"wino3x3 multi in={sizes}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}",
-                        4.0 * (sum(x.numel() for x in xs) + U.numel() + (sum(t.numel() for t in ys) if full else 0) + (sum(t.numel() for t in yps) if pool else 0))))
+        return f"in={sizes}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}", _numel(xs, ys or (), yps or ())
+    return segs, Cin, ys, yps, flops, describe
+
+
+def _wino_book(flops, kind, describe, filter_floats, *direct):
+    """Profile entry of a Winograd trunk launch: `flops` executed in the transform domain, label "wino3x3 <kind>multi ...", bytes of every
+    operand once, then the direct-form FLOPs where the family books them."""
+    def book(e0, e1):
+        label, act = describe()
+        PROFILE.append((flops, e0, e1, f"wino3x3 {kind}multi {label}", 4.0 * (act + filter_floats)) + direct)
+    return book
+
+
+def wino_conv3x3_multi(xs, U, bias, relu=True, full=True, pool=False):
+    """One trunk layer over several map sizes in ONE launch (the scales of the detector's image pyramid): xs = dense
+    channels-last [N_i,H_i,W_i,Cin] tensors cut from one buffer (alloc_like_segments / the outputs of the previous layer).
+    Returns (list of y_i or None, list of maxpool2x2(y_i) or None)."""
+    _need_gpu(U, bias, *xs)
+    Cout = U.shape[2]
+    segs, Cin, ys, yps, flops, describe = _wino_table("wino_conv3x3_multi", xs, Cout, full, pool)
+    if tuple(U.shape) != (Cin // 8, 16, Cout, 8) or not U.is_contiguous() or bias.numel() != Cout:
+        raise ValueError(f"wino_conv3x3_multi: U must be contiguous {(Cin // 8, 16, Cout, 8)}")
+    ws = workspace(xs[0].device)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_wino_conv3x3_multi(segs, len(xs), Cin, _ptr(U), _ptr(bias), Cout, int(relu), _ptr(ws), ws.numel() * 4,
+                                                                _stream()), "g6d_wino_conv3x3_multi"),
+           _wino_book(flops / 2.25, "", describe, U.numel()))
     return ys, yps
 
 
@@ -564,37 +568,16 @@ def wino43_conv3x3_multi(xs, U43, bias, relu=True, full=True, pool=False):
     (1.78x fewer than F(2x2,3x3)) at ~5x the fp32 error — for the layers whose parity budget has the room (the detector's pyramid).
     U43 = backbone.winograd43_filters(w) (shape w43_shape(Cin/8, Cout)), Cout % 64 == 0."""
     _need_gpu(U43, bias, *xs)
-    if not 1 <= len(xs) <= 4:
-        raise ValueError("wino43_conv3x3_multi: 1..4 segments")
-    Cin, Cout = xs[0].shape[3], bias.numel()
+    Cout = bias.numel()
+    segs, Cin, ys, yps, flops, describe = _wino_table("wino43_conv3x3_multi", xs, Cout, full, pool)
     if tuple(U43.shape) != w43_shape(Cin // 8, Cout) or not U43.is_contiguous():
         raise ValueError(f"wino43_conv3x3_multi: U43 must be contiguous {w43_shape(Cin // 8, Cout)}")
-    for x in xs:
-        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[3] != Cin:
-            raise ValueError("wino43_conv3x3_multi: segments must be contiguous float32 [N,H,W,Cin]")
-    dev = xs[0].device
-    ys = alloc_like_segments([(x.shape[0], x.shape[1], x.shape[2], Cout) for x in xs], dev) if full else None
-    yps = alloc_like_segments([(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, Cout) for x in xs], dev) if pool else None
-    segs = (_lib.G6dWinoSeg * len(xs))()
-    flops = 0.0
-    for i, x in enumerate(xs):
-        N, H, W, _ = x.shape
-        segs[i] = _lib.G6dWinoSeg(in_=x.data_ptr(), out_full=ys[i].data_ptr() if full else None,
-                                  out_pool=yps[i].data_ptr() if pool else None, N=N, H=H, W=W, ld_in=Cin, ld_full=Cout, ld_pool=Cout)
-        flops += 2.0 * N * H * W * Cout * 9 * Cin
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(dev)
-    _lib.check(_lib.load().g6d_wino43_conv3x3_multi(segs, len(xs), Cin, _ptr(U43), _ptr(bias), Cout, int(relu), _ptr(ws), ws.numel() * 4,
-                                                   _stream()), "g6d_wino43_conv3x3_multi")
-    if PROFILE is not None:
-        e1.record()
-        sizes = "+".join(f"{x.shape[0]}x{x.shape[1]}x{x.shape[2]}" for x in xs)
-        # direct-form FLOPs / 4 = multiplications executed in the F(4x4,3x3) domain (36 per 16 outputs instead of 144)
-        PROFILE.append((flops / 4, e0, e1, f"wino3x3 F43 multi in={sizes}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}",
-                        4.0 * (sum(x.numel() for x in xs) + U43.numel() + (sum(t.numel() for t in ys) if full else 0) + (sum(t.numel() for t in yps) if pool else 0)),
-                        flops))
+    ws = workspace(xs[0].device)
+    # direct-form FLOPs / 4 = multiplications executed in the F(4x4,3x3) domain (36 per 16 outputs instead of 144)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_wino43_conv3x3_multi(segs, len(xs), Cin, _ptr(U43), _ptr(bias), Cout, int(relu), _ptr(ws), ws.numel() * 4,
+                                                                  _stream()), "g6d_wino43_conv3x3_multi"),
+           _wino_book(flops / 4, "F43 ", describe, U43.numel(), flops))
     return ys, yps
 
 
@@ -608,28 +591,15 @@ def corr2d_wino43_multi(xs, U43, outs, kblocks=5, k_true=None):
     Cin, Cout = xs[0].shape[4], outs[0].shape[4]
     if tuple(U43.shape) != w43_shape(kblocks * kblocks * (Cin // 8), Cout) or not U43.is_contiguous():
         raise ValueError(f"corr2d_wino43_multi: U43 must be contiguous {w43_shape(kblocks * kblocks * (Cin // 8), Cout)}")
-    segs = (_lib.G6dCorrSeg * len(xs))()
-    flops, sizes = 0.0, []
     k = 3 * kblocks
-    for i, (x, o) in enumerate(zip(xs, outs)):
-        N, D, H, W, Cx, ld_in = _cl5(x, "corr2d_wino43.x")
-        No, _, Ho, Wo, Co, ld_out = _cl5(o, "corr2d_wino43.out")
-        if D != 1 or No != N or (Ho, Wo) != (H, W) or Cx != Cin or Co != Cout or not (x.is_contiguous() and o.is_contiguous()):
-            raise ValueError("corr2d_wino43_multi: shape mismatch (maps must be dense)")
-        segs[i] = _lib.G6dCorrSeg(in_=x.data_ptr(), out=o.data_ptr(), H=H, W=W, ld_in=ld_in, ld_out=ld_out, N=N)
-        flops += 2.0 * N * H * W * Cout * k * k * Cin
-        sizes.append(f"{N}x{H}x{W}" if N > 1 else f"{H}x{W}")
+    segs, flops, sizes = _corr_table("corr2d_wino43_multi", "corr2d_wino43", xs, outs, Cin, Cout, k)
     kt = k_true or k
     ws = workspace(U43.device)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().g6d_corr2d_wino43_multi(segs, len(xs), Cin, _ptr(U43), Cout, int(kblocks), _ptr(ws), ws.numel() * 4, _stream()),
-               "g6d_corr2d_wino43_multi")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((flops / 4, e0, e1, f"wino3x3 F43 corr multi in={'+'.join(sizes)}x{Cin} out={Cout} k={kt}x{kt} ({kblocks}x{kblocks} blocks of 3x3)",
-                        4.0 * (sum(x.numel() for x in xs) + sum(o.numel() for o in outs) + U43.numel()), flops * kt * kt / (k * k)))
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_corr2d_wino43_multi(segs, len(xs), Cin, _ptr(U43), Cout, int(kblocks), _ptr(ws), ws.numel() * 4, _stream()),
+                              "g6d_corr2d_wino43_multi"),
+           lambda e0, e1: PROFILE.append((flops / 4, e0, e1, f"wino3x3 F43 corr multi in={sizes}x{Cin} out={Cout} k={kt}x{kt} ({kblocks}x{kblocks} blocks of 3x3)",
+                                          4.0 * (_numel(xs, outs) + U43.numel()), flops * kt * kt / (k * k))))
     return outs
 
 
@@ -637,40 +607,18 @@ def wino16_conv3x3_multi(xs, U16, bias, relu=True, full=True, pool=False):
     """wino_conv3x3_multi with 16-bit matrix-core operands (MATH_MODE 1 = bf16, 2 = fp16; fp32 activations in and out): U16
     [Cin/16,16,Cout,16] in torch.bfloat16 / torch.float16 (backbone.winograd_filters16).  xs as wino_conv3x3_multi."""
     _need_gpu(U16, bias, *xs)
-    if not 1 <= len(xs) <= 4:
-        raise ValueError("wino16_conv3x3_multi: 1..4 segments")
     mm = {torch.bfloat16: 1, torch.float16: 2}.get(U16.dtype)
-    Cin, Cout = xs[0].shape[3], U16.shape[2]
+    Cout = U16.shape[2]
+    segs, Cin, ys, yps, flops, describe = _wino_table("wino16_conv3x3_multi", xs, Cout, full, pool)
     if mm is None or tuple(U16.shape) != (Cin // 16, 16, Cout, 16) or not U16.is_contiguous() or bias.numel() != Cout:
         raise ValueError(f"wino16_conv3x3_multi: U16 must be contiguous bfloat16 / float16 {(Cin // 16, 16, Cout, 16)}")
-    for x in xs:
-        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[3] != Cin:
-            raise ValueError("wino16_conv3x3_multi: segments must be contiguous float32 [N,H,W,Cin]")
-    dev = xs[0].device
-    ys = alloc_like_segments([(x.shape[0], x.shape[1], x.shape[2], Cout) for x in xs], dev) if full else None
-    yps = alloc_like_segments([(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, Cout) for x in xs], dev) if pool else None
-    segs = (_lib.G6dWinoSeg * len(xs))()
-    flops = 0.0
-    for i, x in enumerate(xs):
-        N, H, W, _ = x.shape
-        segs[i] = _lib.G6dWinoSeg(in_=x.data_ptr(), out_full=ys[i].data_ptr() if full else None,
-                                  out_pool=yps[i].data_ptr() if pool else None, N=N, H=H, W=W, ld_in=Cin, ld_full=Cout, ld_pool=Cout)
-        flops += 2.0 * N * H * W * Cout * 9 * Cin
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    ws = workspace(dev)
-    _lib.check(_lib.load().g6d_wino16_conv3x3_multi(segs, len(xs), Cin, _ptr(U16), _ptr(bias), Cout, int(relu), mm, _ptr(ws), ws.numel() * 4,
-                                                   _stream()), "g6d_wino16_conv3x3_multi")
-    if PROFILE is not None:
-        e1.record()
-        sizes = "+".join(f"{x.shape[0]}x{x.shape[1]}x{x.shape[2]}" for x in xs)
-        PROFILE.append((flops / 2.25, e0, e1, f"wino3x3 {'bf16' if mm == 1 else 'fp16'} multi in={sizes}x{Cin} out={Cout}{' full' if full else ''}{' pool' if pool else ''}",
-                        4.0 * (sum(x.numel() for x in xs) + U16.numel() / 2 + (sum(t.numel() for t in ys) if full else 0) + (sum(t.numel() for t in yps) if pool else 0))))
+    ws = workspace(xs[0].device)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_wino16_conv3x3_multi(segs, len(xs), Cin, _ptr(U16), _ptr(bias), Cout, int(relu), mm, _ptr(ws), ws.numel() * 4,
+                                                                  _stream()), "g6d_wino16_conv3x3_multi"),
+           _wino_book(flops / 2.25, "bf16 " if mm == 1 else "fp16 ", describe, U16.numel() / 2))
     return ys, yps
 
-
-_T16 = {1: torch.bfloat16, 2: torch.float16, 3: torch.float16}
 
 # ---- range control of fp16 hi / lo pair maps (G6dRange16, include/gen6d_hip.h) ---------------------------------------------------------
 # A pair map holds v * 2^-e: e = 0 while the map's largest |v| (A) lies in [2^-4, 2^14) — today's bits — else floor(log2 A), so the scaled
@@ -801,6 +749,15 @@ class Conv16Filters:
         self.data, self.layout, self.mode, self.acc_scale, self.Cout, self.taps, self.Cin = data, layout, mode, acc_scale, Cout, taps, Cin
 
 
+def _split_hi_lo(w_taps):
+    """fp32 filters -> (hi, lo, 1 / S): the fp16 parts of w * S, split in fp64, for the largest power of two S <= 2^14 that keeps |w| S below
+    2048 — the lo parts then stay normal fp16 numbers, and the kernels multiply their accumulators by 1 / S."""
+    S = 2.0 ** min(14, math.floor(math.log2(2048.0 / max(float(w_taps.abs().max()), 1e-30))))
+    w = w_taps.double() * S
+    hi = w.to(torch.float16)
+    return hi, (w - hi.double()).to(torch.float16), 1.0 / S
+
+
 def conv16_pack(w_taps, mode, layout=1):
     """[Cout, taps, Cin] fp32 filters (tap = (kz*3 + ky)*3 + kx) -> Conv16Filters for `mode` (1 bf16, 2 fp16, 3 fp16 hi / lo pairs).
     layout 1 (fragment-major, include/gen6d_hip.h): [Cout/128][Cin/BK][taps][BK/16][planes][4][64 lanes][8], BK = 64 (pairs: 32), lane l
@@ -817,14 +774,8 @@ def conv16_pack(w_taps, mode, layout=1):
         raise ValueError("conv16_pack: Cout % 128 == 0 (pairs, 2-D: also 64) and Cin % 64 (pairs: 32) == 0 expected")
     acc_scale = 1.0
     if mode == 3:
-        import math
-        amax = float(w_taps.abs().max())
-        S = 2.0 ** min(14, math.floor(math.log2(2048.0 / max(amax, 1e-30))))
-        w = w_taps.double() * S
-        hi = w.to(torch.float16)
-        lo = (w - hi.double()).to(torch.float16)
+        hi, lo, acc_scale = _split_hi_lo(w_taps)
         planes = torch.stack([hi, lo], 0)
-        acc_scale = 1.0 / S
     else:
         planes = w_taps.to(_T16[mode])[None]
     if layout == 0:
@@ -962,18 +913,13 @@ def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, s
         flops += 2.0 * N * D * H * W * Cout * taps * Cin
         nbytes += x.numel() * 2.0 + sum(t.numel() * t.element_size() for t in (f, q) if t is not None)
         sizes.append("x".join(str(v) for v in lead))
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().g6d_conv16_direct_multi_ex(segs, len(xs), Cin, _ptr(filt.data), int(filt.layout), float(filt.acc_scale), _ptr(bias), Cout,
-                                                     int(kd), int(bool(relu)), code[full], code[pool], int(mode), _ptr(stats), int(rows_per_group), ra,
-                                                     _stream()),
-               "g6d_conv16_direct_multi")
-    if PROFILE is not None:
-        e1.record()
-        # mode 3 executes three 16-bit MFMAs per product: booked as "conv16x3" with the DIRECT-FORM flops (what the fp32 kernels it replaces are booked with / 4)
-        PROFILE.append((flops, e0, e1, f"{'conv16x3' if pair else 'conv16'} direct in={'+'.join(sizes)}x{Cin} out={Cout} k={'3x' if kd == 3 else ''}3x3"
-                        f"{' full' if full is not None else ''}{' pool' if pool is not None else ''}{' stats' if stats is not None else ''}", nbytes, flops))
+    # mode 3 executes three 16-bit MFMAs per product: booked as "conv16x3" with the DIRECT-FORM flops (what the fp32 kernels it replaces are booked with / 4)
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_conv16_direct_multi_ex(
+               segs, len(xs), Cin, _ptr(filt.data), int(filt.layout), float(filt.acc_scale), _ptr(bias), Cout, int(kd), int(bool(relu)), code[full],
+               code[pool], int(mode), _ptr(stats), int(rows_per_group), ra, _stream()), "g6d_conv16_direct_multi"),
+           lambda e0, e1: PROFILE.append((flops, e0, e1, f"{'conv16x3' if pair else 'conv16'} direct in={'+'.join(sizes)}x{Cin} out={Cout} k={'3x' if kd == 3 else ''}3x3"
+                                          f"{' full' if full is not None else ''}{' pool' if pool is not None else ''}{' stats' if stats is not None else ''}", nbytes, flops)))
     if rng is not None:
         fulls = [_wrap(f, rng) if full == "t16" else f for f in fulls]
         pools = [_wrap(q, rng) if pool == "t16" else q for q in pools]
@@ -989,13 +935,7 @@ def corr16_pack(w_taps, mode):
         raise ValueError("corr16_pack: 32 references and Cin % 32 == 0 expected")
     acc_scale = 1.0
     if mode == 3:
-        import math
-        amax = float(w_taps.abs().max())
-        S = 2.0 ** min(14, math.floor(math.log2(2048.0 / max(amax, 1e-30))))
-        w = w_taps.double() * S
-        hi = w.to(torch.float16)
-        lo = (w - hi.double()).to(torch.float16)
-        acc_scale = 1.0 / S
+        hi, lo, acc_scale = _split_hi_lo(w_taps)
         x = torch.stack([hi, lo], 0).reshape(2, 32, taps, ci // 16, 2, 8)           # plane, r, tap, slice, half, e
         x = x.permute(3, 2, 0, 4, 1, 5).contiguous()                                 # slice, tap, plane, half, r, e
     else:
@@ -1032,14 +972,11 @@ def corr16_multi(xs, filt, outs):
         flops += 2.0 * N * H * W * 32 * filt.taps * Cin
         nbytes += x.numel() * 2.0 + o.numel() * 4.0
         sizes.append(f"{N}x{H}x{W}")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().g6d_corr16_multi_ex(segs, len(xs), Cin, _ptr(filt.data), float(filt.acc_scale), 32, int(filt.k), int(mode), ra, _stream()),
-               "g6d_corr16_multi")
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((flops, e0, e1, f"{'conv16x3' if pair else 'conv16'} corr in={'+'.join(sizes)}x{Cin} out=32 k={filt.k}x{filt.k}", nbytes, flops))
+    _timed(PROFILE is not None,
+           lambda: _lib.check(_lib.load().g6d_corr16_multi_ex(segs, len(xs), Cin, _ptr(filt.data), float(filt.acc_scale), 32, int(filt.k), int(mode), ra,
+                                                             _stream()), "g6d_corr16_multi"),
+           lambda e0, e1: PROFILE.append((flops, e0, e1, f"{'conv16x3' if pair else 'conv16'} corr in={'+'.join(sizes)}x{Cin} out=32 k={filt.k}x{filt.k}",
+                                          nbytes, flops)))
     return outs
 
 
@@ -1333,7 +1270,6 @@ def linear_gemv(x, W, bias, act=0):
 def warp_perspective(src_u8, H, dh, dw, out_float=False):
     """src_u8 uint8 [sh,sw,ch] on the GPU; H = 3x3 source->destination pixel homography (numpy, as cv2.warpPerspective
     takes it; a 2x3 affine as cv2.warpAffine takes it is accepted too) -> [dh,dw,ch] uint8 or float32 in [0,1]."""
-    import numpy as np
     _need_gpu(src_u8)
     if src_u8.dtype != torch.uint8 or src_u8.dim() != 3 or not src_u8.is_contiguous():
         raise ValueError("warp_perspective: src must be a contiguous uint8 [H,W,C] tensor")

@@ -153,7 +153,8 @@ int g6d_corr2d_patch(const float* in, int H, int W, int Cin, int ld_in, const fl
                      g6d_stream_t stream);
 /* The same correlation for up to 4 map sizes in one launch: the scales of the detector's image pyramid against the same reference
  * filters, N maps (the queries of a batch, network/detector.py:291-304 takes [qn,H,W,3]) per size; the tiles of all maps form one
- * flat work list (fewer splits, one launch).  Buffers within 2^30 floats of each other. */
+ * flat work list (fewer splits, one launch).  Inputs within 2^30 floats of each other (g6d_corr2d_wino_multi,
+ * g6d_corr2d_wino43_multi: 2^29), outputs within 2^31. */
 typedef struct G6dCorrSeg {
   const float* in;        /* [N][H][W][ld_in] */
   float* out;             /* [N][H*W][ld_out] */
@@ -251,7 +252,8 @@ int g6d_wino_conv3x3(const float* in, int N, int H, int W, int Cin, int ld_in, c
 /* The same layer over up to 4 map sizes in one launch: the scales of the detector's image pyramid (network/detector.py:236-241)
  * share every trunk layer's filters, and the quarters of all segments form one flat work list, so the small scales fill the
  * blocks the large ones leave over.  All segments give the same kinds of output (out_full / out_pool both set or both NULL
- * across segments), and their buffers lie within 2^30 floats of each other (allocate them from one buffer). */
+ * across segments), their inputs lie within 2^29 floats of each other and their outputs of each kind within 2^31 (allocate them from
+ * one buffer). */
 typedef struct G6dWinoSeg {
   const float* in;        /* [N][H][W][ld_in] */
   float* out_full;        /* [N][H][W][ld_full] or NULL */
