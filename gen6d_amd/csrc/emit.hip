@@ -11,31 +11,11 @@
 // block-uniform.  A tile with an empty list (almost every tile) is a convert-and-copy: three dword loads per thread and row where the
 // canvas rows are dword-aligned, dword / dwordx4 stores where the sink's are.  Only listed primitives are tested per pixel.  A thread's
 // 8 pixels live in 8 scalar words (a byte array here was moved to LDS by the compiler); no scratch (tests/test_emit_cpu.py).
-#include "g6d_common.h"
+#include "emit_common.h"
 #include "pose_algebra.h"
 
 namespace {
 
-constexpr int TW = 128, TH = 16;
-constexpr int QMIN = -8192, QMAX = 16383;      // corner range inside which the 64-bit edge rule is exact (header)
-
-__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
-
-// pixel centre within thickness / 2 of the segment a-b, th2 = thickness^2 (header: every term < 2^63)
-__device__ __forceinline__ bool edge_hit(int x, int y, int ax, int ay, int bx, int by, long long th2) {
-  const long long dx = bx - ax, dy = by - ay, px = x - ax, py = y - ay;
-  const long long L = dx * dx + dy * dy, pp = px * px + py * py;
-  if (L == 0) return 4 * pp <= th2;
-  const long long s = px * dx + py * dy, t = min(max(s, 0LL), L);
-  return L * pp - 2 * t * s + t * t <= ((th2 * L) >> 2);
-}
-
-// 4 consecutive pixels of one row, each R | G << 8 | B << 16 (scalars, not a byte array: the compiler keeps them in registers)
-struct Row { unsigned a, b, c, d; };
-
-__device__ __forceinline__ unsigned pixel(const unsigned char* p, bool in) {
-  return in ? (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) : 0u;
-}
 // picture pixels (X .. X+3, y) of image `slot`, black outside the pw x ph picture; three dword loads where the address allows
 __device__ __forceinline__ Row fill_row(const unsigned char* __restrict__ imgs, int slot, int H, int W, int X, int y, int pw, int ph) {
   Row r{0u, 0u, 0u, 0u};
@@ -49,44 +29,6 @@ __device__ __forceinline__ Row fill_row(const unsigned char* __restrict__ imgs, 
     r.a = pixel(src, true); r.b = pixel(src + 3, X + 1 < pw); r.c = pixel(src + 6, X + 2 < pw); r.d = pixel(src + 9, X + 3 < pw);
   }
   return r;
-}
-__device__ __forceinline__ void paint(Row& r, unsigned e, unsigned d, unsigned line, unsigned dot) {
-  r.a = (e & 1u) ? line : ((d & 1u) ? dot : r.a); r.b = (e & 2u) ? line : ((d & 2u) ? dot : r.b);
-  r.c = (e & 4u) ? line : ((d & 4u) ? dot : r.c); r.d = (e & 8u) ? line : ((d & 8u) ? dot : r.d);
-}
-__device__ __forceinline__ unsigned swap1(unsigned p) { return ((p & 0xffu) << 16) | (p & 0xff00u) | (p >> 16); }
-__device__ __forceinline__ void swap_rb(Row& r) { r.a = swap1(r.a); r.b = swap1(r.b); r.c = swap1(r.c); r.d = swap1(r.d); }
-__device__ __forceinline__ unsigned luma(unsigned p, int cyr, int cyg, int cyb) {
-  return (unsigned)sat8((cyr * (int)(p & 255u) + cyg * (int)((p >> 8) & 255u) + cyb * (int)(p >> 16) + (1 << 19) + (16 << 20)) >> 20);
-}
-// 4 bytes at o (the first `left` of them when the sink ends inside): one dword where the address allows
-__device__ __forceinline__ void put4(unsigned char* o, unsigned w, bool full, int left) {
-  if (full && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) { *reinterpret_cast<unsigned*>(o) = w; return; }
-  if (left > 0) o[0] = (unsigned char)w;
-  if (left > 1) o[1] = (unsigned char)(w >> 8);
-  if (left > 2) o[2] = (unsigned char)(w >> 16);
-  if (left > 3) o[3] = (unsigned char)(w >> 24);
-}
-// 4 packed 3-byte pixels (12 bytes; the first `left` bytes when the sink ends inside)
-__device__ __forceinline__ void put12(unsigned char* o, const Row& r, bool full, int left) {
-  const unsigned w0 = r.a | (r.b << 24), w1 = (r.b >> 8) | (r.c << 16), w2 = (r.c >> 16) | (r.d << 8);
-  if (full && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
-    unsigned* o32 = reinterpret_cast<unsigned*>(o);
-    o32[0] = w0; o32[1] = w1; o32[2] = w2;
-    return;
-  }
-  put4(o, w0, false, left); put4(o + 4, w1, false, left - 4); put4(o + 8, w2, false, left - 8);
-}
-// 4 packed 4-byte pixels with alpha 255 (the first `left` pixels when the sink ends inside)
-__device__ __forceinline__ void put16(unsigned char* o, const Row& r, bool full, int left) {
-  const unsigned w0 = r.a | 0xff000000u, w1 = r.b | 0xff000000u, w2 = r.c | 0xff000000u, w3 = r.d | 0xff000000u;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(o);
-  if (full && (al & 15u) == 0) { *reinterpret_cast<uint4*>(o) = make_uint4(w0, w1, w2, w3); return; }
-  const bool dw = (al & 3u) == 0;
-  if (left > 0) put4(o, w0, dw, 4);
-  if (left > 1) put4(o + 4, w1, dw, 4);
-  if (left > 2) put4(o + 8, w2, dw, 4);
-  if (left > 3) put4(o + 12, w3, dw, 4);
 }
 
 __global__ void __launch_bounds__(256) frame_emit_kernel(const G6dSink* __restrict__ sinks, const unsigned char* __restrict__ imgs, int B,
@@ -116,40 +58,7 @@ __global__ void __launch_bounds__(256) frame_emit_kernel(const G6dSink* __restri
 
   for (int tile = tile0; tile < ntiles; tile += tiles) {   // (block-uniform trip count)
     const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
-    if (t < 64) {                                          // wave 0: the tile's primitive list
-      bool hit = false;
-      int ax = 0, ay = 0, bx = 0, by = 0;
-      const bool bad = draw && t < 8 && (q[2 * t] < QMIN || q[2 * t] > QMAX || q[2 * t + 1] < QMIN || q[2 * t + 1] > QMAX);
-      if (draw && t < 20 && X0 < pw && Y0 < ph) {
-        const int x1 = min(X0 + TW, pw) - 1, y1 = min(Y0 + TH, ph) - 1;     // pixel rectangle [X0, x1] x [Y0, y1] inside the picture
-        if (t < 12) {
-          const int a = t < 4 ? t : (t < 8 ? t : t - 8), b = t < 4 ? ((t + 1) & 3) : (t < 8 ? 4 + ((t + 1) & 3) : t - 4);
-          ax = q[2 * a]; ay = q[2 * a + 1]; bx = q[2 * b]; by = q[2 * b + 1];
-          const int hw = (th + 1) >> 1;
-          hit = th > 0 && max(ax, bx) + hw >= X0 && min(ax, bx) - hw <= x1 && max(ay, by) + hw >= Y0 && min(ay, by) - hw <= y1;
-          const long long dx = bx - ax, dy = by - ay, L = dx * dx + dy * dy;
-          if (hit && L > 0) {
-            // the supporting line: cross(d, c - a) is linear in c, so if it has one sign at the rectangle's four corners, every pixel's
-            // |cross| is at least the smallest corner value, and a pixel is covered only if cross^2 <= thickness^2 L / 4
-            const long long c00 = dx * (Y0 - ay) - dy * (X0 - ax), c01 = dx * (Y0 - ay) - dy * (x1 - ax);
-            const long long c10 = dx * (y1 - ay) - dy * (X0 - ax), c11 = dx * (y1 - ay) - dy * (x1 - ax);
-            const long long lo = min(min(c00, c01), min(c10, c11)), hi = max(max(c00, c01), max(c10, c11));
-            const long long m = lo > 0 ? lo : (hi < 0 ? -hi : 0);
-            if (m * m > ((th2 * L) >> 2)) hit = false;
-          }
-        } else {
-          ax = q[2 * (t - 12)]; ay = q[2 * (t - 12) + 1];
-          hit = rad >= 0 && ax + rad >= X0 && ax - rad <= x1 && ay + rad >= Y0 && ay - rad <= y1;
-        }
-      }
-      if (__ballot(bad)) hit = false;
-      const unsigned long long m = __ballot(hit);
-      if (hit) {
-        const int pos = __popcll(m & ((1ull << t) - 1));
-        sp[pos][0] = ax; sp[pos][1] = ay; sp[pos][2] = bx; sp[pos][3] = by;
-      }
-      if (t == 0) { sn[0] = __popcll(m & 0xfffull); sn[1] = __popcll(m); }
-    }
+    if (t < 64) cull_tile(sp, sn, t, draw, q, th, th2, rad, X0, Y0, pw, ph);   // wave 0: the tile's primitive list
     __syncthreads();
     const int X = X0 + ((t & 31) << 2), Y = Y0 + ((t >> 5) << 1);
     if (X < sw && Y < sh) {
@@ -158,22 +67,7 @@ __global__ void __launch_bounds__(256) frame_emit_kernel(const G6dSink* __restri
       Row r0 = fill_row(imgs, slot, H, W, X, Y, pw, ph), r1 = fill_row(imgs, slot, H, W, X, Y + 1, pw, ph);
       if (n > 0) {                                         // (block-uniform) listed primitives only; bit i of a mask = pixel X + i
         unsigned e0 = 0, e1 = 0, d0 = 0, d1 = 0;
-        for (int l = 0; l < ne; ++l) {
-          const int ax = sp[l][0], ay = sp[l][1], bx = sp[l][2], by = sp[l][3];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            e0 |= (edge_hit(X + i, Y, ax, ay, bx, by, th2) ? 1u : 0u) << i;
-            e1 |= (edge_hit(X + i, Y + 1, ax, ay, bx, by, th2) ? 1u : 0u) << i;
-          }
-        }
-        for (int l = ne; l < n; ++l) {
-          const int ux = X - sp[l][0], uy = Y - sp[l][1];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            d0 |= ((ux + i) * (ux + i) + uy * uy <= rad2 ? 1u : 0u) << i;
-            d1 |= ((ux + i) * (ux + i) + (uy + 1) * (uy + 1) <= rad2 ? 1u : 0u) << i;
-          }
-        }
+        cover(sp, ne, n, X, Y, th2, rad2, e0, e1, d0, d1);
         const unsigned in = X + 4 <= pw ? 15u : (X < pw ? (1u << (pw - X)) - 1u : 0u);      // pixels inside the picture
         const unsigned in0 = Y < ph ? in : 0u, in1 = Y + 1 < ph ? in : 0u;
         paint(r0, e0 & in0, d0 & in0, line, dot);

@@ -277,6 +277,29 @@ def plan(frame, canvas_hw):
     return out_h, out_w, pixel_map(frame, out_h, out_w) @ K
 
 
+def source_K(frame, canvas_hw):
+    """Intrinsics (float64 [3,3]) of the frame's own, unturned pixel grid under which a pose found on the canvas projects into the SOURCE
+    picture (emit.Sink(view="source")): Frame.K if the frame has one, else inv(pixel_map) @ pseudo_K of the planned picture.  Either
+    way pixel_map @ source_K is the K' that `plan` hands the networks: the pose is the same, only the pixel grid differs, quarter turn
+    included.  A frame with a lens has no such K (its source is distorted: a straight box edge is a curve in it)."""
+    if frame.lens is not None:
+        raise ValueError("source_K: a frame with a lens has a distorted source picture; the source view of lens frames is out of scope")
+    if frame.K is not None:
+        return frame.K.copy()
+    out_h, out_w, K = plan(frame, canvas_hw)
+    return np.linalg.inv(pixel_map(frame, out_h, out_w)) @ K
+
+
+class Staged:
+    """What `ingest_frames_keep` leaves on the device: `table`, the uint8 tensor of the call's n lib.G6dFrame records (record i
+    is frames[i]; its `slot` field is the frame's canvas slot), for launches that read the source pictures again
+    (emit.emit_source_frames).  It keeps the staging buffer and the device-resident planes referenced; `batch` is the canvas count B."""
+
+    def __init__(self, table, frames, slots, batch):
+        self.table, self.frames, self.slots, self.batch = table, frames, slots, batch
+        self.n, self.device = len(frames), table.device
+
+
 def _host(p):
     return p.numpy() if torch.is_tensor(p) else p
 
@@ -302,6 +325,17 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
     non-blocking copy (copying planes that already are pinned one by one was measured slower); device-resident planes
     are recorded on the stream.  Frames with a lens make it one launch of g6d_frame_ingest_mesh instead: a camera's mesh is built on its
     first frame, travels in the same copy and stays on the device.  Does not synchronise.  Slots no frame names keep their content."""
+    return _ingest(frames, out, K_out, slots, stream, False)
+
+
+def ingest_frames_keep(frames, out, K_out, slots=None, stream=None):
+    """`ingest_frames` that returns (out, staged): `staged` (a `Staged`) holds the device-resident frame table of this call and keeps the
+    staging buffer and the device planes alive, so that a later launch on the same stream can read the source pictures again
+    (emit.emit_source_frames).  The launch is the same."""
+    return _ingest(frames, out, K_out, slots, stream, True)
+
+
+def _ingest(frames, out, K_out, slots, stream, keep):
     frames = list(frames)
     n = len(frames)
     if out.dim() != 4 or out.shape[3] != 3:
@@ -343,7 +377,7 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
                 _meshes.move_to_end(key)                             # most recently used
             meshes[i] = m
     if n == 0:
-        return out
+        return (out, Staged(torch.empty(0, dtype=torch.uint8, device=dev), [], [], B)) if keep else out
     # layout of the upload (one pinned buffer, one copy): staged planes | new meshes | table | mesh table
     offs, total = [], 0
     for p in [p for _, _, p in staged] + [m.host.reshape(-1).view(np.uint8) for m in fresh.values()]:
@@ -402,4 +436,4 @@ def ingest_frames(frames, out, K_out, slots=None, stream=None):
     finally:
         if ctx is not None:
             ctx.__exit__(None, None, None)
-    return out
+    return (out, Staged(buf[toff:moff], frames, slots, B)) if keep else out

@@ -1589,3 +1589,20 @@ def frame_emit(table, n, imgs, pts, valid):
             pts.shape[0] not in (1, 2) or tuple(pts.shape[1:]) != (B, 8, 2) or tuple(valid.shape) != (pts.shape[0], B)):
         raise ValueError("frame_emit: pts must be a contiguous int32 [sets,B,8,2] tensor and valid int32 [sets,B], sets 1 or 2")
     _lib.check(_lib.load().g6d_frame_emit(_ptr(table), n, _ptr(imgs), B, H, W, _ptr(pts), _ptr(valid), _stream()), "g6d_frame_emit")
+
+
+def frame_emit_source(table, n, frames, nf, pts, valid, max_w, max_h):
+    """One launch of g6d_frame_emit_source: `table` holds n lib.G6dSink records whose `slot` names one of the nf lib.G6dFrame records of
+    `frames` (both contiguous uint8 device tensors, 8-byte aligned; built and validated by gen6d_amd.emit.emit_source_frames and
+    gen6d_amd.ingest.ingest_frames), pts int32 [sets,B,8,2] and valid int32 [sets,B] indexed by the frame's canvas slot.  Every sink
+    receives the camera's own frame with the box drawn in source pixels; max_w x max_h bounds the sinks' sizes."""
+    _track_same_device("frame_emit_source", table, frames, pts, valid)
+    n, nf = int(n), int(nf)
+    for what, t, count, size in (("table", table, n, C.sizeof(_lib.G6dSink)), ("frames", frames, nf, C.sizeof(_lib.G6dFrame))):
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or count < 0 or t.numel() < count * size or t.data_ptr() % 8:
+            raise ValueError(f"frame_emit_source: {what} must be a contiguous, 8-byte aligned uint8 tensor of {count} * {size} bytes")
+    if (pts.dtype != torch.int32 or valid.dtype != torch.int32 or not pts.is_contiguous() or not valid.is_contiguous() or pts.dim() != 4 or
+            pts.shape[0] not in (1, 2) or tuple(pts.shape[2:]) != (8, 2) or tuple(valid.shape) != tuple(pts.shape[:2])):
+        raise ValueError("frame_emit_source: pts must be a contiguous int32 [sets,B,8,2] tensor and valid int32 [sets,B], sets 1 or 2")
+    _lib.check(_lib.load().g6d_frame_emit_source(_ptr(table), n, _ptr(frames), nf, _ptr(pts), _ptr(valid), pts.shape[0], pts.shape[1],
+                                                 int(max_w), int(max_h), _stream()), "g6d_frame_emit_source")

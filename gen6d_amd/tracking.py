@@ -22,7 +22,10 @@ many streams (cameras or clients watching one object) at once:
     (raw and / or smoothed pose), in an encoder's or a display's format, into device or pinned host buffers the caller names
     (`gen6d_amd.emit.Sink`).  After the lane's tick (or the commit of an init chunk) the corners are projected on the device and ONE
     g6d_frame_emit launch per lane and tick fills that lane's sinks, stream-ordered on the lane's stream, outside the captured graph
-    (DESIGN.md §4.18).  A tracker used without sinks launches nothing of this;
+    (DESIGN.md §4.18).  A tracker used without sinks launches nothing of this.  A sink with view="source" receives the camera's own
+    frame (full resolution, not turned) with the box drawn in its pixel grid instead: the lane's ingest keeps its frame table on the
+    device, the corners are projected once more under the sources' intrinsics and ONE g6d_frame_emit_source launch per lane and tick
+    fills those sinks (DESIGN.md §4.20).  A push without source-view sinks launches nothing of this;
   * with `health=HealthPolicy(...)` every stream carries a status (TRACKING / SUSPECT / LOST) that the device keeps: a gate parks lost
     streams and non-finite table rows before the gather, a health launch judges every refined pose before the commit (a bad frame is
     not committed), the detector can check the committed poses every n-th tick, and the host, which sees the status with a fixed lag,
@@ -258,16 +261,28 @@ class StreamTracker:
         sinks: None, or one entry per stream id: an `emit.Sink`, a list of them (predict.py writes the raw and the smoothed picture of a
         frame) or None.  Each sink receives the stream's working-resolution frame with the box of this frame's pose drawn on it; the
         picture's size is the frame's `ingest.plan` with `frame_size`, the whole image otherwise.  Device sinks are written on the lane's
-        stream; host sinks are valid after `wait_emitted` or `result`.  Does not synchronise."""
+        stream; host sinks are valid after `wait_emitted` or `result`.  Sinks with view="source" (mixed freely with the others)
+        receive the stream's `ingest.Frame` of this push as the camera delivered it, with the box in source pixels; they need a
+        tracker with `frame_size` and a frame without a lens (ValueError before anything is launched).  Does not synchronise."""
         ids = self._ids(stream_ids)
         if len(imgs) != len(ids) or (Ks is not None and len(Ks) != len(ids)):
             raise ValueError("StreamTracker.push: one image (and K) per stream id expected")
         self._sinks = self._sink_lists(ids, sinks)
+        source = {s for s, lst in self._sinks.items() if any(k.view == "source" for k in lst)}
+        if source and self.frame_size is None:
+            self._sinks = {}
+            raise ValueError("StreamTracker.push: a source-view sink needs a tracker with frame_size (without it the canvas is the only "
+                             "source there is)")
         if self.frame_size is not None:
             if Ks is not None:
                 raise ValueError("StreamTracker.push: a tracker with frame_size takes the intrinsics in Frame.K, not in Ks")
             frames = [im if isinstance(im, I.Frame) else I.Frame(self._rgb(im)) for im in imgs]
             Ks = [None] * len(ids)
+            for s, f in zip(ids, frames):
+                if s in source and f.lens is not None:
+                    self._sinks = {}
+                    raise ValueError(f"StreamTracker.push: stream {s}'s frame has a lens, so its source picture is distorted (a straight "
+                                     "box edge is a curve in it); the source view of lens frames is out of scope, use a canvas sink")
         else:
             frames = [self._frame(im) for im in imgs]
             Ks = [EV.pseudo_K(*self._shape[:2])] * len(ids) if Ks is None else Ks
@@ -410,20 +425,38 @@ class StreamTracker:
             pic[e.slot] = self._picture(e)[::-1]
         return pic
 
-    def _emit(self, imgs, K9, slot_map, ents):
-        """Project the box under the raw / smoothed poses just committed and fill the sinks of these streams: at most two
-        g6d_track_corners launches and one g6d_frame_emit launch on the current (lane's) stream."""
-        todo = [(e, k) for e in ents for k in self._sinks.get(e.stream, ())]
-        if not todo:
-            return
-        n = slot_map.shape[0]                  # a corner set is read only by sinks that name it, so only those sets are computed
+    def _corners(self, K9, slot_map, sinks):
+        """The box under the raw / smoothed poses just committed -> (pts [2,n,8,2], valid [2,n]): one g6d_track_corners launch per
+        corner set that one of `sinks` names (a set is read only by sinks that name it)."""
+        n = slot_map.shape[0]
         pts = torch.empty((2, n, 8, 2), dtype=torch.int32, device=self.dev)
         valid = torch.empty((2, n), dtype=torch.int32, device=self.dev)
         for name, table in (("raw", self.pose_table), ("smooth", self.smooth_table)):
-            if any(k.box and k.pose == name for _, k in todo):
+            if any(k.box and k.pose == name for k in sinks):
                 ops.track_corners(table, K9, slot_map, self.box, pts[E.POSES[name]], valid[E.POSES[name]])
-        sizes = [self._picture(e) for e, _ in todo]
-        E.emit_frames(imgs, pts, valid, [k for _, k in todo], slots=[e.slot for e, _ in todo], pic_sizes=sizes)
+        return pts, valid
+
+    def _wants_source(self, ents):
+        return any(k.view == "source" for e in ents for k in self._sinks.get(e.stream, ()))
+
+    def _emit(self, imgs, K9, slot_map, ents, staged=None):
+        """Project the box under the raw / smoothed poses just committed and fill the sinks of these streams on the current (lane's)
+        stream.  Canvas sinks: at most two g6d_track_corners launches and one g6d_frame_emit launch.  Source-view sinks (staged: the
+        frame table the ingest of `ents` kept): one pinned upload of the sources' intrinsics, at most two more g6d_track_corners
+        launches under them, with the same slot map and therefore the same health behaviour, and one g6d_frame_emit_source launch."""
+        todo = [(i, e, k) for i, e in enumerate(ents) for k in self._sinks.get(e.stream, ())]
+        canvas = [(e, k) for _, e, k in todo if k.view == "canvas"]
+        if canvas:
+            pts, valid = self._corners(K9, slot_map, [k for _, k in canvas])
+            sizes = [self._picture(e) for e, _ in canvas]
+            E.emit_frames(imgs, pts, valid, [k for _, k in canvas], slots=[e.slot for e, _ in canvas], pic_sizes=sizes)
+        source = [(i, e, k) for i, e, k in todo if k.view == "source"]
+        if source:
+            Ks = np.tile(np.eye(3, dtype=np.float32).reshape(9), (slot_map.shape[0], 1))      # rows of slots nobody draws stay harmless
+            for _, e, _ in source:
+                Ks[e.slot] = I.source_K(e.frame, self._shape[:2]).astype(np.float32).reshape(9)
+            pts, valid = self._corners(self._upload(Ks), slot_map, [k for _, _, k in source])
+            E.emit_source_frames(staged, pts, valid, [k for _, _, k in source], sources=[i for i, _, _ in source])
 
     @staticmethod
     def _rgb(im):
@@ -498,8 +531,12 @@ class StreamTracker:
         m[[e.slot for e in ents]] = [e.stream for e in ents]
         if self.graphs and lane.graph is None:
             self._capture(lane)
+        staged = None
         if self.frame_size is not None:        # one launch fills the named slots of the static image and K buffers
-            I.ingest_frames([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
+            if self._wants_source(ents):       # ... and leaves its frame table on the device for the source-view emit
+                staged = I.ingest_frames_keep([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])[1]
+            else:
+                I.ingest_frames([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
         else:
             for e in ents:
                 lane.img[e.slot].copy_(e.frame)
@@ -520,7 +557,7 @@ class StreamTracker:
             self._records.append(_Record(out.clone(), [(e.slot, e.stream, self._frames[e.stream]) for e in ents],
                                          commit.clone() if judged else None, self.health_table[:, 0].clone() if judged else None))
         if self._sinks:
-            self._emit(lane.img, lane.K.reshape(self.batch, 9), draw, ents)
+            self._emit(lane.img, lane.K.reshape(self.batch, 9), draw, ents, staged)
 
     def _verify(self, lane):
         """The detector's check of the poses this tick committed: the detection half of query_batch on the lane's image batch in chunks
@@ -537,11 +574,14 @@ class StreamTracker:
     def _init(self, ents):
         n, (H, W) = len(ents), self._shape[:2]
         ents = [e._replace(slot=i) for i, e in enumerate(ents)]
-        native = self.frame_size is not None
+        native, staged = self.frame_size is not None, None
         if native:
             imgs = torch.empty((n,) + self._shape, dtype=torch.uint8, device=self.dev)
             Ks = torch.empty((n, 3, 3), dtype=torch.float32, device=self.dev)
-            I.ingest_frames([e.frame for e in ents], imgs, Ks)
+            if self._wants_source(ents):
+                staged = I.ingest_frames_keep([e.frame for e in ents], imgs, Ks)[1]
+            else:
+                I.ingest_frames([e.frame for e in ents], imgs, Ks)
         else:
             imgs = torch.stack([e.frame for e in ents], 0)
             Ks = torch.stack([e.K for e in ents], 0)
@@ -557,7 +597,7 @@ class StreamTracker:
             self._records.append(_Record(out, [(e.slot, e.stream, self._frames[e.stream]) for e in ents], commit if judged else None,
                                          self.health_table[:, 0].clone() if judged else None))
         if self._sinks:
-            self._emit(imgs, K9, draw, ents)
+            self._emit(imgs, K9, draw, ents, staged)
 
     def _check_range(self):
         bad = []

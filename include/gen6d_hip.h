@@ -705,6 +705,35 @@ int g6d_frame_emit(const G6dSink* sinks, int n, const uint8_t* imgs, int B, int 
                    g6d_stream_t stream);
 int g6d_sizeof_sink_desc(void);
 
+/* g6d_frame_emit_source, the source view of g6d_frame_emit (gen6d_amd/emit.py, Sink(view="source")); additive within ABI 12.  ONE launch
+ * writes n sinks; sink i shows the camera's own picture frames[sinks[i].slot] (a G6dFrame table of nf records as g6d_frame_ingest
+ * takes it, e.g. the one an ingest launch of the same tick read) with a box drawn in the SOURCE's pixel grid: the picture is the
+ * frame's width x height at the sink's top-left corner, not scaled and not turned.  A sink whose `slot` lies outside [0, nf) is skipped.
+ * The corners are pts[box][frames[slot].slot] of pts [sets][B][8][2] / valid [sets][B] (sets 1 or 2): the frame's own `slot` is its
+ * canvas slot, so corner sets indexed like the canvas serve both views; they must have been projected with the SOURCE's intrinsics
+ * (ingest.source_K).  A frame whose own slot lies outside [0, B) is drawn without a box.  Not read: the sink's pic_w / pic_h and the
+ * frame's rotate, out_w, out_h and K.  max_w x max_h bounds the sinks' sizes (1..8192): it sizes the tile walk of the launch and never
+ * changes a result.  Both tables live in DEVICE memory; the caller validates them as for g6d_frame_ingest and g6d_frame_emit.
+ * Exact integer rules (the numpy restatement in tests/test_emit_source_cpu.py is bit-identical).
+ * Source RGB at source pixel (x, y), 0 <= x < width, 0 <= y < height: the ingest's tap rule at an integer position, i.e. what
+ * g6d_frame_ingest writes for a same-size, unturned frame (a = b = 0).  Packed formats: R, G, B by channel order (alpha ignored).
+ * NV12: Y[y][x] and UV[y>>1][x>>1] through the inverse formulas above with the frame's matrix.
+ * Annotation: g6d_frame_emit's rules unchanged, in source pixels: priority edges, discs, picture; the same edge and disc inequalities;
+ * nothing is drawn when box is not 0 or 1, valid is 0 or a corner lies outside [-8192, 16383]; sizes <= 8192, so the 64-bit bound above
+ * holds as written.
+ * Sink pixel (x, y) = the annotated source pixel when x < width and y < height of the frame, else RGB (0, 0, 0).
+ * Output: packed formats and NV12 by g6d_frame_emit's forward formulas on the annotated RGB, EXCEPT an NV12 frame into an NV12 sink
+ * of the same matrix, which is a pass-through (call a pixel covered when an edge or a disc covers it):
+ *   a Y sample of a sink pixel inside the picture that no primitive covers is the source's Y byte; a covered pixel's Y comes from the
+ *   forward formula on line_rgb / dot_rgb;
+ *   a UV pair whose 2 x 2 block lies inside the picture and has no covered pixel is the source's UV pair; a block with at least one
+ *   covered pixel comes from the forward formula on the channel sums of its four annotated pixels, the uncovered ones contributing
+ *   their converted source RGB;
+ *   outside the picture Y = 16 and UV = (128, 128), what the forward formulas make of black.  Both pictures have even sizes and share
+ *   the origin, so no block straddles the picture's edge.  A pass-through sink without a box is a byte copy of the picture. */
+int g6d_frame_emit_source(const G6dSink* sinks, int n, const G6dFrame* frames, int nf, const int32_t* pts, const int32_t* valid, int sets,
+                          int B, int max_w, int max_h, g6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,10 @@
-"""The frame-emit kernel alone (csrc/emit.hip): 32 device-resident images per launch into 32 device sinks of the same size, with a valid
-box on every image, four cases:
+"""The frame-emit kernels alone (csrc/emit.hip, csrc/emit_source.hip): 32 device-resident images per launch into 32 device sinks of
+the same size, with a valid box on every image, four canvas cases and three source-view cases (device-resident camera frames):
 
   540p-nv12  / 540p-rgb24     32 x (540x960 RGB  -> NV12 / rgb24)
   1080p-nv12 / 1080p-rgb24    32 x (1080x1920 RGB -> NV12 / rgb24)
+  src-1080p-nv12-pass / src-540p-nv12-pass    32 x (NV12 frame -> NV12 sink of the same matrix: the pass-through)
+  src-1080p-rgb24-nv12                        32 x (1080x1920 rgb24 frame -> NV12 sink)
 
 Bytes are counted from shapes: the image bytes a launch reads plus the sink bytes it writes (pixel bytes only).  Timing: device events
 around `--launches` back-to-back calls (includes the table upload of each call), or, under the profiler, the kernel's own durations:
@@ -21,14 +23,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM_BPS = 6.3e12          # achievable HBM rate the shares are quoted against
 CASES = {"540p-nv12": ((540, 960), "nv12"), "540p-rgb24": ((540, 960), "rgb24"), "1080p-nv12": ((1080, 1920), "nv12"),
-         "1080p-rgb24": ((1080, 1920), "rgb24")}
+         "1080p-rgb24": ((1080, 1920), "rgb24"),
+         # source view: (size, sink format, source format)
+         "src-1080p-nv12-pass": ((1080, 1920), "nv12", "nv12"), "src-1080p-rgb24-nv12": ((1080, 1920), "nv12", "rgb24"),
+         "src-540p-nv12-pass": ((540, 960), "nv12", "nv12")}
 N = 32
 WARM = 3
 
 
 def case_bytes(c):
-    (h, w), fmt = c
-    return N * (h * w * 3 + (h * w * 3 // 2 if fmt == "nv12" else h * w * 3))
+    (h, w), fmt = c[:2]
+    read = h * w * 3 // 2 if c[2:] == ("nv12",) else h * w * 3
+    return N * (read + (h * w * 3 // 2 if fmt == "nv12" else h * w * 3))
 
 
 def trace_table(path, launches, tick_ms):
@@ -65,23 +71,32 @@ def main():
                         "box on every image; bytes = image bytes read + sink bytes written, from shapes.\n\n" + txt + "\n")
         return
     import torch
-    from gen6d_amd.emit import Sink, emit_frames
+    from gen6d_amd.emit import Sink, emit_frames, emit_source_frames
+    from gen6d_amd.ingest import Frame, ingest_frames_keep
     if not torch.cuda.is_available():
         sys.exit("emit_bench: needs the GPU (the kernel has no CPU fallback)")
     rng = np.random.RandomState(0)
-    for name, ((h, w), fmt) in CASES.items():
-        imgs = torch.from_numpy(rng.randint(0, 256, (N, h, w, 3)).astype(np.uint8)).cuda()
+    for name, ((h, w), fmt, *src) in CASES.items():
         shape = (h * 3 // 2, w) if fmt == "nv12" else (h, w, 3)
-        sinks = [Sink(torch.zeros(shape, dtype=torch.uint8, device="cuda"), fmt) for _ in range(N)]
+        sinks = [Sink(torch.zeros(shape, dtype=torch.uint8, device="cuda"), fmt, view="source" if src else "canvas") for _ in range(N)]
         q = np.stack([rng.randint(w // 8, w - w // 8, (N, 8)), rng.randint(h // 8, h - h // 8, (N, 8))], -1).astype(np.int32)
         pts, valid = torch.from_numpy(q).cuda(), torch.ones(N, dtype=torch.int32, device="cuda")
+        if src:                                  # device-resident camera frames; their table comes from one ingest into a small canvas
+            sshape = (h * 3 // 2, w) if src[0] == "nv12" else (h, w, 3)
+            imgs = [Frame(torch.from_numpy(rng.randint(0, 256, sshape).astype(np.uint8)).cuda(), src[0]) for _ in range(N)]
+            _, staged = ingest_frames_keep(imgs, torch.zeros((N, 16, 32, 3), dtype=torch.uint8, device="cuda"),
+                                           torch.zeros((N, 3, 3), device="cuda"))
+            call = lambda: emit_source_frames(staged, pts, valid, sinks)
+        else:
+            imgs = torch.from_numpy(rng.randint(0, 256, (N, h, w, 3)).astype(np.uint8)).cuda()
+            call = lambda: emit_frames(imgs, pts, valid, sinks)
         for _ in range(WARM):
-            emit_frames(imgs, pts, valid, sinks)
+            call()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(args.launches):
-            emit_frames(imgs, pts, valid, sinks)
+            call()
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / args.launches

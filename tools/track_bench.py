@@ -10,6 +10,8 @@ each; the table gives the median and the spread (max - min) / median.
   python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p[,nv12-1080p-lens]   (graphs only, the variants alternated)
   python tools/track_bench.py --streams 32 --emit nv12 [--emit-host]            (graphs only: no sinks / device sinks / pinned host sinks
                                                                                  of the working-resolution picture, alternated)
+  python tools/track_bench.py --streams 32 --ingest nv12-1080p --emit nv12 --emit-source [--emit-host]   (the same plus one SOURCE-view sink
+                                                                                 per stream: the camera's own 1080x1920 frame, NV12 pass-through)
   python tools/track_bench.py --streams 32 --health off,lax,verify10 [--lens 10000]   (graphs only: no HealthPolicy / every soft
                                                      gate off / the same with the detector's check every 10th tick; --lens: see health_policy)
   rocprofv3 --kernel-trace --stats -d DIR -o track -- python tools/track_bench.py --profile 32      (one configuration, graphs)
@@ -74,15 +76,15 @@ def native_frames(frames, K, mode):
     return out, (540, 960)
 
 
-def make_sinks(S, hw, fmt, host):
-    """One sink per stream for the smoothed picture at working resolution, in device memory or in pinned host memory; reused every tick
-    (a lane's emits are ordered on its stream)."""
+def make_sinks(S, hw, fmt, host, view="canvas"):
+    """One sink per stream for the smoothed picture, in device memory or in pinned host memory; reused every tick (a lane's emits are
+    ordered on its stream).  hw: the working resolution for canvas sinks, the camera frame's size for source-view sinks."""
     import torch
     from gen6d_amd.emit import Sink
     h, w = hw
     shape = (h * 3 // 2, w) if fmt == "nv12" else (h, w, 3)
     mk = (lambda: torch.zeros(shape, dtype=torch.uint8).pin_memory()) if host else (lambda: torch.zeros(shape, dtype=torch.uint8, device="cuda"))
-    return [Sink(mk(), fmt) for _ in range(S)]
+    return [Sink(mk(), fmt, view=view) for _ in range(S)]
 
 
 def health_policy(mode):
@@ -98,10 +100,10 @@ def health_policy(mode):
     return {"health": HealthPolicy.lax(verify_every={"lax": 0, "verify10": 10}[mode])}
 
 
-def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=False, health=None, lost=None):
+def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=False, health=None, lost=None, emit_view="canvas"):
     """-> (seconds of the timed ticks, timed ticks).  lost: a list that receives the number of LOST streams at the end of a health run.  ingest: None (plain frames, the tracker without frame_size) or a mode of
-    native_frames.  emit: None, or the format of one sink per stream filled on every push (emit_host: pinned host sinks).  health: a
-    mode of health_policy."""
+    native_frames.  emit: None, or the format of one sink per stream filled on every push (emit_host: pinned host sinks; emit_view
+    "source": the camera's own frame at its own size, which needs an ingest mode).  health: a mode of health_policy."""
     import torch
     from gen6d_amd.tracking import StreamTracker
     ids = list(range(S))
@@ -115,7 +117,12 @@ def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=F
         tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas, **hk)
         Ks = None
     frame = lambda s, t: frames[(7 * s + t) % len(frames)]
-    kw = {"sinks": make_sinks(S, canvas, emit, emit_host)} if emit else {}
+    if emit and emit_view == "source":
+        if ingest in (None, "none"):
+            sys.exit("track_bench: source-view sinks need camera frames (--ingest same / nv12-1080p)")
+        kw = {"sinks": make_sinks(S, (frames[0].height, frames[0].width), emit, emit_host, "source")}
+    else:
+        kw = {"sinks": make_sinks(S, canvas, emit, emit_host)} if emit else {}
     for t in range(2):                                  # first frames, then the tick that captures the lanes' graphs
         tr.push(ids, [frame(s, t) for s in ids], Ks, **kw)
     tr.result()
@@ -185,6 +192,8 @@ def main():
     ap.add_argument("--emit", default=None, choices=["nv12", "rgb24"], help="graphs runs without sinks and with one device sink of this "
                     "format per stream, alternated (with --profile: the profiled run emits)")
     ap.add_argument("--emit-host", action="store_true", help="--emit: pinned host sinks as a third variant (--profile: instead of device sinks)")
+    ap.add_argument("--emit-source", action="store_true", help="--emit: one source-view sink per stream (the camera's own frame at its own "
+                    "size; needs --ingest) as further variants (--profile: instead of the canvas sinks)")
     ap.add_argument("--tick-ms", type=float, default=0.0)
     ap.add_argument("--health", default=None, help="comma list of off / lax / verify10: graphs runs "
                     "with these health policies, alternated (with --profile: the one policy of the profiled run)")
@@ -206,8 +215,10 @@ def main():
         K = (np.asarray(K, np.float32) * np.array([[args.lens, 1, 1], [1, args.lens, 1], [1, 1, 1]])).astype(np.float32)
     if args.profile:
         S = args.profile
-        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest, args.emit, args.emit_host, args.health)
-        print(f"profile S={S} ingest={args.ingest} emit={args.emit}{' (host)' if args.emit and args.emit_host else ''} "
+        dt, n = run(est, frames, K, S, args.frames, args.batch or min(S, 8), True, args.ingest, args.emit, args.emit_host, args.health,
+                    emit_view="source" if args.emit_source else "canvas")
+        print(f"profile S={S} ingest={args.ingest} emit={args.emit}{' (host)' if args.emit and args.emit_host else ''}"
+              f"{' (source view)' if args.emit and args.emit_source else ''} "
               f"health={args.health}: {n} ticks, "
               f"{dt / n * 1e3:.3f} ms/tick")
         return
@@ -224,11 +235,14 @@ def main():
               "check on every 10th tick; lost: streams LOST at the end of each run.")
     elif args.emit:
         dev = {"ingest": args.ingest, "emit": args.emit}
+        src = dict(dev, emit_view="source")
         sweep(est, frames, K, args, configs,
-              [("none", {"ingest": args.ingest}), ("device", dev)] + ([("host", dict(dev, emit_host=True))] if args.emit_host else []), "sinks",
+              [("none", {"ingest": args.ingest}), ("device", dev)] + ([("host", dict(dev, emit_host=True))] if args.emit_host else []) +
+              ([("source", src)] + ([("source-host", dict(src, emit_host=True))] if args.emit_host else []) if args.emit_source else []), "sinks",
               f"Tracked frames/s with annotated frame output (tools/track_bench.py --emit {args.emit})",
               graphs + each + f"variant, alternated.  none: no sinks; device: one {args.emit} device sink per stream and frame (the smoothed "
-              "picture at working resolution); host: the same into pinned host memory, copy included.")
+              "picture at working resolution); host: the same into pinned host memory, copy included; source / source-host: one "
+              "source-view sink per stream instead (the camera's own frame at its own size with the box in source pixels).")
     elif args.ingest:
         sweep(est, frames, K, args, configs, [(m, {"ingest": m}) for m in args.ingest.split(",")], "frames",
               "Tracked frames/s by frame source (tools/track_bench.py --ingest)",
