@@ -240,6 +240,19 @@ __device__ __forceinline__ void c16_stats_flush(const C16Params& p, const C16Seg
   }
 }
 
+// A banded tile (several small images per tile, conv16w_kernel) may span several statistics groups; the launcher then admits only
+// groups of whole epilogue passes, and the wave-private sums are flushed after EVERY pass under the pass's own group (g = the pass's
+// first row of the tall image; a pass past the last image holds no valid pixel and flushes nothing) and start again from zero.
+template <int CH>
+__device__ __forceinline__ void c16_stats_flush_pass(const C16Params& p, const C16Seg& sg, int lane, int cbase, int g, double (&wst)[2]) {
+  if (g < sg.rows) c16_stats_flush<CH>(p, sg, lane, cbase, g, wst);      // (block-uniform: every lane takes part)
+  wst[0] = 0.0; wst[1] = 0.0;
+}
+// (block-uniform) the tile of TH rows x W columns holds more than one statistics group
+__device__ __forceinline__ bool c16w_stats_per_pass(const C16Params& p, const C16Seg& sg, int tw_log2) {
+  return p.stats != nullptr && p.stat_rows_per_group > 0 && p.stat_rows_per_group < (C16_BM >> tw_log2) * sg.W;
+}
+
 // Epilogue of the per-tap kernels: two passes of 64 channels through ONE fp32 LDS tile.
 template <int MM, typename WriteTile>
 __device__ __forceinline__ void c16_epilogue(const C16Params& p, const C16Seg& sg, char* lds, int tid, int nt, int g0, int x0, int tw_log2, int ylim,
@@ -878,8 +891,10 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
     unsigned amax = 0;
     double wst[2] = {0.0, 0.0};
-    // the passes, specialised on the launch's output format (full_type, pool_type, statistics: -1 = read from p in the pass)
-    auto passes = [&](auto ftc, auto ptc, auto stc) {
+    // the passes, specialised on the launch's output format (full_type, pool_type, statistics: -1 = read from p in the pass) and on where
+    // the statistics are flushed (spc: 0 = once per tile by the caller, 1 = after every pass under the pass's own group, -1 = per_pass)
+    const bool per_pass = c16w_stats_per_pass(p, sg, f_tw_log2);
+    auto passes = [&](auto ftc, auto ptc, auto stc, auto spc) {
 #pragma unroll
       for (int ps = 0; ps < 8 / MTP; ++ps) {
 #pragma unroll
@@ -895,17 +910,22 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
             }
         c16_epilogue_pass<2, 64, R::NPX, CW, decltype(ftc)::value, decltype(ptc)::value, decltype(stc)::value>(
             p, sg, ep, nullptr, lane, chan0, gm.t.g0, gm.t.x0, f_tw_log2, gm.t.ylim, ps * R::NPX, amax, wst);
+        if (decltype(spc)::value > 0 || (decltype(spc)::value < 0 && per_pass))
+          c16_stats_flush_pass<CW>(p, sg, lane, chan0, gm.t.g0 + ((ps * R::NPX) >> f_tw_log2), wst);
       }
     };
     typedef std::integral_constant<int, -1> any_;
     typedef std::integral_constant<int, 0> c0_;
+    typedef std::integral_constant<int, 1> c1_;
     // the trunks' forms (pair outputs, no statistics) and the selector's (fp32 map and statistics); anything else: the general form
-    if (!p.stats && p.full_type == 3 && p.pool_type == 0) passes(std::integral_constant<int, 3>{}, c0_{}, c0_{});
-    else if (!p.stats && p.full_type == 0 && p.pool_type == 3) passes(c0_{}, std::integral_constant<int, 3>{}, c0_{});
-    else if (!p.stats && p.full_type == 3 && p.pool_type == 3) passes(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, c0_{});
-    else if (p.stats && p.full_type == 2 && p.pool_type == 0) passes(std::integral_constant<int, 2>{}, c0_{}, std::integral_constant<int, 1>{});
-    else passes(any_{}, any_{}, any_{});
-    if (p.stats) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
+    // (and the feature net's 8 x 8 maps: the same with one statistics group per pass)
+    if (!p.stats && p.full_type == 3 && p.pool_type == 0) passes(std::integral_constant<int, 3>{}, c0_{}, c0_{}, c0_{});
+    else if (!p.stats && p.full_type == 0 && p.pool_type == 3) passes(c0_{}, std::integral_constant<int, 3>{}, c0_{}, c0_{});
+    else if (!p.stats && p.full_type == 3 && p.pool_type == 3) passes(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{}, c0_{}, c0_{});
+    else if (p.stats && p.full_type == 2 && p.pool_type == 0 && !per_pass) passes(std::integral_constant<int, 2>{}, c0_{}, c1_{}, c0_{});
+    else if (p.stats && p.full_type == 2 && p.pool_type == 0) passes(std::integral_constant<int, 2>{}, c0_{}, c1_{}, c1_{});
+    else passes(any_{}, any_{}, any_{}, any_{});
+    if (p.stats && !per_pass) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
     g6d_range_record(p.rng, amax);
   } else {
     // ---- fragment geometry of this wave's tile: m-tile mt = tile pixels 32 mt + (lane & 31) -> patch row of tap (0, 0)
@@ -1022,6 +1042,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     const float as = ldexpf(p.acc_scale, g6d_exp_in(p.rng));     // pair input held as x * 2^-e_in
     unsigned amax = 0;
     double wst[2] = {0.0, 0.0};
+    const bool per_pass = c16w_stats_per_pass(p, sg, f_tw_log2);
     auto passes = [&](auto ftc, auto ptc, auto stc) {              // (specialised on the output format as in the pair branch)
 #pragma unroll
       for (int ps = 0; ps < 4 / MTP; ++ps) {
@@ -1038,6 +1059,8 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
             }
         c16_epilogue_pass<MM, 64, R::NPX, CW, decltype(ftc)::value, decltype(ptc)::value, decltype(stc)::value>(
             p, sg, ep, nullptr, lane, chan0, gm.t.g0, gm.t.x0, f_tw_log2, gm.t.ylim, ps * R::NPX, amax, wst);
+        if (decltype(stc)::value != 0 && per_pass)                   // (statistics run on the general form only)
+          c16_stats_flush_pass<CW>(p, sg, lane, chan0, gm.t.g0 + ((ps * R::NPX) >> f_tw_log2), wst);
       }
     };
     typedef std::integral_constant<int, -1> any_;
@@ -1047,7 +1070,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     else if (!p.stats && p.full_type == 0 && p.pool_type == 1) passes(c0_{}, c1_{}, c0_{});
     else if (!p.stats && p.full_type == 1 && p.pool_type == 1) passes(c1_{}, c1_{}, c0_{});
     else passes(any_{}, any_{}, any_{});
-    if (p.stats) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
+    if (p.stats && !per_pass) c16_stats_flush<CW>(p, sg, lane, chan0, gm.t.g0, wst);
     if (p.full_type == 3 || p.pool_type == 3) g6d_range_record(p.rng, amax);
   }
 }
@@ -1116,8 +1139,10 @@ __global__ void __launch_bounds__(256) product_split_kernel(const float* __restr
 // kernel cannot.  HBM-bound elementwise pass; image n uses table n / per_n (0: one table).
 template <int MM>
 __global__ void __launch_bounds__(256) affine_split16_kernel(const float* __restrict__ in, int ld_in, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                            int per_n, int relu, int pool, int H, int W, int C, char* __restrict__ out, long total,
-                                                            const G6dRange16 rng) {
+                                                            int per_n, int relu, int pool, int H, int W, int C, char* __restrict__ out, int ld_out,
+                                                            int plane, long total, const G6dRange16 rng) {
+  // out: the map's channel 0 of pixel 0 inside rows of ld_out 16-bit elements, the lo plane `plane` elements after the hi plane (dense:
+  // ld_out = 2 C, plane = C; a channel slice of a wider pair map: that map's row length and channel count)
   typedef typename C16T3<MM>::T T;
   typedef typename C16T3<MM>::V V8;
   const int c8 = C >> 3, Ho = pool ? H >> 1 : H, Wo = pool ? W >> 1 : W;
@@ -1163,11 +1188,133 @@ __global__ void __launch_bounds__(256) affine_split16_kernel(const float* __rest
       V8 lo;
 #pragma unroll
       for (int e = 0; e < 8; ++e) lo[e] = (T)(v[e] - (float)hi[e]);
-      char* o = out + (r * 2 * C + c) * 2;
+      char* o = out + (r * ld_out + c) * 2;
       *reinterpret_cast<V8*>(o) = hi;
-      *reinterpret_cast<V8*>(o + (long)C * 2) = lo;
+      *reinterpret_cast<V8*>(o + (long)plane * 2) = lo;
     } else {
-      *reinterpret_cast<V8*>(out + (r * C + c) * 2) = hi;
+      *reinterpret_cast<V8*>(out + (r * ld_out + c) * 2) = hi;
+    }
+  }
+  if constexpr (MM == 3) g6d_range_record_block<4>(rng, amax);
+}
+
+// upsample_split16_kernel: g6d_upsample_bilinear (x f, align_corners = False, the per-image InstanceNorm affine applied to the four
+// neighbours: the arithmetic of upsample_bilinear_kernel, elementwise.hip) written in the 16-bit activation format — the ends of the
+// feature net's 16 x 16 / 8 x 8 branches (reference network/refiner.py:72-76), which land in their channel slice of the pair `cat` map.
+// out / ld_out / plane: as affine_split16_kernel.
+__device__ __forceinline__ f32x4 c16_aff4(f32x4 v, f32x4 sc, f32x4 sh, bool has) {
+  if (has) v = v * sc + sh;
+  return v;
+}
+template <int MM>
+__global__ void __launch_bounds__(256) upsample_split16_kernel(const float* __restrict__ in, int ld_in, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, int per_n, int H, int W, int C, int f, char* __restrict__ out,
+                                                              int ld_out, int plane, long total, const G6dRange16 rng) {
+  typedef typename C16T3<MM>::T T;
+  typedef typename C16T3<MM>::V V8;
+  const int c8 = C >> 3, Ho = H * f, Wo = W * f;
+  const float rs = 1.f / (float)f;
+  const int eo = MM == 3 ? g6d_exp_out(rng) : 0;
+  unsigned amax = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % c8) * 8;
+    const long r = i / c8;                                     // output pixel (n Ho + y) Wo + x
+    const int x = (int)(r % Wo);
+    const long ny = r / Wo;
+    const int y = (int)(ny % Ho);
+    const long n = ny / Ho;
+    float sy = rs * (y + 0.5f) - 0.5f; if (sy < 0.f) sy = 0.f;
+    float sx = rs * (x + 0.5f) - 0.5f; if (sx < 0.f) sx = 0.f;
+    const int y0 = (int)sy, x0 = (int)sx;
+    const int y1 = y0 + (y0 < H - 1), x1 = x0 + (x0 < W - 1);
+    const float ly = sy - y0, lx = sx - x0, hy = 1.f - ly, hx = 1.f - lx;
+    const bool has = scale != nullptr;
+    const float* b = in + (size_t)n * H * W * ld_in + c;
+    float v[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                              // the fp32 kernel's item: four channels
+      f32x4 sc = {1, 1, 1, 1}, sh = {0, 0, 0, 0};
+      if (has) {
+        const size_t o = (size_t)(per_n ? n / per_n : 0) * C + c + 4 * h;
+        sc = *reinterpret_cast<const f32x4*>(scale + o); sh = *reinterpret_cast<const f32x4*>(shift + o);
+      }
+      const f32x4 v00 = c16_aff4(*reinterpret_cast<const f32x4*>(b + ((size_t)y0 * W + x0) * ld_in + 4 * h), sc, sh, has);
+      const f32x4 v01 = c16_aff4(*reinterpret_cast<const f32x4*>(b + ((size_t)y0 * W + x1) * ld_in + 4 * h), sc, sh, has);
+      const f32x4 v10 = c16_aff4(*reinterpret_cast<const f32x4*>(b + ((size_t)y1 * W + x0) * ld_in + 4 * h), sc, sh, has);
+      const f32x4 v11 = c16_aff4(*reinterpret_cast<const f32x4*>(b + ((size_t)y1 * W + x1) * ld_in + 4 * h), sc, sh, has);
+      const f32x4 u = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[4 * h + e] = u[e];
+    }
+    if constexpr (MM == 3) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { amax = max(amax, g6d_abs_bits(v[e])); v[e] = ldexpf(v[e], -eo); }
+    }
+    V8 hi;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) hi[e] = (T)v[e];
+    char* o = out + (r * ld_out + c) * 2;
+    *reinterpret_cast<V8*>(o) = hi;
+    if constexpr (MM == 3) {
+      V8 lo;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) lo[e] = (T)(v[e] - (float)hi[e]);
+      *reinterpret_cast<V8*>(o + (long)plane * 2) = lo;
+    }
+  }
+  if constexpr (MM == 3) g6d_range_record_block<4>(rng, amax);
+}
+
+// l2norm_split16_kernel: F.normalize over the channels of an fp32 channels-last tap (the arithmetic of l2norm_rows_kernel, elementwise.hip:
+// one wave per pixel, lane l sums channels 4 l .. 4 l + 3 of every 256-channel chunk, the same wave reduction) written in the 16-bit
+// activation format instead of in place — the trunk's taps on their way into the feature net's first convs (reference
+// network/refiner.py:69-71).  The row stays in registers between the two steps (NCH chunks of 256 channels): 4 bytes read and 4 (2)
+// written per value.  16-byte stores: lanes 2 j and 2 j + 1 hold channels 8 j .. 8 j + 7 of a chunk — the even lane stores their hi
+// halves, the odd lane their lo halves (16-bit modes: the even lane stores the eight values).
+template <int MM, int NCH>
+__global__ void __launch_bounds__(256) l2norm_split16_kernel(const float* __restrict__ x, int ld_in, int rows, char* __restrict__ out, const G6dRange16 rng) {
+  typedef typename C16T3<MM>::T T;
+  typedef T T4 __attribute__((ext_vector_type(4)));
+  constexpr int C = 256 * NCH;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int eo = MM == 3 ? g6d_exp_out(rng) : 0;
+  unsigned amax = 0;
+  if (row < rows) {                                            // (wave-uniform; no return before the block-wide record)
+    const float* p = x + (size_t)row * ld_in;
+    f32x4 v[NCH];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      v[k] = *reinterpret_cast<const f32x4*>(p + lane * 4 + 256 * k);
+      s += v[k][0] * v[k][0] + v[k][1] * v[k][1] + v[k][2] * v[k][2] + v[k][3] * v[k][3];
+    }
+    const float inv = 1.f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+    char* o = out + (size_t)row * (MM == 3 ? 2 * C : C) * 2;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const f32x4 u = v[k] * inv;
+      T4 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float w = u[e];
+        if constexpr (MM == 3) { amax = max(amax, g6d_abs_bits(w)); w = ldexpf(w, -eo); }
+        hi[e] = (T)w; lo[e] = (T)(w - (float)hi[e]);
+      }
+      // the partner lane needs: (even lane) the odd lane's hi halves, (odd lane) the even lane's lo halves
+      const bool odd = lane & 1;
+      uint2 mine_hi, mine_lo;
+      __builtin_memcpy(&mine_hi, &hi, 8); __builtin_memcpy(&mine_lo, &lo, 8);
+      const uint2 send = odd ? mine_hi : mine_lo;
+      uint2 recv;
+      recv.x = (unsigned)__shfl_xor((int)send.x, 1, 64); recv.y = (unsigned)__shfl_xor((int)send.y, 1, 64);
+      const int c = (lane >> 1) * 8 + 256 * k;
+      if (!odd) {
+        const uint4 q = {mine_hi.x, mine_hi.y, recv.x, recv.y};
+        *reinterpret_cast<uint4*>(o + c * 2) = q;
+      } else if constexpr (MM == 3) {
+        const uint4 q = {recv.x, recv.y, mine_lo.x, mine_lo.y};
+        *reinterpret_cast<uint4*>(o + (C + c) * 2) = q;
+      }
     }
   }
   if constexpr (MM == 3) g6d_range_record_block<4>(rng, amax);
@@ -1459,9 +1606,11 @@ int c16_pick_tw(int W, int pool) {
 
 }  // namespace
 
-extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
-                                          const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,
-                                          int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream) {
+namespace {
+// g6d_conv16_direct_multi_ex; plan_only: validate and choose the kernel, launch nothing (g6d_conv16_direct_plan's return value)
+int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale, const float* bias, int Cout, int kd, int relu,
+               int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream,
+               bool plan_only) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("conv16_direct: 1..4 segments and filters expected"); return G6D_EINVAL; }
   if (math_mode < 1 || math_mode > 3 || (w_layout != 0 && w_layout != 1) || (math_mode == 3 && w_layout != 1)) {
     g6d_set_error("conv16_direct: math_mode 1 (bf16) / 2 (fp16) / 3 (fp16 hi-lo pairs, fragment-major filters only)"); return G6D_EINVAL;
@@ -1485,6 +1634,7 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
   p.w_bytes = (unsigned)wb;
   p.nN = Cout / C16_BN;
   int tiles = 0, D0 = segs[0].D;
+  bool pertap_stats_ok = true;
   for (int i = 0; i < nseg; ++i) {
     const G6dConv16Seg& s = segs[i];
     C16Seg& o = p.seg[i];
@@ -1505,7 +1655,8 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
     int l2 = 0; while ((1 << l2) < tw) ++l2;
     o.tw_log2 = l2; o.tiles_x = (s.W + tw - 1) / tw; o.tile0 = tiles;
     const int th = C16_BM / tw;
-    if (stats && stat_rows_per_group > 0 && ((long)stat_rows_per_group % ((long)th * s.W) != 0)) { g6d_set_error("conv16_direct: statistics groups must be whole tile rows"); return G6D_EINVAL; }
+    // (the per-tap kernels flush a tile's statistics under ONE group; the halo-patch kernel has its own rule below)
+    if (stats && stat_rows_per_group > 0 && ((long)stat_rows_per_group % ((long)th * s.W) != 0)) pertap_stats_ok = false;
     tiles += o.tiles_x * ((o.rows + th - 1) / th);
     // the descriptor starts (kd == 3 ? H W : 0) + W + 1 pixels before the tensor: tap offsets are then non-negative
     const long back = ((long)(kd == 3 ? s.H * s.W : 0) + s.W + 1) * s.ld_in * 2;
@@ -1518,7 +1669,7 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
   hipStream_t st = static_cast<hipStream_t>(stream);
   // fragment-major filters, 2-D layer: the halo-patch kernel when every segment has a tiling for it (knob conv16_halo = 0: never)
   if (w_layout == 1 && kd == 1 && g6d_knob(G6D_KNOB_CONV16_HALO) != 0) {
-    bool ok = true;
+    bool ok = true, per_pass = false;
     int htiles = 0;
     for (int i = 0; i < nseg && ok; ++i) {
       int nt_ = 0;
@@ -1527,8 +1678,14 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
       if (stats && stat_rows_per_group > 0 && ok) {
         const C16Seg& o = p.seg[i];
         const int th = C16_BM >> o.h_tw_log2;
-        // a tile must lie inside one statistics group: in-image tiles do when groups are whole images; tiles of whole images when the group is too
-        ok = (stat_rows_per_group % (segs[i].H * segs[i].W) == 0) && (o.h_tpi > 0 || ((long)stat_rows_per_group % ((long)th * segs[i].W) == 0));
+        // groups are whole images.  In-image tiles then lie inside one group; a banded tile (whole small images) does when the group is
+        // whole tiles, or else spans groups of whole epilogue passes (flushed per pass).  A group smaller than a pass, or not aligned to
+        // one, has no place to be summed: no halo tiling, and the per-tap kernels reject it too
+        const long tile_px = (long)th * segs[i].W, pass_px = (long)(C16W<3>::NPX >> o.h_tw_log2) * segs[i].W;
+        static_assert(C16W<1>::NPX == C16W<3>::NPX && C16W<2>::NPX == C16W<3>::NPX, "one pass size in every mode");
+        ok = (stat_rows_per_group % (segs[i].H * segs[i].W) == 0) &&
+             (o.h_tpi > 0 || stat_rows_per_group % tile_px == 0 || (stat_rows_per_group < tile_px && stat_rows_per_group % pass_px == 0));
+        per_pass = per_pass || (ok && stat_rows_per_group < tile_px);       // (what c16w_stats_per_pass finds in the kernel)
       }
     }
     if (!ok && half_tile) { g6d_set_error("conv16_direct: Cout = 64 needs a halo tiling for every segment"); return G6D_EINVAL; }
@@ -1538,6 +1695,7 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
       const int wm = Cout % (4 * cw) == 0 ? 1 : 2;
       p.ptiles = htiles;
       p.nN = Cout / (cw * (4 / wm));
+      if (plan_only) return per_pass ? 2 : 1;
       const int hblocks = ((htiles + wm - 1) / wm + 7) / 8 * 8 * p.nN;
       auto launch = [&](auto kern, int main_lds, int ep_lds) {
         const int bytes = main_lds > ep_lds ? main_lds : ep_lds;
@@ -1557,6 +1715,8 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
     }
   }
   if (half_tile) { g6d_set_error("conv16_direct: Cout = 64 runs on the halo-patch kernel only (knob conv16_halo, tile shapes)"); return G6D_EINVAL; }
+  if (!pertap_stats_ok) { g6d_set_error("conv16_direct: statistics groups must be whole tile rows (small maps: whole 64-pixel epilogue passes)"); return G6D_EINVAL; }
+  if (plan_only) return 0;
   const int blocks = (tiles + 7) / 8 * 8 * p.nN;
   if (w_layout == 0) {
     if (math_mode == 1) {
@@ -1580,6 +1740,20 @@ extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, in
     hipLaunchKernelGGL((conv16r_kernel<3, NST>), dim3(blocks), dim3(256), LDSR, st, p);
   }
   return g6d_check_launch("conv16r_direct");
+}
+}  // namespace
+
+extern "C" int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
+                                          const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,
+                                          int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream) {
+  return c16_direct(segs, nseg, Cin, W16, w_layout, acc_scale, bias, Cout, kd, relu, full_type, pool_type, math_mode, stats, stat_rows_per_group, range,
+                    stream, false);
+}
+
+extern "C" int g6d_conv16_direct_plan(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, int Cout, int kd, int full_type,
+                                      int pool_type, int math_mode, double* stats, int stat_rows_per_group) {
+  return c16_direct(segs, nseg, Cin, W16, w_layout, 1.f, nullptr, Cout, kd, 0, full_type, pool_type, math_mode, stats, stat_rows_per_group, nullptr,
+                    nullptr, true);
 }
 
 extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
@@ -1669,21 +1843,76 @@ extern "C" int g6d_product_split16(const float* ref, const float* que, const flo
   return g6d_product_split16_ex(ref, que, scale, shift, out, qn, D, P, C, math_mode, nullptr, stream);
 }
 
-extern "C" int g6d_affine_split16_ex(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
-                                     int W, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream) {
+namespace {
+// The output of a producer that may write a channel slice of wider 16-bit rows: channels [c_off, c_off + C) of rows of ld_out elements
+// whose lo plane (pairs) lies `plane` elements after the hi plane.  Returns the slice's first byte, nullptr if it does not fit.
+char* c16_slice_out(void* out, int C, int ld_out, int plane, int c_off, int math_mode) {
+  const bool pairs = math_mode == 3;
+  if (!out || !g6d_aligned16(out) || ((ld_out | plane | c_off) & 7) || c_off < 0 || ld_out < 1) return nullptr;
+  if (pairs ? (plane < c_off + C || (long)plane + c_off + C > ld_out) : (c_off + C > ld_out)) return nullptr;
+  return static_cast<char*>(out) + (long)c_off * 2;
+}
+}  // namespace
+
+extern "C" int g6d_affine_split16_to(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
+                                     int W, int C, void* out, int ld_out, int plane, int c_off, int math_mode, const G6dRange16* range,
+                                     g6d_stream_t stream) {
   if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || ld_in < C || (ld_in & 3) || (scale && !shift) || affine_per_n < 0 || math_mode < 1 ||
       math_mode > 3 || (pool && ((H | W) & 1)) || !g6d_aligned16(in) || !g6d_aligned16(out) || (scale && (!g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("affine_split16: bad args (C % 8 == 0, 16-byte aligned rows, even map with pooling, math_mode 1..3)"); return G6D_EINVAL;
   }
+  char* o = c16_slice_out(out, C, ld_out, plane, c_off, math_mode);
+  if (!o) { g6d_set_error("affine_split16: the channel slice does not fit the output rows (multiples of 8, c_off + C <= plane, plane + c_off + C <= ld_out)"); return G6D_EINVAL; }
   const long total = (long)N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C >> 3);
   const int blocks = (int)((total + 255) / 256 < 256 * 64 ? (total + 255) / 256 : 256 * 64);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const G6dRange16 rng = range ? *range : G6dRange16{};
+  if (math_mode == 1) hipLaunchKernelGGL(affine_split16_kernel<1>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, ld_out, plane, total, rng);
+  else if (math_mode == 2) hipLaunchKernelGGL(affine_split16_kernel<2>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, ld_out, plane, total, rng);
+  else hipLaunchKernelGGL(affine_split16_kernel<3>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, ld_out, plane, total, rng);
+  return g6d_check_launch("affine_split16");
+}
+
+extern "C" int g6d_affine_split16_ex(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
+                                     int W, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream) {
+  return g6d_affine_split16_to(in, ld_in, scale, shift, affine_per_n, relu, pool, N, H, W, C, out, math_mode == 3 ? 2 * C : C, C, 0, math_mode, range, stream);
+}
+
+extern "C" int g6d_upsample_bilinear_split16(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int N, int H, int W, int C,
+                                             int factor, void* out, int ld_out, int plane, int c_off, int math_mode, const G6dRange16* range,
+                                             g6d_stream_t stream) {
+  if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || ld_in < C || (ld_in & 3) || (scale && !shift) || affine_per_n < 0 || factor < 1 ||
+      math_mode < 1 || math_mode > 3 || !g6d_aligned16(in) || (scale && (!g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
+    g6d_set_error("upsample_bilinear_split16: bad args (C % 8 == 0, 16-byte aligned rows, factor >= 1, math_mode 1..3)"); return G6D_EINVAL;
+  }
+  char* o = c16_slice_out(out, C, ld_out, plane, c_off, math_mode);
+  if (!o) { g6d_set_error("upsample_bilinear_split16: the channel slice does not fit the output rows (multiples of 8, c_off + C <= plane, plane + c_off + C <= ld_out)"); return G6D_EINVAL; }
+  const long total = (long)N * H * factor * W * factor * (C >> 3);
+  const int blocks = (int)((total + 255) / 256 < 256 * 64 ? (total + 255) / 256 : 256 * 64);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const G6dRange16 rng = range ? *range : G6dRange16{};
+  if (math_mode == 1) hipLaunchKernelGGL(upsample_split16_kernel<1>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, H, W, C, factor, o, ld_out, plane, total, rng);
+  else if (math_mode == 2) hipLaunchKernelGGL(upsample_split16_kernel<2>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, H, W, C, factor, o, ld_out, plane, total, rng);
+  else hipLaunchKernelGGL(upsample_split16_kernel<3>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, H, W, C, factor, o, ld_out, plane, total, rng);
+  return g6d_check_launch("upsample_bilinear_split16");
+}
+
+extern "C" int g6d_l2norm_split16(const float* in, int ld_in, int rows, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream) {
+  if (!in || !out || rows < 1 || (C != 256 && C != 512) || ld_in < C || (ld_in & 3) || math_mode < 1 || math_mode > 3 || !g6d_aligned16(in) || !g6d_aligned16(out)) {
+    g6d_set_error("l2norm_split16: bad args (C = 256 or 512, 16-byte aligned rows, math_mode 1..3)"); return G6D_EINVAL;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
   char* o = static_cast<char*>(out);
   const G6dRange16 rng = range ? *range : G6dRange16{};
-  if (math_mode == 1) hipLaunchKernelGGL(affine_split16_kernel<1>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
-  else if (math_mode == 2) hipLaunchKernelGGL(affine_split16_kernel<2>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
-  else hipLaunchKernelGGL(affine_split16_kernel<3>, dim3(blocks), dim3(256), 0, st, in, ld_in, scale, shift, affine_per_n, relu, pool, H, W, C, o, total, rng);
-  return g6d_check_launch("affine_split16");
+  const dim3 grid((rows + 3) / 4);
+#define L2S_LAUNCH(MM_) \
+  do { if (C == 256) hipLaunchKernelGGL((l2norm_split16_kernel<MM_, 1>), grid, dim3(256), 0, st, in, ld_in, rows, o, rng); \
+       else hipLaunchKernelGGL((l2norm_split16_kernel<MM_, 2>), grid, dim3(256), 0, st, in, ld_in, rows, o, rng); } while (0)
+  if (math_mode == 1) L2S_LAUNCH(1);
+  else if (math_mode == 2) L2S_LAUNCH(2);
+  else L2S_LAUNCH(3);
+#undef L2S_LAUNCH
+  return g6d_check_launch("l2norm_split16");
 }
 
 extern "C" int g6d_affine_split16(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H, int W,

@@ -4,6 +4,8 @@ One refinement step (reference forward, refiner.py:249-269):
     own channels-last Winograd trunk (backbone.py) on the 6 reference crops + the query crop, g6d_l2norm_rows on its taps
     RefineFeatureNet 2-D convs on g6d_conv_igemm; every InstanceNorm2d is a per-image (sum, sumsq) epilogue of the
         producing conv and an affine(+ReLU) in the loader of the consuming conv / up-sampler      refiner.py:24-51,64-78
+        (batched calls of the fp32 path: on fp16 hi / lo pairs, g6d_conv16_direct_multi with g6d_l2norm_split16, g6d_affine_split16 and
+        the slice producers g6d_affine_split16_to / g6d_upsample_bilinear_split16 as hand-over passes — FEATNET_PAIR_BRANCHES)
     g6d_refiner_volume: projection + bilinear sampling + mean/std over references, fused            refiner.py:183-247
     RefineVolumeEncodingNet 3x3x3 convs on g6d_conv_igemm (32^3 layers: Winograd F(4x4,3x3), depth taps folded into the reduction;
         16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K)
@@ -29,6 +31,11 @@ F43_MIN_QUERIES = 4
 # (profiles/r04_layer_table_featnet_f43.md): 512->256 @16x16 159 vs 173 us, 192->128 @32x32 119 vs 148, 128->128 @32x32 107 vs 129 kept;
 # 256->64 @32x32 131 vs 94, 256->64 @16x16 88 vs 60, 512->256 @8x8 108 vs 80 stay on F(2x2,3x3)
 FEATNET_F43_LAYERS = {("conv1", 0), ("conv_out", 0), ("conv_out", 3)}
+# feature-net branches (two 3x3 layers each) that run on the fp16 hi / lo pair kernel (conv16w_kernel<3,.>, fp32-class products on the
+# 16-bit matrix cores) in the big calls of the fp32 path — decided per branch at 112 crops against the routes above, hand-over passes
+# included (tools/featnet_layers.py, profiles/r16_featnet_pairs.md).  A branch that is not listed keeps its route; run_feature_net joins
+# either kind (the branch ends write fp32 or pair slices of `cat` from the same fp32 map + affine)
+FEATNET_PAIR_BRANCHES = ("conv0", "conv1", "conv2", "conv_out")
 VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
@@ -163,12 +170,23 @@ class VolumeRefiner(ParamBank):
         n, _, h, w = imgs.shape
         dev = imgs.device
         big = (n >= F43_MIN_QUERIES * 7) if f43 is None else bool(f43)
+        rng = self._pair_rng()
+        # branches on the pair kernel: big calls of the fp32 path whose maps the kernel tiles (one statistics group per image)
+        on16 = self._featnet_pair_branches(n, h, w) if (big and rng is not None) else ()
         with self._mm("trunk"):
-            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), True, f43=big, rng=self._pair_rng(),
-                                        pairs=self.pairs_on)            # channels-last, L2-normalised
+            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), False, f43=big, rng=rng, pairs=self.pairs_on)   # channels-last
+
+        def tap(name, f, slot):
+            """The L2-normalised tap as the branch reads it: pairs (one pass that normalises and splits), or fp32 in place."""
+            if name in on16:
+                return ops.l2norm_split16(f[:, 0], 3, rng=(rng, rng.slot(slot)))
+            ops.l2norm_rows(f)                  # in place: a tap is never the input of a later layer
+            return f
 
         def pair(name, x):
             """conv, IN, ReLU, conv, (IN returned as affine) — per-image statistics."""
+            if name in on16:
+                return pair16(name, x)
             (w0, b0), (w1, b1) = pk[name]
             u0, u1 = pk[name][0].u, pk[name][1].u
             v0, v1 = (pk[name][0].u43, pk[name][1].u43) if big else (None, None)
@@ -182,26 +200,64 @@ class VolumeRefiner(ParamBank):
                                 stats=s1, rows_per_group=hh * ww, w_wino=u1, w_wino43=v1, finalize=hh * ww)
             return y1, sc1, sh1
 
+        def pair16(name, x):
+            """The same on the pair kernel (the selector's stack pattern): x a PairMap [n,hh,ww,2,Cin]; each conv writes its fp32 map and
+            adds the per-image sums in its epilogue, one small launch finalises them, and the InstanceNorm affine + ReLU between the two
+            convs is the elementwise pass that writes the second conv's pairs."""
+            _, hh, ww, _, _ = x.shape
+
+            def conv16(layer, xin):
+                co = layer[0].shape[0]
+                y = torch.empty((n, 1, hh, ww, co), dtype=torch.float32, device=dev)
+                st = ops.new_stats(n, co, dev)
+                ops.conv16_direct_multi([xin], layer.w16(3), layer[1], relu=False, full=torch.float32, stats=st, rows_per_group=hh * ww,
+                                        out_full=[y[:, 0]])
+                return (y,) + ops.stats_finalize(st, hh * ww)
+
+            y0, sc0, sh0 = conv16(pk[name][0], x)
+            mid = ops.affine_split16(y0, sc0, sh0, 1, True, False, 3, rng=(rng, rng.slot(f"featnet.{name}.mid")))
+            return conv16(pk[name][1], mid)
+
         hq, wq = h // 4, w // 4
-        cat = torch.empty((n, 1, hq, wq, 192), dtype=torch.float32, device=dev)
-        def b0():
-            y, sc, sh = pair("conv0", f3)
-            ops.affine_act_pool(y, cat[..., 0:64], sc, sh, per_n=True)
+        # the three branches meet in `cat`: pairs when conv_out reads them (the three slices share ONE exponent slot), else fp32
+        cat16 = "conv_out" in on16
+        cat = ops.new_map16(n, hq, wq, 192, 3, dev, rng=(rng, rng.slot("featnet.cat"))) if cat16 else \
+            torch.empty((n, 1, hq, wq, 192), dtype=torch.float32, device=dev)
 
-        def b1():
-            y, sc, sh = pair("conv1", f5)
-            ops.upsample_bilinear(y, cat[..., 64:128], 2, sc, sh, per_n=True)
-
-        def b2():
-            y, sc, sh = pair("conv2", f7)
-            ops.upsample_bilinear(y, cat[..., 128:192], 4, sc, sh, per_n=True)
+        def branch(name, f, slot, c_off, factor):
+            y, sc, sh = pair(name, tap(name, f, slot))
+            if cat16:
+                if factor == 1:
+                    ops.affine_split16_to(y, sc, sh, 1, False, 3, cat, c_off)
+                else:
+                    ops.upsample_bilinear_split16(y, cat, c_off, factor, sc, sh, 1, 3)
+            elif factor == 1:
+                ops.affine_act_pool(y, cat[..., c_off:c_off + 64], sc, sh, per_n=True)
+            else:
+                ops.upsample_bilinear(y, cat[..., c_off:c_off + 64], factor, sc, sh, per_n=True)
 
         with self._mm("featnet"):
-            ops.fork_join([b0, b1, b2], dev)
+            ops.fork_join([lambda: branch("conv0", f3, "featnet.f3", 0, 1), lambda: branch("conv1", f5, "featnet.f5", 64, 2),
+                           lambda: branch("conv2", f7, "featnet.f7", 128, 4)], dev)
             y, sc, sh = pair("conv_out", cat)
         out = torch.empty((n, 1, hq, wq, 128), dtype=torch.float32, device=dev)
         ops.affine_act_pool(y, out, sc, sh, per_n=True)
         return out.view(n, hq, wq, 128)
+
+    def _featnet_pair_branches(self, n, h, w):
+        """The branches of FEATNET_PAIR_BRANCHES whose maps, for n crops of h x w, the pair kernel tiles with one statistics group per image
+        (asked of the library's own validation, once per crop count and size); the others keep their routes."""
+        key = (n, h, w)
+        memo = self.__dict__.setdefault("_featnet16", {})
+        if key not in memo:
+            shapes = {"conv0": (4, 256, 64, 64), "conv1": (8, 512, 256, 64), "conv2": (16, 512, 256, 64), "conv_out": (4, 192, 128, 128)}
+
+            def fits(name):
+                d, ci, cm, co = shapes[name]
+                hh, ww = h // d, w // d
+                return all(ops.conv16_direct_plan(n, hh, ww, a, b, 3, stats_rows=hh * ww) in (1, 2) for a, b in ((ci, cm), (cm, co)))
+            memo[key] = tuple(name for name in FEATNET_PAIR_BRANCHES if h % 16 == 0 and w % 16 == 0 and fits(name))
+        return memo[key]
 
     # ------------------------------------------------------------------ 3-D volume net + regressor
     def run_volume_net(self, mean_in, std, sn):

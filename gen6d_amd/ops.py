@@ -826,6 +826,75 @@ def affine_split16(x, scale, shift, per_n, relu, pool, mode, rng=None):
     return _wrap(out, rng)
 
 
+def new_map16(N, H, W, Cc, mode, device, rng=None):
+    """An empty map in the activation format of conv16_direct_multi: [N,H,W,C] (mode 1 / 2) or [N,H,W,2,C] fp16 pairs (mode 3; with rng =
+    (RangeTable, slot) a PairMap of that slot) — the destination the slice producers below fill channel slice by channel slice."""
+    if rng is not None and mode != 3:
+        raise ValueError("new_map16: a range applies to pairs (mode 3) only")
+    return _wrap(torch.empty((N, H, W, 2, Cc) if mode == 3 else (N, H, W, Cc), dtype=_T16[mode], device=device), rng)
+
+
+def _slice16(out, N, Ho, Wo, Cc, c_off, mode, what):
+    """The channel slice [c_off, c_off + Cc) of the 16-bit map `out` (a new_map16 result) as the slice producers take it:
+    (tensor, ld_out, plane, range argument or None)."""
+    table, slot = (out.table, out.slot) if isinstance(out, PairMap) else (None, -1)
+    t = out.data if isinstance(out, PairMap) else out
+    if table is not None and mode != 3:
+        raise ValueError(f"{what}: a PairMap output needs mode 3")
+    _need_gpu(t)
+    Ct = t.shape[-1]
+    want = (N, Ho, Wo, 2, Ct) if mode == 3 else (N, Ho, Wo, Ct)
+    if t.dtype != _T16[mode] or not t.is_contiguous() or tuple(t.shape) != want or c_off < 0 or c_off % 8 or Ct % 8 or c_off + Cc > Ct:
+        raise ValueError(f"{what}: out must be a dense {_T16[mode]} map of shape {want[:-1]} + (C,) that holds channels [{c_off}, {c_off + Cc})")
+    return t, (2 * Ct if mode == 3 else Ct), Ct, (C.byref(table.arg(-1, slot)) if table is not None else None)
+
+
+def affine_split16_to(x, scale, shift, per_n, relu, mode, out, c_off=0):
+    """affine_split16 (no pooling) into channels [c_off, c_off + C) of the wider 16-bit map `out` (new_map16; g6d_affine_split16_to): nothing
+    else of a row is touched.  A PairMap `out` gives the exponent and the record slot: the slices of one map share them.  Returns out."""
+    _need_gpu(x)
+    N, D, H, W, Cc, ld_in = _cl5(x, "affine_split16_to.x")
+    if D != 1:
+        raise ValueError("affine_split16_to: 2-D maps expected")
+    t, ld_out, plane, ra = _slice16(out, N, H, W, Cc, c_off, mode, "affine_split16_to")
+    _timed_hbm("affine_split16", (4.0 + (4.0 if mode == 3 else 2.0)) * N * H * W * Cc, lambda: _lib.check(_lib.load().g6d_affine_split16_to(
+        _ptr(x), ld_in, _ptr(scale), _ptr(shift), int(per_n), int(bool(relu)), 0, N, H, W, Cc, _ptr(t), ld_out, plane, int(c_off), int(mode), ra,
+        _stream()), "g6d_affine_split16_to"))
+    return out
+
+
+def upsample_bilinear_split16(x, out, c_off, factor, scale, shift, per_n, mode):
+    """upsample_bilinear (x factor, the affine applied to the four neighbours) into channels [c_off, c_off + C) of the 16-bit map `out`
+    (new_map16; g6d_upsample_bilinear_split16).  x [N,1,H,W,C] fp32 view; per_n: images per affine table.  Returns out."""
+    _need_gpu(x)
+    N, D, H, W, Cc, ld_in = _cl5(x, "upsample_bilinear_split16.x")
+    if D != 1:
+        raise ValueError("upsample_bilinear_split16: 2-D maps expected")
+    Ho, Wo = H * int(factor), W * int(factor)
+    t, ld_out, plane, ra = _slice16(out, N, Ho, Wo, Cc, c_off, mode, "upsample_bilinear_split16")
+    _timed_hbm("upsample_split16", 4.0 * N * H * W * Cc + (4.0 if mode == 3 else 2.0) * N * Ho * Wo * Cc, lambda: _lib.check(
+        _lib.load().g6d_upsample_bilinear_split16(_ptr(x), ld_in, _ptr(scale), _ptr(shift), int(per_n), N, H, W, Cc, int(factor), _ptr(t), ld_out,
+                                                  plane, int(c_off), int(mode), ra, _stream()), "g6d_upsample_bilinear_split16"))
+    return out
+
+
+def l2norm_split16(x, mode, rng=None):
+    """F.normalize over the channels of an fp32 channels-last tap x [N,H,W,C] (C = 256 or 512; the arithmetic of l2norm_rows) written in
+    the activation format of conv16_direct_multi instead of in place (g6d_l2norm_split16): [N,H,W,C] (mode 1 / 2) or [N,H,W,2,C] pairs.
+    rng as product_split16."""
+    if rng is not None and mode != 3:
+        raise ValueError("l2norm_split16: a range applies to pairs (mode 3) only")
+    _need_gpu(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4:
+        raise ValueError("l2norm_split16: a dense float32 [N,H,W,C] tap expected")
+    N, H, W, Cc = x.shape
+    out = torch.empty((N, H, W, 2, Cc) if mode == 3 else (N, H, W, Cc), dtype=_T16[mode], device=x.device)
+    ra = _range_arg(None, -1, rng)
+    _timed_hbm("l2norm_split16", 4.0 * x.numel() + 2.0 * out.numel(), lambda: _lib.check(_lib.load().g6d_l2norm_split16(
+        _ptr(x), Cc, N * H * W, Cc, _ptr(out), int(mode), ra, _stream()), "g6d_l2norm_split16"))
+    return _wrap(out, rng)
+
+
 def vgg_conv1_pool_nhwc16(x, w_oihw, bias, out=None, norm=None, mode=None, rng=None):
     """vgg_conv1_pool_nhwc with a 16-bit channels-last result (g6d_vgg_conv1_pool_nhwc16): mode 1 / 2 (default: the current math mode) =
     bf16 / fp16 [N,H/2,W/2,64], the first layer of the reduced-precision mode's 16-bit activation path; mode 3 = fp16 hi / lo pairs
@@ -924,6 +993,21 @@ def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, s
         fulls = [_wrap(f, rng) if full == "t16" else f for f in fulls]
         pools = [_wrap(q, rng) if pool == "t16" else q for q in pools]
     return fulls, pools
+
+
+def conv16_direct_plan(N, H, W, Cin, Cout, mode, stats_rows=0, full=torch.float32):
+    """The kernel conv16_direct_multi would launch for ONE 2-D map [N,H,W,Cin] -> Cout with fragment-major filters (g6d_conv16_direct_plan:
+    validation only, nothing is launched or dereferenced): None = rejected, 0 = the per-tap kernels, 1 = the halo-patch kernel, 2 = the
+    halo-patch kernel with statistics groups of whole epilogue passes (stats_rows: pixels per statistics group, 0 = no statistics)."""
+    pair = mode == 3
+    code = {None: 0, "t16": 3 if pair else 1, torch.float32: 2}[full]
+    any_ = 1 << 12                                             # (a non-null, 16-byte aligned stand-in: the plan tests pointers only)
+    ldf = 2 * Cout if code == 3 else Cout
+    seg = (_lib.G6dConv16Seg * 1)(_lib.G6dConv16Seg(in_=any_, out_full=any_ if code else None, out_pool=None, N=N, D=1, H=H, W=W,
+                                                    ld_in=(2 if pair else 1) * Cin, ld_full=ldf if code else 0, ld_pool=0))
+    rc = _lib.load().g6d_conv16_direct_plan(seg, 1, Cin, C.c_void_p(any_), 1, Cout, 1, code, 0, int(mode), C.c_void_p(any_ if stats_rows else 0),
+                                            int(stats_rows))
+    return rc if rc >= 0 else None
 
 
 def corr16_pack(w_taps, mode):

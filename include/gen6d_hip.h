@@ -293,7 +293,10 @@ int g6d_wino16_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const vo
  *                                             3 = fp16 pairs [pixel][2][Cout] (mode 3; ld_full >= 2 Cout)
  *   out_pool [N][H/2][W/2][ld_pool] = maxpool2x2(y) (2-D only, H and W even)     element type pool_type, same coding
  *   stats (optional) [groups][Cout][2] fp64, zeroed by the caller: sum and sum of squares of y (fp32 values, before rounding) per
- *        (image group, channel) are ADDED; group of a pixel = (its index in [N][D][H][W]) / stat_rows_per_group (0 = one group)
+ *        (image group, channel) are ADDED; group of a pixel = (its index in [N][D][H][W]) / stat_rows_per_group (0 = one group).
+ *        A 128-pixel tile is summed under ONE group, so groups are whole tiles; on the halo-patch kernel (fragment-major 2-D layers) whole
+ *        images do, and where a tile holds several small images (8 x 8: two) a group may also be whole 64-pixel epilogue passes of the
+ *        tile — one 8 x 8 image per group.  Groups smaller than a pass, or not aligned to one, are rejected (G6D_EINVAL)
  * Up to 4 map sizes per launch (the scales of the detector's pyramid) like g6d_wino_conv3x3_multi; all segments share D and the
  * kinds of output.  No workspace: the K loop is never split. */
 typedef struct G6dConv16Seg {
@@ -345,6 +348,11 @@ typedef struct G6dRange16 {
 int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale, const float* bias,
                                int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group,
                                const G6dRange16* range, g6d_stream_t stream);
+/* The validation and kernel choice of g6d_conv16_direct_multi_ex WITHOUT a launch (no pointer is dereferenced, no HIP call): G6D_EINVAL with
+ * the launch's message, else 0 = the per-tap kernels, 1 = the halo-patch kernel (statistics, if any, one group per tile), 2 = the halo-patch
+ * kernel with statistics groups of whole epilogue passes inside a tile of several small images. */
+int g6d_conv16_direct_plan(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, int Cout, int kd, int full_type, int pool_type,
+                           int math_mode, double* stats, int stat_rows_per_group);
 int g6d_corr16_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
                         const G6dRange16* range, g6d_stream_t stream);
 int g6d_product_split16_ex(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,
@@ -354,6 +362,22 @@ int g6d_affine_split16_ex(const float* in, int ld_in, const float* scale, const 
 int g6d_vgg_conv1_pool_nhwc16_ex(const float* in, int N, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout,
                                  const float* mean_host, const float* std_host, void* out16, int math_mode, const G6dRange16* range,
                                  g6d_stream_t stream);
+
+/* Hand-over passes of the refiner's 2-D feature net to g6d_conv16_direct_multi (network/refiner.py:64-78; additive to ABI v12).  Their
+ * output may be a CHANNEL SLICE of wider 16-bit rows — the three branches of the feature net write one `cat` map: `out` points at pixel 0 of
+ * rows of ld_out 16-bit elements, the slice is channels [c_off, c_off + C), and for math_mode 3 the lo plane lies `plane` elements after the
+ * hi plane (a dense pair map [pixel][2][C]: ld_out = 2 C, plane = C, c_off = 0; modes 1 / 2: one plane, `plane` is not read).  ld_out, plane
+ * and c_off are multiples of 8; nothing else of a row is touched.  Slices of one map must be written with ONE slot_out.
+ *   g6d_affine_split16_to          g6d_affine_split16_ex with such an output (the dense entry calls it)
+ *   g6d_upsample_bilinear_split16  g6d_upsample_bilinear (x factor, the per-image affine applied to the four neighbours, same arithmetic)
+ *   g6d_l2norm_split16             g6d_l2norm_rows (F.normalize over C, same arithmetic) of an fp32 tap in[rows][ld_in], C = 256 or 512,
+ *                                  written as a dense 16-bit map instead of in place: [rows][C], or [rows][2][C] pairs */
+int g6d_affine_split16_to(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu, int pool, int N, int H,
+                          int W, int C, void* out, int ld_out, int plane, int c_off, int math_mode, const G6dRange16* range, g6d_stream_t stream);
+int g6d_upsample_bilinear_split16(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int N, int H, int W, int C,
+                                  int factor, void* out, int ld_out, int plane, int c_off, int math_mode, const G6dRange16* range,
+                                  g6d_stream_t stream);
+int g6d_l2norm_split16(const float* in, int ld_in, int rows, int C, void* out, int math_mode, const G6dRange16* range, g6d_stream_t stream);
 
 /* g6d_wino_conv3x3_multi on the Winograd F(4x4,3x3) kernel (ABI v8, fp32 on v_mfma_f32_16x16x4_f32): 36 multiplications per 16
  * outputs — 4x fewer than the direct form, 1.78x fewer than F(2x2,3x3) — with the interpolation points (0, +-3/4, +-3/2, inf), whose
