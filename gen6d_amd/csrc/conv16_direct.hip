@@ -655,10 +655,19 @@ __device__ __forceinline__ void c16_wait_vm(int n) {
   }
 }
 
-template <int MM, int WM, int NT2 = C16W<MM>::NT2>
+// KD = 3 (pairs only): a 3x3x3 layer with its DEPTH TAPS FOLDED INTO THE REDUCTION.  The map is the tall image of N D planes of H x W, a
+// tile lies inside one plane (the launcher admits only such tilings), and the filters are packed as a 2-D bank of 3 Cin channels in the
+// order (dz, ci): slice c of the K loop is channel slice c % (Cin / 32) of depth tap dz = c / (Cin / 32), and its patch is the SAME halo
+// patch one plane down or up — the piece offsets move by (dz - 1) H W pixels, LDS holds what it holds for a 2-D layer.  Where plane
+// z + dz - 1 lies outside the volume (the plane after z = D - 1 is plane 0 of the NEXT volume: padding, not data) the slice contributes
+// zero: its pieces are requested out of range, so that the DMA overwrites the stage with zeros (the pieces zeroed once and never
+// requested — in-plane halo outside the map — stay zero for every slice).  Slices are ordered by dz, so a block whose tiles ALL lie in
+// plane 0 (D - 1) simply starts its loop after the dz = 0 slices (ends it before the dz = 2 slices) and walks the filters from there.
+template <int MM, int WM, int NT2 = C16W<MM>::NT2, int KD = 1>
 __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   typedef typename C16T3<MM>::V V8;
   typedef C16W<MM> R;
+  static_assert(KD == 1 || (KD == 3 && MM == 3), "depth taps fold into the pair kernel's reduction only");
   constexpr int WN = 4 / WM, NP = R::NP, KS = R::KS, NBL = KS * NP * NT2, CW = 32 * NT2;   // (NT2 = 1 in a 16-bit mode: 32-channel waves for Cout = 64)
   constexpr bool SINGLE = MM == 3 && WM == 2;                  // one patch stage instead of two (see the slice hand-over below)
   constexpr int TILE_B = NP * R::PLANE, STAGE = WM * TILE_B;
@@ -669,7 +678,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   const int cb = jj % p.nN, tg = (jj / p.nN) * 8 + xcd;
   if (tg * WM >= p.ptiles) return;
   const int wm = wv / WN, wn = wv % WN;
-  const int nchunk = p.Cin >> 5;
+  const int nchunk = KD == 1 ? p.Cin >> 5 : 3 * (p.Cin >> 5);
   typedef __attribute__((address_space(3))) void* lds_ptr;
 
   // ---- the patch pieces this lane requests per slice: tile tl, pieces ii = wv + 4 j of its ni pieces per plane (rows 16 ii + lane / 4),
@@ -717,18 +726,42 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     }
     pmask[tl] = __builtin_amdgcn_readfirstlane(pm);
   }
+  // KD = 3: the plane of each tile inside its volume, and the slices [c_lo, c_hi) the block walks (all of them unless every tile of the
+  // block lies in the first / last plane)
+  int c_lo_ = 0, c_hi_ = nchunk;
+  [[maybe_unused]] int zt[WM];
+  [[maybe_unused]] const int ncs = p.Cin >> 5;
+  if constexpr (KD == 3) {
+    bool first = true, last = true;
+#pragma unroll
+    for (int tl = 0; tl < WM; ++tl) {
+      zt[tl] = (int)((unsigned)gms[tl].t.img % (unsigned)p.D);
+      first = first && zt[tl] == 0; last = last && zt[tl] == p.D - 1;
+    }
+    c_lo_ = first ? ncs : 0; c_hi_ = last ? 2 * ncs : 3 * ncs;
+  }
+  const int c_lo = c_lo_, c_hi = c_hi_;
   const unsigned plane_b = (unsigned)(p.Cin * 2);
   auto issue_patch = [&](int c, int stage) {
-    if (c >= nchunk) return;                                           // (no request past the last slice: the waits count 0 pieces there)
-    const unsigned ck = (unsigned)(c * 64);
+    if (c >= c_hi) return;                                             // (no request past the last slice: the waits count 0 pieces there)
+    [[maybe_unused]] int dz = 1;
+    unsigned ck;
+    if constexpr (KD == 3) { dz = (c >= ncs ? 1 : 0) + (c >= 2 * ncs ? 1 : 0); ck = (unsigned)((c - dz * ncs) * 64); }
+    else ck = (unsigned)(c * 64);
 #pragma unroll
     for (int tl = 0; tl < WM; ++tl) {
       const C16Seg& sg = p.seg[gms[tl].si];
       const __amdgpu_buffer_rsrc_t rs_in = c16_rsrc(sg.in, sg.in_bytes - sg.back);
+      unsigned ckt = ck;
+      bool pad = false;
+      if constexpr (KD == 3) {
+        ckt = ck + (unsigned)((dz - 1) * (sg.H * sg.W * sg.ld_in * 2));    // the same patch one plane down / up (wraps to the true offset)
+        pad = (unsigned)(zt[tl] + dz - 1) >= (unsigned)p.D;                // ... which lies outside the volume: zeros
+      }
 #pragma unroll
       for (int j = 0; j < NPJ; ++j) {
         if (pmask[tl] >> j & 1) {
-          const unsigned vo = poff[tl][j] == C16_OOB ? C16_OOB : poff[tl][j] + ck;      // (C16_OOB + a plane stays beyond the buffer)
+          const unsigned vo = (poff[tl][j] == C16_OOB || pad) ? C16_OOB : poff[tl][j] + ckt;      // (C16_OOB + a plane stays beyond the buffer)
 #pragma unroll
           for (int pl = 0; pl < NP; ++pl)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_ptr)(lds + stage * STAGE + tl * TILE_B + pl * R::PLANE + (wv + 4 * j) * 1024), 16,
@@ -761,8 +794,8 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
   // The requests walk the packed filters in step order with a running pointer: + 16 KB per tap; at a slice boundary + 16 KB for pairs,
   // and for the 16-bit modes (two 32-channel slices per packed step) + 8 KB - 8 x 16 KB into an odd slice, + 8 KB out of it.  Past the
   // last step the pointer stays on the first one (a harmless reload: the request count per step stays uniform).
-  const char* wp = wtile;
-  int wleft = nchunk * 9;
+  const char* wp = KD == 1 ? wtile : wtile + (long)c_lo * (9 * 16384);
+  int wleft = (c_hi - c_lo) * 9;
   auto load_b = [&](int c, int t, V8 (&b)[NBL]) {                // (c, t): the step being requested — requests are issued in step order
     const unsigned long wa = (unsigned long)(wleft > 0 ? wp : wtile);
     const char* ws = reinterpret_cast<const char*>((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)wa) |
@@ -824,7 +857,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     // pair g + 3 — consumed 24 MFMAs later.  The first three pairs of a slice are read after its barrier.
     V8 bs[3][NBL];
     V8 fa[3][2][NP];
-    issue_patch(0, 0);
+    issue_patch(c_lo, 0);
     load_b(0, 0, bs[0]);
     load_b(0, 1, bs[1]);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (lgkmcnt: the zeroed halo pieces)
@@ -834,7 +867,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
     for (int mp = 0; mp < 3; ++mp) read_pair(mp, tap_off(0, 0), fa[mp]);
     int stage = 0;
 #pragma unroll 1
-    for (int c = 0; c < ((C16W_ABLATE & 8) ? 0 : nchunk); ++c) {      // (ablation bit 3: no K loop at all — what a block costs outside it)
+    for (int c = c_lo; c < ((C16W_ABLATE & 8) ? 0 : c_hi); ++c) {      // (ablation bit 3: no K loop at all — what a block costs outside it)
       // (opaque to the optimiser: it would otherwise hoist the per-(tap, m-tile) addresses out of the slice loop and spill them)
 #pragma unroll
       for (int mt = 0; mt < 8; ++mt) asm volatile("" : "+v"(qb[mt]));
@@ -868,7 +901,7 @@ __global__ __launch_bounds__(256, 2) void conv16w_kernel(const C16Params p) {
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
           } else stage ^= 1;
-          if (c + 1 < nchunk) {
+          if (c + 1 < c_hi) {
 #pragma unroll
             for (int mp = 0; mp < 3; ++mp) read_pair(mp, tap_off(0, stage), fa[mp]);
           }
@@ -1563,8 +1596,9 @@ __global__ __launch_bounds__(64 * (CORR16_NW + 1), 1) void corr16_kernel(const C
 
 
 // Tiling of one segment for the halo-patch kernel: the tile width (32 / 16 / 8 / 4) with the least overhang; false if none fits
-// (a map lower than the tile must divide it: tiles of whole images).  pairs: the fp16 pair kernel's slot swizzle (its fragment reads differ)
-bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs) {
+// (a map lower than the tile must divide it: tiles of whole images).  pairs: the fp16 pair kernel's slot swizzle (its fragment reads differ);
+// in_image: only tilings whose tiles lie inside one image (depth-folded layers: s.N counts planes, and a tile must not span two)
+bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs, bool in_image = false) {
   double best = 1e30;
   bool found = false;
   for (int tw = 32; tw >= 4; tw >>= 1) {
@@ -1572,7 +1606,7 @@ bool c16_halo_tiling(const G6dConv16Seg& s, C16Seg& o, int& tiles, bool pairs) {
     long nt; int tpi, segh, bands;
     if (s.H >= th) { tpi = tx * ((s.H + th - 1) / th); nt = (long)s.N * tpi; segh = th; bands = 1; }
     else {
-      if (th % s.H) continue;
+      if (th % s.H || in_image) continue;
       tpi = 0; nt = (long)tx * (((long)s.N * s.H + th - 1) / th); segh = s.H; bands = th / s.H;
     }
     if (bands * (segh + 2) * (tw + 2) > 288) continue;
@@ -1612,12 +1646,15 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
                int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream,
                bool plan_only) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("conv16_direct: 1..4 segments and filters expected"); return G6D_EINVAL; }
-  if (math_mode < 1 || math_mode > 3 || (w_layout != 0 && w_layout != 1) || (math_mode == 3 && w_layout != 1)) {
+  // w_layout 2: fragment-major filters of a 3x3x3 layer packed as the 2-D bank [Cout][9][3 Cin], channel order (dz, ci) — the pair
+  // kernel folds the depth taps into its reduction (conv16w_kernel<3, ., 1, 3>)
+  const bool folded = w_layout == 2;
+  if (math_mode < 1 || math_mode > 3 || w_layout < 0 || w_layout > 2 || (math_mode == 3 && w_layout == 0) || (folded && (math_mode != 3 || kd != 3))) {
     g6d_set_error("conv16_direct: math_mode 1 (bf16) / 2 (fp16) / 3 (fp16 hi-lo pairs, fragment-major filters only)"); return G6D_EINVAL;
   }
   const int bk = math_mode == 3 ? 32 : C16_BK, planes = math_mode == 3 ? 2 : 1;
   // Cout = 64 (the selector's first product layer): halo-patch kernel only, filters packed as one 128-channel tile whose upper half is zero
-  const bool half_tile = Cout == 64 && w_layout == 1 && kd == 1;      // (32-channel waves: two pixel tiles x two channel groups per block)
+  const bool half_tile = Cout == 64 && ((w_layout == 1 && kd == 1) || folded);      // (32-channel waves: two pixel tiles x two channel groups per block)
   if (Cin % bk || (Cout % C16_BN && !half_tile) || (kd != 1 && kd != 3)) { g6d_set_error("conv16_direct: Cin % 64 (32 for pairs), Cout % 128 (64: fragment-major 2-D layers), kd in {1,3} expected"); return G6D_EINVAL; }
   const int t16 = math_mode == 3 ? 3 : 1;                    // the 16-bit output coding of this mode
   auto type_ok = [&](int t) { return t == 0 || t == 2 || t == t16; };
@@ -1668,11 +1705,20 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
   p.ptiles = tiles;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // fragment-major filters, 2-D layer: the halo-patch kernel when every segment has a tiling for it (knob conv16_halo = 0: never)
-  if (w_layout == 1 && kd == 1 && g6d_knob(G6D_KNOB_CONV16_HALO) != 0) {
+  if (((w_layout == 1 && kd == 1) || folded) && g6d_knob(G6D_KNOB_CONV16_HALO) != 0) {
     bool ok = true, per_pass = false;
     int htiles = 0;
     for (int i = 0; i < nseg && ok; ++i) {
       int nt_ = 0;
+      if (folded) {
+        // the planes of the volumes are the images of the tiling; statistics groups are whole volumes (a tile lies inside one plane)
+        G6dConv16Seg planes_ = segs[i];
+        planes_.N = segs[i].N * segs[i].D; planes_.D = 1;
+        ok = (long)segs[i].N * segs[i].D < (1L << 31) && c16_halo_tiling(planes_, p.seg[i], nt_, true, true);
+        p.seg[i].h_tile0 = htiles; htiles += nt_;
+        if (stats && stat_rows_per_group > 0 && ok) ok = stat_rows_per_group % ((long)segs[i].D * segs[i].H * segs[i].W) == 0;
+        continue;
+      }
       ok = c16_halo_tiling(segs[i], p.seg[i], nt_, math_mode == 3);
       p.seg[i].h_tile0 = htiles; htiles += nt_;
       if (stats && stat_rows_per_group > 0 && ok) {
@@ -1707,6 +1753,10 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
         if (math_mode == 1) launch(&conv16w_kernel<1, 2, 1>, 2 * 2 * C16W<1>::PLANE, 4 * C16W<1>::EPW);
         else launch(&conv16w_kernel<2, 2, 1>, 2 * 2 * C16W<2>::PLANE, 4 * C16W<2>::EPW);
       }
+      else if (folded) {
+        if (wm == 1) launch(&conv16w_kernel<3, 1, 1, 3>, 2 * C16W<3>::NP * C16W<3>::PLANE, 4 * C16W<3>::EPW);
+        else launch(&conv16w_kernel<3, 2, 1, 3>, 2 * C16W<3>::NP * C16W<3>::PLANE, 4 * C16W<3>::EPW);      // (one stage of two tiles)
+      }
       else if (math_mode == 1) { if (wm == 1) C16W_LAUNCH(1, 1); else C16W_LAUNCH(1, 2); }
       else if (math_mode == 2) { if (wm == 1) C16W_LAUNCH(2, 1); else C16W_LAUNCH(2, 2); }
       else { if (wm == 1) C16W_LAUNCH(3, 1); else C16W_LAUNCH(3, 2); }   // (two tiles per block: Cout = 64)
@@ -1714,6 +1764,7 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
       return g6d_check_launch("conv16w_direct");
     }
   }
+  if (folded) { g6d_set_error("conv16_direct: depth-folded filters run on the halo-patch kernel only (planes at least one tile high, statistics groups of whole volumes)"); return G6D_EINVAL; }
   if (half_tile) { g6d_set_error("conv16_direct: Cout = 64 runs on the halo-patch kernel only (knob conv16_halo, tile shapes)"); return G6D_EINVAL; }
   if (!pertap_stats_ok) { g6d_set_error("conv16_direct: statistics groups must be whole tile rows (small maps: whole 64-pixel epilogue passes)"); return G6D_EINVAL; }
   if (plan_only) return 0;

@@ -63,6 +63,7 @@ C16G_HD bool finish(Tiling& t, long ntiles) {
 struct Tile {         // one 128-pixel tile (block-uniform)
   int g0, x0, y0, ylim;                  // first row of the tall image, first column, first row inside its image, tile rows inside the image
   int interior;                          // the whole halo patch lies inside ONE image: every patch pixel is a valid request
+  int img;                               // index of the tile's image (tiles inside one image; 0 for tiles of whole small images)
 };
 // t: tile index inside the segment
 C16G_HD Tile tile_of(const Tiling& tl, int H, int W, int t) {
@@ -73,10 +74,12 @@ C16G_HD Tile tile_of(const Tiling& tl, int H, int W, int t) {
     const int ty = (int)div31((unsigned)r, tl.h_r_tx), tx = r - ty * tl.h_tiles_x;
     o.y0 = ty * TH; o.x0 = tx * TW; o.g0 = n * H + o.y0; o.ylim = TH < H - o.y0 ? TH : H - o.y0;
     o.interior = o.y0 >= 1 && o.y0 + TH < H && o.x0 >= 1 && o.x0 + TW < W;
+    o.img = n;
   } else {                                                     // tiles of TH / H whole images: every band touches its image's edges
     const int ty = (int)div31((unsigned)t, tl.h_r_tx), tx = t - ty * tl.h_tiles_x;
     o.y0 = 0; o.x0 = tx * TW; o.g0 = ty * TH; o.ylim = TH;
     o.interior = 0;
+    o.img = 0;
   }
   return o;
 }

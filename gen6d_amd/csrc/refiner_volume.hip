@@ -8,6 +8,7 @@
 // The rfn+1 projections of a voxel are spread over the lanes of its half-wave (lane v = view v) and exchanged with
 // shuffles: done redundantly by all 32 lanes they were ~600 VALU instructions per voxel, as long as the gathers.
 #include "g6d_common.h"
+#include <type_traits>
 
 #define MAX_RFN 8
 
@@ -77,17 +78,41 @@ __device__ __forceinline__ f32x4 gather_view(const float* __restrict__ fmap_c, c
 struct VolViews { const float* projs; const float* ref_Ks; const float* ref_poses; const float* K_in; const float* pose_in;
                   const float* rot; int rot_ld; };
 
+// PAIRS: the two volumes as fp16 hi / lo pair maps in the layout conv16w_kernel reads — per voxel the hi plane, then the lo plane
+// (mean_in: 2 x 2C halves, std: 2 x C) — each under its own exponent slot and range record (G6dRange16: split16(v * 2^-e), the
+// elementwise producers' protocol).  The same gathers and arithmetic, the same number of bytes written; 8-byte stores per lane.
+struct VolPairs { G6dRange16 mean, stdv; };
+
+__device__ __forceinline__ void store_pair4(_Float16* hi_p, int plane, f32x4 v, int e, unsigned& amax) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  h4 hi, lo;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    amax = max(amax, g6d_abs_bits(v[i]));
+    const float u = ldexpf(v[i], -e);
+    hi[i] = (_Float16)u; lo[i] = (_Float16)(u - (float)hi[i]);
+  }
+  *reinterpret_cast<h4*>(hi_p) = hi;
+  *reinterpret_cast<h4*>(hi_p + plane) = lo;
+}
+
+template <bool PAIRS>
 __global__ void __launch_bounds__(256, 4) refiner_volume_kernel(const float* __restrict__ feats, const VolViews vw,
                                                              const float* __restrict__ lin, int rfn, int fh, int fw,
                                                              int C, float h_in, float w_in, int sn,
-                                                             float* __restrict__ mean_in, float* __restrict__ stdv) {
+                                                             typename std::conditional<PAIRS, _Float16, float>::type* __restrict__ mean_in,
+                                                             typename std::conditional<PAIRS, _Float16, float>::type* __restrict__ stdv,
+                                                             const VolPairs vp) {
   // blockIdx.y = query of the batch (g6d_refiner_volume_kp): its views, cameras and volumes follow those of the previous query
   const int bq = blockIdx.y;
   const float* __restrict__ rot = vw.rot + bq * 12;
   const int rl = vw.rot_ld;
   const int nvox = sn * sn * sn;
   feats += (size_t)bq * (rfn + 1) * fh * fw * C;
-  mean_in += (size_t)bq * nvox * 2 * C; stdv += (size_t)bq * nvox * C;
+  // (pairs: 2 x 2C and 2 x C halves per voxel — the same element counts as the fp32 volumes' byte counts / 2)
+  mean_in += (size_t)bq * nvox * (PAIRS ? 4 : 2) * C; stdv += (size_t)bq * nvox * (PAIRS ? 2 : 1) * C;
+  [[maybe_unused]] const int e_mean = PAIRS ? g6d_exp_out(vp.mean) : 0, e_std = PAIRS ? g6d_exp_out(vp.stdv) : 0;
+  [[maybe_unused]] unsigned amax_mean = 0, amax_std = 0;
   int half = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;         // one half-wave per voxel
   const int l32 = threadIdx.x & 31;
   const bool live = half < nvox;                                   // (whole half-waves; keep them for the shuffles)
@@ -136,9 +161,20 @@ __global__ void __launch_bounds__(256, 4) refiner_volume_kernel(const float* __r
     f32x4 sd = {sqrtf(var[0]), sqrtf(var[1]), sqrtf(var[2]), sqrtf(var[3])};
     const f32x4 q = gather_view(feats + rfn * fsz + c, taps_from(mine, rfn));
     if (!live || !c_in) continue;
-    *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + c) = mean;
-    *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + C + c) = q;
-    *reinterpret_cast<f32x4*>(stdv + (size_t)half * C + c) = sd;
+    if constexpr (PAIRS) {
+      store_pair4(mean_in + (size_t)half * 4 * C + c, 2 * C, mean, e_mean, amax_mean);
+      store_pair4(mean_in + (size_t)half * 4 * C + C + c, 2 * C, q, e_mean, amax_mean);
+      store_pair4(stdv + (size_t)half * 2 * C + c, C, sd, e_std, amax_std);
+    } else {
+      *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + c) = mean;
+      *reinterpret_cast<f32x4*>(mean_in + (size_t)half * 2 * C + C + c) = q;
+      *reinterpret_cast<f32x4*>(stdv + (size_t)half * C + c) = sd;
+    }
+  }
+  if constexpr (PAIRS) {                                           // (every thread arrives here: no return above)
+    g6d_range_record_block<4>(vp.mean, amax_mean);
+    __syncthreads();                                               // (the two records share the block's reduction array)
+    g6d_range_record_block<4>(vp.stdv, amax_std);
   }
 }
 
@@ -154,9 +190,9 @@ extern "C" int g6d_refiner_volume(const float* feats, const float* projs, const 
   }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {projs, nullptr, nullptr, nullptr, nullptr, rot_in, 3};
-  hipLaunchKernelGGL(refiner_volume_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(refiner_volume_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), feats, vw, lin, rfn, fh, fw, C, (float)h_in, (float)w_in, sn,
-                     mean_in, stdv);
+                     mean_in, stdv, VolPairs{});
   return g6d_check_launch("refiner_volume");
 }
 
@@ -173,8 +209,32 @@ extern "C" int g6d_refiner_volume_kp(const float* feats, const float* ref_Ks, co
   }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {nullptr, ref_Ks, ref_poses, K_in, pose_in, pose_in, 4};
-  hipLaunchKernelGGL(refiner_volume_kernel, dim3((unsigned)((threads + 255) / 256), batch), dim3(256), 0,
+  hipLaunchKernelGGL(refiner_volume_kernel<false>, dim3((unsigned)((threads + 255) / 256), batch), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), feats, vw, lin, rfn, fh, fw, C, (float)h_in, (float)w_in, sn,
-                     mean_in, stdv);
+                     mean_in, stdv, VolPairs{});
   return g6d_check_launch("refiner_volume_kp");
+}
+
+// g6d_refiner_volume_kp with both volumes written as fp16 hi / lo pair maps (mean_in16 [batch][sn^3][2][2C], std16 [batch][sn^3][2][C]
+// halves): the input format of g6d_conv16_direct_multi, math_mode 3.  range_mean / range_std: the exponent slot and range record of each
+// map (slot_out; NULL = unscaled, not recorded).
+extern "C" int g6d_refiner_volume_kp_pairs(const float* feats, const float* ref_Ks, const float* ref_poses, const float* K_in,
+                                           const float* pose_in, const float* lin, int rfn, int fh, int fw, int C, int h_in, int w_in, int sn,
+                                           void* mean_in16, void* std16, int batch, const G6dRange16* range_mean, const G6dRange16* range_std,
+                                           g6d_stream_t stream) {
+  if (!feats || !ref_Ks || !ref_poses || !K_in || !pose_in || !lin || !mean_in16 || !std16 || rfn < 1 || rfn > MAX_RFN || C < 4 || (C & 3) ||
+      fh <= 0 || fw <= 0 || h_in <= 0 || w_in <= 0 || sn < 1 || sn > 256 || batch < 1 || batch > 65535 || !g6d_aligned16(feats) ||
+      !g6d_aligned16(mean_in16) || !g6d_aligned16(std16)) {
+    g6d_set_error("refiner_volume_kp_pairs: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
+  }
+  const long long threads = (long long)sn * sn * sn * 32;
+  const VolViews vw = {nullptr, ref_Ks, ref_poses, K_in, pose_in, pose_in, 4};
+  VolPairs vp = {};
+  vp.mean.slot_in = vp.mean.slot_out = vp.stdv.slot_in = vp.stdv.slot_out = -1;
+  if (range_mean) vp.mean = *range_mean;
+  if (range_std) vp.stdv = *range_std;
+  hipLaunchKernelGGL(refiner_volume_kernel<true>, dim3((unsigned)((threads + 255) / 256), batch), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), feats, vw, lin, rfn, fh, fw, C, (float)h_in, (float)w_in, sn,
+                     static_cast<_Float16*>(mean_in16), static_cast<_Float16*>(std16), vp);
+  return g6d_check_launch("refiner_volume_kp_pairs");
 }

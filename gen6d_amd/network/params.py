@@ -17,12 +17,13 @@ class ConvW(tuple):
         t.u, t.u43, t._w16 = u, u43, {}
         return t
 
-    def w16(self, mode):
+    def w16(self, mode, layout=1):
         """The filters for the direct kernel on 16-bit activations (ops.conv16_pack, fragment-major) in `mode` (1 / 2 = rounded to bf16 /
-        fp16, 3 = fp16 hi / lo pairs), built on first use."""
-        if mode not in self._w16:
-            self._w16[mode] = ops.conv16_pack(self[0], mode, layout=1)
-        return self._w16[mode]
+        fp16, 3 = fp16 hi / lo pairs), built on first use.  layout 2: a 3x3x3 layer's depth taps folded into the reduction."""
+        key = mode if layout == 1 else (mode, layout)
+        if key not in self._w16:
+            self._w16[key] = ops.conv16_pack(self[0], mode, layout=layout)
+        return self._w16[key]
 
 
 class ParamBank(nn.Module):

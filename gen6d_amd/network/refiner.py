@@ -9,6 +9,8 @@ One refinement step (reference forward, refiner.py:249-269):
     g6d_refiner_volume: projection + bilinear sampling + mean/std over references, fused            refiner.py:183-247
     RefineVolumeEncodingNet 3x3x3 convs on g6d_conv_igemm (32^3 layers: Winograd F(4x4,3x3), depth taps folded into the reduction;
         16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K)
+        (batched calls of the fp32 path: the 32^3 layers of VOLUME_PAIR_LAYERS on fp16 hi / lo pairs, g6d_conv16_direct_multi with
+        depth-folded filters; g6d_refiner_volume_kp_pairs writes their input volumes as pairs)
     g6d_linear_gemv_batch: the 32768->512 FC is a 67 MB weight stream, read once per 8 queries                                    refiner.py:153-166
 """
 import numpy as np
@@ -36,6 +38,15 @@ FEATNET_F43_LAYERS = {("conv1", 0), ("conv_out", 0), ("conv_out", 3)}
 # included (tools/featnet_layers.py, profiles/r16_featnet_pairs.md).  A branch that is not listed keeps its route; run_feature_net joins
 # either kind (the branch ends write fp32 or pair slices of `cat` from the same fp32 map + affine)
 FEATNET_PAIR_BRANCHES = ("conv0", "conv1", "conv2", "conv_out")
+# stride-1 layers of the volume net's 32^3 stage that run on the pair kernel with their depth taps folded into the reduction
+# (conv16w_kernel<3, ., 1, 3>, filter layout 2) in the big calls of the fp32 path: "mean_embed" / "var_embed" = the embed's two layers with
+# the InstanceNorm + ReLU pass between them written as pairs, "conv0" = the 128 -> 64 layer behind them (its input then is ONE 128-channel
+# pair map the two embeds fill slice by slice).  The two input volumes are then written as pairs by g6d_refiner_volume_kp_pairs and never
+# exist in fp32, so both embeds go together.  "conv2" = the 128 -> 128 layer at 16^3 on the same kernel (conv1's InstanceNorm affine + ReLU,
+# which F(2x2,3x3) applies in its operand prologue, becomes the pass that writes its pairs).  Decided per layer at 16 volumes with the
+# hand-over passes included (tools/volume_layers.py, profiles/r17_volume_pairs.md: embeds 1675 -> 1308 and 1093 -> 833 us, conv0 642 -> 512,
+# conv2 294 -> 128); a layer that is not listed keeps its route
+VOLUME_PAIR_LAYERS = ("mean_embed", "var_embed", "conv0", "conv2")
 VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
@@ -260,13 +271,44 @@ class VolumeRefiner(ParamBank):
         return memo[key]
 
     # ------------------------------------------------------------------ 3-D volume net + regressor
+    def volume_pair_route(self, qn, sn):
+        """Whether a batch of qn volumes of sn^3 voxels takes the pair route through the 32^3 stage of the volume net: a big call of the
+        fp32 path (the F43_MIN_QUERIES condition of the fp32-core route, pairs on), both embeds listed, and every listed layer accepted by
+        the library's own validation (asked once per batch and volume size)."""
+        if qn < F43_MIN_QUERIES or self._pair_rng() is None or not {"mean_embed", "var_embed"} <= set(VOLUME_PAIR_LAYERS):
+            return False
+        memo = self.__dict__.setdefault("_volume16", {})
+        key = (qn, sn, tuple(VOLUME_PAIR_LAYERS))
+        if key not in memo:
+            shapes = [(sn, 256, 64), (sn, 128, 64), (sn, 64, 64)] + ([(sn, 128, 64)] if "conv0" in VOLUME_PAIR_LAYERS else []) + \
+                ([(sn // 2, 128, 128)] if "conv2" in VOLUME_PAIR_LAYERS else [])
+            memo[key] = all(ops.conv16_direct_plan(qn, s, s, ci, co, 3, stats_rows=s ** 3, D=s) == 1 for s, ci, co in shapes)
+        return memo[key]
+
+    def feature_volumes(self, feats, ref_Ks, ref_poses, K_in, pose_in, h_in, w_in, sn):
+        """The two input volumes of the volume net from the crops' features (g6d_refiner_volume_kp): fp32 mean_in [.., sn^3, 2C] and std
+        [.., sn^3, C], or — volume_pair_route — the same as PairMaps [qn,sn,sn,sn,2,2C] / [qn,sn,sn,sn,2,C], one exponent slot each."""
+        dev = feats.device
+        lin = _linspace(sn, dev)
+        C = feats.shape[-1]
+        args = (feats, ref_Ks.contiguous(), ref_poses.contiguous(), K_in.contiguous(), pose_in.contiguous(), lin, h_in, w_in)
+        if feats.dim() == 5 and self.volume_pair_route(feats.shape[0], sn):
+            rng = self._pair_rng()
+            return ops.refiner_volume_kp_pairs(*args, rng_mean=(rng, rng.slot("volume.mean_in")), rng_std=(rng, rng.slot("volume.std")))
+        lead = (feats.shape[0],) if feats.dim() == 5 else ()
+        mean_in = torch.empty(lead + (sn ** 3, 2 * C), dtype=torch.float32, device=dev)
+        std = torch.empty(lead + (sn ** 3, C), dtype=torch.float32, device=dev)
+        # projections K @ pose and the volume's rotation are formed inside the kernel (reference refiner.py:208-226)
+        return ops.refiner_volume_kp(*args, mean_in, std)
+
     def run_volume_net(self, mean_in, std, sn):
         """mean_in [sn^3,256], std [sn^3,128] -> code [(sn/8)^3, 512] (reference refiner.py:136-143); or a batch of qn volumes
         ([qn,sn^3,256], [qn,sn^3,128] -> [qn,(sn/8)^3,512]) through the same launches: every InstanceNorm3d keeps one statistics group
-        and one affine table per volume."""
+        and one affine table per volume.  PairMap volumes (feature_volumes on the pair route): the sn^3 stage runs on the pair kernel."""
         pk = self._pack()
-        dev = mean_in.device
-        batched = mean_in.dim() == 3
+        pairs_in = isinstance(mean_in, ops.PairMap)
+        dev = mean_in.data.device if pairs_in else mean_in.device
+        batched = pairs_in or mean_in.dim() == 3
         qn = mean_in.shape[0] if batched else 1
         pn = 1 if qn > 1 else 0                      # per-volume tables / groups only when there is more than one
 
@@ -285,21 +327,59 @@ class VolumeRefiner(ParamBank):
             return torch.empty((qn, s, s, s, c), dtype=torch.float32, device=dev)
 
         vox = sn ** 3
-        cat = buf(sn, 128)
-        def embed(name, x, sl):
+        rng = self._pair_rng() if pairs_in else None
+        cat16 = pairs_in and "conv0" in VOLUME_PAIR_LAYERS
+        # the two embeds meet in `cat`: ONE 128-channel pair map (one exponent slot for both slices) when conv0 reads pairs, else fp32
+        cat = ops.new_map16(qn * sn, sn, sn, 128, 3, dev, rng=(rng, rng.slot("volume.cat"))) if cat16 else buf(sn, 128)
+
+        def c16(layer, xin, y, stats_c=None, count=vox):
+            """A stride-1 3x3x3 layer on the pair kernel (depth taps folded into the reduction): xin a PairMap [qn,s,s,s,2,Cin], y the fp32
+            output (a dense map or a channel slice of one); with stats_c: the per-volume sums (count voxels) in the epilogue and one small
+            launch that finalises them -> the affine (scale, shift) of the InstanceNorm that follows."""
+            st = ops.new_stats(qn, stats_c, dev) if stats_c else None
+            ops.conv16_direct_multi([xin], layer.w16(3, layout=2), layer[1], relu=False, full=torch.float32, kd=3, stats=st,
+                                    rows_per_group=count if stats_c else 0, out_full=[y])
+            return ops.stats_finalize(st, count) if stats_c else None
+
+        def embed(name, x, c_off):
+            if pairs_in:
+                return embed16(name, x, c_off)
             y = buf(sn, 64)
             aff = c3(x, pk[name][0], y, stats_c=64, count=vox)
-            c3(y, pk[name][1], cat[..., sl], aff=aff)
+            c3(y, pk[name][1], cat[..., c_off:c_off + 64], aff=aff)
+
+        def embed16(name, x, c_off):
+            """conv, IN, ReLU, conv on pairs: the InstanceNorm affine + ReLU between the two layers is the elementwise pass that writes the
+            second layer's pairs (planes as images: sn planes per affine table); the second layer's fp32 map goes into its slice of `cat`
+            — directly (fp32 `cat`), or through the pass that splits it into the pair map conv0 reads."""
+            y0 = buf(sn, 64)
+            sc, sh = c16(pk[name][0], x, y0, stats_c=64)
+            mid = ops.affine_split16(y0.view(qn * sn, 1, sn, sn, 64), sc, sh, sn, True, False, 3, rng=(rng, rng.slot(f"volume.{name[2:]}.mid")))
+            if not cat16:
+                c16(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), cat[..., c_off:c_off + 64])
+                return
+            y1 = buf(sn, 64)
+            c16(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), y1)
+            ops.affine_split16_to(y1.view(qn * sn, 1, sn, sn, 64), None, None, 0, False, 3, cat, c_off)
 
         with self._mm("embed"):
-            embed("v_mean_embed", mean_in.view(qn, sn, sn, sn, 256), slice(0, 64))
-            embed("v_var_embed", std.view(qn, sn, sn, sn, 128), slice(64, 128))
+            embed("v_mean_embed", mean_in.view(qn, sn, sn, sn, 2, 256) if pairs_in else mean_in.view(qn, sn, sn, sn, 256), 0)
+            embed("v_var_embed", std.view(qn, sn, sn, sn, 2, 128) if pairs_in else std.view(qn, sn, sn, sn, 128), 64)
         x, aff, s = cat, None, sn
         with self._mm("stack"):
             for name, co, stride in (("v_conv0", 64, 1), ("v_conv1", 128, 2), ("v_conv2", 128, 1), ("v_conv3", 256, 2),
                                      ("v_conv4", 256, 1)):
                 s = s // stride
                 y = buf(s, co)
+                if name == "v_conv0" and cat16:
+                    # fp32 output with the sums: conv1 (stride 2, implicit GEMM) still takes the affine in its operand prologue
+                    x, aff = y, c16(pk[name], cat.view(qn, sn, sn, sn, 2, 128), y, stats_c=co)
+                    continue
+                if name == "v_conv2" and pairs_in and "conv2" in VOLUME_PAIR_LAYERS:
+                    # conv1's InstanceNorm affine + ReLU is the pass that writes conv2's pairs (planes as images: s planes per table)
+                    xin = ops.affine_split16(x.view(qn * s, 1, s, s, 128), aff[0], aff[1], s, True, False, 3, rng=(rng, rng.slot("volume.conv2.in")))
+                    x, aff = y, c16(pk[name], xin.view(qn, s, s, s, 2, 128), y, stats_c=co, count=s ** 3)
+                    continue
                 x, aff = y, c3(x, pk[name], y, stride=stride, aff=aff, stats_c=co, count=s ** 3)
         s = s // 2
         y = buf(s, 512)
@@ -346,17 +426,10 @@ class VolumeRefiner(ParamBank):
         else:
             imgs = torch.cat([ref_imgs, que_img], 0)                                         # query last
         feats = self.run_feature_net(imgs)
-        lin = _linspace(sn, dev)
-        C = feats.shape[-1]
-        lead = (qn,) if batched else ()
-        mean_in = torch.empty(lead + (sn ** 3, 2 * C), dtype=torch.float32, device=dev)
-        std = torch.empty(lead + (sn ** 3, C), dtype=torch.float32, device=dev)
         feats = feats.contiguous()
         if batched:
             feats = feats.view(qn, rfn + 1, *feats.shape[1:])
-        # projections K @ pose and the volume's rotation are formed inside the kernel (reference refiner.py:208-226)
-        ops.refiner_volume_kp(feats, ref_Ks.contiguous(), ref_poses.contiguous(), K_in.contiguous(), pose_in.contiguous(),
-                              lin, h_in, w_in, mean_in, std)
+        mean_in, std = self.feature_volumes(feats, ref_Ks, ref_poses, K_in, pose_in, h_in, w_in, sn)
         return self.run_regressor(self.run_volume_net(mean_in, std, sn))
 
     def _step_from_feats(self, que_img, K_in, pose_in, ref_feats, ref_Ks, ref_poses):
@@ -369,16 +442,9 @@ class VolumeRefiner(ParamBank):
         qf = self.run_feature_net(que_img)                                               # [qn,fh,fw,C]
         if batched:
             feats = torch.cat([ref_feats, qf[:, None]], 1).contiguous()                  # [qn,rfn+1,fh,fw,C], query last
-            lead = (ref_feats.shape[0],)
         else:
             feats = torch.cat([ref_feats, qf], 0).contiguous()
-            lead = ()
-        lin = _linspace(sn, dev)
-        C = feats.shape[-1]
-        mean_in = torch.empty(lead + (sn ** 3, 2 * C), dtype=torch.float32, device=dev)
-        std = torch.empty(lead + (sn ** 3, C), dtype=torch.float32, device=dev)
-        ops.refiner_volume_kp(feats, ref_Ks.contiguous(), ref_poses.contiguous(), K_in.contiguous(), pose_in.contiguous(),
-                              lin, h_in, w_in, mean_in, std)
+        mean_in, std = self.feature_volumes(feats, ref_Ks, ref_poses, K_in, pose_in, h_in, w_in, sn)
         return self.run_regressor(self.run_volume_net(mean_in, std, sn))
 
     def forward(self, data):

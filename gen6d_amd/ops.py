@@ -742,8 +742,9 @@ def _wrap(t, rng):
 
 
 class Conv16Filters:
-    """Filters of g6d_conv16_direct_multi: `data` (16-bit, flat), `layout` (0 = [Cout][taps][Cin] rows, 1 = fragment-major), `mode`
-    (1 bf16, 2 fp16, 3 fp16 hi / lo pairs), `acc_scale` (1 / the power-of-two scale the filters carry), and the layer's shape."""
+    """Filters of g6d_conv16_direct_multi: `data` (16-bit, flat), `layout` (0 = [Cout][taps][Cin] rows, 1 = fragment-major, 2 = fragment-major
+    with the depth taps of a 3x3x3 layer folded into the channels), `mode` (1 bf16, 2 fp16, 3 fp16 hi / lo pairs), `acc_scale` (1 / the
+    power-of-two scale the filters carry), and the layer's shape."""
 
     def __init__(self, data, layout, mode, acc_scale, Cout, taps, Cin):
         self.data, self.layout, self.mode, self.acc_scale, self.Cout, self.taps, self.Cin = data, layout, mode, acc_scale, Cout, taps, Cin
@@ -758,11 +759,27 @@ def _split_hi_lo(w_taps):
     return hi, (w - hi.double()).to(torch.float16), 1.0 / S
 
 
+def conv16_fold_depth(w_taps):
+    """[Cout, 27, Cin] filters of a 3x3x3 layer (tap = (kz*3 + ky)*3 + kx) -> the 2-D bank [Cout, 9, 3 Cin] whose channel kz * Cin + ci of
+    in-plane tap ky*3 + kx is filter (kz, ky, kx) of channel ci: the depth taps become part of the reduction."""
+    co, taps, ci = w_taps.shape
+    if taps != 27:
+        raise ValueError("conv16_fold_depth: [Cout, 27, Cin] expected")
+    return w_taps.reshape(co, 3, 9, ci).permute(0, 2, 1, 3).reshape(co, 9, 3 * ci).contiguous()
+
+
 def conv16_pack(w_taps, mode, layout=1):
     """[Cout, taps, Cin] fp32 filters (tap = (kz*3 + ky)*3 + kx) -> Conv16Filters for `mode` (1 bf16, 2 fp16, 3 fp16 hi / lo pairs).
     layout 1 (fragment-major, include/gen6d_hip.h): [Cout/128][Cin/BK][taps][BK/16][planes][4][64 lanes][8], BK = 64 (pairs: 32), lane l
     of group j holds filter co = 128 tile + 32 j + (l & 31), ci = BK slice + 16 ks + 8 (l >> 5) + e.  Mode 3: the filters are scaled by an
-    exact power of two S (their lo parts stay normal fp16 numbers; the kernel multiplies the accumulators by 1 / S) and split in fp64."""
+    exact power of two S (their lo parts stay normal fp16 numbers; the kernel multiplies the accumulators by 1 / S) and split in fp64.
+    layout 2 (pairs, 27 taps): the depth taps folded into the reduction — the 2-D bank [Cout, 9, 3 Cin] with channel order (dz, ci)
+    (conv16_fold_depth) in layout 1; the halo-patch kernel walks it as 3 Cin / 32 slices of nine in-plane taps."""
+    if layout == 2:
+        if mode != 3 or w_taps.shape[1] != 27:
+            raise ValueError("conv16_pack: the depth-folded layout takes 27-tap filters in mode 3 (fp16 pairs)")
+        f = conv16_pack(conv16_fold_depth(w_taps), mode, layout=1)
+        return Conv16Filters(f.data, 2, mode, f.acc_scale, f.Cout, 27, w_taps.shape[2])
     co, taps, ci = w_taps.shape
     bk = 32 if mode == 3 else 64
     co_true = co
@@ -995,18 +1012,19 @@ def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, s
     return fulls, pools
 
 
-def conv16_direct_plan(N, H, W, Cin, Cout, mode, stats_rows=0, full=torch.float32):
+def conv16_direct_plan(N, H, W, Cin, Cout, mode, stats_rows=0, full=torch.float32, D=None):
     """The kernel conv16_direct_multi would launch for ONE 2-D map [N,H,W,Cin] -> Cout with fragment-major filters (g6d_conv16_direct_plan:
     validation only, nothing is launched or dereferenced): None = rejected, 0 = the per-tap kernels, 1 = the halo-patch kernel, 2 = the
-    halo-patch kernel with statistics groups of whole epilogue passes (stats_rows: pixels per statistics group, 0 = no statistics)."""
+    halo-patch kernel with statistics groups of whole epilogue passes (stats_rows: pixels per statistics group, 0 = no statistics).
+    D: the same question for a 3x3x3 layer on N volumes [N,D,H,W,Cin] with depth-folded filters (layout 2): 1 or None."""
     pair = mode == 3
     code = {None: 0, "t16": 3 if pair else 1, torch.float32: 2}[full]
     any_ = 1 << 12                                             # (a non-null, 16-byte aligned stand-in: the plan tests pointers only)
     ldf = 2 * Cout if code == 3 else Cout
-    seg = (_lib.G6dConv16Seg * 1)(_lib.G6dConv16Seg(in_=any_, out_full=any_ if code else None, out_pool=None, N=N, D=1, H=H, W=W,
+    seg = (_lib.G6dConv16Seg * 1)(_lib.G6dConv16Seg(in_=any_, out_full=any_ if code else None, out_pool=None, N=N, D=D or 1, H=H, W=W,
                                                     ld_in=(2 if pair else 1) * Cin, ld_full=ldf if code else 0, ld_pool=0))
-    rc = _lib.load().g6d_conv16_direct_plan(seg, 1, Cin, C.c_void_p(any_), 1, Cout, 1, code, 0, int(mode), C.c_void_p(any_ if stats_rows else 0),
-                                            int(stats_rows))
+    rc = _lib.load().g6d_conv16_direct_plan(seg, 1, Cin, C.c_void_p(any_), 2 if D else 1, Cout, 3 if D else 1, code, 0, int(mode),
+                                            C.c_void_p(any_ if stats_rows else 0), int(stats_rows))
     return rc if rc >= 0 else None
 
 
@@ -1213,6 +1231,31 @@ def refiner_volume_kp(feats, ref_Ks, ref_poses, K_in, pose_in, lin, h_in, w_in, 
                                                                     _ptr(lin), V - 1, fh, fw, Cc, int(h_in), int(w_in), sn, _ptr(mean_in),
                                                                     _ptr(std), B, _stream()), "g6d_refiner_volume_kp"))
     return mean_in, std
+
+
+def refiner_volume_kp_pairs(feats, ref_Ks, ref_poses, K_in, pose_in, lin, h_in, w_in, rng_mean=None, rng_std=None):
+    """refiner_volume_kp (batched operands) with both volumes written as fp16 hi / lo pair maps, the input format of conv16_direct_multi in
+    mode 3 (g6d_refiner_volume_kp_pairs): -> (mean_in [B,sn,sn,sn,2,2C], std [B,sn,sn,sn,2,C]) fp16.  rng_mean / rng_std = (RangeTable,
+    slot): the map carries that slot's exponent, is recorded and comes back as a PairMap."""
+    _need_gpu(feats, ref_Ks, ref_poses, K_in, pose_in, lin)
+    if feats.dim() != 5:
+        raise ValueError("refiner_volume_kp_pairs: batched operands expected")
+    B, V, fh, fw, Cc = feats.shape
+    sn = lin.numel()
+    for t in (feats, ref_Ks, ref_poses, K_in, pose_in, lin):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError("refiner_volume_kp_pairs: operands must be contiguous float32")
+    if (tuple(ref_Ks.shape) != (B, V - 1, 3, 3) or tuple(ref_poses.shape) != (B, V - 1, 3, 4) or tuple(K_in.shape) != (B, 3, 3) or
+            tuple(pose_in.shape) != (B, 3, 4)):
+        raise ValueError("refiner_volume_kp_pairs: shape mismatch")
+    mean_in = torch.empty((B, sn, sn, sn, 2, 2 * Cc), dtype=torch.float16, device=feats.device)
+    std = torch.empty((B, sn, sn, sn, 2, Cc), dtype=torch.float16, device=feats.device)
+    ra_m, ra_s = _range_arg(None, -1, rng_mean), _range_arg(None, -1, rng_std)
+    _timed_hbm("refiner_volume", 4.0 * B * (V * fh * fw * Cc + 3 * sn ** 3 * Cc),
+               lambda: _lib.check(_lib.load().g6d_refiner_volume_kp_pairs(
+                   _ptr(feats), _ptr(ref_Ks), _ptr(ref_poses), _ptr(K_in), _ptr(pose_in), _ptr(lin), V - 1, fh, fw, Cc, int(h_in), int(w_in), sn,
+                   _ptr(mean_in), _ptr(std), B, ra_m, ra_s, _stream()), "g6d_refiner_volume_kp_pairs"))
+    return _wrap(mean_in, rng_mean), _wrap(std, rng_std)
 
 
 def cat1(ts, dim=0):

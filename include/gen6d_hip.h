@@ -450,6 +450,13 @@ int g6d_refiner_volume(const float* feats, const float* projs, const float* rot_
 int g6d_refiner_volume_kp(const float* feats, const float* ref_Ks, const float* ref_poses, const float* K_in, const float* pose_in,
                           const float* lin, int rfn, int fh, int fw, int C, int h_in, int w_in, int sn, float* mean_in, float* stdv,
                           int batch, g6d_stream_t stream);
+/* g6d_refiner_volume_kp with both volumes written as fp16 hi / lo PAIR maps in the activation format of g6d_conv16_direct_multi, math_mode 3
+ * (additive to ABI v12): mean_in16 [batch][sn^3][2][2C] and std16 [batch][sn^3][2][C] fp16 — per voxel the hi plane, then the lo plane; the
+ * same gathers and arithmetic as the fp32 entry and the same number of bytes written.  Each map has its own exponent slot and range record
+ * (range_mean / range_std: slot_out; NULL = unscaled and not recorded), the protocol of the elementwise pair producers above. */
+int g6d_refiner_volume_kp_pairs(const float* feats, const float* ref_Ks, const float* ref_poses, const float* K_in, const float* pose_in,
+                                const float* lin, int rfn, int fh, int fw, int C, int h_in, int w_in, int sn, void* mean_in16, void* std16,
+                                int batch, const G6dRange16* range_mean, const G6dRange16* range_std, g6d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Detector score assembly (network/detector.py:225-229,243-245,207-216): for one detection scale, take the three raw

@@ -1,0 +1,21 @@
+"""Per-kernel hashes of the conv16w_kernel instantiations in two device-assembly files, to show that a change left an instantiation's
+code as it was:
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -w -S --cuda-device-only -I include -o new.s gen6d_amd/csrc/conv16_direct.hip   (both trees)
+    python tools/conv16w_asm_hash.py old.s new.s
+Instructions and directives only: comments, block-label numbering and the kernel's own mangled name are normalised, and a trailing
+KD = 1 template argument is dropped from the name, so that an instantiation keeps its key when the template gains that parameter."""
+import re, sys, hashlib
+def bodies(path):
+    text = open(path).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\w*conv16w_kernel\w*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
+        name = m.group(1)
+        body = m.group(2).replace(name, "KERNEL")
+        body = re.sub(r"\.LBB\d+_", ".LBB_", body)
+        body = "\n".join(l.split(";")[0].rstrip() for l in body.split("\n") if l.split(";")[0].strip())
+        key = re.sub(r"(ILi\dELi\dELi\d)ELi1(EEEvNS)", r"\1\2", name)
+        out[key] = (hashlib.sha256(body.encode()).hexdigest()[:16], body.count("\n") + 1)
+    return out
+a, b = bodies(sys.argv[1]), bodies(sys.argv[2])
+for k in sorted(set(a) | set(b)):
+    print(k, a.get(k), b.get(k), "SAME" if a.get(k) == b.get(k) else "DIFF")
