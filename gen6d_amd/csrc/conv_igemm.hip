@@ -45,10 +45,34 @@ __device__ __forceinline__ f32x4 ldg(const float* __restrict__ base, int elem_of
   return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + ((unsigned)elem_off << 2));
 }
 
+// Pair mode (MM = 3): the kernel signature is shared by all modes, so its two device pointers — the activation exponent
+// &exps[slot_out] and the range record &rec[slot_out] of the launch's G6dRange16 (slot_in is not read) — ride in the kernel's own COPY of the descriptor, in the Winograd filter
+// pointers that this kernel never reads (launch_mm sets them; the caller's descriptor is not touched).
+__device__ __forceinline__ const int* pair_exp_ptr(const G6dConv& p) { return reinterpret_cast<const int*>(p.weight_wino16); }
+__device__ __forceinline__ unsigned* pair_rec_ptr(const G6dConv& p) { return reinterpret_cast<unsigned*>(const_cast<float*>(p.weight_wino43)); }
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// one thread's 4 channels (4 seg .. 4 seg + 3) of an LDS row as pairs: hi = rn16(u), lo = rn16(u - hi) into the row's two 64-byte planes
+__device__ __forceinline__ void store_pair(float* row, int seg, f32x4 u) {
+  f16x4 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { hi[e] = (_Float16)u[e]; lo[e] = (_Float16)(u[e] - (float)hi[e]); }
+  char* r = reinterpret_cast<char*>(row);
+  *reinterpret_cast<f16x4*>(r + 8 * seg) = hi;
+  *reinterpret_cast<f16x4*>(r + 64 + 8 * seg) = lo;
+}
+
 // MODE: 0 = plain operand, 1 = affine(+ReLU) with one table, 2 = affine(+ReLU) with a table per image group (n / in_affine_per_n),
 //       3 = elementwise multiplier + affine with one table (selector product), 4 = multiplier + a table per image group (the
 //       selector product of a BATCH of queries: multiplier and table of query n / k, input image n % k — G6dConv.in_image_mod).
-// MM: 0 = fp32 MFMA (default); 1 / 2 = bf16 / fp16 operands, fp32 accumulation (G6dConv.math_mode, g6d_common.h).
+// MM: 0 = fp32 MFMA (default); 1 / 2 = bf16 / fp16 operands, fp32 accumulation (G6dConv.math_mode, g6d_common.h);
+//     3 = fp16 hi / lo PAIRS, fp32-class results on the 16-bit matrix cores: the loader still fetches fp32 and applies the prologue, then
+//     splits every value ONCE — hi = rn16(u), lo = rn16(u - hi), u = activation * 2^-e_in or filter * 2^w_exp — and stores two 16-bit planes
+//     into the LDS row: bytes [0, 64) the 32 hi channels of the K step, [64, 128) the 32 lo channels, inside the same 144-byte row stride.
+//     A lane's fragment of v_mfma_f32_32x32x16_f16 is 8 consecutive channels of one plane: ONE ds_read_b128 at row * 144 + 64 plane +
+//     32 ks + 16 (lane >> 5) — the address pattern of the fp32 fragments (row * 36 + 8 kc + 4 (lane >> 5) floats), so conflict-free the
+//     same way — and nothing is converted at the use site.  Per 16 channels and accumulator: hi x hi, hi x lo, lo x hi (lo x lo dropped,
+//     as c16_mfma<3> in conv16_direct.hip).  The accumulators (and split partials) stay unscaled fp32 sums of the scaled operands; the
+//     epilogue multiplies by 2^(e_in - w_exp).  The largest |activation| after the prologue is recorded (G6dRange16, one atomic per block).
 template <int BM, int BN, int WGM, int WGN, int MODE, int MM>
 __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, const int M, const int T,
                                                          const int nChunks, const int itersPerSplit,
@@ -101,6 +125,13 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
   const float* __restrict__ gsc = p.in_scale;
   const float* __restrict__ gsh = p.in_shift;
   const int relu = p.in_relu;
+  // pair mode: operand scales (exact powers of two) and this thread's running max of the |activation| bits
+  float a_mul = 1.f, w_mul = 1.f, o_mul = 1.f;
+  unsigned amax = 0u;
+  if constexpr (MM == 3) {
+    const int e_in = pair_exp_ptr(p) ? *pair_exp_ptr(p) : 0;
+    a_mul = __builtin_ldexpf(1.f, -e_in); w_mul = __builtin_ldexpf(1.f, p.w_exp); o_mul = __builtin_ldexpf(1.f, e_in - p.w_exp);
+  }
 
   // ---- per-thread rows of the activation tile: decode the output position once.  On this matrix pipe every vector-ALU
   //      instruction beside an fp32 MFMA is paid in full (tools/ubench/mfma_fill.hip), so the per-K-step work of the loader is
@@ -224,11 +255,18 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
       b &= va[s][j];
       v = __builtin_bit_cast(f32x4, b);
     }
-    *reinterpret_cast<f32x4*>(As + (lrow + 32 * j) * LDS_K + 4 * lseg) = v;
+    if constexpr (MM == 3) {
+      const u32x4 b = __builtin_bit_cast(u32x4, v) & 0x7fffffffu;
+      amax = max(amax, max(max(b[0], b[1]), max(b[2], b[3])));
+      store_pair(As + (lrow + 32 * j) * LDS_K, lseg, v * a_mul);
+    } else {
+      *reinterpret_cast<f32x4*>(As + (lrow + 32 * j) * LDS_K + 4 * lseg) = v;
+    }
   };
   auto store_b = [&](auto S, float* Bs, int j) {
     constexpr int s = decltype(S)::value;
-    *reinterpret_cast<f32x4*>(Bs + (lrow + 32 * j) * LDS_K + 4 * lseg) = rb[s][j];
+    if constexpr (MM == 3) store_pair(Bs + (lrow + 32 * j) * LDS_K, lseg, rb[s][j] * w_mul);
+    else *reinterpret_cast<f32x4*>(Bs + (lrow + 32 * j) * LDS_K + 4 * lseg) = rb[s][j];
   };
 
   f32x4 dummy = {0.f, 0.f, 0.f, 0.f};   // G6D_ABLATE == 6 only
@@ -271,7 +309,49 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     constexpr int par = decltype(PAR)::value;
     using SL = std::integral_constant<int, par>;
     using SS = std::integral_constant<int, par ^ 1>;
-    if constexpr (MM != 0) {
+    if constexpr (MM == 3) {
+      // pairs: a K step is 2 * 3 * MT * NT MFMAs of K = 16 on fragments read straight from the two planes; loads first, stores last
+#pragma unroll
+      for (int j = 0; j < RA; ++j) load_a(SL{}, j);
+#pragma unroll
+      for (int j = 0; j < RB; ++j) load_b(SL{}, j);
+      const char* Ab = reinterpret_cast<const char*>(As + (wm * WM + li) * LDS_K) + 16 * lh;
+      const char* Bb = reinterpret_cast<const char*>(Bs + (wn * WN + li) * LDS_K) + 16 * lh;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        f16x8 ah[MT], al[MT], bh[NT], bl[NT];
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          ah[i] = *reinterpret_cast<const f16x8*>(Ab + i * 32 * LDS_K * 4 + 32 * ks);
+          al[i] = *reinterpret_cast<const f16x8*>(Ab + i * 32 * LDS_K * 4 + 64 + 32 * ks);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          bh[j] = *reinterpret_cast<const f16x8*>(Bb + j * 32 * LDS_K * 4 + 32 * ks);
+          bl[j] = *reinterpret_cast<const f16x8*>(Bb + j * 32 * LDS_K * 4 + 64 + 32 * ks);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            if (ONE_ACC && ks == 1) {        // the lone accumulator alternates with acc_odd as in the fp32 schedule
+              acc_odd = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc_odd, 0, 0, 0);
+              acc_odd = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc_odd, 0, 0, 0);      // hi x lo
+              acc_odd = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc_odd, 0, 0, 0);      // lo x hi
+            } else {
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);  // hi x lo
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);  // lo x hi
+            }
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < RA; ++j) store_a(SS{}, An, j);
+#pragma unroll
+      for (int j = 0; j < RB; ++j) store_b(SS{}, Bn, j);
+      advance(); begin_step(SS{});
+      return;
+    } else if constexpr (MM != 0) {
       // reduced precision: a K step is 2 * MT * NT MFMAs of K = 16 (two 8-channel fragment slices each); the step is bound by
       // the loads, so they are simply issued first, the stores last
 #pragma unroll
@@ -355,6 +435,18 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     if (G6D_ABLATE == 6) acc[0][0][0] += dummy[0] + dummy[1] + dummy[2] + dummy[3];
   }
 
+  if constexpr (MM == 3) {
+    // range record: the block's largest |activation| (integer max of the IEEE bits: NaN > inf > finite), one atomic per block and only
+    // when it exceeds a coherent read of the record.  Every wave passed the K loop's last barrier: the second LDS stage is free, and the
+    // epilogue below only touches the head of the first.
+    if (pair_rec_ptr(p)) {
+      unsigned* red = reinterpret_cast<unsigned*>(lds + STAGE);
+      amax = g6d_wave_max_u(amax);
+      if (lane == 0) red[wave] = amax;
+      __syncthreads();
+      if (tid == 0) g6d_range_max(pair_rec_ptr(p), max(max(red[0], red[1]), max(red[2], red[3])));
+    }
+  }
   // ---------------------------------------------------------------- epilogue
   if constexpr (ONE_ACC) {
 #pragma unroll
@@ -432,7 +524,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = row_m(wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-        float v = apply_act(acc[i][j][r] + bv, p.out_act);
+        float v = apply_act((MM == 3 ? acc[i][j][r] * o_mul : acc[i][j][r]) + bv, p.out_act);
         if (row < M && cval) {
           p.out[(size_t)row * p.ld_out + col] = v;
           if (do_stats) {
@@ -481,7 +573,7 @@ bool igemm_position_major(const G6dConv& d, int bm, int splits) {
 }
 
 template <int BM, int BN, int WGM, int WGN, int MODE, int MM>
-int launch_mm(const G6dConv& d, int M, int T, int nChunks, int splits, hipStream_t stream) {
+int launch_mm(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks, int splits, hipStream_t stream) {
   const int total = T * nChunks;
   const int ips = (total + splits - 1) / splits;
   splits = (total + ips - 1) / ips;
@@ -498,25 +590,39 @@ int launch_mm(const G6dConv& d, int M, int T, int nChunks, int splits, hipStream
   const unsigned in_bytes = (unsigned)((n_in * d.Di * d.Hi * d.Wi * d.ld_in + pad_a) * 4);
   const unsigned w_bytes = (unsigned)((long long)d.Cout * T * d.Cin * 4);
   const unsigned mul_bytes = (unsigned)((n_mul * d.Hi * d.Wi * d.Cin + pad_m) * 4);
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, MODE, MM>), grid, dim3(256), lds_bytes, stream, d, M, T, nChunks,
+  G6dConv k = d;
+  if constexpr (MM == 3) {      // the kernel's copy carries the pair mode's device pointers (pair_exp_ptr / pair_rec_ptr)
+    k.weight_wino = nullptr;
+    k.weight_wino16 = rng.exps && rng.slot_out >= 0 ? rng.exps + rng.slot_out : nullptr;
+    k.weight_wino43 = rng.rec && rng.slot_out >= 0 ? reinterpret_cast<const float*>(rng.rec + rng.slot_out) : nullptr;
+  }
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, MODE, MM>), grid, dim3(256), lds_bytes, stream, k, M, T, nChunks,
                      ips, total, splits, in_bytes, w_bytes, mul_bytes, pm_hw, pm_tiles, ny);
   return g6d_check_launch("conv_igemm");
 }
 
 template <int BM, int BN, int WGM, int WGN, int MODE>
-int launch_mode(const G6dConv& d, int M, int T, int nChunks, int splits, hipStream_t stream) {
-  if (d.math_mode == 1) return launch_mm<BM, BN, WGM, WGN, MODE, 1>(d, M, T, nChunks, splits, stream);
-  if (d.math_mode == 2) return launch_mm<BM, BN, WGM, WGN, MODE, 2>(d, M, T, nChunks, splits, stream);
-  return launch_mm<BM, BN, WGM, WGN, MODE, 0>(d, M, T, nChunks, splits, stream);
+int launch_mode(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks, int splits, hipStream_t stream) {
+  if (d.math_mode == 1) return launch_mm<BM, BN, WGM, WGN, MODE, 1>(d, rng, M, T, nChunks, splits, stream);
+  if (d.math_mode == 2) return launch_mm<BM, BN, WGM, WGN, MODE, 2>(d, rng, M, T, nChunks, splits, stream);
+  if (d.math_mode == 3) {
+    // The routed layers (refiner.VOLUME_IGEMM_PAIR_LAYERS) reach MODE 2 on the 64x64 and 128x64 tiles.  The other six instantiations —
+    // MODE 0 / 1 on those tiles and on 128x128 — are reached by tests/test_conv_igemm_pairs_gpu.py and by the selector's candidate fuse0
+    // (128x128, MODE 0: tools/igemm_pair_layers.py; selector.SELECTOR_IGEMM_PAIR_LAYERS is empty, so no product call runs them today)
+    // (a table per image group never meets the 128x128 tile: g6d_conv_igemm narrows it to 128x64)
+    if constexpr (MODE <= 2 && BN >= 64 && !(BN == 128 && MODE == 2)) return launch_mm<BM, BN, WGM, WGN, MODE, 3>(d, rng, M, T, nChunks, splits, stream);
+    g6d_set_error("conv: math_mode 3 (fp16 pairs) has no kernel for this tile / prologue"); return G6D_EINVAL;
+  }
+  return launch_mm<BM, BN, WGM, WGN, MODE, 0>(d, rng, M, T, nChunks, splits, stream);
 }
 
 template <int BM, int BN, int WGM, int WGN>
-int launch_cfg(const G6dConv& d, int M, int T, int nChunks, int splits, hipStream_t stream) {
-  if (d.mul) return d.in_affine_per_n ? launch_mode<BM, BN, WGM, WGN, 4>(d, M, T, nChunks, splits, stream)
-                                      : launch_mode<BM, BN, WGM, WGN, 3>(d, M, T, nChunks, splits, stream);
-  if (!d.in_scale) return launch_mode<BM, BN, WGM, WGN, 0>(d, M, T, nChunks, splits, stream);
-  if (d.in_affine_per_n) return launch_mode<BM, BN, WGM, WGN, 2>(d, M, T, nChunks, splits, stream);
-  return launch_mode<BM, BN, WGM, WGN, 1>(d, M, T, nChunks, splits, stream);
+int launch_cfg(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks, int splits, hipStream_t stream) {
+  if (d.mul) return d.in_affine_per_n ? launch_mode<BM, BN, WGM, WGN, 4>(d, rng, M, T, nChunks, splits, stream)
+                                      : launch_mode<BM, BN, WGM, WGN, 3>(d, rng, M, T, nChunks, splits, stream);
+  if (!d.in_scale) return launch_mode<BM, BN, WGM, WGN, 0>(d, rng, M, T, nChunks, splits, stream);
+  if (d.in_affine_per_n) return launch_mode<BM, BN, WGM, WGN, 2>(d, rng, M, T, nChunks, splits, stream);
+  return launch_mode<BM, BN, WGM, WGN, 1>(d, rng, M, T, nChunks, splits, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -613,10 +719,11 @@ int conv_narrow_launch(const G6dConv& d, hipStream_t stream) {
 }  // namespace
 
 // Which kernel family g6d_conv_igemm will run this descriptor on: 0 generic implicit GEMM, 1 LDS-patch kernel, 2 Winograd kernel,
-// 3 F(4x4,3x3) kernel, 4 the narrow-output kernel on the vector ALUs
+// 3 F(4x4,3x3) kernel, 4 the narrow-output kernel on the vector ALUs, 5 the implicit GEMM on fp16 hi / lo pairs (math_mode 3: no hand-off)
 // (no launch; bench.py uses it to book the executed FLOPs of a launch in the right roofline family).
 extern "C" int g6d_conv_plan(const G6dConv* desc) {
   if (!desc) return G6D_EINVAL;
+  if (desc->math_mode == 3) return 5;
   if (conv_narrow_eligible(*desc)) return 4;
   if (g6d_wino43_eligible(*desc)) return 3;
   if (g6d_wino_eligible(*desc)) return 2;
@@ -624,12 +731,23 @@ extern "C" int g6d_conv_plan(const G6dConv* desc) {
   return (use_patch && g6d_conv_patch_eligible(*desc)) ? 1 : 0;
 }
 
-extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) {
+extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) { return g6d_conv_igemm_ex(desc, nullptr, stream_); }
+
+extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g6d_stream_t stream_) {
   if (!desc) return G6D_EINVAL;
   const G6dConv& d = *desc;
+  const G6dRange16 rng = range ? *range : G6dRange16{nullptr, nullptr, -1, -1};
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!d.in || !d.weight || !d.out) { g6d_set_error("conv: null pointer"); return G6D_EINVAL; }
-  if (d.math_mode < 0 || d.math_mode > 2) { g6d_set_error("conv: math_mode must be 0 (fp32), 1 (bf16) or 2 (fp16)"); return G6D_EINVAL; }
+  if (d.math_mode < 0 || d.math_mode > 3) { g6d_set_error("conv: math_mode must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (fp16 pairs)"); return G6D_EINVAL; }
+  const bool pairs = d.math_mode == 3;
+  if (pairs) {
+    if (d.weight_wino16) { g6d_set_error("conv: math_mode 3 (fp16 pairs) runs on the implicit-GEMM kernel: weight_wino16 must be NULL"); return G6D_EINVAL; }
+    if (d.Cin & 7) { g6d_set_error("conv: math_mode 3 (fp16 pairs) needs Cin % 8 == 0 (a fragment is 8 channels of one plane)"); return G6D_EINVAL; }
+    if (d.Cout <= 32) { g6d_set_error("conv: math_mode 3 (fp16 pairs) needs Cout > 32 (no 32-channel tile)"); return G6D_EINVAL; }
+    if (d.mul) { g6d_set_error("conv: math_mode 3 (fp16 pairs) takes no multiplier"); return G6D_EINVAL; }
+    if (d.w_exp < -64 || d.w_exp > 64) { g6d_set_error("conv: w_exp out of range (|w_exp| <= 64)"); return G6D_EINVAL; }
+  } else if (range) { g6d_set_error("conv: a G6dRange16 applies to math_mode 3 only"); return G6D_EINVAL; }
   if (d.N <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.Do <= 0 || d.Ho <= 0 || d.Wo <= 0 || d.kd <= 0 || d.kh <= 0 || d.kw <= 0) {
     g6d_set_error("conv: bad shape"); return G6D_EINVAL;
   }
@@ -657,11 +775,13 @@ extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) {
   const long long Mll = (long long)d.N * d.Do * d.Ho * d.Wo;
   if (Mll > (1ll << 30)) { g6d_set_error("conv: M too large"); return G6D_EINVAL; }
   const int M = (int)Mll;
-  if (conv_narrow_eligible(d)) return conv_narrow_launch(d, stream);
-  if (g6d_wino43_eligible(d)) return g6d_wino43_launch(d, stream);
-  if (g6d_wino_eligible(d)) return g6d_wino_launch(d, stream);
-  const bool use_patch = g6d_knob(G6D_KNOB_CONV_PATCH) != 0;
-  if (use_patch && g6d_conv_patch_eligible(d)) return g6d_conv_patch_launch(d, M, stream);
+  if (!pairs) {      // math_mode 3 is the implicit-GEMM kernel itself: no hand-off
+    if (conv_narrow_eligible(d)) return conv_narrow_launch(d, stream);
+    if (g6d_wino43_eligible(d)) return g6d_wino43_launch(d, stream);
+    if (g6d_wino_eligible(d)) return g6d_wino_launch(d, stream);
+    const bool use_patch = g6d_knob(G6D_KNOB_CONV_PATCH) != 0;
+    if (use_patch && g6d_conv_patch_eligible(d)) return g6d_conv_patch_launch(d, M, stream);
+  }
   const int T = d.kd * d.kh * d.kw;
   const int nChunks = (d.Cin + BK - 1) / BK;
   const int total = T * nChunks;
@@ -708,8 +828,8 @@ extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) {
       if (splits < 2) splits = 1;
     }
   }
-  if (bm == 64) return launch_cfg<64, 64, 2, 2>(d, M, T, nChunks, splits, stream);
-  if (bn == 32) return launch_cfg<128, 32, 4, 1>(d, M, T, nChunks, splits, stream);
-  if (bn == 64) return launch_cfg<128, 64, 2, 2>(d, M, T, nChunks, splits, stream);
-  return launch_cfg<128, 128, 2, 2>(d, M, T, nChunks, splits, stream);
+  if (bm == 64) return launch_cfg<64, 64, 2, 2>(d, rng, M, T, nChunks, splits, stream);
+  if (bn == 32) return launch_cfg<128, 32, 4, 1>(d, rng, M, T, nChunks, splits, stream);
+  if (bn == 64) return launch_cfg<128, 64, 2, 2>(d, rng, M, T, nChunks, splits, stream);
+  return launch_cfg<128, 128, 2, 2>(d, rng, M, T, nChunks, splits, stream);
 }

@@ -68,10 +68,22 @@ class G6dConv(C.Structure):
         ("weight_wino", C.c_void_p),
         ("fin_scale", C.c_void_p), ("fin_shift", C.c_void_p), ("fin_counter", C.c_void_p),
         ("fin_count", C.c_double), ("fin_eps", C.c_double), ("fin_groups", C.c_int32),
-        ("in_image_mod", C.c_int32), ("mul_group_images", C.c_int32), ("reserved_", C.c_int32),
+        ("in_image_mod", C.c_int32), ("mul_group_images", C.c_int32), ("reserved_", C.c_int32),      # = the header's w_exp: see __init__
         ("weight_wino16", C.c_void_p), ("weight_wino43", C.c_void_p),
     ]
 
+
+# The header names the former reserved_ field w_exp (math_mode 3's filter exponent).  The binding keeps the field under its earlier
+# name in _fields_ — recorded descriptors (tests/test_multi_launch_cpu.py) list the fields by name — and exposes it as `w_exp`, the name
+# the package uses: G6dConv(w_exp=...) and d.w_exp read and write that field.
+def _conv_init(self, *a, w_exp=0, **k):
+    C.Structure.__init__(self, *a, **k)
+    if w_exp:
+        self.reserved_ = int(w_exp)
+
+
+G6dConv.__init__ = _conv_init
+G6dConv.w_exp = property(lambda self: self.reserved_, lambda self, v: setattr(self, "reserved_", int(v)))
 
 _P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
 
@@ -79,6 +91,7 @@ _P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
 SIGNATURES = {
     "g6d_marker": [_I, _P],
     "g6d_conv_igemm": [C.POINTER(G6dConv), _P],
+    "g6d_conv_igemm_ex": [C.POINTER(G6dConv), _P, _P],
     "g6d_conv_plan": [C.POINTER(G6dConv)],
     "g6d_corr2d_patch": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, C.c_size_t, _I, _P],
     "g6d_corr2d_patch_multi": [_P, _I, _I, _P, _I, _I, _I, _P, C.c_size_t, _I, _P],

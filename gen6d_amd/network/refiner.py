@@ -8,7 +8,8 @@ One refinement step (reference forward, refiner.py:249-269):
         the slice producers g6d_affine_split16_to / g6d_upsample_bilinear_split16 as hand-over passes — FEATNET_PAIR_BRANCHES)
     g6d_refiner_volume: projection + bilinear sampling + mean/std over references, fused            refiner.py:183-247
     RefineVolumeEncodingNet 3x3x3 convs on g6d_conv_igemm (32^3 layers: Winograd F(4x4,3x3), depth taps folded into the reduction;
-        16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K)
+        16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K — in batched calls of the fp32 path the layers of
+        VOLUME_IGEMM_PAIR_LAYERS in that kernel's own fp16 hi / lo pair mode)
         (batched calls of the fp32 path: the 32^3 layers of VOLUME_PAIR_LAYERS on fp16 hi / lo pairs, g6d_conv16_direct_multi with
         depth-folded filters; g6d_refiner_volume_kp_pairs writes their input volumes as pairs)
     g6d_linear_gemv_batch: the 32768->512 FC is a 67 MB weight stream, read once per 8 queries                                    refiner.py:153-166
@@ -47,6 +48,12 @@ FEATNET_PAIR_BRANCHES = ("conv0", "conv1", "conv2", "conv_out")
 # hand-over passes included (tools/volume_layers.py, profiles/r17_volume_pairs.md: embeds 1675 -> 1308 and 1093 -> 833 us, conv0 642 -> 512,
 # conv2 294 -> 128); a layer that is not listed keeps its route
 VOLUME_PAIR_LAYERS = ("mean_embed", "var_embed", "conv0", "conv2")
+# layers of the volume net the halo-patch kernel cannot express — stride 2, or maps small enough to need split-K — that run on the
+# implicit-GEMM kernel's own pair mode (conv_igemm_kernel<., MM = 3>: operands split into fp16 hi / lo pairs in the loader, behind the
+# InstanceNorm affine + ReLU prologue, so no hand-over pass) in the big calls of the fp32 path: "conv1" (32^3 -> 16^3), "conv3"
+# (16^3 -> 8^3), "conv5.0" (8^3 -> 4^3), "conv5.3" (4^3); candidates that lose stay unlisted ("conv4", 8^3, competes with F(2x2,3x3)).
+# Decided per layer at 16 volumes (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md)
+VOLUME_IGEMM_PAIR_LAYERS = ("conv1", "conv3", "conv5.0", "conv5.3")
 VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
@@ -161,6 +168,10 @@ class VolumeRefiner(ParamBank):
             for name in ("conv0", "conv1", "conv2", "conv3", "conv4"):
                 pk["v_" + name] = self.conv_w(f"volume_net.{name}.0", wino_kd=3 if name in ("conv0", "conv2", "conv4") else 0,
                                               f43=name in VOLUME_F43_LAYERS)
+            # filter exponents of the layers that may run on the implicit-GEMM pair mode: computed here (a device-to-host read of
+            # max |w|), not at their first launch, which may sit inside a graph capture
+            for wb in (pk["v_conv1"], pk["v_conv3"], pk["v_conv4"], pk["v_conv5"][0], pk["v_conv5"][1]):
+                ops.pair_filter_prepare(wb[0])
             # fc.0.0 consumes x.flatten(1) of [512,4,4,4] (index c*64+v); our code is [v][c] -> permute once
             w = self.p("regressor.fc.0.0.weight")
             pk["fc0"] = (w.reshape(512, 512, 64).permute(0, 2, 1).reshape(512, 32768).contiguous(),
@@ -312,16 +323,20 @@ class VolumeRefiner(ParamBank):
         qn = mean_in.shape[0] if batched else 1
         pn = 1 if qn > 1 else 0                      # per-volume tables / groups only when there is more than one
 
-        def c3(x, wb, out, stride=1, aff=None, stats_c=None, count=None):
-            """3x3x3 conv; with stats_c: returns the affine (scale, shift) of the InstanceNorm that follows (count values)."""
+        def c3(x, wb, out, stride=1, aff=None, stats_c=None, count=None, name=None):
+            """3x3x3 conv; with stats_c: returns the affine (scale, shift) of the InstanceNorm that follows (count values).
+            name: the layer's entry in VOLUME_IGEMM_PAIR_LAYERS, if it has one."""
             st = ops.new_stats(qn, stats_c, dev) if stats_c else None
             sc, sh = aff if aff is not None else (None, None)
+            # big calls of the fp32 path (the condition of volume_pair_route): a listed layer on the implicit-GEMM kernel's pair mode
+            # (_pair_rng: None with fp32_cores, during a fallback recompute and inside a 16-bit part)
+            r = self._pair_rng() if (qn >= F43_MIN_QUERIES and name in VOLUME_IGEMM_PAIR_LAYERS) else None
+            route = {"pairs": (r, r.slot(f"volume.{name}.igemm"))} if r is not None else \
+                {"w_wino": getattr(wb, "u", None) if stride == 1 else None,
+                 "w_wino43": getattr(wb, "u43", None) if (stride == 1 and qn >= F43_MIN_QUERIES) else None}
             return ops.conv(x, wb[0], wb[1], out, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh,
                             in_relu=aff is not None, per_n=pn if aff is not None else 0, stats=st,
-                            rows_per_group=pn * (count or 0) if stats_c else 0,
-                            w_wino=getattr(wb, "u", None) if stride == 1 else None,
-                            w_wino43=getattr(wb, "u43", None) if (stride == 1 and qn >= F43_MIN_QUERIES) else None,
-                            finalize=count if stats_c else None)
+                            rows_per_group=pn * (count or 0) if stats_c else 0, finalize=count if stats_c else None, **route)
 
         def buf(s, c):
             return torch.empty((qn, s, s, s, c), dtype=torch.float32, device=dev)
@@ -380,13 +395,13 @@ class VolumeRefiner(ParamBank):
                     xin = ops.affine_split16(x.view(qn * s, 1, s, s, 128), aff[0], aff[1], s, True, False, 3, rng=(rng, rng.slot("volume.conv2.in")))
                     x, aff = y, c16(pk[name], xin.view(qn, s, s, s, 2, 128), y, stats_c=co, count=s ** 3)
                     continue
-                x, aff = y, c3(x, pk[name], y, stride=stride, aff=aff, stats_c=co, count=s ** 3)
+                x, aff = y, c3(x, pk[name], y, stride=stride, aff=aff, stats_c=co, count=s ** 3, name=name[2:])
         s = s // 2
         y = buf(s, 512)
         with self._mm("tail"):
-            aff = c3(x, pk["v_conv5"][0], y, stride=2, aff=aff, stats_c=512, count=s ** 3)
+            aff = c3(x, pk["v_conv5"][0], y, stride=2, aff=aff, stats_c=512, count=s ** 3, name="conv5.0")
             code = buf(s, 512)
-            c3(y, pk["v_conv5"][1], code, aff=aff)
+            c3(y, pk["v_conv5"][1], code, aff=aff, name="conv5.3")
         return code.view(qn, s ** 3, 512) if batched else code.view(s ** 3, 512)
 
     def run_regressor(self, code):

@@ -39,6 +39,12 @@ _K133, _P011 = (1, 3, 3), (0, 1, 1)
 MAX_BATCH = 32         # queries that share one set of launches (BASELINE configs[4]: 32 concurrent queries; g6d_selector_levels runs them
                        # in groups of 8 query rows per pass over the reference cache)
 FEAT_LD = 516          # 512 corr channels + 3 vps channels + 1 zero pad (16-byte rows)
+# 1x1 layers that run on the implicit-GEMM kernel's own fp16 hi / lo pair mode (conv_igemm_kernel<., MM = 3>, ops.conv(pairs=...)) in
+# batched calls of the fp32 path.  Candidate: "fuse0" (768 -> 512 over the qn*D hypothesis maps), 590 -> 310 us per launch at 16 queries
+# (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md).  NOT listed: the selector then differs between a batched and a single call by
+# more than the logits' fp32 noise, and the stream tracker's re-acquisition (a chunk of 2 queries against the single-query chain on a scene
+# whose poses amplify it) left the project's 3e-4 bar for batched rows (6.8e-4, tests/test_track_health_gpu.py; profiles/r18_bench.md)
+SELECTOR_IGEMM_PAIR_LAYERS = ()
 
 
 class ViewpointSelector(ParamBank):
@@ -323,7 +329,10 @@ class ViewpointSelector(ParamBank):
             y = torch.empty((qn * D, 1, 4, 4, 512), dtype=torch.float32, device=dev)
             st = ops.new_stats(qn, 512, dev)
             if not self.sharded:
-                sc, sh = ops.conv(cat, pk["fuse0"][0], pk["fuse0"][1], y, stats=st, finalize=Dg * 16, rows_per_group=grp * 16)
+                # batched calls of the fp32 path: on the implicit-GEMM kernel's pair mode (SELECTOR_IGEMM_PAIR_LAYERS)
+                r = self._pair_rng() if (qn > 1 and "fuse0" in SELECTOR_IGEMM_PAIR_LAYERS) else None
+                kw = {"pairs": (r, r.slot("fuse0.igemm"))} if r is not None else {}
+                sc, sh = ops.conv(cat, pk["fuse0"][0], pk["fuse0"][1], y, stats=st, finalize=Dg * 16, rows_per_group=grp * 16, **kw)
             else:
                 ops.conv(cat, pk["fuse0"][0], pk["fuse0"][1], y, stats=st, rows_per_group=grp * 16)
                 self._allreduce([st])

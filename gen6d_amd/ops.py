@@ -150,14 +150,18 @@ FUSED_FINALIZE = True
 
 def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=None, in_scale=None, in_shift=None,
          in_relu=False, per_n=False, out_act=0, stats=None, rows_per_group=0, split_k=0, w_wino=None, finalize=None, eps=1e-5,
-         in_mod=0, mul_group=0, w_wino43=None):
+         in_mod=0, mul_group=0, w_wino43=None, pairs=None):
     """Implicit-GEMM convolution (g6d_conv_igemm). x [N,Di,Hi,Wi,Cin], w [Cout,taps,Cin], out [N,Do,Ho,Wo,Cout] views.
     stats [G,Cout,2] fp64 (zeroed): per-(group, channel) sum / sum of squares of the output are accumulated into it.
     finalize=count: additionally turn the completed statistics into the affine of the following InstanceNorm (count values
     per group) inside the same launch and return (scale, shift) [G,Cout] instead of out.
     per_n: False / 0 = one affine table; True / 1 = a table per image; k = a table per run of k images.
     Query batches (G6dConv.in_image_mod / mul_group_images): in_mod = k — x holds k images and output image n reads x[n % k];
-    mul_group = k — mul is [N/k,Hi,Wi,Cin] and image n is multiplied by mul[n // k]."""
+    mul_group = k — mul is [N/k,Hi,Wi,Cin] and image n is multiplied by mul[n // k].
+    pairs = (RangeTable, slot): the fp32 path's pair mode of the implicit-GEMM kernel itself (G6dConv.math_mode 3, g6d_conv_igemm_ex) — the
+    loader splits both operands into fp16 hi / lo pairs after the prologue, fp32-class results on the 16-bit matrix cores; the activations
+    carry the slot's exponent and their largest |value| is recorded in it; the filter exponent (pair_filter_exponent) is cached on `w`.
+    No Winograd / patch hand-off.  A reduced-precision MATH_MODE keeps precedence: pairs is then ignored."""
     _need_gpu(x, w, out)
     Nx, Di, Hi, Wi, Cin, ld_in = _cl5(x, "conv.x")
     No, Do, Ho, Wo, Cout, ld_out = _cl5(out, "conv.out")
@@ -181,7 +185,14 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         raise ValueError(f"conv.w_wino: expected contiguous {(kd * (Cin // 8), 16, Cout, 8)}, got {tuple(w_wino.shape)}")
     if w_wino43 is not None and (tuple(w_wino43.shape) != w43_shape(kd * (Cin // 8), Cout) or not w_wino43.is_contiguous()):
         raise ValueError(f"conv.w_wino43: expected contiguous {w43_shape(kd * (Cin // 8), Cout)}, got {tuple(w_wino43.shape)}")
+    if MATH_MODE:
+        pairs = None
     u16 = None
+    if pairs is not None:
+        w_wino = w_wino43 = None
+        # (the networks prepare the exponent when they pack their weights; a weight that was not prepared pays a device-to-host read
+        # of max |w| here, once — which a stream capture does not allow)
+        w_exp = pair_filter_prepare(w)
     if MATH_MODE and w_wino is not None and Cin % 16 == 0 and Cout % 64 == 0:
         # reduced-precision mode: the layer's Winograd filters rounded to the operand type, built once per (layer, type) and kept
         # on the fp32 filter tensor (a new weight pack drops both)
@@ -200,7 +211,8 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         N=N, Di=Di, Hi=Hi, Wi=Wi, Cin=Cin, ld_in=ld_in, Do=Do, Ho=Ho, Wo=Wo, Cout=Cout, ld_out=ld_out,
         kd=kd, kh=kh, kw=kw, sd=stride[0], sh=stride[1], sw=stride[2], pd=pad[0], ph=pad[1], pw=pad[2],
         in_relu=int(in_relu), in_affine_per_n=int(per_n), out_act=int(out_act),
-        stat_rows_per_group=int(rows_per_group), split_k=int(split_k), math_mode=int(MATH_MODE),
+        stat_rows_per_group=int(rows_per_group), split_k=int(split_k), math_mode=3 if pairs is not None else int(MATH_MODE),
+        w_exp=int(w_exp) if pairs is not None else 0,
         weight_wino=w_wino.data_ptr() if w_wino is not None else None, in_image_mod=int(in_mod), mul_group_images=int(mul_group),
         weight_wino16=u16.data_ptr() if u16 is not None else None,
         weight_wino43=w_wino43.data_ptr() if (w_wino43 is not None and not MATH_MODE) else None)
@@ -223,11 +235,15 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
                 PROFILE_HBM.setdefault("conv_narrow", []).append((4.0 * (N * Di * Hi * Wi * Cin + w.numel() + N * Do * Ho * Wo * Cout), e0, e1))
         else:
             PROFILE.append((fl / 4 if fam == 3 else (fl / 2.25 if fam == 2 else fl), e0, e1,      # Winograd kernels: FLOPs executed in the transform domain
-                        ("wino3x3 F43 " if fam == 3 else "wino3x3 " if fam == 2 else "") + f"conv N={N} in={Di}x{Hi}x{Wi}x{Cin} out={Do}x{Ho}x{Wo}x{Cout} k={kd}x{kh}x{kw} s={stride[0]}{stride[1]}{stride[2]}"
+                        ("wino3x3 F43 " if fam == 3 else "wino3x3 " if fam == 2 else "conv16x3 igemm " if fam == 5 else "") + f"conv N={N} in={Di}x{Hi}x{Wi}x{Cin} out={Do}x{Ho}x{Wo}x{Cout} k={kd}x{kh}x{kw} s={stride[0]}{stride[1]}{stride[2]}"
                         f"{' mul' if mul is not None else ''}{' aff' if in_scale is not None else ''}{' stats' if stats is not None else ''}",
                         # algorithmic bytes: every operand once (input images, multiplier maps, filters, output)
                         4.0 * ((in_mod or N) * Di * Hi * Wi * Cin + (mul.numel() if mul is not None else 0) + w.numel() + N * Do * Ho * Wo * Cout), fl))
-    _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm"), book)
+    if pairs is not None:
+        ra = C.byref(pairs[0].arg(-1, pairs[1]))
+        _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm_ex(C.byref(d), ra, _stream()), "g6d_conv_igemm_ex"), book)
+    else:
+        _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm"), book)
     if finalize is not None:
         return fin if fin is not None else stats_finalize(stats, finalize, eps)
     return out
@@ -750,10 +766,24 @@ class Conv16Filters:
         self.data, self.layout, self.mode, self.acc_scale, self.Cout, self.taps, self.Cin = data, layout, mode, acc_scale, Cout, taps, Cin
 
 
-def _split_hi_lo(w_taps):
-    """fp32 filters -> (hi, lo, 1 / S): the fp16 parts of w * S, split in fp64, for the largest power of two S <= 2^14 that keeps |w| S below
+def pair_filter_exponent(w_taps):
+    """log2 of the power of two S the pair kernels scale their filters by before the split: the largest S <= 2^14 that keeps |w| S below
     2048 — the lo parts then stay normal fp16 numbers, and the kernels multiply their accumulators by 1 / S."""
-    S = 2.0 ** min(14, math.floor(math.log2(2048.0 / max(float(w_taps.abs().max()), 1e-30))))
+    return min(14, math.floor(math.log2(2048.0 / max(float(w_taps.abs().max()), 1e-30))))
+
+
+def pair_filter_prepare(w):
+    """The filter exponent of `w` for ops.conv(pairs=...), computed once (a device-to-host read) and cached on the weight tensor like the
+    other derived packs; call it where the weights are packed so that no launch path synchronises."""
+    e = w.__dict__.get("_g6d_w_exp")
+    if e is None:
+        e = w.__dict__["_g6d_w_exp"] = pair_filter_exponent(w)
+    return e
+
+
+def _split_hi_lo(w_taps):
+    """fp32 filters -> (hi, lo, 1 / S): the fp16 parts of w * S, S = 2^pair_filter_exponent(w), split in fp64."""
+    S = 2.0 ** pair_filter_exponent(w_taps)
     w = w_taps.double() * S
     hi = w.to(torch.float16)
     return hi, (w - hi.double()).to(torch.float16), 1.0 / S

@@ -98,7 +98,13 @@ typedef struct G6dConv {
   int32_t stat_rows_per_group;  /* output rows per statistics group (0 = all rows in one group) */
   int32_t split_k;              /* 0 = choose automatically; 1 = never split; >1 = force */
   int32_t math_mode;            /* 0 = fp32 MFMA (default, the parity path); 1 = bf16, 2 = fp16 operands with fp32 accumulation:
-                                   v_mfma_f32_32x32x16_{bf16,f16}, opt-in speed mode graded separately (BASELINE configs[2], [4]) */
+                                   v_mfma_f32_32x32x16_{bf16,f16}, opt-in speed mode graded separately (BASELINE configs[2], [4]);
+                                   3 = fp32-CLASS arithmetic on the fp16 matrix cores, used by the fp32 path: the implicit-GEMM kernel's
+                                   loader splits every fp32 operand (after the prologue) into an fp16 hi / lo pair, three
+                                   v_mfma_f32_32x32x16_f16 per product (hi x hi + hi x lo + lo x hi).  Always the implicit-GEMM kernel
+                                   (no Winograd / patch / narrow hand-off; weight_wino16 must be NULL), strided, 3-D, split-K and 1x1
+                                   layers included; Cin % 8 == 0, Cout > 32, no `mul`.  Filters are split as weight * 2^w_exp, activations
+                                   as x * 2^-e with e and the range record from g6d_conv_igemm_ex's G6dRange16 */
   const float* weight_wino;     /* optional: the same filters transformed for Winograd F(2x2,3x3), [kd][Cin/8][16][Cout][8] in the
                                    layout of g6d_wino_conv3x3 (per depth tap for 3x3x3).  When set and the layer is eligible
                                    (stride 1, "same" padding, maps >= 6x6, Cin % 8 == 0, Cout % 32 == 0, fp32), the launch runs on
@@ -123,7 +129,9 @@ typedef struct G6dConv {
      together with in_affine_per_n = k and stat_rows_per_group = k * Do * Ho * Wo every query keeps its own InstanceNorm. */
   int32_t in_image_mod;
   int32_t mul_group_images;
-  int32_t reserved_;
+  int32_t w_exp;                /* math_mode 3: the filters are split as weight * 2^w_exp (an exact scaling, undone on the accumulators) so
+                                   that the lo parts of small filters stay normal fp16 numbers — choose the largest w_exp <= 14 with
+                                   max |weight| * 2^w_exp < 2048; not read in the other modes (the former reserved_ field: 0 = unscaled) */
   const void* weight_wino16;    /* optional, used when math_mode != 0: the Winograd-domain filters ROUNDED to the operand type of
                                    math_mode (bf16 / fp16), [kd][Cin/16][16][Cout][16] 16-bit values in the layout of
                                    g6d_wino16_conv3x3_multi's U16 (per depth tap for 3x3x3).  Eligible layers (as weight_wino, and
@@ -138,8 +146,19 @@ typedef struct G6dConv {
 } G6dConv;
 
 int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream);
+/* g6d_conv_igemm with the range control of math_mode 3 (additive to ABI v12; G6dRange16 below; NULL = exponent 0, nothing recorded;
+   a non-NULL range with another math_mode is G6D_EINVAL): the kernel is producer and consumer of its operand pairs, so ONE slot serves —
+   the loader splits x * 2^-exps[slot_out] (x after the multiplier / affine / ReLU prologue; padding stays exactly zero), folds
+   2^exps[slot_out] back into the accumulator scale, and records the largest |x| in rec[slot_out] (at most one atomicMax per block, only
+   when it exceeds a coherent read of the record).  slot_in is not read.
+   Implementation note: the kernel takes the descriptor by value, and in math_mode 3 the launcher's private COPY of it carries the two
+   device pointers &exps[slot_out] and &rec[slot_out] in `weight_wino16` / `weight_wino43`, fields this kernel never reads as filters (that
+   keeps one kernel signature and the other modes' code unchanged).  The caller's descriptor is not modified, and a caller's own values in
+   those two fields are not forwarded in math_mode 3 (weight_wino16 must be NULL, weight_wino43 is ignored). */
+struct G6dRange16;
+int g6d_conv_igemm_ex(const G6dConv* desc, const struct G6dRange16* range, g6d_stream_t stream);
 /* Kernel family g6d_conv_igemm will run `desc` on (no launch): 0 generic implicit GEMM, 1 LDS-patch kernel, 2 Winograd F(2x2,3x3) kernel,
-   3 Winograd F(4x4,3x3) kernel */
+   3 Winograd F(4x4,3x3) kernel, 4 narrow-output kernel, 5 implicit GEMM on fp16 hi / lo pairs (math_mode 3) */
 int g6d_conv_plan(const G6dConv* desc);
 /* sizeof(G6dConv) as compiled into the library: bindings check their struct layout against it */
 int g6d_sizeof_conv_desc(void);

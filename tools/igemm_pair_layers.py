@@ -1,0 +1,92 @@
+"""The layers the halo-patch pair kernel cannot express — stride 2, small volumes that need split-K, 1x1 — launch by launch: today's
+fp32-core route (g6d_conv_igemm: conv_igemm_kernel<., MM = 0>, or F(2x2,3x3) for conv4) against the implicit-GEMM kernel's own fp16
+hi / lo pair mode (conv_igemm_kernel<., MM = 3>, ops.conv(pairs=...)), at the bench's shapes.
+    python tools/igemm_pair_layers.py [volumes / queries = 16]
+us per launch, the best of three rounds of 10, with direct-form TFLOP/s.  The table decides refiner.VOLUME_IGEMM_PAIR_LAYERS and
+selector.SELECTOR_IGEMM_PAIR_LAYERS (profiles/r18_igemm_pairs.md): a layer is listed only where it is faster at 16; run it with 1 for
+the single-query times (recorded, not routed on)."""
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import toolenv                                                  # noqa: E402,F401  (G6D_LIB_PATH / KNOBS)
+from gen6d_amd import lib, ops, synth                           # noqa: E402
+from gen6d_amd.network import name2network                      # noqa: E402
+from featnet_layers import timed                                # noqa: E402
+
+_K3, _P3 = (3, 3, 3), (1, 1, 1)
+
+
+def main():
+    lib.load()
+    qn = int(sys.argv[1]) if len(sys.argv) > 1 else 16
+    dev = torch.device("cuda", 0)
+    ops.USE_ARENA = False
+    net = name2network["refiner"]({"name": "igemm_pair_layers"}).eval()
+    net.load_state_dict(synth.synth_state_dict("refiner"))
+    net.to(dev)
+    pk = net._pack()
+    pn = 1 if qn > 1 else 0
+    table = ops.RangeTable(dev)
+    print(f"# {qn} volumes / queries: us per launch (best of 3 rounds of 10), direct-form TFLOP/s")
+    print("| layer | shape | fp32-core route | us | TFLOP/s | pair route | us | TFLOP/s | |\n|---|---|---|---|---|---|---|---|---|")
+
+    def row(name, shape, on, of, nf, fl):
+        to, tn = timed(of), timed(nf)
+        print(f"| {name} | {shape} | {on} | {to:.1f} | {fl / to / 1e6:.0f} | conv_igemm pairs | {tn:.1f} | {fl / tn / 1e6:.0f} | "
+              f"{'pairs faster' if tn < to else 'fp32 cores faster'} ({to / tn:.2f}x) |", flush=True)
+
+    # the volume net: (name, layer, input edge, Cin, Cout, stride); every layer takes the previous InstanceNorm's affine + ReLU in its
+    # operand prologue (a table per volume) and adds its own sums with the fused finalize, as run_volume_net launches it
+    for name, layer, s, ci, co, stride, stats in (("conv1", pk["v_conv1"], 32, 64, 128, 2, True), ("conv3", pk["v_conv3"], 16, 128, 256, 2, True),
+                                                  ("conv4", pk["v_conv4"], 8, 256, 256, 1, True), ("conv5.0", pk["v_conv5"][0], 8, 256, 512, 2, True),
+                                                  ("conv5.3", pk["v_conv5"][1], 4, 512, 512, 1, False)):
+        so = s // stride
+        x = torch.rand((qn, s, s, s, ci), device=dev) - 0.5
+        y = torch.empty((qn, so, so, so, co), dtype=torch.float32, device=dev)
+        sc, sh = torch.rand((qn if pn else 1, ci), device=dev) + 0.5, torch.rand((qn if pn else 1, ci), device=dev) - 0.5
+        st = ops.new_stats(qn, co, dev) if stats else None
+
+        def launch(pairs, layer=layer, x=x, y=y, sc=sc, sh=sh, st=st, stride=stride, so=so):
+            kw = {"pairs": (table, table.slot(name))} if pairs else {"w_wino": getattr(layer, "u", None) if stride == 1 else None}
+            ops.conv(x, layer[0], layer[1], y, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh, in_relu=True, per_n=pn, stats=st,
+                     rows_per_group=pn * so ** 3 if st is not None else 0, finalize=so ** 3 if st is not None else None, **kw)
+        fl = 2.0 * qn * so ** 3 * co * 27 * ci
+        old = "F(2x2,3x3)" if (stride == 1 and getattr(layer, "u", None) is not None) else "conv_igemm fp32"
+        row(name, f"{s}^3 -> {so}^3, {ci} -> {co}, s{stride}, aff{' stats' if stats else ''}", old, lambda: launch(False), lambda: launch(True), fl)
+        del x, y
+
+    # the selector: fuse0, a 1x1 conv 768 -> 512 over qn * D hypothesis maps of 4x4 with per-query sums and the fused finalize; sp0 (516 ->
+    # 512 over qn * D rows) as a candidate of the tail
+    sel = name2network["selector"]({"name": "igemm_pair_layers", "selector_angle_num": 5}).eval()
+    sel.load_state_dict(synth.synth_state_dict("selector", an=5))
+    sel.to(dev)
+    sp = sel._pack()
+    D = 64 * 5
+    grp = D if qn > 1 else 0
+    cat = torch.rand((qn * D, 1, 4, 4, 768), device=dev) - 0.5
+    y = torch.empty((qn * D, 1, 4, 4, 512), dtype=torch.float32, device=dev)
+    st = ops.new_stats(qn, 512, dev)
+
+    def fuse0(pairs):
+        kw = {"pairs": (table, table.slot("fuse0"))} if pairs else {}
+        ops.conv(cat, sp["fuse0"][0], sp["fuse0"][1], y, stats=st, finalize=D * 16, rows_per_group=grp * 16, **kw)
+    row("fuse0", f"1x1 768 -> 512, {qn * D * 16} rows, stats", "conv_igemm fp32", lambda: fuse0(False), lambda: fuse0(True), 2.0 * qn * D * 16 * 512 * 768)
+    from gen6d_amd.network.selector import FEAT_LD
+    feats = torch.rand((qn * D, FEAT_LD), device=dev) - 0.5
+    t0 = torch.empty((1, 1, 1, qn * D, 512), dtype=torch.float32, device=dev)
+    if FEAT_LD % 8 == 0:
+        def sp0(pairs):
+            kw = {"pairs": (table, table.slot("sp0"))} if pairs else {}
+            ops.conv(feats.view(1, 1, 1, qn * D, FEAT_LD), sp["sp0"][0], sp["sp0"][1], t0, out_act=1, **kw)
+        row("sp0 (candidate)", f"1x1 {FEAT_LD} -> 512, {qn * D} rows", "conv_igemm fp32", lambda: sp0(False), lambda: sp0(True), 2.0 * qn * D * 512 * FEAT_LD)
+    else:
+        print(f"| sp0 (candidate) | 1x1 {FEAT_LD} -> 512 | the pair mode takes Cin % 8 == 0: stays | | | | | | |")
+
+
+if __name__ == "__main__":
+    main()
