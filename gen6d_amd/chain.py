@@ -130,15 +130,30 @@ class DeviceChain:
         the estimator-level counterpart of `TensorPipeline.query` with the data flow between the stages real.
         pose_init [B,3,4] (device; tracking, gen6d_amd/tracking.py): detection and selection are skipped ('det', 'sel', 'logits' and
         'crop' are None) and `refine_iter` steps (default 1) run from it; B <= refiner.MAX_BATCH then."""
+        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, None)
+
+    def query_batch_source(self, que_imgs, que_Ks, source, pose_init=None, refine_iter=None):
+        """`query_batch` with the two crops it cuts from que_imgs, the selector's after detection and the refiner's query crop of every
+        step, cut from the camera-native pictures instead: source is the `ingest.SourceTable` of the B canvases, and one g6d_frame_crop
+        launch stands in place of each of those warp launches.  A slot without a source record keeps its canvas crop.
+        Reference crops, the detector's input and the intrinsics are what they are in `query_batch`: the composition happens inside the
+        sampler."""
+        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, source)
+
+    def _query_batch(self, que_imgs, que_Ks, pose_init, refine_iter, source):
         est, size = self.est, self.size
         astep = est.refiner.angle_step() if est.refiner is not None else 0.0
         B = que_imgs.shape[0]
         with torch.no_grad():
-            ar = torch.arange(B, dtype=torch.int32, device=self.dev)
+            if source is None:
+                ar = torch.arange(B, dtype=torch.int32, device=self.dev)
+                cut = lambda hinv, n: ops.warp_batch(que_imgs, None, ar, hinv, n, n)
+            else:
+                cut = lambda hinv, n: ops.frame_crop(source.table, source.rec, que_imgs, hinv, n, n)
             K9 = que_Ks.reshape(B, 9).contiguous()
             if pose_init is None:
                 det5 = self.detect_batch(que_imgs)
-                crop = ops.warp_batch(que_imgs, None, ar, ops.chain_crop_from_detection(det5, size), size, size)
+                crop = cut(ops.chain_crop_from_detection(det5, size), size)
                 logits, angles = est.selector.compute_view_point_feats(crop)
                 pose, sel = ops.chain_pose_from_selection(det5, logits.contiguous(), angles.contiguous(), self.ref_poses, self.ref_Ks, K9,
                                                           self.center)
@@ -154,7 +169,7 @@ class DeviceChain:
                                                 angle_step=astep)
                 geo, idx = prep[0], prep[1]
                 hinv = geo[:, 33 + 21 * R:].reshape(B, 1 + R, 9)
-                que_crops = ops.warp_batch(que_imgs, None, ar, hinv[:, 0].contiguous(), rs, rs)
+                que_crops = cut(hinv[:, 0].contiguous(), rs)
                 ref_crops = ops.warp_batch(self.stack, None, idx.reshape(-1), hinv[:, 1:].reshape(B * R, 9).contiguous(), rs, rs)
                 rot, off, scl = est.refiner._step(que_crops, geo[:, 0:9].reshape(B, 3, 3), geo[:, 9:21].reshape(B, 3, 4),
                                                   ref_crops.view(B, R, 3, rs, rs), geo[:, 33:33 + 9 * R].reshape(B, R, 3, 3),

@@ -11,7 +11,7 @@
 // NV12 sample are computed once for the taps of its 2 x 2 block (at 2:1 all four taps of a pixel share one).
 // g6d_frame_ingest_mesh (second half of the file) is the same launch with a lens per frame: blocks of a frame with a mesh take their
 // source coordinates from it (nodes in LDS, 64-bit integer interpolation), blocks of a frame without one run the plain tile.
-#include "g6d_common.h"
+#include "frame_src.h"
 
 namespace {
 
@@ -24,30 +24,6 @@ __device__ __forceinline__ unsigned sample_word(int t, int tgt, int src) {
   f = f < 0 ? 0 : (f > hi ? hi : f);
   const unsigned i0 = (unsigned)(f >> 11), w = (unsigned)(f & 2047);
   return i0 | ((i0 + 1 < (unsigned)src ? 1u : 0u) << 13) | (w << 14);
-}
-
-struct Src {
-  const unsigned char* p0; const unsigned char* p1;
-  int pitch0, pitch1, bpp, ro, nv12;
-  int cvr, cug, cvg, cub;
-};
-
-__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
-
-// NV12: the chroma terms of one UV sample (shared by the up to four luma taps of its 2 x 2 block), then one luma tap -> RGB
-struct Chroma { int r, g, b; };
-__device__ __forceinline__ Chroma chroma(const Src& s, int cx, int cy) {
-  const unsigned char* uv = s.p1 + (size_t)cy * s.pitch1 + 2 * cx;
-  const int d = (int)uv[0] - 128, e = (int)uv[1] - 128;
-  return Chroma{s.cvr * e + (1 << 19), -s.cug * d - s.cvg * e + (1 << 19), s.cub * d + (1 << 19)};
-}
-__device__ __forceinline__ void tap_nv12(const Src& s, const Chroma& k, int x, int y, int& r, int& g, int& b) {
-  const int c = max((int)s.p0[(size_t)y * s.pitch0 + x] - 16, 0) * 1220542;
-  r = sat8((c + k.r) >> 20); g = sat8((c + k.g) >> 20); b = sat8((c + k.b) >> 20);
-}
-__device__ __forceinline__ void tap_packed(const Src& s, int x, int y, int& r, int& g, int& b) {
-  const unsigned char* p = s.p0 + (size_t)y * s.pitch0 + (size_t)x * s.bpp;
-  r = p[s.ro]; g = p[1]; b = p[2 - s.ro];
 }
 
 __global__ void __launch_bounds__(256) frame_ingest_kernel(const G6dFrame* __restrict__ frames, unsigned char* __restrict__ out, int B, int H,
@@ -170,18 +146,6 @@ __device__ __forceinline__ void gather(const Src& s, int x0, int x1, int y0, int
   }
 #undef G6D_ACC
   r = ar >> 22; g = ag >> 22; b = ab >> 22;
-}
-
-__device__ __forceinline__ Src source_of(const G6dFrame& f) {
-  Src s;
-  s.p0 = static_cast<const unsigned char*>(f.plane0); s.p1 = static_cast<const unsigned char*>(f.plane1);
-  s.pitch0 = f.pitch0; s.pitch1 = f.pitch1;
-  s.nv12 = f.format == G6D_FMT_NV12;
-  s.bpp = f.format >= G6D_FMT_RGBA32 ? 4 : 3;
-  s.ro = (f.format == G6D_FMT_BGR24 || f.format == G6D_FMT_BGRA32) ? 2 : 0;
-  const bool m709 = f.matrix == 1;
-  s.cvr = m709 ? 1880097 : 1673527; s.cug = m709 ? 223347 : 409993; s.cvg = m709 ? 558891 : 852492; s.cub = m709 ? 2214593 : 2116026;
-  return s;
 }
 
 // a thread's 4 pixels -> canvas row Y of image `slot` from column X on

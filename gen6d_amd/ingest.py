@@ -24,6 +24,7 @@ FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4}
 MATRICES = {"bt601": 0, "bt709": 1}
 BPP = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1}
 MAX_SIZE = 8192
+RECORD_BYTES = C.sizeof(_lib.G6dFrame)                   # one record of a frame table
 LENS_MODELS = {"brown": (4, 5, 8), "fisheye": (4,)}      # model -> admissible numbers of coefficients
 MESH_STEPS = (16, 8, 4, 2)
 MESH_CACHE = 64                                          # device meshes kept per process (one per camera, plan and device)
@@ -293,11 +294,55 @@ def source_K(frame, canvas_hw):
 class Staged:
     """What `ingest_frames_keep` leaves on the device: `table`, the uint8 tensor of the call's n lib.G6dFrame records (record i
     is frames[i]; its `slot` field is the frame's canvas slot), for launches that read the source pictures again
-    (emit.emit_source_frames).  It keeps the staging buffer and the device-resident planes referenced; `batch` is the canvas count B."""
+    (emit.emit_source_frames, ops.frame_crop through a `SourceTable`).  It keeps the staging buffer and the device-resident planes referenced; `batch` is the canvas count B."""
 
     def __init__(self, table, frames, slots, batch):
         self.table, self.frames, self.slots, self.batch = table, frames, slots, batch
         self.n, self.device = len(frames), table.device
+
+
+class SourceTable:
+    """The source pictures of a batch of canvases, for launches that cut from them (`DeviceChain.query_batch_source`,
+    ops.frame_crop): `table`, a uint8 tensor of lib.G6dFrame records, and `rec` int32 [B]: the record of canvas slot b, or -1 for a slot
+    without one, which is served from its canvas.  Both live on the device and are read there, so a captured graph can hold them.
+    `SourceTable.of(staged)` pairs a `Staged` table with the map of its slots; `load(staged)` refills a static pair (a lane's, read by
+    its captured graph) with them.  The kernel cannot check rec against the table (a wrong value is an out-of-bounds read): the map is
+    built on the host and checked there, before it travels."""
+
+    def __init__(self, table, rec):
+        self.table, self.rec = table, rec
+
+    @staticmethod
+    def _upload(rec, n, dev):
+        """Host map (int32 numpy) of a table of n records -> device tensor on the current stream, no synchronisation."""
+        if rec.size and int(rec.max()) >= n:
+            raise ValueError(f"SourceTable: a slot names record {int(rec.max())} of a table of {n}")
+        t = torch.from_numpy(rec)
+        return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev)
+
+    @staticmethod
+    def slot_records(staged):
+        """-> int32 [B] numpy, B the canvas count of the ingest: rec[slot of frame i] = i, -1 elsewhere.  A frame with a `Lens` gets -1
+        as well: its source picture is distorted, the canvas is the undistorted one."""
+        rec = np.full(staged.batch, -1, np.int32)
+        for i, (f, s) in enumerate(zip(staged.frames, staged.slots)):
+            if f.lens is None:
+                rec[s] = i
+        return rec
+
+    @classmethod
+    def of(cls, staged):
+        """The table an `ingest_frames_keep` call left, with its slot map uploaded on the current stream (no synchronisation)."""
+        return cls(staged.table, cls._upload(cls.slot_records(staged), staged.n, staged.device))
+
+    def load(self, staged):
+        """Copy the table and the slot map of an `ingest_frames_keep` call into this pair's own buffers, on the current stream.  The
+        caller keeps `staged` alive as long as launches read this pair: the records point into its planes."""
+        if staged.table.numel() > self.table.numel() or staged.batch != self.rec.numel():
+            raise ValueError(f"SourceTable.load: {staged.n} records for {staged.batch} slots do not fit a table of "
+                             f"{self.table.numel() // RECORD_BYTES} records and {self.rec.numel()} slots")
+        self.table[:staged.table.numel()].copy_(staged.table)
+        self.rec.copy_(self._upload(self.slot_records(staged), staged.n, staged.device))
 
 
 def _host(p):

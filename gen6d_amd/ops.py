@@ -1763,3 +1763,30 @@ def frame_emit_source(table, n, frames, nf, pts, valid, max_w, max_h):
         raise ValueError("frame_emit_source: pts must be a contiguous int32 [sets,B,8,2] tensor and valid int32 [sets,B], sets 1 or 2")
     _lib.check(_lib.load().g6d_frame_emit_source(_ptr(table), n, _ptr(frames), nf, _ptr(pts), _ptr(valid), pts.shape[0], pts.shape[1],
                                                  int(max_w), int(max_h), _stream()), "g6d_frame_emit_source")
+
+
+def frame_crop(table, rec, imgs, hinv, dh, dw, out=None):
+    """One launch of g6d_frame_crop: warp_batch's crops of the canvases imgs uint8 [B,H,W,3] under hinv float32 [B,9], cut from the
+    camera-native pictures instead: slot b samples record rec[b] (int32 [B]) of `table` (a contiguous, 8-byte aligned uint8 device tensor
+    of lib.G6dFrame records, built and validated by gen6d_amd.ingest.ingest_frames_keep; the caller vouches that rec indexes it), or
+    its canvas when rec[b] < 0 -> float32 [B,3,dh,dw] in [0,1] (uint8-rounded); `out`: optional contiguous destination.  rec and the
+    table are read on the device when the kernel runs."""
+    _track_same_device("frame_crop", table, rec, imgs, hinv)
+    size = C.sizeof(_lib.G6dFrame)
+    if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or table.numel() < size or table.data_ptr() % 8:
+        raise ValueError(f"frame_crop: table must be a contiguous, 8-byte aligned uint8 tensor of at least one {size}-byte record")
+    if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or not imgs.is_contiguous():
+        raise ValueError("frame_crop: imgs must be a contiguous uint8 [B,H,W,3] tensor")
+    B, H, W = imgs.shape[:3]
+    if rec.dtype != torch.int32 or tuple(rec.shape) != (B,) or not rec.is_contiguous():
+        raise ValueError("frame_crop: rec must be a contiguous int32 [B] tensor")
+    _f32c(hinv)
+    dh, dw = int(dh), int(dw)
+    if hinv.numel() != 9 * B or dh < 1 or dw < 1:
+        raise ValueError("frame_crop: hinv [B,9] and a crop of at least 1 x 1 expected")
+    dst = out if out is not None else torch.empty((B, 3, dh, dw), dtype=torch.float32, device=imgs.device)
+    if tuple(dst.shape) != (B, 3, dh, dw) or dst.dtype != torch.float32 or not dst.is_contiguous() or dst.device != imgs.device:
+        raise ValueError("frame_crop: out must be a contiguous float32 [B,3,dh,dw] tensor")
+    _lib.check(_lib.load().g6d_frame_crop(_ptr(table), _ptr(rec), _ptr(imgs), B, H, W, _ptr(hinv), _ptr(dst), dh, dw, _stream()),
+               "g6d_frame_crop")
+    return dst

@@ -26,6 +26,11 @@ many streams (cameras or clients watching one object) at once:
     frame (full resolution, not turned) with the box drawn in its pixel grid instead: the lane's ingest keeps its frame table on the
     device, the corners are projected once more under the sources' intrinsics and ONE g6d_frame_emit_source launch per lane and tick
     fills those sinks (DESIGN.md §4.20).  A push without source-view sinks launches nothing of this;
+  * with `crops="source"` (needs `frame_size`) the networks' query crops, the refiner's look-at crop of every step and the selector's
+    crop of a first frame, are cut from the camera-native pictures instead of the working-resolution canvas: the lane's ingest keeps
+    its frame table, the tick copies it into a static table beside a slot -> record map, and ONE g6d_frame_crop launch stands where
+    each of those warp launches stood, inside the tick's graph.  Frames with a lens keep their canvas crops.  The
+    default `crops="canvas"` launches what it always launched;
   * with `health=HealthPolicy(...)` every stream carries a status (TRACKING / SUSPECT / LOST) that the device keeps: a gate parks lost
     streams and non-finite table rows before the gather, a health launch judges every refined pose before the commit (a bad frame is
     not committed), the detector can check the committed poses every n-th tick, and the host, which sees the status with a fixed lag,
@@ -121,6 +126,7 @@ _Record = collections.namedtuple("_Record", "out rows commit status")
 class _Lane:                                   # what a tick touches
     def __init__(self, stream):
         self.stream, self.graph, self.img, self.K, self.map, self.out = stream, None, None, None, None, None
+        self.source = self.staged = None       # crops="source": the static ingest.SourceTable; the Staged of the lane's last tick
         self.emitted = None                    # event recorded after the lane's last emit (wait_emitted)
         self.eff = self.commit = self.draw = self.pic = None   # health: slot maps and picture sizes of the tick (static)
         self.ticks = {}                        # health: ticks per group of slots (the detector's check runs on every n-th)
@@ -202,7 +208,7 @@ class _HealthMirror:
 
 class StreamTracker:
     def __init__(self, estimator, max_streams, batch=8, lanes=2, track_iter=1, smooth_num=5, smooth_std=2.5, object_pts=None,
-                 graphs=True, frame_size=None, health=None):
+                 graphs=True, frame_size=None, health=None, crops="canvas"):
         if estimator.refiner is None:
             raise ValueError("StreamTracker: the estimator has no refiner (tracking refines every frame)")
         self.max_streams, self.batch, self.nlanes = int(max_streams), int(batch), int(lanes)
@@ -246,6 +252,12 @@ class StreamTracker:
                 raise ValueError("StreamTracker: frame_size must be (H, W) with H, W >= 1")
             self.frame_size = (int(frame_size[0]), int(frame_size[1]))
             self._shape = self.frame_size + (3,)
+        if crops not in ("canvas", "source"):
+            raise ValueError(f"StreamTracker: crops must be \"canvas\" or \"source\", not {crops!r}")
+        if crops == "source" and self.frame_size is None:
+            raise ValueError("StreamTracker: crops=\"source\" needs a tracker with frame_size (without it the canvas is the only source "
+                             "there is)")
+        self.source_crops = crops == "source"  # the query crops are cut from the camera-native pictures (g6d_frame_crop)
         self._records = None                   # track_streams: [_Record]
         self._sinks = {}                       # the running push: stream id -> [Sink, ...]
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
@@ -487,6 +499,9 @@ class StreamTracker:
             lane.img = torch.zeros((B, h, w, 3), dtype=torch.uint8, device=self.dev)
             lane.K = torch.from_numpy(np.repeat(EV.pseudo_K(h, w)[None], B, 0)).to(self.dev)
             lane.map = torch.full((B,), -1, dtype=torch.int32, device=self.dev)
+            if self.source_crops:              # B frame records and the slot -> record map the tick's graph reads (-1: the canvas)
+                lane.source = I.SourceTable(torch.zeros(B * I.RECORD_BYTES, dtype=torch.uint8, device=self.dev),
+                                            torch.full((B,), -1, dtype=torch.int32, device=self.dev))
             if self.policy is not None:
                 lane.eff, lane.commit, lane.draw = (torch.full((B,), -1, dtype=torch.int32, device=self.dev) for _ in range(3))
                 lane.pic = torch.tensor([[w, h]] * B, dtype=torch.int32, device=self.dev)
@@ -507,13 +522,18 @@ class StreamTracker:
         if self.policy is not None:
             eff = ops.track_gate(self.pose_table, self.health_table, lane.map, lane.eff)
         pose0 = ops.track_gather(self.pose_table, eff, self.parking)
-        r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
+        if lane.source is None:
+            r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
+        else:
+            r = self.chain.query_batch_source(lane.img, lane.K, lane.source, pose_init=pose0, refine_iter=self.track_iter)
         commit, draw = self._judge(pose0, r["pose"], K9, lane.pic, None, eff, lane.commit, lane.draw)
         return ops.track_commit(r["pose"], K9, commit, False, self.box, self.num, self.std, self.pose_table, self.hist, self.hist_count,
                                 self.smooth_table), commit, draw
 
     def _capture(self, lane, warmup=2):
         lane.map.fill_(-1)
+        if lane.source is not None:            # warm-up and capture run on the canvases: the table holds no frame yet
+            lane.source.rec.fill_(-1)
         for _ in range(warmup):
             self._tick_fn(lane)
         graph = torch.cuda.CUDAGraph()
@@ -533,8 +553,8 @@ class StreamTracker:
             self._capture(lane)
         staged = None
         if self.frame_size is not None:        # one launch fills the named slots of the static image and K buffers
-            if self._wants_source(ents):       # ... and leaves its frame table on the device for the source-view emit
-                staged = I.ingest_frames_keep([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])[1]
+            if self.source_crops or self._wants_source(ents):      # ... and leaves its frame table on the device for the source-view
+                staged = I.ingest_frames_keep([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])[1]     # emit and crops
             else:
                 I.ingest_frames([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
         else:
@@ -542,6 +562,9 @@ class StreamTracker:
                 lane.img[e.slot].copy_(e.frame)
                 lane.K[e.slot].copy_(e.K)
         lane.map.copy_(self._upload(m))
+        if lane.source is not None:            # the graph reads the planes after push has returned: the Staged lives until the next tick
+            lane.source.load(staged)
+            lane.staged = staged
         if lane.pic is not None:               # (a policy's static buffer)
             lane.pic.copy_(self._upload(self._pic(ents, self.batch)))
         if self.graphs:
@@ -578,14 +601,14 @@ class StreamTracker:
         if native:
             imgs = torch.empty((n,) + self._shape, dtype=torch.uint8, device=self.dev)
             Ks = torch.empty((n, 3, 3), dtype=torch.float32, device=self.dev)
-            if self._wants_source(ents):
+            if self.source_crops or self._wants_source(ents):
                 staged = I.ingest_frames_keep([e.frame for e in ents], imgs, Ks)[1]
             else:
                 I.ingest_frames([e.frame for e in ents], imgs, Ks)
         else:
             imgs = torch.stack([e.frame for e in ents], 0)
             Ks = torch.stack([e.K for e in ents], 0)
-        r = self.chain.query_batch(imgs, Ks)
+        r = self.chain.query_batch_source(imgs, Ks, I.SourceTable.of(staged)) if self.source_crops else self.chain.query_batch(imgs, Ks)
         pose, K9 = r["pose"].reshape(n, 12), Ks.reshape(n, 9)
         ids = self._upload(np.asarray([e.stream for e in ents], np.int32))
         pic = self._upload(self._pic(ents, n)) if native and self.policy is not None else None
@@ -692,7 +715,8 @@ def host_track(estimator, frames, Ks, track_iter=1, smooth_num=5, smooth_std=2.5
 def track_streams(estimator, streams, Ks=None, **tracker_kw):
     """S frame sequences (possibly of different lengths; uint8 [H,W,3] frames of one shape) -> per stream (poses [T,3,4], smoothed
     [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  With
-    `frame_size=(H, W)` the frames are `ingest.Frame`s (or [h,w,3] arrays) of any size and format, carry their own K, and Ks stays None.  Frame t of
+    `frame_size=(H, W)` the frames are `ingest.Frame`s (or [h,w,3] arrays) of any size and format, carry their own K, and Ks stays None;
+    `crops="source"` then cuts the networks' query crops from them (StreamTracker), also when the sequences are recomputed.  Frame t of
     every stream that has one is pushed in tick t; one synchronisation at the end.  Runs under the estimator's range guard: if an fp16
     pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32.
     With `health=HealthPolicy(...)` every stream's tuple is (poses, smoothed, status [T] int32): the status after each frame; a frame
@@ -705,8 +729,8 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
         raise ValueError("track_streams: with frame_size the intrinsics travel in Frame.K, not in Ks")
     Kss = None if native else _stream_Ks(Ks, seqs)
 
-    def run():
-        tr = StreamTracker(estimator, len(seqs), **kw)
+    def run(**over):
+        tr = StreamTracker(estimator, len(seqs), **{**kw, **over})
         tr._records = []
         for t in range(max((len(s) for s in seqs), default=0)):
             ids = [s for s in range(len(seqs)) if t < len(seqs[s])]
@@ -719,6 +743,9 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
         host = [_ingest_to_host(frames, kw["frame_size"], estimator.device) for frames in seqs] if native else zip(seqs, Kss)
         return [host_track(estimator, fr, Kh, kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
                 for fr, Kh in host]
+    if kw.get("crops", "canvas") == "source":
+        # the host-driven loop sees canvases only: the recomputation is the same ticks run eagerly, which follow the networks' routes
+        return estimator._range_guarded(run, lambda: run(graphs=False))
     if kw.get("health") is None:
         return estimator._range_guarded(run, recompute)
     return estimator._range_guarded(run, lambda: [r + (np.full(len(r[0]), TRACKING, np.int32),) for r in recompute()])

@@ -784,6 +784,30 @@ int g6d_sizeof_sink_desc(void);
 int g6d_frame_emit_source(const G6dSink* sinks, int n, const G6dFrame* frames, int nf, const int32_t* pts, const int32_t* valid, int sets,
                           int B, int max_w, int max_h, g6d_stream_t stream);
 
+/* g6d_frame_crop, g6d_warp_batch's query crops cut from the camera-native frames (gen6d_amd/chain.py query_batch_source, DESIGN.md
+ * §4.24); additive within ABI 12.  ONE launch fills dst [B][3][dh][dw] float32 in [0,1], the layout and the uint8-rounded values of
+ * g6d_warp_batch.  hinv [B][9] maps crop pixels to pixels of the working-resolution canvas, as for g6d_warp_batch; slot b samples the
+ * camera's own picture frames[rec[b]] (a G6dFrame table as g6d_frame_ingest takes it; the record's `slot` field is not used) through that
+ * map composed with the inverse of the ingest's scaling and quarter turn.  A slot with rec[b] < 0 has no source: it takes g6d_warp_batch's
+ * rule on imgs[b] (imgs [B][H][W][3] uint8, the canvases), bit for bit.  frames, rec, imgs and hinv live in DEVICE memory and are read when
+ * the kernel runs (the launch can sit inside a captured graph); the caller validates the table as for g6d_frame_ingest and that
+ * rec[b] names one of its records.
+ * Rule of a slot with r = rec[b] >= 0, all in float32, with ws x hs the source and wt x ht the scaled picture before rotation
+ * ((out_w, out_h) for rotate 0 / 180, (out_h, out_w) for 90 / 270) of frames[r], at crop pixel (x, y):
+ *   1. (cx, cy) = (X, Y) / Wd of hinv[b] * (x, y, 1), with 1 / Wd taken as 0 when Wd == 0 (g6d_warp_batch's rule);
+ *   2. the quarter turn undone (the ingest's rule above, read for real coordinates): rotate 0: (px, py) = (cx, cy), 90: (cy, ht-1-cx),
+ *      180: (wt-1-cx, ht-1-cy), 270: (wt-1-cy, cx);
+ *   3. fx = px * ax + bx (one fused multiply-add) with ax = (float)(ws / wt) and bx = 0.5f * ax - 0.5f, fy likewise with hs / ht: the inverse of the ingest's
+ *      u' = (u + 0.5) * wt / ws - 0.5.  A same-size source has ax = 1, bx = 0 and fx = px exactly;
+ *   4. g6d_warp_batch from here, on the source: fx = clamp(fx, -4, ws + 4), x0 = floor(fx), a = fx - x0, x1 = x0 + 1, y likewise (b);
+ *      weights (1-a)(1-b), a(1-b), (1-a)b, ab; a tap outside the source contributes zero;
+ *   5. each tap becomes RGB by the ingest's tap rules: packed formats by channel order (alpha ignored), NV12 through the integer
+ *      conversion above with chroma UV[y>>1][x>>1] and the frame's matrix;
+ *   6. per channel v = sum of weight * tap, dst = clamp(rint(v), 0, 255) / 255.
+ * The sampler is the point-sampled bilinear of every warp here: a crop pixel that covers several source pixels aliases. */
+int g6d_frame_crop(const G6dFrame* frames, const int32_t* rec, const uint8_t* imgs, int B, int H, int W, const float* hinv, float* dst,
+                   int dh, int dw, g6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
