@@ -51,7 +51,8 @@ __device__ __forceinline__ f32x4 ldg(const float* __restrict__ base, int elem_of
 __device__ __forceinline__ const int* pair_exp_ptr(const G6dConv& p) { return reinterpret_cast<const int*>(p.weight_wino16); }
 __device__ __forceinline__ unsigned* pair_rec_ptr(const G6dConv& p) { return reinterpret_cast<unsigned*>(const_cast<float*>(p.weight_wino43)); }
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-// one thread's 4 channels (4 seg .. 4 seg + 3) of an LDS row as pairs: hi = rn16(u), lo = rn16(u - hi) into the row's two 64-byte planes
+// one thread's 4 channels (4 seg .. 4 seg + 3) of an LDS row as pairs: hi = rn16(u), lo = rn16(u - hi) (the split of pair16.h, the format's
+// definition, restated) into the row's two 64-byte planes
 __device__ __forceinline__ void store_pair(float* row, int seg, f32x4 u) {
   f16x4 hi, lo;
 #pragma unroll

@@ -83,6 +83,7 @@ struct VolViews { const float* projs; const float* ref_Ks; const float* ref_pose
 // elementwise producers' protocol).  The same gathers and arithmetic, the same number of bytes written; 8-byte stores per lane.
 struct VolPairs { G6dRange16 mean, stdv; };
 
+// (restates c16_pair_split of pair16.h, the definition of the format)
 __device__ __forceinline__ void store_pair4(_Float16* hi_p, int plane, f32x4 v, int e, unsigned& amax) {
   typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   h4 hi, lo;

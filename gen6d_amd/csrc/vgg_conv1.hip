@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(256) vgg_conv1_pool_mfma_kernel(const float* _
           const float m1 = fmaxf(fmaxf(acc1[4 * j], acc1[4 * j + 1]), fmaxf(acc1[4 * j + 2], acc1[4 * j + 3])) + b1;
           OT* o = out + ((size_t)(n * Ho + py) * Wo + px) * (PAIR ? 2 * C1_COUT : C1_COUT);
           float r0 = fmaxf(m0, 0.f), r1 = fmaxf(m1, 0.f);                     // relu(max) == max(relu)
-          if constexpr (PAIR) {
+          if constexpr (PAIR) {                                               // (restates c16_pair_split of pair16.h, the definition)
             amax = max(amax, max(g6d_abs_bits(r0), g6d_abs_bits(r1)));
             r0 = ldexpf(r0, -eo); r1 = ldexpf(r1, -eo);
           }

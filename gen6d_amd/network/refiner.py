@@ -183,7 +183,18 @@ class VolumeRefiner(ParamBank):
             self._packed = pk
         return self._packed
 
-    # ------------------------------------------------------------------ 2-D feature net
+    # ------------------------------------------------------------------ a layer on the pair kernel
+    @staticmethod
+    def _pair_conv(layer, xin, y, groups, count, kd=1):
+        """A stride-1 3x3 (kd = 1) or 3x3x3 (kd = 3: depth taps folded into the reduction) layer on the pair kernel: xin a PairMap
+        [N,(D,)H,W,2,Cin], y the fp32 output view (a dense map or a channel slice of one).  groups > 0: the per-group sums of the
+        InstanceNorm that follows (groups of count values) in the epilogue and one small launch that finalises them -> its affine
+        (scale, shift); else None."""
+        st = ops.new_stats(groups, y.shape[-1], y.device) if groups else None
+        ops.conv16_direct_multi([xin], layer.w16(3) if kd == 1 else layer.w16(3, layout=2), layer[1], relu=False, full=torch.float32, kd=kd,
+                                stats=st, rows_per_group=count if groups else 0, out_full=[y])
+        return ops.stats_finalize(st, count) if groups else None
+
     def run_feature_net(self, imgs, f43=None):
         """imgs [n,3,h,w] in [0,1] -> channels-last features [n,h/4,w/4,128] (reference refiner.py:64-78).
         f43: None = the F(4x4,3x3) kernels from 4 queries (28 crops) per launch on (below that F(2x2,3x3) is faster); False = never
@@ -229,12 +240,8 @@ class VolumeRefiner(ParamBank):
             _, hh, ww, _, _ = x.shape
 
             def conv16(layer, xin):
-                co = layer[0].shape[0]
-                y = torch.empty((n, 1, hh, ww, co), dtype=torch.float32, device=dev)
-                st = ops.new_stats(n, co, dev)
-                ops.conv16_direct_multi([xin], layer.w16(3), layer[1], relu=False, full=torch.float32, stats=st, rows_per_group=hh * ww,
-                                        out_full=[y[:, 0]])
-                return (y,) + ops.stats_finalize(st, hh * ww)
+                y = torch.empty((n, 1, hh, ww, layer[0].shape[0]), dtype=torch.float32, device=dev)
+                return (y,) + self._pair_conv(layer, xin, y[:, 0], n, hh * ww)
 
             y0, sc0, sh0 = conv16(pk[name][0], x)
             mid = ops.affine_split16(y0, sc0, sh0, 1, True, False, 3, rng=(rng, rng.slot(f"featnet.{name}.mid")))
@@ -347,15 +354,6 @@ class VolumeRefiner(ParamBank):
         # the two embeds meet in `cat`: ONE 128-channel pair map (one exponent slot for both slices) when conv0 reads pairs, else fp32
         cat = ops.new_map16(qn * sn, sn, sn, 128, 3, dev, rng=(rng, rng.slot("volume.cat"))) if cat16 else buf(sn, 128)
 
-        def c16(layer, xin, y, stats_c=None, count=vox):
-            """A stride-1 3x3x3 layer on the pair kernel (depth taps folded into the reduction): xin a PairMap [qn,s,s,s,2,Cin], y the fp32
-            output (a dense map or a channel slice of one); with stats_c: the per-volume sums (count voxels) in the epilogue and one small
-            launch that finalises them -> the affine (scale, shift) of the InstanceNorm that follows."""
-            st = ops.new_stats(qn, stats_c, dev) if stats_c else None
-            ops.conv16_direct_multi([xin], layer.w16(3, layout=2), layer[1], relu=False, full=torch.float32, kd=3, stats=st,
-                                    rows_per_group=count if stats_c else 0, out_full=[y])
-            return ops.stats_finalize(st, count) if stats_c else None
-
         def embed(name, x, c_off):
             if pairs_in:
                 return embed16(name, x, c_off)
@@ -368,13 +366,13 @@ class VolumeRefiner(ParamBank):
             second layer's pairs (planes as images: sn planes per affine table); the second layer's fp32 map goes into its slice of `cat`
             — directly (fp32 `cat`), or through the pass that splits it into the pair map conv0 reads."""
             y0 = buf(sn, 64)
-            sc, sh = c16(pk[name][0], x, y0, stats_c=64)
+            sc, sh = self._pair_conv(pk[name][0], x, y0, qn, vox, kd=3)
             mid = ops.affine_split16(y0.view(qn * sn, 1, sn, sn, 64), sc, sh, sn, True, False, 3, rng=(rng, rng.slot(f"volume.{name[2:]}.mid")))
             if not cat16:
-                c16(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), cat[..., c_off:c_off + 64])
+                self._pair_conv(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), cat[..., c_off:c_off + 64], 0, vox, kd=3)
                 return
             y1 = buf(sn, 64)
-            c16(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), y1)
+            self._pair_conv(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), y1, 0, vox, kd=3)
             ops.affine_split16_to(y1.view(qn * sn, 1, sn, sn, 64), None, None, 0, False, 3, cat, c_off)
 
         with self._mm("embed"):
@@ -388,12 +386,12 @@ class VolumeRefiner(ParamBank):
                 y = buf(s, co)
                 if name == "v_conv0" and cat16:
                     # fp32 output with the sums: conv1 (stride 2, implicit GEMM) still takes the affine in its operand prologue
-                    x, aff = y, c16(pk[name], cat.view(qn, sn, sn, sn, 2, 128), y, stats_c=co)
+                    x, aff = y, self._pair_conv(pk[name], cat.view(qn, sn, sn, sn, 2, 128), y, qn, vox, kd=3)
                     continue
                 if name == "v_conv2" and pairs_in and "conv2" in VOLUME_PAIR_LAYERS:
                     # conv1's InstanceNorm affine + ReLU is the pass that writes conv2's pairs (planes as images: s planes per table)
                     xin = ops.affine_split16(x.view(qn * s, 1, s, s, 128), aff[0], aff[1], s, True, False, 3, rng=(rng, rng.slot("volume.conv2.in")))
-                    x, aff = y, c16(pk[name], xin.view(qn, s, s, s, 2, 128), y, stats_c=co, count=s ** 3)
+                    x, aff = y, self._pair_conv(pk[name], xin.view(qn, s, s, s, 2, 128), y, qn, s ** 3, kd=3)
                     continue
                 x, aff = y, c3(x, pk[name], y, stride=stride, aff=aff, stats_c=co, count=s ** 3, name=name[2:])
         s = s // 2

@@ -217,7 +217,7 @@ class ViewpointSelector(ParamBank):
                 mode16 = self._product16_mode(first, D * h * w, co) if first else self._stack16_mode(D * h * w, co, wgt.shape[2])
                 if mode16 and not first:
                     # round 6: the stack layers too — the InstanceNorm affine + ReLU of the previous layer is applied by one elementwise pass that
-                    # writes the map in the direct kernel's format (g6d_affine_split16), the conv adds this layer's sums in its epilogue
+                    # writes the map in the direct kernel's format (g6d_affine_split16, csrc/split16.hip), the conv adds this layer's sums in its epilogue
                     x16 = ops.affine_split16(x, scale, shift, grp if scale is not None else 0, relu, False, mode16, **self._rng_kw(mode16, f"stack{l}.{li}"))
                     filt = pk["corr"][l][li].w16(mode16)
                     ci = wgt.shape[2]
@@ -230,7 +230,7 @@ class ViewpointSelector(ParamBank):
                     res, fin = out, None
                 elif mode16:
                     # round 6: the product layer on the direct 16-bit convolution (csrc/conv16_direct.hip): the normalised query x reference
-                    # product is written once in the kernel's activation format (fp32 path: fp16 hi / lo pairs, fp32-class results), the conv
+                    # product is written once in the kernel's activation format (csrc/split16.hip; fp32 path: fp16 hi / lo pairs, fp32-class results), the conv
                     # adds this level's InstanceNorm sums in its epilogue, the affine of that norm comes from one small finalize launch
                     prod = ops.product_split16(cache.view(D, h * w, 512), q.view(qn, h * w, 512), scale, shift, mode16, **self._rng_kw(mode16, f"prod{l}"))
                     prod = prod.view(qn * D, h, w, 2, 512) if mode16 == 3 else prod.view(qn * D, h, w, 512)

@@ -835,21 +835,31 @@ def conv16_pack(w_taps, mode, layout=1):
     return Conv16Filters(x.reshape(-1), 1, mode, acc_scale, co_true, taps, ci)
 
 
+def _pair_out(what, lead, Cc, mode, device, rng, out=None):
+    """The head the producers of 16-bit maps share.  A range (RangeTable, slot) applies to pairs (mode 3) only; the result is [*lead, C] of
+    the mode's 16-bit type or [*lead, 2, C] fp16 pairs (`out`, if given, must be that map) -> (out, the launch's G6dRange16 argument)."""
+    if rng is not None and mode != 3:
+        raise ValueError(f"{what}: a range applies to pairs (mode 3) only")
+    shape = (*lead, 2, Cc) if mode == 3 else (*lead, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=_T16[mode], device=device)
+    elif out.dtype != _T16[mode] or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise ValueError(f"{what}: out must be a dense {_T16[mode]} tensor of shape {shape}")
+    return out, _range_arg(None, -1, rng)
+
+
 def product_split16(ref, que, scale, shift, mode, rng=None):
     """The selector's query x reference product in the activation format of conv16_direct_multi (g6d_product_split16): ref [D,P,C], que
     [qn,P,C], scale / shift [qn,C] fp32 -> [qn*D, P, C] (mode 1 / 2) or [qn*D, P, 2, C] fp16 pairs (mode 3).  rng = (RangeTable, slot):
     mode 3 only, the pairs carry the slot's exponent and are recorded (returns a PairMap)."""
-    if rng is not None and mode != 3:
-        raise ValueError("product_split16: a range applies to pairs (mode 3) only")
     _need_gpu(ref, que, scale, shift)
     D, P, Cc = ref.shape
     qn = que.shape[0]
     if tuple(que.shape) != (qn, P, Cc) or tuple(scale.shape) != (qn, Cc) or tuple(shift.shape) != (qn, Cc) or not all(
             t.is_contiguous() and t.dtype == torch.float32 for t in (ref, que, scale, shift)):
         raise ValueError("product_split16: dense fp32 ref [D,P,C], que [qn,P,C], scale / shift [qn,C] expected")
-    out = torch.empty((qn * D, P, 2, Cc) if mode == 3 else (qn * D, P, Cc), dtype=_T16[mode], device=ref.device)
+    out, ra = _pair_out("product_split16", (qn * D, P), Cc, mode, ref.device, rng)
     nbytes = 4.0 * (ref.numel() + que.numel()) + 2.0 * out.numel()
-    ra = _range_arg(None, -1, rng)
     _timed_hbm("product_split16", nbytes, lambda: _lib.check(_lib.load().g6d_product_split16_ex(
         _ptr(ref), _ptr(que), _ptr(scale), _ptr(shift), _ptr(out), qn, D, P, Cc, int(mode), ra, _stream()), "g6d_product_split16"))
     return _wrap(out, rng)
@@ -858,15 +868,12 @@ def product_split16(ref, que, scale, shift, mode, rng=None):
 def affine_split16(x, scale, shift, per_n, relu, pool, mode, rng=None):
     """affine_act_pool (pool False / True = 2x2 max) with the result in the activation format of conv16_direct_multi (g6d_affine_split16):
     x [N,1,H,W,C] fp32 view -> [N,Ho,Wo,C] (mode 1 / 2) or [N,Ho,Wo,2,C] fp16 pairs (mode 3).  rng as product_split16."""
-    if rng is not None and mode != 3:
-        raise ValueError("affine_split16: a range applies to pairs (mode 3) only")
     _need_gpu(x)
     N, D, H, W, Cc, ld_in = _cl5(x, "affine_split16.x")
     if D != 1:
         raise ValueError("affine_split16: 2-D maps expected")
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    out = torch.empty((N, Ho, Wo, 2, Cc) if mode == 3 else (N, Ho, Wo, Cc), dtype=_T16[mode], device=x.device)
-    ra = _range_arg(None, -1, rng)
+    out, ra = _pair_out("affine_split16", (N, Ho, Wo), Cc, mode, x.device, rng)
     _timed_hbm("affine_split16", 4.0 * N * H * W * Cc + 2.0 * out.numel(), lambda: _lib.check(_lib.load().g6d_affine_split16_ex(
         _ptr(x), ld_in, _ptr(scale), _ptr(shift), int(per_n), int(bool(relu)), int(bool(pool)), N, H, W, Cc, _ptr(out), int(mode), ra, _stream()),
         "g6d_affine_split16"))
@@ -876,9 +883,7 @@ def affine_split16(x, scale, shift, per_n, relu, pool, mode, rng=None):
 def new_map16(N, H, W, Cc, mode, device, rng=None):
     """An empty map in the activation format of conv16_direct_multi: [N,H,W,C] (mode 1 / 2) or [N,H,W,2,C] fp16 pairs (mode 3; with rng =
     (RangeTable, slot) a PairMap of that slot) — the destination the slice producers below fill channel slice by channel slice."""
-    if rng is not None and mode != 3:
-        raise ValueError("new_map16: a range applies to pairs (mode 3) only")
-    return _wrap(torch.empty((N, H, W, 2, Cc) if mode == 3 else (N, H, W, Cc), dtype=_T16[mode], device=device), rng)
+    return _wrap(_pair_out("new_map16", (N, H, W), Cc, mode, device, rng)[0], rng)
 
 
 def _slice16(out, N, Ho, Wo, Cc, c_off, mode, what):
@@ -929,14 +934,11 @@ def l2norm_split16(x, mode, rng=None):
     """F.normalize over the channels of an fp32 channels-last tap x [N,H,W,C] (C = 256 or 512; the arithmetic of l2norm_rows) written in
     the activation format of conv16_direct_multi instead of in place (g6d_l2norm_split16): [N,H,W,C] (mode 1 / 2) or [N,H,W,2,C] pairs.
     rng as product_split16."""
-    if rng is not None and mode != 3:
-        raise ValueError("l2norm_split16: a range applies to pairs (mode 3) only")
     _need_gpu(x)
     if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4:
         raise ValueError("l2norm_split16: a dense float32 [N,H,W,C] tap expected")
     N, H, W, Cc = x.shape
-    out = torch.empty((N, H, W, 2, Cc) if mode == 3 else (N, H, W, Cc), dtype=_T16[mode], device=x.device)
-    ra = _range_arg(None, -1, rng)
+    out, ra = _pair_out("l2norm_split16", (N, H, W), Cc, mode, x.device, rng)
     _timed_hbm("l2norm_split16", 4.0 * x.numel() + 2.0 * out.numel(), lambda: _lib.check(_lib.load().g6d_l2norm_split16(
         _ptr(x), Cc, N * H * W, Cc, _ptr(out), int(mode), ra, _stream()), "g6d_l2norm_split16"))
     return _wrap(out, rng)
@@ -950,20 +952,14 @@ def vgg_conv1_pool_nhwc16(x, w_oihw, bias, out=None, norm=None, mode=None, rng=N
     mode = MATH_MODE if mode is None else mode
     if mode not in _T16:
         raise RuntimeError("vgg_conv1_pool_nhwc16: mode 1 (bf16), 2 (fp16) or 3 (fp16 pairs)")
-    if rng is not None and mode != 3:
-        raise ValueError("vgg_conv1_pool_nhwc16: a range applies to pairs (mode 3) only")
     N, Cin, H, W = x.shape
     Cout = w_oihw.shape[0]
-    shape = (N, H // 2, W // 2, 2, Cout) if mode == 3 else (N, H // 2, W // 2, Cout)
-    if out is None:
-        out = torch.empty(shape, dtype=_T16[mode], device=x.device)
-    if out.dtype != _T16[mode] or not out.is_contiguous() or tuple(out.shape) != shape:
-        raise ValueError(f"vgg_conv1_pool_nhwc16: out must be a dense {_T16[mode]} tensor of shape {shape}")
+    out, ra = _pair_out("vgg_conv1_pool_nhwc16", (N, H // 2, W // 2), Cout, mode, x.device, rng, out)
     mean = std = None
     if norm is not None:
         mean, std = (C.c_float * 3)(*norm[0]), (C.c_float * 3)(*norm[1])
     _lib.check(_lib.load().g6d_vgg_conv1_pool_nhwc16_ex(_ptr(x.contiguous()), N, H, W, _ptr(w_oihw.contiguous()), _ptr(bias), Cin, Cout,
-                                                        mean, std, _ptr(out), int(mode), _range_arg(None, -1, rng), _stream()),
+                                                        mean, std, _ptr(out), int(mode), ra, _stream()),
                "g6d_vgg_conv1_pool_nhwc16")
     return _wrap(out, rng)
 

@@ -328,7 +328,8 @@ int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int Cin, const v
                             int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group,
                             g6d_stream_t stream);
 
-/* The selector's query x reference product (network/selector.py:183-186) in the 16-bit activation format of g6d_conv16_direct_multi (ABI v12):
+/* The selector's query x reference product (network/selector.py:183-186) in the 16-bit activation format of g6d_conv16_direct_multi (ABI v12;
+ * this and the other *_split16 hand-over passes: csrc/split16.hip, the formats: csrc/pair16.h):
  * out[(q D + d) P + px][plane][c] = split16((ref[d][px][c] * que[q][px][c]) * scale[q][c] + shift[q][c]); ref [D][P][C], que [qn][P][C], scale /
  * shift [qn][C] fp32; out 16-bit: [qn D P][C] for math_mode 1 (bf16) / 2 (fp16), [qn D P][2][C] fp16 hi / lo pairs for math_mode 3.  C % 8 == 0. */
 int g6d_product_split16(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,

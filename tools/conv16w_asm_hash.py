@@ -1,14 +1,16 @@
 """Per-kernel hashes of the conv16w_kernel instantiations in two device-assembly files, to show that a change left an instantiation's
 code as it was:
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -w -S --cuda-device-only -I include -o new.s gen6d_amd/csrc/conv16_direct.hip   (both trees)
-    python tools/conv16w_asm_hash.py old.s new.s
+    python tools/conv16w_asm_hash.py old.s new.s [kernel-name pattern]
+The optional third argument is a regular expression for the kernels' (mangled) names, default conv16w_kernel: `kernel` covers every
+kernel of a translation unit, whichever file the two assembly files were built from.
 Instructions and directives only: comments, block-label numbering and the kernel's own mangled name are normalised, and a trailing
 KD = 1 template argument is dropped from the name, so that an instantiation keeps its key when the template gains that parameter."""
 import re, sys, hashlib
-def bodies(path):
+def bodies(path, pat):
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_Z\w*conv16w_kernel\w*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
+    for m in re.finditer(r"^(_Z\w*(?:%s)\w*):[^\n]*\n(.*?)^\.Lfunc_end\d+:" % pat, text, re.S | re.M):
         name = m.group(1)
         body = m.group(2).replace(name, "KERNEL")
         body = re.sub(r"\.LBB\d+_", ".LBB_", body)
@@ -16,6 +18,7 @@ def bodies(path):
         key = re.sub(r"(ILi\dELi\dELi\d)ELi1(EEEvNS)", r"\1\2", name)
         out[key] = (hashlib.sha256(body.encode()).hexdigest()[:16], body.count("\n") + 1)
     return out
-a, b = bodies(sys.argv[1]), bodies(sys.argv[2])
+pat = sys.argv[3] if len(sys.argv) > 3 else "conv16w_kernel"
+a, b = bodies(sys.argv[1], pat), bodies(sys.argv[2], pat)
 for k in sorted(set(a) | set(b)):
     print(k, a.get(k), b.get(k), "SAME" if a.get(k) == b.get(k) else "DIFF")
