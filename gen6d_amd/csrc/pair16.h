@@ -14,6 +14,18 @@ template <> struct C16T<1> { typedef __bf16 T; typedef bf16x8 V; };
 template <> struct C16T<2> { typedef _Float16 T; typedef f16x8 V; };
 template <int MM> struct C16T3 { typedef typename C16T<MM == 3 ? 2 : MM>::T T; typedef typename C16T<MM == 3 ? 2 : MM>::V V; };
 
+// What the 16-bit kernels (conv16_direct.hip, corr16.hip) share: the 32x32x16 MFMA of a mode (pairs: of its fp16 planes), the buffer
+// descriptor of their LDS-DMA and buffer loads, and the offset that always lies beyond it (the out-of-range zero fill).
+template <int MM>
+__device__ __forceinline__ f32x16 c16_mfma(typename C16T3<MM>::V a, typename C16T3<MM>::V b, f32x16 c) {
+  if constexpr (MM == 1) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t c16_rsrc(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+constexpr unsigned C16_OOB = 0x80000000u;
+
 // The per-value rule: record |v| into amax, scale by 2^-eo, split.
 template <typename T>
 __device__ __forceinline__ void c16_pair_split(float v, int eo, unsigned& amax, T& hi, T& lo) {

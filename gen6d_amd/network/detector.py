@@ -151,7 +151,7 @@ class Detector(ParamBank):
             assert is_16bit(xs[0]) == (route == "corr16"), "the trunk did not hand the level over in the format of its route"
             if route == "corr16":
                 # 16-bit activations (reduced precision) or fp16 hi / lo pairs (fp32 path): the halo-patch correlation kernel on the 16-bit
-                # matrix cores (csrc/conv16_direct.hip, corr16_kernel)
+                # matrix cores (csrc/corr16.hip, corr16_kernel)
                 mode = 3 if len(xs[0].shape) == 5 else (1 if xs[0].dtype == torch.bfloat16 else 2)
                 filt = self._corr16_filters(l, mode)
                 outs = [torch.empty((qn, 1, x.shape[1], x.shape[2], rfn), dtype=torch.float32, device=dev) for x in xs]

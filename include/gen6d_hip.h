@@ -342,8 +342,8 @@ int g6d_affine_split16(const float* in, int ld_in, const float* scale, const flo
                        int C, void* out, int math_mode, g6d_stream_t stream);
 
 /* The detector's K x K correlation (network/detector.py:188-197,222-224: query feature map x the 32 reference-centre features) on 16-bit
- * activations, halo-patch kernel with the K^2 taps of a slice split over the eight waves of a block (ABI v12; csrc/conv16_direct.hip,
- * corr16_kernel).  segs[i]: in = [N][H][W][ld_in] of the mode's 16-bit type (mode 3: [pixel][2][Cin] fp16 hi / lo pairs), out_full = fp32
+ * activations, halo-patch kernel with the K^2 taps of a slice split over the eleven computing waves of a block (ABI v12;
+ * csrc/corr16.hip, corr16_kernel).  segs[i]: in = [N][H][W][ld_in] of the mode's 16-bit type (mode 3: [pixel][2][Cin] fp16 hi / lo pairs), out_full = fp32
  * [N][H][W][ld_full] (ld_full >= 32), D = 1; out = acc_scale * sum_{ky,kx,c} in[y + ky - K/2][x + kx - K/2][c] * w[r][ky K + kx][c] with zero
  * padding.  W16 (host: ops.corr16_pack): [Cin / S][K K][2][64 lanes][8 values] 16-bit — S = 32 channels per slice and fragment f = the
  * slice's 16-channel group (modes 1 / 2), or S = 16 and f = hi / lo plane (mode 3); lane l of a fragment holds reference r = l & 31,

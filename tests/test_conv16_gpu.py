@@ -123,6 +123,8 @@ CORR_CASES = [
     dict(N=3, sizes=[(22, 30), (9, 13)], Cin=64, k=15),                                   # ragged maps, two sizes
     dict(N=2, sizes=[(11, 15), (32, 40)], Cin=128, k=7),
     dict(N=1, sizes=[(88, 116), (60, 80), (44, 60), (32, 40)], Cin=512, k=15),           # the headline's pyramid, one query
+    dict(N=2, sizes=[(3, 31), (7, 15), (15, 7), (31, 3)], Cin=96, k=7),                   # tile widths 32, 16, 8, 4; 3 (pairs: 6) slices
+    dict(N=2, sizes=[(9, 13), (15, 7), (22, 30)], Cin=96, k=15),                          # tile widths 16, 8, 16, all ragged
 ]
 
 

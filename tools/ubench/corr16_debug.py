@@ -1,4 +1,4 @@
-"""Debug aid: error of g6d_corr16_multi on a few shapes.  python tools/ubench/corr16_debug.py"""
+"""Debug aid: error of g6d_corr16_multi (corr16_kernel, gen6d_amd/csrc/corr16.hip) on a few shapes.  python tools/ubench/corr16_debug.py"""
 import os, sys
 import torch, torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

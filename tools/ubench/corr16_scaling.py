@@ -1,4 +1,4 @@
-"""corr16_kernel: rate against the size of the filter set (Cin) on the headline's pyramid — does re-streaming the filters per tile bound it?
+"""corr16_kernel (gen6d_amd/csrc/corr16.hip): rate against the size of the filter set (Cin) on the headline's pyramid — does re-streaming the filters per tile bound it?
 python tools/ubench/corr16_scaling.py [batch]"""
 import os, sys
 import torch
