@@ -45,8 +45,8 @@ __device__ __forceinline__ f32x4 ldg(const float* __restrict__ base, int elem_of
   return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + ((unsigned)elem_off << 2));
 }
 
-// Pair mode (MM = 3): the kernel signature is shared by all modes, so its two device pointers — the activation exponent
-// &exps[slot_out] and the range record &rec[slot_out] of the launch's G6dRange16 (slot_in is not read) — ride in the kernel's own COPY of the descriptor, in the Winograd filter
+// Pair modes (MM = 3, 4, 5): the kernel signature is shared by all modes, so its two device pointers — the activation exponent
+// &exps[slot_out] and the range record &rec[slot_out] of the launch's G6dRange16 (MM = 5: &exps[slot_in] and no record) — ride in the kernel's own COPY of the descriptor, in the Winograd filter
 // pointers that this kernel never reads (launch_mm sets them; the caller's descriptor is not touched).
 __device__ __forceinline__ const int* pair_exp_ptr(const G6dConv& p) { return reinterpret_cast<const int*>(p.weight_wino16); }
 __device__ __forceinline__ unsigned* pair_rec_ptr(const G6dConv& p) { return reinterpret_cast<unsigned*>(const_cast<float*>(p.weight_wino43)); }
@@ -74,6 +74,15 @@ __device__ __forceinline__ void store_pair(float* row, int seg, f32x4 u) {
 //     same way — and nothing is converted at the use site.  Per 16 channels and accumulator: hi x hi, hi x lo, lo x hi (lo x lo dropped,
 //     as around c16_mfma<3> (pair16.h) in conv16_direct.hip and corr16.hip).  The accumulators (and split partials) stay unscaled fp32 sums of the scaled operands; the
 //     epilogue multiplies by 2^(e_in - w_exp).  The largest |activation| after the prologue is recorded (G6dRange16, one atomic per block).
+//     4 / 5 = the same LDS image, fragment reads, MFMA sequence, split-K finish and epilogue as 3 with operands that arrive PRE-SPLIT, so the
+//     loader copies instead of converting (the split costs ~25 vector instructions per 4-channel row piece, in every K step of every block):
+//     4 = filters packed on the host as [Cout][taps][Cin / 32][hi 32 | lo 32] fp16 of w * 2^w_exp (include/gen6d_hip.h) — a row's K step is the
+//         128 bytes the fp32 row occupies, so the fp32 loader's addresses hold and a thread's 16 bytes go to row * 144 + 16 lseg unconverted;
+//         activations as in 3 (prologue, split, record).  Bit-identical to 3.
+//     5 = additionally the activations are a pair map (pair16.h: per pixel the hi plane, ld_in / 2 elements further the lo plane, rows of
+//         ld_in 16-bit elements): lseg >> 2 selects the plane, its byte offset folds into the row's constant offset; tap and chunk offsets
+//         stay uniform, padding rows keep the out-of-range zero fill.  MODE 0 only (the producer applied the prologue and recorded the range);
+//         the exponent is exps[slot_in].
 template <int BM, int BN, int WGM, int WGN, int MODE, int MM>
 __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, const int M, const int T,
                                                          const int nChunks, const int itersPerSplit,
@@ -86,6 +95,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
   constexpr int RA = BM / 32, RB = BN / 32;
   constexpr int STAGE = (BM + BN) * LDS_K;
   constexpr bool AFF = MODE != 0, PER_N = MODE == 2 || MODE == 4, MUL = MODE == 3 || MODE == 4;
+  constexpr bool SPLIT_A = MM == 3 || MM == 4, SPLIT_B = MM == 3, IN16 = MM == 5;      // which operands the loader splits; pair-map input
+  static_assert(!IN16 || MODE == 0, "pre-split activations take no prologue");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -129,7 +140,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
   // pair mode: operand scales (exact powers of two) and this thread's running max of the |activation| bits
   float a_mul = 1.f, w_mul = 1.f, o_mul = 1.f;
   unsigned amax = 0u;
-  if constexpr (MM == 3) {
+  if constexpr (MM >= 3) {
     const int e_in = pair_exp_ptr(p) ? *pair_exp_ptr(p) : 0;
     a_mul = __builtin_ldexpf(1.f, -e_in); w_mul = __builtin_ldexpf(1.f, p.w_exp); o_mul = __builtin_ldexpf(1.f, e_in - p.w_exp);
   }
@@ -160,7 +171,10 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
       for (int k = 0; k < p.kh; ++k) amy[j] |= (unsigned)((unsigned)(ay0 + k) < (unsigned)p.Hi) << k;
       for (int k = 0; k < p.kw; ++k) amx[j] |= (unsigned)((unsigned)(ax0 + k) < (unsigned)p.Wi) << k;
       const int n_in = p.in_image_mod > 0 ? n % p.in_image_mod : n;          // query batches share the input images
-      avoff[j] = (unsigned)((((n_in * p.Di + az0) * p.Hi + ay0) * p.Wi + ax0) * p.ld_in + pad_a + 4 * lseg) << 2;
+      if constexpr (IN16)       // bytes of 16-bit elements: 8 channels per segment, segments 4 .. 7 in the lo plane ld_in / 2 elements on
+        avoff[j] = ((unsigned)((((n_in * p.Di + az0) * p.Hi + ay0) * p.Wi + ax0) * p.ld_in + pad_a + 8 * (lseg & 3)) << 1) + (unsigned)((lseg >> 2) * p.ld_in);
+      else
+        avoff[j] = (unsigned)((((n_in * p.Di + az0) * p.Hi + ay0) * p.Wi + ax0) * p.ld_in + pad_a + 4 * lseg) << 2;
       if constexpr (MUL) {
         const int mg = p.mul_group_images > 0 ? n / p.mul_group_images : 0;    // the image group's own multiplier map
         mvoff[j] = (unsigned)(((mg * p.Hi + ay0) * p.Wi + ax0) * Cin + pad_m + 4 * lseg) << 2;
@@ -175,7 +189,8 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     const int co = n0 + lrow + 32 * j;
     bvoff[j] = co < p.Cout ? (unsigned)(co * T * Cin + 4 * lseg) << 2 : 0x80000000u;
   }
-  const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in) - pad_a, 0, in_bytes, 0x00020000);
+  const auto rs_in = IN16 ? __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<short*>(const_cast<float*>(p.in)) - pad_a, 0, in_bytes, 0x00020000)
+                          : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in) - pad_a, 0, in_bytes, 0x00020000);
   const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.weight), 0, w_bytes, 0x00020000);
   const auto rs_mul = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(MUL ? p.mul - pad_m : p.in), 0, mul_bytes, 0x00020000);
   // channels of the last (partial) chunk that exist for this thread: all of them unless Cin % 32 != 0
@@ -223,7 +238,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     cch = cc * BK + 4 * lseg;
     cv = (cch < Cin) & live;
     cm = live ? (cc == nChunks - 1 ? thr_last : 0xffffffffu) : 0u;
-    toff = live ? (((kz * p.Hi + ky) * p.Wi + kx) * p.ld_in + cc * BK) << 2 : 0;
+    toff = live ? (((kz * p.Hi + ky) * p.Wi + kx) * p.ld_in + cc * BK) << (IN16 ? 1 : 2) : 0;
     moff = live ? ((ky * p.Wi + kx) * Cin + cc * BK) << 2 : 0;
     woff = live ? (((kz * p.kh + ky) * p.kw + kx) * Cin + cc * BK) << 2 : 0;
     if constexpr (AFF && !PER_N) { rsc[s][0] = ldg(gsc, cv ? cch : 0); rsh[s][0] = ldg(gsh, cv ? cch : 0); }
@@ -256,7 +271,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
       b &= va[s][j];
       v = __builtin_bit_cast(f32x4, b);
     }
-    if constexpr (MM == 3) {
+    if constexpr (SPLIT_A) {
       const u32x4 b = __builtin_bit_cast(u32x4, v) & 0x7fffffffu;
       amax = max(amax, max(max(b[0], b[1]), max(b[2], b[3])));
       store_pair(As + (lrow + 32 * j) * LDS_K, lseg, v * a_mul);
@@ -266,7 +281,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
   };
   auto store_b = [&](auto S, float* Bs, int j) {
     constexpr int s = decltype(S)::value;
-    if constexpr (MM == 3) store_pair(Bs + (lrow + 32 * j) * LDS_K, lseg, rb[s][j] * w_mul);
+    if constexpr (SPLIT_B) store_pair(Bs + (lrow + 32 * j) * LDS_K, lseg, rb[s][j] * w_mul);
     else *reinterpret_cast<f32x4*>(Bs + (lrow + 32 * j) * LDS_K + 4 * lseg) = rb[s][j];
   };
 
@@ -310,7 +325,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     constexpr int par = decltype(PAR)::value;
     using SL = std::integral_constant<int, par>;
     using SS = std::integral_constant<int, par ^ 1>;
-    if constexpr (MM == 3) {
+    if constexpr (MM >= 3) {
       // pairs: a K step is 2 * 3 * MT * NT MFMAs of K = 16 on fragments read straight from the two planes; loads first, stores last
 #pragma unroll
       for (int j = 0; j < RA; ++j) load_a(SL{}, j);
@@ -436,7 +451,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
     if (G6D_ABLATE == 6) acc[0][0][0] += dummy[0] + dummy[1] + dummy[2] + dummy[3];
   }
 
-  if constexpr (MM == 3) {
+  if constexpr (SPLIT_A) {
     // range record: the block's largest |activation| (integer max of the IEEE bits: NaN > inf > finite), one atomic per block and only
     // when it exceeds a coherent read of the record.  Every wave passed the K loop's last barrier: the second LDS stage is free, and the
     // epilogue below only touches the head of the first.
@@ -525,7 +540,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_kernel(const G6dConv p, con
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = row_m(wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-        float v = apply_act((MM == 3 ? acc[i][j][r] * o_mul : acc[i][j][r]) + bv, p.out_act);
+        float v = apply_act((MM >= 3 ? acc[i][j][r] * o_mul : acc[i][j][r]) + bv, p.out_act);
         if (row < M && cval) {
           p.out[(size_t)row * p.ld_out + col] = v;
           if (do_stats) {
@@ -588,14 +603,15 @@ int launch_mm(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks
   const long long pad_a = ((long long)(d.pd * d.Hi + d.ph) * d.Wi + d.pw) * d.ld_in, pad_m = (long long)(d.ph * d.Wi + d.pw) * d.Cin;
   const long long n_in = d.in_image_mod > 0 ? d.in_image_mod : d.N;
   const long long n_mul = d.mul_group_images > 0 ? (d.N + d.mul_group_images - 1) / d.mul_group_images : 1;
-  const unsigned in_bytes = (unsigned)((n_in * d.Di * d.Hi * d.Wi * d.ld_in + pad_a) * 4);
+  const unsigned in_bytes = (unsigned)((n_in * d.Di * d.Hi * d.Wi * d.ld_in + pad_a) * (MM == 5 ? 2 : 4));     // 5: ld_in counts 16-bit elements
   const unsigned w_bytes = (unsigned)((long long)d.Cout * T * d.Cin * 4);
   const unsigned mul_bytes = (unsigned)((n_mul * d.Hi * d.Wi * d.Cin + pad_m) * 4);
   G6dConv k = d;
-  if constexpr (MM == 3) {      // the kernel's copy carries the pair mode's device pointers (pair_exp_ptr / pair_rec_ptr)
+  if constexpr (MM >= 3) {      // the kernel's copy carries the pair modes' device pointers (pair_exp_ptr / pair_rec_ptr)
+    const int slot = MM == 5 ? rng.slot_in : rng.slot_out;      // 5 consumes a map its producer scaled and recorded
     k.weight_wino = nullptr;
-    k.weight_wino16 = rng.exps && rng.slot_out >= 0 ? rng.exps + rng.slot_out : nullptr;
-    k.weight_wino43 = rng.rec && rng.slot_out >= 0 ? reinterpret_cast<const float*>(rng.rec + rng.slot_out) : nullptr;
+    k.weight_wino16 = rng.exps && slot >= 0 ? rng.exps + slot : nullptr;
+    k.weight_wino43 = MM != 5 && rng.rec && slot >= 0 ? reinterpret_cast<const float*>(rng.rec + slot) : nullptr;
   }
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, MODE, MM>), grid, dim3(256), lds_bytes, stream, k, M, T, nChunks,
                      ips, total, splits, in_bytes, w_bytes, mul_bytes, pm_hw, pm_tiles, ny);
@@ -613,6 +629,14 @@ int launch_mode(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChun
     // (a table per image group never meets the 128x128 tile: g6d_conv_igemm narrows it to 128x64)
     if constexpr (MODE <= 2 && BN >= 64 && !(BN == 128 && MODE == 2)) return launch_mm<BM, BN, WGM, WGN, MODE, 3>(d, rng, M, T, nChunks, splits, stream);
     g6d_set_error("conv: math_mode 3 (fp16 pairs) has no kernel for this tile / prologue"); return G6D_EINVAL;
+  }
+  if (d.math_mode == 4) {      // pre-split filters: the tiles and prologues of mode 3 (the routed layers: MODE 2 on 64x64 and 128x64)
+    if constexpr (MODE <= 2 && BN >= 64 && !(BN == 128 && MODE == 2)) return launch_mm<BM, BN, WGM, WGN, MODE, 4>(d, rng, M, T, nChunks, splits, stream);
+    g6d_set_error("conv: math_mode 4 (fp16 pairs, pre-split filters) has no kernel for this tile / prologue"); return G6D_EINVAL;
+  }
+  if (d.math_mode == 5) {      // both operands pre-split: no prologue, so one instantiation per tile
+    if constexpr (MODE == 0 && BN >= 64) return launch_mm<BM, BN, WGM, WGN, 0, 5>(d, rng, M, T, nChunks, splits, stream);
+    g6d_set_error("conv: math_mode 5 (fp16 pairs, pre-split operands) has no kernel for this tile / prologue"); return G6D_EINVAL;
   }
   return launch_mm<BM, BN, WGM, WGN, MODE, 0>(d, rng, M, T, nChunks, splits, stream);
 }
@@ -724,7 +748,7 @@ int conv_narrow_launch(const G6dConv& d, hipStream_t stream) {
 // (no launch; bench.py uses it to book the executed FLOPs of a launch in the right roofline family).
 extern "C" int g6d_conv_plan(const G6dConv* desc) {
   if (!desc) return G6D_EINVAL;
-  if (desc->math_mode == 3) return 5;
+  if (desc->math_mode >= 3 && desc->math_mode <= 5) return 5;
   if (conv_narrow_eligible(*desc)) return 4;
   if (g6d_wino43_eligible(*desc)) return 3;
   if (g6d_wino_eligible(*desc)) return 2;
@@ -740,9 +764,23 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
   const G6dRange16 rng = range ? *range : G6dRange16{nullptr, nullptr, -1, -1};
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (!d.in || !d.weight || !d.out) { g6d_set_error("conv: null pointer"); return G6D_EINVAL; }
-  if (d.math_mode < 0 || d.math_mode > 3) { g6d_set_error("conv: math_mode must be 0 (fp32), 1 (bf16), 2 (fp16) or 3 (fp16 pairs)"); return G6D_EINVAL; }
-  const bool pairs = d.math_mode == 3;
+  if (d.math_mode < 0 || d.math_mode > 5) {
+    g6d_set_error("conv: math_mode must be 0 (fp32), 1 (bf16), 2 (fp16), 3 (fp16 pairs), 4 (pairs, pre-split filters) or 5 (pairs, pre-split operands)");
+    return G6D_EINVAL;
+  }
+  const bool pairs = d.math_mode >= 3;
   if (pairs) {
+    if (d.math_mode >= 4 && (d.Cin & 31)) {
+      g6d_set_error("conv: math_mode 4 / 5 (pre-split pairs) need Cin % 32 == 0 (a K step is the hi and the lo plane of 32 channels)"); return G6D_EINVAL;
+    }
+    if (d.math_mode == 5 && (d.in_scale || d.in_shift || d.mul || d.in_relu)) {
+      g6d_set_error("conv: math_mode 5 (pre-split operands) takes no prologue and no multiplier: the producer of the pair map applied them");
+      return G6D_EINVAL;
+    }
+    if (d.math_mode == 5 && ((d.ld_in & 15) || d.ld_in < 2 * d.Cin)) {
+      g6d_set_error("conv: math_mode 5 (pre-split operands) needs ld_in % 16 == 0 and ld_in >= 2 Cin (16-bit elements per pixel, lo plane at ld_in / 2)");
+      return G6D_EINVAL;
+    }
     if (d.weight_wino16) { g6d_set_error("conv: math_mode 3 (fp16 pairs) runs on the implicit-GEMM kernel: weight_wino16 must be NULL"); return G6D_EINVAL; }
     if (d.Cin & 7) { g6d_set_error("conv: math_mode 3 (fp16 pairs) needs Cin % 8 == 0 (a fragment is 8 channels of one plane)"); return G6D_EINVAL; }
     if (d.Cout <= 32) { g6d_set_error("conv: math_mode 3 (fp16 pairs) needs Cout > 32 (no 32-channel tile)"); return G6D_EINVAL; }

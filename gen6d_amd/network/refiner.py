@@ -52,8 +52,13 @@ VOLUME_PAIR_LAYERS = ("mean_embed", "var_embed", "conv0", "conv2")
 # implicit-GEMM kernel's own pair mode (conv_igemm_kernel<., MM = 3>: operands split into fp16 hi / lo pairs in the loader, behind the
 # InstanceNorm affine + ReLU prologue, so no hand-over pass) in the big calls of the fp32 path: "conv1" (32^3 -> 16^3), "conv3"
 # (16^3 -> 8^3), "conv5.0" (8^3 -> 4^3), "conv5.3" (4^3); candidates that lose stay unlisted ("conv4", 8^3, competes with F(2x2,3x3)).
-# Decided per layer at 16 volumes (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md)
-VOLUME_IGEMM_PAIR_LAYERS = ("conv1", "conv3", "conv5.0", "conv5.3")
+# Decided per layer at 16 volumes (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md).  The value is the loader variant
+# (ops.conv(pairs=(table, slot, variant)), G6dConv.math_mode): 3 = both operands split in the loader, 4 = filters pre-split by the weight
+# pack (bit-identical to 3), 5 = activations pre-split as well by ONE affine_split16 pass in front of the launch (the InstanceNorm affine +
+# ReLU leaves the loader).  Per layer the fastest variant that beats the parent's route by more than that route's spread
+# (profiles/r22_igemm_presplit.md).  conv4 stays on F(2x2,3x3): its label there is `wino3x3`, and a listed layer may only gain the
+# `conv16x3 igemm` prefix (tests/test_igemm_pair_routes_gpu.py)
+VOLUME_IGEMM_PAIR_LAYERS = {"conv1": 5, "conv3": 5, "conv5.0": 5, "conv5.3": 5}
 VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
@@ -168,10 +173,11 @@ class VolumeRefiner(ParamBank):
             for name in ("conv0", "conv1", "conv2", "conv3", "conv4"):
                 pk["v_" + name] = self.conv_w(f"volume_net.{name}.0", wino_kd=3 if name in ("conv0", "conv2", "conv4") else 0,
                                               f43=name in VOLUME_F43_LAYERS)
-            # filter exponents of the layers that may run on the implicit-GEMM pair mode: computed here (a device-to-host read of
-            # max |w|), not at their first launch, which may sit inside a graph capture
+            # filter exponents and pre-split packs of the layers that may run on the implicit-GEMM pair modes: computed here (a
+            # device-to-host read of max |w|, an allocation), not at their first launch, which may sit inside a graph capture
             for wb in (pk["v_conv1"], pk["v_conv3"], pk["v_conv4"], pk["v_conv5"][0], pk["v_conv5"][1]):
                 ops.pair_filter_prepare(wb[0])
+                ops.pair_filter_pack(wb[0])
             # fc.0.0 consumes x.flatten(1) of [512,4,4,4] (index c*64+v); our code is [v][c] -> permute once
             w = self.p("regressor.fc.0.0.weight")
             pk["fc0"] = (w.reshape(512, 512, 64).permute(0, 2, 1).reshape(512, 32768).contiguous(),
@@ -338,7 +344,8 @@ class VolumeRefiner(ParamBank):
             # big calls of the fp32 path (the condition of volume_pair_route): a listed layer on the implicit-GEMM kernel's pair mode
             # (_pair_rng: None with fp32_cores, during a fallback recompute and inside a 16-bit part)
             r = self._pair_rng() if (qn >= F43_MIN_QUERIES and name in VOLUME_IGEMM_PAIR_LAYERS) else None
-            route = {"pairs": (r, r.slot(f"volume.{name}.igemm"))} if r is not None else \
+            variant = VOLUME_IGEMM_PAIR_LAYERS[name] if (r is not None and isinstance(VOLUME_IGEMM_PAIR_LAYERS, dict)) else 3     # a plain list of names: 3
+            route = {"pairs": (r, r.slot(f"volume.{name}.igemm"), variant)} if r is not None else \
                 {"w_wino": getattr(wb, "u", None) if stride == 1 else None,
                  "w_wino43": getattr(wb, "u43", None) if (stride == 1 and qn >= F43_MIN_QUERIES) else None}
             return ops.conv(x, wb[0], wb[1], out, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh,

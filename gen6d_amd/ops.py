@@ -161,9 +161,49 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
     pairs = (RangeTable, slot): the fp32 path's pair mode of the implicit-GEMM kernel itself (G6dConv.math_mode 3, g6d_conv_igemm_ex) — the
     loader splits both operands into fp16 hi / lo pairs after the prologue, fp32-class results on the 16-bit matrix cores; the activations
     carry the slot's exponent and their largest |value| is recorded in it; the filter exponent (pair_filter_exponent) is cached on `w`.
-    No Winograd / patch hand-off.  A reduced-precision MATH_MODE keeps precedence: pairs is then ignored."""
-    _need_gpu(x, w, out)
-    Nx, Di, Hi, Wi, Cin, ld_in = _cl5(x, "conv.x")
+    No Winograd / patch hand-off.  A reduced-precision MATH_MODE keeps precedence: pairs is then ignored.
+    pairs = (RangeTable, slot, variant) names the loader (G6dConv.math_mode): 3 (the default) as above; 4 = the filters come pre-split
+    from pair_filter_pack(w) (cached on `w`), bit-identical to 3; 5 = the activations come pre-split as well: the prologue (or, without
+    one, the bare split) runs ONCE as the hand-over pass affine_split16 — the volume's planes as images, one table per per_n * Di planes,
+    under the layer's own slot, so exponent and record stay where variant 3 keeps them — and the launch copies both operands (booked
+    under the label of variant 3, the pass with the HBM kernels).  x may also be a PairMap [N,Di,Hi,Wi,2,Cin] (a channel slice of a
+    wider dense map included) some producer wrote: variant 5 without a pass, the exponent read from the map's slot."""
+    variant = 3
+    if pairs is not None and len(pairs) == 3:
+        pairs, variant = pairs[:2], int(pairs[2])
+        if variant not in (3, 4, 5):
+            raise ValueError("conv: pairs variant must be 3, 4 or 5")
+    if MATH_MODE:
+        pairs = None
+    x16 = None
+    if isinstance(x, PairMap):
+        if pairs is None or mul is not None or in_scale is not None or in_mod:
+            raise ValueError("conv: a PairMap input needs pairs=... and takes no prologue, multiplier or in_mod")
+        if x.table is not pairs[0]:
+            raise ValueError("pair input and output belong to different range tables")
+        x16, variant = x, 5
+    elif pairs is not None and variant == 5:
+        if mul is not None or in_mod:
+            raise ValueError("conv: pairs variant 5 takes no multiplier and no in_mod")
+        _need_gpu(x)
+        n5, d5, h5, w5, c5, _ = _cl5(x, "conv.x")
+        x16 = affine_split16(x.view(n5 * d5, 1, h5, w5, c5), in_scale, in_shift, int(per_n) * d5 if in_scale is not None else 0,
+                             in_relu and in_scale is not None, False, 3, rng=pairs).view(n5, d5, h5, w5, 2, c5)
+    label_aff = in_scale is not None            # the layer's label names its affine whichever launch applies it
+    if x16 is not None:
+        x, slot_in = x16.data, x16.slot
+        _need_gpu(x, w, out)
+        st = x.stride()
+        # per pixel the hi plane, then the lo plane ld_in / 2 elements on (the dense map's 2 C, or the wider map a channel slice lives in)
+        if x.dim() != 6 or x.dtype != torch.float16 or x.shape[4] != 2 or st[5] != 1 or 2 * st[4] != st[3] or st[2] != x.shape[3] * st[3] or \
+                st[1] != x.shape[2] * st[2] or st[0] != x.shape[1] * st[1]:
+            raise ValueError("conv.x: a pair map [N,Di,Hi,Wi,2,Cin] fp16 with dense pixels and the lo plane half a pixel row on expected")
+        (Nx, Di, Hi, Wi, _, Cin), ld_in = x.shape, st[3]
+        in_scale = in_shift = None
+        in_relu, per_n = False, 0
+    else:
+        _need_gpu(x, w, out)
+        Nx, Di, Hi, Wi, Cin, ld_in = _cl5(x, "conv.x")
     No, Do, Ho, Wo, Cout, ld_out = _cl5(out, "conv.out")
     N = No if in_mod else Nx
     if in_mod and Nx != in_mod:
@@ -185,14 +225,17 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         raise ValueError(f"conv.w_wino: expected contiguous {(kd * (Cin // 8), 16, Cout, 8)}, got {tuple(w_wino.shape)}")
     if w_wino43 is not None and (tuple(w_wino43.shape) != w43_shape(kd * (Cin // 8), Cout) or not w_wino43.is_contiguous()):
         raise ValueError(f"conv.w_wino43: expected contiguous {w43_shape(kd * (Cin // 8), Cout)}, got {tuple(w_wino43.shape)}")
-    if MATH_MODE:
-        pairs = None
     u16 = None
+    w_dev = w
     if pairs is not None:
         w_wino = w_wino43 = None
-        # (the networks prepare the exponent when they pack their weights; a weight that was not prepared pays a device-to-host read
-        # of max |w| here, once — which a stream capture does not allow)
+        # (the networks prepare the exponent — and the pre-split pack of variants 4 / 5 — when they pack their weights; a weight that was
+        # not prepared pays a device-to-host read of max |w| here, once — which a stream capture does not allow)
         w_exp = pair_filter_prepare(w)
+        if variant >= 4:
+            if Cin % 32:
+                raise ValueError("conv: pairs variants 4 / 5 need Cin % 32 == 0")
+            w_dev = pair_filter_pack(w)
     if MATH_MODE and w_wino is not None and Cin % 16 == 0 and Cout % 64 == 0:
         # reduced-precision mode: the layer's Winograd filters rounded to the operand type, built once per (layer, type) and kept
         # on the fp32 filter tensor (a new weight pack drops both)
@@ -206,12 +249,12 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         in_=x.data_ptr(), mul=mul.data_ptr() if mul is not None else None,
         in_scale=in_scale.data_ptr() if in_scale is not None else None,
         in_shift=in_shift.data_ptr() if in_shift is not None else None,
-        weight=w.data_ptr(), bias=bias.data_ptr() if bias is not None else None, out=out.data_ptr(),
+        weight=w_dev.data_ptr(), bias=bias.data_ptr() if bias is not None else None, out=out.data_ptr(),
         stats=stats.data_ptr() if stats is not None else None, workspace=ws.data_ptr(), workspace_bytes=ws.numel() * 4,
         N=N, Di=Di, Hi=Hi, Wi=Wi, Cin=Cin, ld_in=ld_in, Do=Do, Ho=Ho, Wo=Wo, Cout=Cout, ld_out=ld_out,
         kd=kd, kh=kh, kw=kw, sd=stride[0], sh=stride[1], sw=stride[2], pd=pad[0], ph=pad[1], pw=pad[2],
         in_relu=int(in_relu), in_affine_per_n=int(per_n), out_act=int(out_act),
-        stat_rows_per_group=int(rows_per_group), split_k=int(split_k), math_mode=3 if pairs is not None else int(MATH_MODE),
+        stat_rows_per_group=int(rows_per_group), split_k=int(split_k), math_mode=variant if pairs is not None else int(MATH_MODE),
         w_exp=int(w_exp) if pairs is not None else 0,
         weight_wino=w_wino.data_ptr() if w_wino is not None else None, in_image_mod=int(in_mod), mul_group_images=int(mul_group),
         weight_wino16=u16.data_ptr() if u16 is not None else None,
@@ -236,11 +279,11 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         else:
             PROFILE.append((fl / 4 if fam == 3 else (fl / 2.25 if fam == 2 else fl), e0, e1,      # Winograd kernels: FLOPs executed in the transform domain
                         ("wino3x3 F43 " if fam == 3 else "wino3x3 " if fam == 2 else "conv16x3 igemm " if fam == 5 else "") + f"conv N={N} in={Di}x{Hi}x{Wi}x{Cin} out={Do}x{Ho}x{Wo}x{Cout} k={kd}x{kh}x{kw} s={stride[0]}{stride[1]}{stride[2]}"
-                        f"{' mul' if mul is not None else ''}{' aff' if in_scale is not None else ''}{' stats' if stats is not None else ''}",
+                        f"{' mul' if mul is not None else ''}{' aff' if label_aff else ''}{' stats' if stats is not None else ''}",
                         # algorithmic bytes: every operand once (input images, multiplier maps, filters, output)
                         4.0 * ((in_mod or N) * Di * Hi * Wi * Cin + (mul.numel() if mul is not None else 0) + w.numel() + N * Do * Ho * Wo * Cout), fl))
     if pairs is not None:
-        ra = C.byref(pairs[0].arg(-1, pairs[1]))
+        ra = C.byref(pairs[0].arg(slot_in, -1) if variant == 5 else pairs[0].arg(-1, pairs[1]))
         _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm_ex(C.byref(d), ra, _stream()), "g6d_conv_igemm_ex"), book)
     else:
         _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm(C.byref(d), _stream()), "g6d_conv_igemm"), book)
@@ -779,6 +822,25 @@ def pair_filter_prepare(w):
     if e is None:
         e = w.__dict__["_g6d_w_exp"] = pair_filter_exponent(w)
     return e
+
+
+def pair_filter_pack(w):
+    """The filters of ops.conv's pairs variants 4 / 5 (G6dConv.math_mode 4 / 5), built once and cached on the weight tensor beside its
+    exponent: [Cout, taps, Cin] fp32 -> [Cout, taps, Cin / 32, 2, 32] fp16, per 32-channel chunk the hi halves of w * 2^w_exp, then the lo
+    halves (the split of _split_hi_lo with the exponent of pair_filter_prepare) — a chunk fills the 128 bytes its fp32 values do, so the
+    kernel's loader keeps the fp32 addresses.  Call it where the weights are packed: no launch path may synchronise or allocate."""
+    e = pair_filter_prepare(w)
+    e_pk, pk = w.__dict__.get("_g6d_w_pairs", (None, None))
+    if e_pk != e:                 # (the pack carries the exponent it was split with: the descriptor's w_exp must be that one)
+        co, taps, ci = w.shape
+        if ci % 32:
+            raise ValueError("pair_filter_pack: Cin % 32 == 0 expected")
+        u = w.double() * 2.0 ** e
+        hi = u.to(torch.float16)
+        lo = (u - hi.double()).to(torch.float16)
+        pk = torch.stack([hi.view(co, taps, ci // 32, 32), lo.view(co, taps, ci // 32, 32)], 3).contiguous()
+        w.__dict__["_g6d_w_pairs"] = (e, pk)
+    return pk
 
 
 def _split_hi_lo(w_taps):

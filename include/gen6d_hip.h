@@ -104,7 +104,18 @@ typedef struct G6dConv {
                                    v_mfma_f32_32x32x16_f16 per product (hi x hi + hi x lo + lo x hi).  Always the implicit-GEMM kernel
                                    (no Winograd / patch / narrow hand-off; weight_wino16 must be NULL), strided, 3-D, split-K and 1x1
                                    layers included; Cin % 8 == 0, Cout > 32, no `mul`.  Filters are split as weight * 2^w_exp, activations
-                                   as x * 2^-e with e and the range record from g6d_conv_igemm_ex's G6dRange16 */
+                                   as x * 2^-e with e and the range record from g6d_conv_igemm_ex's G6dRange16;
+                                   4 = mode 3 with PRE-SPLIT FILTERS (additive to ABI v12: values above 3 were rejected): `weight` points at
+                                   [Cout][taps][Cin / 32][2][32] fp16 — per 32-channel chunk the 32 hi halves rn16(u), then the 32 lo halves
+                                   rn16(u - hi), u = w * 2^w_exp: the bytes the chunk's fp32 values would occupy — and the loader copies them;
+                                   activations, prologue, exponent and record as in 3; bit-identical to 3.  Cin % 32 == 0;
+                                   5 = mode 4 with PRE-SPLIT ACTIVATIONS as well: `in` points at a pair map in the format of
+                                   g6d_conv16_direct_multi's math_mode 3 and g6d_affine_split16 — [N][Di][Hi][Wi] pixels of ld_in 16-bit
+                                   elements, a pixel's hi plane of Cin values at its start and its lo plane ld_in / 2 elements further on
+                                   (dense: ld_in = 2 Cin; a channel slice of a wider dense map: that map's row, `in` at the slice's first hi
+                                   value); ld_in % 16 == 0, ld_in >= 2 Cin, Cin % 32 == 0.  No prologue and no multiplier (in_scale,
+                                   in_shift, in_relu, mul must be unset: the map's producer applied them); the map holds x * 2^-e with
+                                   e = exps[slot_in] of g6d_conv_igemm_ex's G6dRange16, and the launch records nothing */
   const float* weight_wino;     /* optional: the same filters transformed for Winograd F(2x2,3x3), [kd][Cin/8][16][Cout][8] in the
                                    layout of g6d_wino_conv3x3 (per depth tap for 3x3x3).  When set and the layer is eligible
                                    (stride 1, "same" padding, maps >= 6x6, Cin % 8 == 0, Cout % 32 == 0, fp32), the launch runs on
@@ -150,15 +161,16 @@ int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream);
    a non-NULL range with another math_mode is G6D_EINVAL): the kernel is producer and consumer of its operand pairs, so ONE slot serves —
    the loader splits x * 2^-exps[slot_out] (x after the multiplier / affine / ReLU prologue; padding stays exactly zero), folds
    2^exps[slot_out] back into the accumulator scale, and records the largest |x| in rec[slot_out] (at most one atomicMax per block, only
-   when it exceeds a coherent read of the record).  slot_in is not read.
-   Implementation note: the kernel takes the descriptor by value, and in math_mode 3 the launcher's private COPY of it carries the two
+   when it exceeds a coherent read of the record).  slot_in is not read.  math_mode 4: the same.  math_mode 5 is a consumer only: it
+   reads the exponent of its pair map from exps[slot_in] (< 0: exponent 0), writes no record and does not read slot_out.
+   Implementation note: the kernel takes the descriptor by value, and in math_mode 3 - 5 the launcher's private COPY of it carries the two
    device pointers &exps[slot_out] and &rec[slot_out] in `weight_wino16` / `weight_wino43`, fields this kernel never reads as filters (that
    keeps one kernel signature and the other modes' code unchanged).  The caller's descriptor is not modified, and a caller's own values in
-   those two fields are not forwarded in math_mode 3 (weight_wino16 must be NULL, weight_wino43 is ignored). */
+   those two fields are not forwarded in math_mode 3 - 5 (weight_wino16 must be NULL, weight_wino43 is ignored). */
 struct G6dRange16;
 int g6d_conv_igemm_ex(const G6dConv* desc, const struct G6dRange16* range, g6d_stream_t stream);
 /* Kernel family g6d_conv_igemm will run `desc` on (no launch): 0 generic implicit GEMM, 1 LDS-patch kernel, 2 Winograd F(2x2,3x3) kernel,
-   3 Winograd F(4x4,3x3) kernel, 4 narrow-output kernel, 5 implicit GEMM on fp16 hi / lo pairs (math_mode 3) */
+   3 Winograd F(4x4,3x3) kernel, 4 narrow-output kernel, 5 implicit GEMM on fp16 hi / lo pairs (math_mode 3, 4, 5) */
 int g6d_conv_plan(const G6dConv* desc);
 /* sizeof(G6dConv) as compiled into the library: bindings check their struct layout against it */
 int g6d_sizeof_conv_desc(void);

@@ -4,7 +4,12 @@ hi / lo pair mode (conv_igemm_kernel<., MM = 3>, ops.conv(pairs=...)), at the be
     python tools/igemm_pair_layers.py [volumes / queries = 16]
 us per launch, the best of three rounds of 10, with direct-form TFLOP/s.  The table decides refiner.VOLUME_IGEMM_PAIR_LAYERS and
 selector.SELECTOR_IGEMM_PAIR_LAYERS (profiles/r18_igemm_pairs.md): a layer is listed only where it is faster at 16; run it with 1 for
-the single-query times (recorded, not routed on)."""
+the single-query times (recorded, not routed on).
+The five volume layers get a second table: the pair mode's three loader variants (ops.conv(pairs=(table, slot, variant))) — 3 splits both
+operands in the loader, 4 copies filters the weight pack split, 5 copies both operands behind ONE affine_split16 pass, whose time is
+included — each with the spread (max - min) of its three rounds.  A layer takes the fastest variant that beats its current route (the
+one refiner.VOLUME_IGEMM_PAIR_LAYERS names, else the fp32-core route) by more than the spread of the current route's rounds
+(profiles/r22_igemm_presplit.md)."""
 import os
 import sys
 
@@ -21,6 +26,20 @@ from featnet_layers import timed                                # noqa: E402
 _K3, _P3 = (3, 3, 3), (1, 1, 1)
 
 
+def timed3(fn, reps=10):
+    """featnet_layers.timed with the spread: (best, max - min) of three rounds of `reps` launches, us per launch."""
+    fn(); fn(); torch.cuda.synchronize()
+    t = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1) / reps * 1e3)
+    return min(t), max(t) - min(t)
+
+
 def main():
     lib.load()
     qn = int(sys.argv[1]) if len(sys.argv) > 1 else 16
@@ -34,6 +53,8 @@ def main():
     table = ops.RangeTable(dev)
     print(f"# {qn} volumes / queries: us per launch (best of 3 rounds of 10), direct-form TFLOP/s")
     print("| layer | shape | fp32-core route | us | TFLOP/s | pair route | us | TFLOP/s | |\n|---|---|---|---|---|---|---|---|---|")
+
+    variants = []            # (name, {route: (us, spread)}) of the volume layers, printed as the second table
 
     def row(name, shape, on, of, nf, fl):
         to, tn = timed(of), timed(nf)
@@ -52,13 +73,31 @@ def main():
         st = ops.new_stats(qn, co, dev) if stats else None
 
         def launch(pairs, layer=layer, x=x, y=y, sc=sc, sh=sh, st=st, stride=stride, so=so):
-            kw = {"pairs": (table, table.slot(name))} if pairs else {"w_wino": getattr(layer, "u", None) if stride == 1 else None}
+            kw = {"pairs": (table, table.slot(name), int(pairs))} if pairs else {"w_wino": getattr(layer, "u", None) if stride == 1 else None}
             ops.conv(x, layer[0], layer[1], y, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh, in_relu=True, per_n=pn, stats=st,
                      rows_per_group=pn * so ** 3 if st is not None else 0, finalize=so ** 3 if st is not None else None, **kw)
         fl = 2.0 * qn * so ** 3 * co * 27 * ci
         old = "F(2x2,3x3)" if (stride == 1 and getattr(layer, "u", None) is not None) else "conv_igemm fp32"
-        row(name, f"{s}^3 -> {so}^3, {ci} -> {co}, s{stride}, aff{' stats' if stats else ''}", old, lambda: launch(False), lambda: launch(True), fl)
+        row(name, f"{s}^3 -> {so}^3, {ci} -> {co}, s{stride}, aff{' stats' if stats else ''}", old, lambda: launch(False), lambda: launch(3), fl)
+        ops.pair_filter_pack(layer[0])
+        variants.append((name, old, {r: timed3(lambda r=r: launch(r)) for r in (0, 3, 4, 5)}))
         del x, y
+
+    from gen6d_amd.network.refiner import VOLUME_IGEMM_PAIR_LAYERS as routed
+    print(f"\n# {qn} volumes: loader variants of the pair mode, us per launch (best of 3 rounds of 10) +- spread (max - min of the rounds); "
+          "variant 5 includes its affine_split16 pass")
+    print("| layer | fp32-core route | us | pairs 3 (split in the loader) | pairs 4 (filters pre-split) | pairs 5 (both pre-split, + pass) | "
+          "current route | decision |\n|---|---|---|---|---|---|---|---|")
+    total = {"current": 0.0, "chosen": 0.0}
+    for name, old, t in variants:
+        cur = (routed[name] if isinstance(routed, dict) else 3) if name in routed else 0
+        best = min((4, 5, 3, 0), key=lambda r: t[r][0])
+        take = best if (best != cur and t[cur][0] - t[best][0] > t[cur][1]) else cur
+        total["current"] += t[cur][0]; total["chosen"] += t[take][0]
+        label = {0: old, 3: "pairs 3", 4: "pairs 4", 5: "pairs 5"}
+        print(f"| {name} | {old} | {t[0][0]:.1f} +- {t[0][1]:.1f} | {t[3][0]:.1f} +- {t[3][1]:.1f} | {t[4][0]:.1f} +- {t[4][1]:.1f} | "
+              f"{t[5][0]:.1f} +- {t[5][1]:.1f} | {label[cur]} | {'stays on ' + label[cur] if take == cur else label[take] + f' ({t[cur][0] / t[take][0]:.2f}x)'} |")
+    print(f"\nsum of the five layers: current routes {total['current']:.1f} us, table's choice {total['chosen']:.1f} us", flush=True)
 
     # the selector: fuse0, a 1x1 conv 768 -> 512 over qn * D hypothesis maps of 4x4 with per-query sums and the fused finalize; sp0 (516 ->
     # 512 over qn * D rows) as a candidate of the tail
