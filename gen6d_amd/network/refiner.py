@@ -5,15 +5,20 @@ One refinement step (reference forward, refiner.py:249-269):
     RefineFeatureNet 2-D convs on g6d_conv_igemm; every InstanceNorm2d is a per-image (sum, sumsq) epilogue of the
         producing conv and an affine(+ReLU) in the loader of the consuming conv / up-sampler      refiner.py:24-51,64-78
         (batched calls of the fp32 path: on fp16 hi / lo pairs, g6d_conv16_direct_multi with g6d_l2norm_split16, g6d_affine_split16 and
-        the slice producers g6d_affine_split16_to / g6d_upsample_bilinear_split16 as hand-over passes — FEATNET_PAIR_BRANCHES)
+        the slice producers g6d_affine_split16_to / g6d_upsample_bilinear_split16 as hand-over passes — the "pair" entries of ROUTES)
     g6d_refiner_volume: projection + bilinear sampling + mean/std over references, fused            refiner.py:183-247
     RefineVolumeEncodingNet 3x3x3 convs on g6d_conv_igemm (32^3 layers: Winograd F(4x4,3x3), depth taps folded into the reduction;
-        16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K — in batched calls of the fp32 path the layers of
-        VOLUME_IGEMM_PAIR_LAYERS in that kernel's own fp16 hi / lo pair mode)
-        (batched calls of the fp32 path: the 32^3 layers of VOLUME_PAIR_LAYERS on fp16 hi / lo pairs, g6d_conv16_direct_multi with
+        16^3: F(2x2,3x3); 8^3/4^3 and stride-2 layers: implicit 3-D GEMM with split-K — in batched calls of the fp32 path the "igemmV"
+        entries of ROUTES in that kernel's own fp16 hi / lo pair mode)
+        (batched calls of the fp32 path: the "pair" entries of ROUTES on fp16 hi / lo pairs, g6d_conv16_direct_multi with
         depth-folded filters; g6d_refiner_volume_kp_pairs writes their input volumes as pairs)
+Both nets are ONE layer table each (FEATNET, VOLUME) walked by _run_net; which kernel a layer takes in the big calls of the fp32 path is
+ONE table (ROUTES), resolved per call by resolve_routes.
     g6d_linear_gemv_batch: the 32768->512 FC is a 67 MB weight stream, read once per 8 queries                                    refiner.py:153-166
 """
+import itertools
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -24,45 +29,149 @@ from .operator import pose_apply_th
 from .params import ParamBank, fold_vgg
 
 # Winograd F(4x4,3x3) (csrc/wino43_conv.hip) for the crops' VGG trunk (1.31-1.35x over F(2x2,3x3) at 56 crops, profiles/r04_w43_bench_v5.md;
-# on the fp32 path the trunk then runs on fp16 hi / lo pairs, backbone.trunk_route), the feature-net layers of FEATNET_F43_LAYERS and the
-# stride-1 3x3x3 layers of the volume net: the two embed pairs and VOLUME_F43_LAYERS of conv0 (32^3), conv2 (16^3), conv4 (8^3).
+# on the fp32 path the trunk then runs on fp16 hi / lo pairs, backbone.trunk_route) and the layers that list "f43" in ROUTES.
 # All of it pays from ~4 queries per launch on: one query's 7 crops / single volume leave most CUs without a block and the kernel's longer
 # per-block prologue / epilogue shows (measured per step at batch 1: crops' trunk 475 vs 320 us, volume layers 541 vs 418 us on
 # F(2x2,3x3); at batch 8: 1.06 vs 1.43 ms and 1.96 vs 3.06 ms the other way round)
 F43_MIN_QUERIES = 4
-# feature-net layers (name, index in the Sequential) that carry F(4x4,3x3) filters — measured per layer at 56 crops against F(2x2,3x3)
-# (profiles/r04_layer_table_featnet_f43.md): 512->256 @16x16 159 vs 173 us, 192->128 @32x32 119 vs 148, 128->128 @32x32 107 vs 129 kept;
-# 256->64 @32x32 131 vs 94, 256->64 @16x16 88 vs 60, 512->256 @8x8 108 vs 80 stay on F(2x2,3x3)
-FEATNET_F43_LAYERS = {("conv1", 0), ("conv_out", 0), ("conv_out", 3)}
-# feature-net branches (two 3x3 layers each) that run on the fp16 hi / lo pair kernel (conv16w_kernel<3,.>, fp32-class products on the
-# 16-bit matrix cores) in the big calls of the fp32 path — decided per branch at 112 crops against the routes above, hand-over passes
-# included (tools/featnet_layers.py, profiles/r16_featnet_pairs.md).  A branch that is not listed keeps its route; run_feature_net joins
-# either kind (the branch ends write fp32 or pair slices of `cat` from the same fp32 map + affine)
-FEATNET_PAIR_BRANCHES = ("conv0", "conv1", "conv2", "conv_out")
-# stride-1 layers of the volume net's 32^3 stage that run on the pair kernel with their depth taps folded into the reduction
-# (conv16w_kernel<3, ., 1, 3>, filter layout 2) in the big calls of the fp32 path: "mean_embed" / "var_embed" = the embed's two layers with
-# the InstanceNorm + ReLU pass between them written as pairs, "conv0" = the 128 -> 64 layer behind them (its input then is ONE 128-channel
-# pair map the two embeds fill slice by slice).  The two input volumes are then written as pairs by g6d_refiner_volume_kp_pairs and never
-# exist in fp32, so both embeds go together.  "conv2" = the 128 -> 128 layer at 16^3 on the same kernel (conv1's InstanceNorm affine + ReLU,
-# which F(2x2,3x3) applies in its operand prologue, becomes the pass that writes its pairs).  Decided per layer at 16 volumes with the
-# hand-over passes included (tools/volume_layers.py, profiles/r17_volume_pairs.md: embeds 1675 -> 1308 and 1093 -> 833 us, conv0 642 -> 512,
-# conv2 294 -> 128); a layer that is not listed keeps its route
-VOLUME_PAIR_LAYERS = ("mean_embed", "var_embed", "conv0", "conv2")
-# layers of the volume net the halo-patch kernel cannot express — stride 2, or maps small enough to need split-K — that run on the
-# implicit-GEMM kernel's own pair mode (conv_igemm_kernel<., MM = 3>: operands split into fp16 hi / lo pairs in the loader, behind the
-# InstanceNorm affine + ReLU prologue, so no hand-over pass) in the big calls of the fp32 path: "conv1" (32^3 -> 16^3), "conv3"
-# (16^3 -> 8^3), "conv5.0" (8^3 -> 4^3), "conv5.3" (4^3); candidates that lose stay unlisted ("conv4", 8^3, competes with F(2x2,3x3)).
-# Decided per layer at 16 volumes (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md).  The value is the loader variant
-# (ops.conv(pairs=(table, slot, variant)), G6dConv.math_mode): 3 = both operands split in the loader, 4 = filters pre-split by the weight
-# pack (bit-identical to 3), 5 = activations pre-split as well by ONE affine_split16 pass in front of the launch (the InstanceNorm affine +
-# ReLU leaves the loader).  Per layer the fastest variant that beats the parent's route by more than that route's spread
-# (profiles/r22_igemm_presplit.md).  conv4 stays on F(2x2,3x3): its label there is `wino3x3`, and a listed layer may only gain the
-# `conv16x3 igemm` prefix (tests/test_igemm_pair_routes_gpu.py)
-VOLUME_IGEMM_PAIR_LAYERS = {"conv1": 5, "conv3": 5, "conv5.0": 5, "conv5.3": 5}
-VOLUME_F43_LAYERS = ("conv0",)          # measured per batch of 8: conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94 us on F(2x2,3x3): only 32^3 pays
 MAX_BATCH = 32         # queries that share one set of launches (g6d_linear_gemv_batch: 8 right-hand sides per weight pass)
-_K3, _P3 = (3, 3, 3), (1, 1, 1)
-_K2, _P2 = (1, 3, 3), (0, 1, 1)
+
+
+class Layer(NamedTuple):
+    """One 3x3 / 3x3x3 layer of the refiner, declared once: _pack, the route plan, the run functions and the per-layer tools
+    (tools/*_layers.py) read names and shapes from here.  `key` also names the layer in ROUTES and prefixes its range slots."""
+    key: str
+    weights: str             # its prefix in the state dict; the packed filters sit under `key` in _pack()
+    cin: int
+    cout: int
+    stride: int
+    div: int                 # its input map's edge: the call's size // div
+    norm: bool               # an InstanceNorm follows: statistics in the epilogue + finalize, handed on as an affine
+    part: str                # the part of _mm it belongs to
+    src: str = None          # the named map it reads (an input volume, a trunk tap, `cat`; also that map's range slot); None: the layer before it
+    dst: tuple = None        # a branch's last layer: (channel offset in `cat`, up-sampling factor)
+
+    # depth taps: the feature net's layers are (1,3,3), the volume net's (3,3,3)
+    kd = property(lambda self: 1 if self.part == "featnet" else 3)
+    # packs F(2x2,3x3) filters (the 8^3 -> 4^3 tail never runs on the Winograd kernel)
+    wino = property(lambda self: self.stride == 1 and self.part != "tail")
+    # what the halo-patch kernel cannot express (stride 2, or maps small enough to need split-K): a candidate of the implicit-GEMM pair mode
+    igemm = property(lambda self: self.kd == 3 and (self.stride == 2 or self.div >= 4))
+    # range slot of the hand-over pass in front of it (names pinned by range_report's readers)
+    pass_slot = property(lambda self: self.key[:-2] + ".mid" if self.key.endswith(".3") else self.key + ".in")
+
+    def edge(self, size, out=False):
+        """Its input (out: output) map's extents for a call of `size` ((h, w) crops, (sn, sn, sn) volumes)."""
+        return tuple(s // (self.div * (self.stride if out else 1)) for s in size)
+
+
+class Net(NamedTuple):
+    name: str
+    layers: tuple
+    together: bool           # the layers that list "pair" take the pair kernel together or not at all (see resolve_routes)
+    align: int               # the pair routes need crop sizes that are multiples of it
+
+    def layer(self, key):
+        return next(L for L in self.layers if L.key == key)
+
+    def reader(self, src):
+        return next(L for L in self.layers if L.src == src)
+
+    def chains(self):
+        """The layers in runs that start at a named map: the branches that end in `cat`, then the chain that reads it."""
+        out = []
+        for L in self.layers:
+            if L.src:
+                out.append([])
+            out[-1].append(L)
+        return out
+
+
+def _branch(net, name, cin, cmid, cout, div, part, src, dst=None):
+    """A conv, IN, ReLU, conv branch (the Sequential's layers 0 and 3); a join into `cat` takes the second layer's own InstanceNorm along."""
+    tree = "feature_net" if net == "featnet" else "volume_net"
+    return (Layer(f"{net}.{name}.0", f"{tree}.{name}.0", cin, cmid, 1, div, True, part, src=f"{net}.{src}"),
+            Layer(f"{net}.{name}.3", f"{tree}.{name}.3", cmid, cout, 1, div, net == "featnet", part, dst=dst))
+
+
+def _stack(name, cin, cout, stride, div, part="stack", norm=True, src=None):
+    return Layer(f"volume.{name}", f"volume_net.{name if '.' in name else name + '.0'}", cin, cout, stride, div, norm, part, src=src)
+
+
+FEATNET = Net("featnet", (*_branch("featnet", "conv0", 256, 64, 64, 4, "featnet", "f3", (0, 1)),
+                          *_branch("featnet", "conv1", 512, 256, 64, 8, "featnet", "f5", (64, 2)),
+                          *_branch("featnet", "conv2", 512, 256, 64, 16, "featnet", "f7", (128, 4)),
+                          *_branch("featnet", "conv_out", 192, 128, 128, 4, "featnet", "cat")), together=False, align=16)
+VOLUME = Net("volume", (*_branch("volume", "mean_embed", 256, 64, 64, 1, "embed", "mean_in", (0, 1)),
+                        *_branch("volume", "var_embed", 128, 64, 64, 1, "embed", "std", (64, 1)),
+                        _stack("conv0", 128, 64, 1, 1, src="volume.cat"), _stack("conv1", 64, 128, 2, 1), _stack("conv2", 128, 128, 1, 2),
+                        _stack("conv3", 128, 256, 2, 2), _stack("conv4", 256, 256, 1, 4), _stack("conv5.0", 256, 512, 2, 4, "tail"),
+                        _stack("conv5.3", 512, 512, 1, 8, "tail", norm=False)), together=True, align=1)
+
+# layer -> its routes in the big calls (from F43_MIN_QUERIES queries) of the fp32 path, in order of preference; resolve_routes turns
+# them into the route each layer takes in one call.  A layer that lists none keeps the fp32 cores' F(2x2,3x3) / implicit GEMM.
+#   "pair"    the fp16 hi / lo pair kernel (conv16w_kernel<3,.>: fp32-class products on the 16-bit matrix cores; 3x3x3 layers with their
+#             depth taps folded into the reduction, filter layout 2), its input handed over as a PairMap.  Feature net: per branch at
+#             112 crops, hand-over passes included, all four faster (tools/featnet_layers.py, profiles/r16_featnet_pairs.md).  Volume
+#             net: per layer at 16 volumes (tools/volume_layers.py, profiles/r17_volume_pairs.md): embeds 1675 -> 1308 and 1093 -> 833 us,
+#             conv0 642 -> 512, conv2 294 -> 128
+#   "igemmV"  the implicit-GEMM kernel's own pair mode with loader variant V (ops.conv(pairs=(table, slot, V))): 3 = both operands split
+#             in the loader, 4 = filters pre-split by the weight pack (bit-identical to 3), 5 = activations pre-split as well by one
+#             affine_split16 pass.  Per layer at 16 volumes the fastest variant that beats the layer's route by more than that route's
+#             spread (tools/igemm_pair_layers.py, profiles/r18_igemm_pairs.md, profiles/r22_igemm_presplit.md).  conv4 (8^3) competes
+#             with F(2x2,3x3) and stays there: a listed layer's label may only gain the `conv16x3 igemm` prefix
+#             (tests/test_igemm_pair_routes_gpu.py)
+#   "f43"     packs F(4x4,3x3) filters: the fp32 cores' kernel of the big calls that are not on pairs.  Feature net per layer at 56 crops
+#             against F(2x2,3x3) (profiles/r04_layer_table_featnet_f43.md): 512->256 @16x16 159 vs 173 us, 192->128 @32x32 119 vs 148,
+#             128->128 @32x32 107 vs 129 kept; 256->64 @32x32 131 vs 94, 256->64 @16x16 88 vs 60, 512->256 @8x8 108 vs 80 not.  Volume net:
+#             the 32^3 layers 1.4-1.5x (profiles/r04_w43_bench_v5.md); per batch of 8 conv2 (16^3) 147 vs 151 us, conv4 (8^3) 144 vs 94: not
+ROUTES = {
+    "featnet.conv0.0": ("pair",), "featnet.conv0.3": ("pair",),
+    "featnet.conv1.0": ("pair", "f43"), "featnet.conv1.3": ("pair",),
+    "featnet.conv2.0": ("pair",), "featnet.conv2.3": ("pair",),
+    "featnet.conv_out.0": ("pair", "f43"), "featnet.conv_out.3": ("pair", "f43"),
+    "volume.mean_embed.0": ("pair", "f43"), "volume.mean_embed.3": ("pair", "f43"),
+    "volume.var_embed.0": ("pair", "f43"), "volume.var_embed.3": ("pair", "f43"),
+    "volume.conv0": ("pair", "f43"), "volume.conv1": ("igemm5",), "volume.conv2": ("pair",), "volume.conv3": ("igemm5",),
+    "volume.conv4": (), "volume.conv5.0": ("igemm5",), "volume.conv5.3": ("igemm5",),
+}
+
+
+def admission_shapes(net, routes, n, size):
+    """{layer: (N, H, W, Cin, Cout, stats_rows, D)}: the questions to ops.conv16_direct_plan for the layers of `net` that list "pair", in a
+    call of n maps of `size` — each with statistics groups of whole maps (D: the depth of a 3x3x3 layer's volumes, else None)."""
+    out = {}
+    for L in net.layers:
+        if "pair" in routes.get(L.key, ()):
+            *d, h, w = L.edge(size)
+            out[L.key] = (n, h, w, L.cin, L.cout, h * w * (d[0] if d else 1), d[0] if d else None)
+    return out
+
+
+def resolve_routes(net, routes, size, big, rng, rng_part, answers):
+    """`routes` resolved for one call -> {layer: "pair" | "igemm3" / "igemm4" / "igemm5" | "f43" | "cores"}.
+    big: the call is big.  rng: a range table is available where the call's inputs are made (what the pair kernel's layers depend on:
+    their inputs exist as pairs from the start).  rng_part: one is available inside the layer's own part of _mm (what the implicit-GEMM
+    pair mode depends on: under an outer reduced-precision mode a part kept on fp32 still runs it).  answers: {layer:
+    ops.conv16_direct_plan's answer} to admission_shapes.
+    "pair" needs big, rng and the halo-patch kernel (answers 1 / 2) for the layer; in the feature net (net.together False) per branch:
+    every layer of it, on crops of multiples of net.align; in the volume net all listed layers or none, with both embeds among them
+    (g6d_refiner_volume_kp_pairs then writes BOTH input volumes as pairs: they never exist in fp32)."""
+    listed = [L for L in net.layers if "pair" in routes.get(L.key, ())]
+    fits = lambda ls: all(L in listed and answers.get(L.key) in (1, 2) for L in ls)
+    chains = net.chains()
+    if not (big and rng) or any(s % net.align for s in size):
+        pair = []
+    elif net.together:
+        pair = listed if fits(listed + [L for c in chains if c[-1].dst for L in c]) else []
+    else:
+        pair = [L for c in chains if fits(c) for L in c]
+    out = {}
+    for L in net.layers:
+        mine = routes.get(L.key, ())
+        igemm = next((r for r in mine if r.startswith("igemm")), None)
+        out[L.key] = "pair" if L in pair else igemm if (igemm and big and rng_part) else "f43" if (big and "f43" in mine) else "cores"
+    return out
 
 
 _LIN = {}
@@ -164,20 +273,13 @@ class VolumeRefiner(ParamBank):
     def _pack(self):
         if self._packed is None:
             pk = {"vgg": pack_trunk(fold_vgg(self, "feature_net.backbone.features"))}
-            for name in ("conv0", "conv1", "conv2", "conv_out"):
-                pk[name] = [self.conv_w(f"feature_net.{name}.{i}", wino_kd=1, f43=(name, i) in FEATNET_F43_LAYERS) for i in (0, 3)]
-            # the 32^3 volume layers (mean_embed, var_embed, conv0) also carry F(4x4,3x3) filters: 1.4-1.5x faster there
-            # at 1.3-3.4e-6 of the layer's range (profiles/r04_w43_bench_v5.md)
-            for name in ("mean_embed", "var_embed", "conv5"):         # conv5 works on 8^3 -> 4^3 maps: never on the Winograd kernel
-                pk["v_" + name] = [self.conv_w(f"volume_net.{name}.{i}", wino_kd=0 if name == "conv5" else 3, f43=True) for i in (0, 3)]
-            for name in ("conv0", "conv1", "conv2", "conv3", "conv4"):
-                pk["v_" + name] = self.conv_w(f"volume_net.{name}.0", wino_kd=3 if name in ("conv0", "conv2", "conv4") else 0,
-                                              f43=name in VOLUME_F43_LAYERS)
-            # filter exponents and pre-split packs of the layers that may run on the implicit-GEMM pair modes: computed here (a
-            # device-to-host read of max |w|, an allocation), not at their first launch, which may sit inside a graph capture
-            for wb in (pk["v_conv1"], pk["v_conv3"], pk["v_conv4"], pk["v_conv5"][0], pk["v_conv5"][1]):
-                ops.pair_filter_prepare(wb[0])
-                ops.pair_filter_pack(wb[0])
+            for L in FEATNET.layers + VOLUME.layers:
+                pk[L.key] = self.conv_w(L.weights, wino_kd=L.kd if L.wino else 0, f43="f43" in ROUTES.get(L.key, ()))
+                if L.igemm:
+                    # filter exponent and pre-split pack of a layer that may run on the implicit-GEMM pair modes: computed here (a
+                    # device-to-host read of max |w|, an allocation), not at its first launch, which may sit inside a graph capture
+                    ops.pair_filter_prepare(pk[L.key][0])
+                    ops.pair_filter_pack(pk[L.key][0])
             # fc.0.0 consumes x.flatten(1) of [512,4,4,4] (index c*64+v); our code is [v][c] -> permute once
             w = self.p("regressor.fc.0.0.weight")
             pk["fc0"] = (w.reshape(512, 512, 64).permute(0, 2, 1).reshape(512, 32768).contiguous(),
@@ -189,135 +291,157 @@ class VolumeRefiner(ParamBank):
             self._packed = pk
         return self._packed
 
-    # ------------------------------------------------------------------ a layer on the pair kernel
+    # ------------------------------------------------------------------ routes, layers, hand-over, join
+    def _plan(self, net, n, size, big, rng):
+        """ROUTES resolved for a call of `net` on n maps of `size` -> (routes without, routes with a range table inside the layer's own
+        part): resolve_routes on the library's admission answers, asked once per (count, size, table content), so that no launch path
+        queries the library."""
+        key = (net.name, n, size, big, rng, tuple(ROUTES.items()))
+        memo = self.__dict__.setdefault("_plans", {})
+        if key not in memo:
+            ask = admission_shapes(net, ROUTES, n, size) if (big and rng) else {}
+            answers = {k: ops.conv16_direct_plan(N, H, W, ci, co, 3, stats_rows=rows, D=D) for k, (N, H, W, ci, co, rows, D) in ask.items()}
+            memo[key] = tuple(resolve_routes(net, ROUTES, size, big, rng, part, answers) for part in (False, True))
+        return memo[key]
+
+    def run_layer(self, L, route, x, y, aff=None, stats=None):
+        """Layer L on `route` (resolve_routes) into the fp32 view y [N,D,H,W,Cout] (a dense map or a channel slice of one; D = 1 in
+        2-D).  x: for "pair" the PairMap it reads (planes as images or whole volumes); else the producer's fp32 map, whose InstanceNorm
+        affine `aff` (+ ReLU) the launch applies in its operand prologue (a table per map from two maps on; the 2-D net: always).
+        stats: the statistics buffer, if the caller took it already.  Returns the affine (scale, shift) of the InstanceNorm that follows
+        the layer (sums in the epilogue; finalised by the launch itself or one small launch), or None."""
+        w = self._pack()[L.key]
+        n, count = y.shape[0], y.shape[1] * y.shape[2] * y.shape[3]
+        st = stats if stats is not None else ops.new_stats(n, L.cout, y.device) if L.norm else None
+        if route == "pair":
+            ops.conv16_direct_multi([x.view(*y.shape[:4], 2, L.cin) if L.kd == 3 else x], w.w16(3, layout=2 if L.kd == 3 else 1), w[1], relu=False,
+                                    full=torch.float32, kd=L.kd, stats=st, rows_per_group=count if L.norm else 0, out_full=[y if L.kd == 3 else y[:, 0]])
+            return ops.stats_finalize(st, count) if L.norm else None
+        if route.startswith("igemm"):       # under the layer's own slot: no hand-over pass but the one variant 5 makes itself
+            table = self.range_table()
+            kernel = {"pairs": (table, table.slot(L.key + ".igemm"), int(route[5:]))}
+        else:
+            kernel = {"w_wino": w.u, "w_wino43": w.u43 if route == "f43" else None}
+        pn = 1 if (n > 1 or L.kd == 1) else 0
+        sc, sh = aff or (None, None)
+        out = ops.conv(x, w[0], w[1], y, ksize=(L.kd, 3, 3), stride=(L.stride if L.kd == 3 else 1, L.stride, L.stride), pad=(L.kd // 2, 1, 1),
+                       in_scale=sc, in_shift=sh, in_relu=aff is not None, per_n=pn if aff is not None else 0, stats=st,
+                       rows_per_group=pn * count if L.norm else 0, finalize=count if L.norm else None, **kernel)
+        return out if L.norm else None
+
+    def to_pairs(self, y, aff, slot):
+        """THE hand-over pass: the fp32 map y [N,D,H,W,C] behind its producer's InstanceNorm affine `aff` + ReLU (None: as it is) -> the
+        PairMap a layer on the pair kernel reads, under range slot `slot` (planes as images: D planes per affine table)."""
+        table = self.range_table()
+        sc, sh = aff or (None, None)
+        return ops.affine_split16(y.view(-1, 1, *y.shape[2:]), sc, sh, y.shape[1] if aff is not None else 0, aff is not None, False, 3,
+                                  rng=(table, table.slot(slot)))
+
     @staticmethod
-    def _pair_conv(layer, xin, y, groups, count, kd=1):
-        """A stride-1 3x3 (kd = 1) or 3x3x3 (kd = 3: depth taps folded into the reduction) layer on the pair kernel: xin a PairMap
-        [N,(D,)H,W,2,Cin], y the fp32 output view (a dense map or a channel slice of one).  groups > 0: the per-group sums of the
-        InstanceNorm that follows (groups of count values) in the epilogue and one small launch that finalises them -> its affine
-        (scale, shift); else None."""
-        st = ops.new_stats(groups, y.shape[-1], y.device) if groups else None
-        ops.conv16_direct_multi([xin], layer.w16(3) if kd == 1 else layer.w16(3, layout=2), layer[1], relu=False, full=torch.float32, kd=kd,
-                                stats=st, rows_per_group=count if groups else 0, out_full=[y])
-        return ops.stats_finalize(st, count) if groups else None
+    def join(y, aff, cat, c_off, factor):
+        """THE join: a branch's fp32 map y [N,D,H,W,C] behind its InstanceNorm affine `aff` (None: as it is; no ReLU), up-sampled by
+        `factor`, into channels [c_off, c_off + C) of `cat` — an fp32 map or a PairMap (whose slices share ONE exponent slot)."""
+        sc, sh = aff or (None, None)
+        if isinstance(cat, ops.PairMap):
+            planes, per = y.view(-1, 1, *y.shape[2:]), y.shape[1] if aff is not None else 0
+            if factor == 1:
+                ops.affine_split16_to(planes, sc, sh, per, False, 3, cat, c_off)
+            else:
+                ops.upsample_bilinear_split16(planes, cat, c_off, factor, sc, sh, per, 3)
+        elif factor == 1:
+            ops.affine_act_pool(y, cat[..., c_off:c_off + y.shape[-1]], sc, sh, per_n=True)
+        else:
+            ops.upsample_bilinear(y, cat[..., c_off:c_off + y.shape[-1]], factor, sc, sh, per_n=True)
+
+    def _run_net(self, net, maps, n, size, big, rng, dev, fork):
+        """The walk over `net`'s layer table for n maps of `size`: each chain reads its named map of `maps` (a function of whether the
+        reader takes pairs, where the two differ), every layer runs on its resolved route (run_layer), and a layer on the pair kernel
+        whose producer left an fp32 map gets it through to_pairs; the branches meet in `cat` — a PairMap when its reader runs on the pair
+        kernel, else fp32 — through join, or by writing their slice themselves where there is nothing to apply.  rng: whether the call's
+        inputs were made with a range table; fork: the branches run as parallel launch sequences.  -> the last layer's (map, affine)."""
+        plan = self._plan(net, n, size, big, rng)
+        reader = net.reader(net.name + ".cat")
+        lead = lambda e: (n, *((1,) if len(e) == 2 else ()), *e)
+        if plan[0][reader.key] == "pair":
+            table, e = self.range_table(), reader.edge(size)
+            cat = ops.new_map16(n * (e[0] if len(e) == 3 else 1), e[-2], e[-1], reader.cin, 3, dev, rng=(table, table.slot(reader.src)))
+        else:
+            cat = torch.empty((*lead(reader.edge(size)), reader.cin), dtype=torch.float32, device=dev)
+        maps = {**maps, reader.src: cat}
+
+        def run(chain):
+            pairs = plan[0][chain[0].key] == "pair"            # (the pair kernel's routes do not depend on the part)
+            y, aff = maps[chain[0].src], None
+            if callable(y):
+                y = y(pairs)
+            # (the 2-D net takes a chain's statistics in front of its launches on the fp32 cores: the order of its arena slots)
+            sts = {L.key: ops.new_stats(n, L.cout, dev) for L in chain} if (chain[0].kd == 1 and not pairs) else {}
+            for part, group in itertools.groupby(chain, key=lambda L: L.part):
+                with self._mm(part):
+                    for L in group:
+                        # (a route that needs a range table inside the part asks for it here, where the math mode is the part's)
+                        route = plan[0][L.key]
+                        if plan[1][L.key] != route and self._pair_rng() is not None:
+                            route = plan[1][L.key]
+                        if route == "pair" and not isinstance(y, ops.PairMap):
+                            y, aff = self.to_pairs(y, aff, L.pass_slot), None
+                        x, aff_in = y, aff
+                        # a branch's last layer writes its slice of an fp32 `cat` itself where there is nothing to apply behind it
+                        own = not (L.dst and L.dst[1] == 1 and not L.norm and not isinstance(cat, ops.PairMap))
+                        y = torch.empty((*lead(L.edge(size, out=True)), L.cout), dtype=torch.float32, device=dev) if own else \
+                            cat[..., L.dst[0]:L.dst[0] + L.cout]
+                        aff = self.run_layer(L, route, x, y, aff_in, sts.get(L.key))
+                        if L.dst and own:
+                            self.join(y, aff, cat, *L.dst)
+            last[:] = y, aff
+
+        last = [None, None]
+        chains = net.chains()
+        branches = [c for c in chains if c[-1].dst]
+        ops.fork_join([lambda c=c: run(c) for c in branches], dev) if fork else [run(c) for c in branches]
+        run(chains[-1])
+        return last
 
     def run_feature_net(self, imgs, f43=None):
         """imgs [n,3,h,w] in [0,1] -> channels-last features [n,h/4,w/4,128] (reference refiner.py:64-78).
-        f43: None = the F(4x4,3x3) kernels from 4 queries (28 crops) per launch on (below that F(2x2,3x3) is faster); False = never
-        (results that are cached per crop must not depend on the batch they were computed in)."""
+        f43: None = the big calls' kernels (ROUTES) from 4 queries (28 crops) per launch on (below that F(2x2,3x3) is faster); False =
+        never (results that are cached per crop must not depend on the batch they were computed in)."""
         pk = self._pack()
         n, _, h, w = imgs.shape
         dev = imgs.device
         big = (n >= F43_MIN_QUERIES * 7) if f43 is None else bool(f43)
         rng = self._pair_rng()
-        # branches on the pair kernel: big calls of the fp32 path whose maps the kernel tiles (one statistics group per image)
-        on16 = self._featnet_pair_branches(n, h, w) if (big and rng is not None) else ()
         with self._mm("trunk"):
-            f3, f5, f7 = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), False, f43=big, rng=rng, pairs=self.pairs_on)   # channels-last
+            taps = trunk_features(pk["vgg"], imgs, ("c3", "c5", "c7_pre"), False, f43=big, rng=rng, pairs=self.pairs_on)   # channels-last
 
-        def tap(name, f, slot):
-            """The L2-normalised tap as the branch reads it: pairs (one pass that normalises and splits), or fp32 in place."""
-            if name in on16:
-                return ops.l2norm_split16(f[:, 0], 3, rng=(rng, rng.slot(slot)))
-            ops.l2norm_rows(f)                  # in place: a tap is never the input of a later layer
-            return f
+        def tap(f, slot):
+            """The L2-normalised tap as its branch reads it: pairs (one pass that normalises and splits), or fp32 in place."""
+            def read(pairs):
+                if pairs:
+                    return ops.l2norm_split16(f[:, 0], 3, rng=(rng, rng.slot(slot)))
+                ops.l2norm_rows(f)                  # in place: a tap is never the input of a later layer
+                return f
+            return read
 
-        def pair(name, x):
-            """conv, IN, ReLU, conv, (IN returned as affine) — per-image statistics."""
-            if name in on16:
-                return pair16(name, x)
-            (w0, b0), (w1, b1) = pk[name]
-            u0, u1 = pk[name][0].u, pk[name][1].u
-            v0, v1 = (pk[name][0].u43, pk[name][1].u43) if big else (None, None)
-            _, _, hh, ww, _ = x.shape
-            y0 = torch.empty((n, 1, hh, ww, w0.shape[0]), dtype=torch.float32, device=dev)
-            s0 = ops.new_stats(n, w0.shape[0], dev)
-            y1 = torch.empty((n, 1, hh, ww, w1.shape[0]), dtype=torch.float32, device=dev)
-            s1 = ops.new_stats(n, w1.shape[0], dev)
-            sc0, sh0 = ops.conv(x, w0, b0, y0, ksize=_K2, pad=_P2, stats=s0, rows_per_group=hh * ww, w_wino=u0, w_wino43=v0, finalize=hh * ww)
-            sc1, sh1 = ops.conv(y0, w1, b1, y1, ksize=_K2, pad=_P2, in_scale=sc0, in_shift=sh0, in_relu=True, per_n=True,
-                                stats=s1, rows_per_group=hh * ww, w_wino=u1, w_wino43=v1, finalize=hh * ww)
-            return y1, sc1, sh1
-
-        def pair16(name, x):
-            """The same on the pair kernel (the selector's stack pattern): x a PairMap [n,hh,ww,2,Cin]; each conv writes its fp32 map and
-            adds the per-image sums in its epilogue, one small launch finalises them, and the InstanceNorm affine + ReLU between the two
-            convs is the elementwise pass that writes the second conv's pairs."""
-            _, hh, ww, _, _ = x.shape
-
-            def conv16(layer, xin):
-                y = torch.empty((n, 1, hh, ww, layer[0].shape[0]), dtype=torch.float32, device=dev)
-                return (y,) + self._pair_conv(layer, xin, y[:, 0], n, hh * ww)
-
-            y0, sc0, sh0 = conv16(pk[name][0], x)
-            mid = ops.affine_split16(y0, sc0, sh0, 1, True, False, 3, rng=(rng, rng.slot(f"featnet.{name}.mid")))
-            return conv16(pk[name][1], mid)
-
-        hq, wq = h // 4, w // 4
-        # the three branches meet in `cat`: pairs when conv_out reads them (the three slices share ONE exponent slot), else fp32
-        cat16 = "conv_out" in on16
-        cat = ops.new_map16(n, hq, wq, 192, 3, dev, rng=(rng, rng.slot("featnet.cat"))) if cat16 else \
-            torch.empty((n, 1, hq, wq, 192), dtype=torch.float32, device=dev)
-
-        def branch(name, f, slot, c_off, factor):
-            y, sc, sh = pair(name, tap(name, f, slot))
-            if cat16:
-                if factor == 1:
-                    ops.affine_split16_to(y, sc, sh, 1, False, 3, cat, c_off)
-                else:
-                    ops.upsample_bilinear_split16(y, cat, c_off, factor, sc, sh, 1, 3)
-            elif factor == 1:
-                ops.affine_act_pool(y, cat[..., c_off:c_off + 64], sc, sh, per_n=True)
-            else:
-                ops.upsample_bilinear(y, cat[..., c_off:c_off + 64], factor, sc, sh, per_n=True)
-
-        with self._mm("featnet"):
-            ops.fork_join([lambda: branch("conv0", f3, "featnet.f3", 0, 1), lambda: branch("conv1", f5, "featnet.f5", 64, 2),
-                           lambda: branch("conv2", f7, "featnet.f7", 128, 4)], dev)
-            y, sc, sh = pair("conv_out", cat)
-        out = torch.empty((n, 1, hq, wq, 128), dtype=torch.float32, device=dev)
-        ops.affine_act_pool(y, out, sc, sh, per_n=True)
-        return out.view(n, hq, wq, 128)
-
-    def _featnet_pair_branches(self, n, h, w):
-        """The branches of FEATNET_PAIR_BRANCHES whose maps, for n crops of h x w, the pair kernel tiles with one statistics group per image
-        (asked of the library's own validation, once per crop count and size); the others keep their routes."""
-        key = (n, h, w)
-        memo = self.__dict__.setdefault("_featnet16", {})
-        if key not in memo:
-            shapes = {"conv0": (4, 256, 64, 64), "conv1": (8, 512, 256, 64), "conv2": (16, 512, 256, 64), "conv_out": (4, 192, 128, 128)}
-
-            def fits(name):
-                d, ci, cm, co = shapes[name]
-                hh, ww = h // d, w // d
-                return all(ops.conv16_direct_plan(n, hh, ww, a, b, 3, stats_rows=hh * ww) in (1, 2) for a, b in ((ci, cm), (cm, co)))
-            memo[key] = tuple(name for name in FEATNET_PAIR_BRANCHES if h % 16 == 0 and w % 16 == 0 and fits(name))
-        return memo[key]
+        maps = {slot: tap(f, slot) for f, slot in zip(taps, ("featnet.f3", "featnet.f5", "featnet.f7"))}
+        y, aff = self._run_net(FEATNET, maps, n, (h, w), big, rng is not None, dev, fork=True)
+        out = torch.empty((n, 1, h // 4, w // 4, 128), dtype=torch.float32, device=dev)
+        ops.affine_act_pool(y, out, aff[0], aff[1], per_n=True)
+        return out.view(n, h // 4, w // 4, 128)
 
     # ------------------------------------------------------------------ 3-D volume net + regressor
-    def volume_pair_route(self, qn, sn):
-        """Whether a batch of qn volumes of sn^3 voxels takes the pair route through the 32^3 stage of the volume net: a big call of the
-        fp32 path (the F43_MIN_QUERIES condition of the fp32-core route, pairs on), both embeds listed, and every listed layer accepted by
-        the library's own validation (asked once per batch and volume size)."""
-        if qn < F43_MIN_QUERIES or self._pair_rng() is None or not {"mean_embed", "var_embed"} <= set(VOLUME_PAIR_LAYERS):
-            return False
-        memo = self.__dict__.setdefault("_volume16", {})
-        key = (qn, sn, tuple(VOLUME_PAIR_LAYERS))
-        if key not in memo:
-            shapes = [(sn, 256, 64), (sn, 128, 64), (sn, 64, 64)] + ([(sn, 128, 64)] if "conv0" in VOLUME_PAIR_LAYERS else []) + \
-                ([(sn // 2, 128, 128)] if "conv2" in VOLUME_PAIR_LAYERS else [])
-            memo[key] = all(ops.conv16_direct_plan(qn, s, s, ci, co, 3, stats_rows=s ** 3, D=s) == 1 for s, ci, co in shapes)
-        return memo[key]
-
     def feature_volumes(self, feats, ref_Ks, ref_poses, K_in, pose_in, h_in, w_in, sn):
         """The two input volumes of the volume net from the crops' features (g6d_refiner_volume_kp): fp32 mean_in [.., sn^3, 2C] and std
-        [.., sn^3, C], or — volume_pair_route — the same as PairMaps [qn,sn,sn,sn,2,2C] / [qn,sn,sn,sn,2,C], one exponent slot each."""
+        [.., sn^3, C], or — where the embeds run on the pair kernel (a big batch of the fp32 path, ROUTES) — the same as PairMaps
+        [qn,sn,sn,sn,2,2C] / [qn,sn,sn,sn,2,C], one exponent slot each."""
         dev = feats.device
         lin = _linspace(sn, dev)
         C = feats.shape[-1]
         args = (feats, ref_Ks.contiguous(), ref_poses.contiguous(), K_in.contiguous(), pose_in.contiguous(), lin, h_in, w_in)
-        if feats.dim() == 5 and self.volume_pair_route(feats.shape[0], sn):
-            rng = self._pair_rng()
+        qn = feats.shape[0] if feats.dim() == 5 else 1
+        big = qn >= F43_MIN_QUERIES
+        rng = self._pair_rng() if big else None
+        if self._plan(VOLUME, qn, (sn,) * 3, big, rng is not None)[0][VOLUME.reader("volume.mean_in").key] == "pair":
             return ops.refiner_volume_kp_pairs(*args, rng_mean=(rng, rng.slot("volume.mean_in")), rng_std=(rng, rng.slot("volume.std")))
         lead = (feats.shape[0],) if feats.dim() == 5 else ()
         mean_in = torch.empty(lead + (sn ** 3, 2 * C), dtype=torch.float32, device=dev)
@@ -328,86 +452,15 @@ class VolumeRefiner(ParamBank):
     def run_volume_net(self, mean_in, std, sn):
         """mean_in [sn^3,256], std [sn^3,128] -> code [(sn/8)^3, 512] (reference refiner.py:136-143); or a batch of qn volumes
         ([qn,sn^3,256], [qn,sn^3,128] -> [qn,(sn/8)^3,512]) through the same launches: every InstanceNorm3d keeps one statistics group
-        and one affine table per volume.  PairMap volumes (feature_volumes on the pair route): the sn^3 stage runs on the pair kernel."""
-        pk = self._pack()
+        and one affine table per volume.  PairMap volumes (feature_volumes): the layers of the pair kernel read them as they are."""
         pairs_in = isinstance(mean_in, ops.PairMap)
         dev = mean_in.data.device if pairs_in else mean_in.device
         batched = pairs_in or mean_in.dim() == 3
         qn = mean_in.shape[0] if batched else 1
-        pn = 1 if qn > 1 else 0                      # per-volume tables / groups only when there is more than one
-
-        def c3(x, wb, out, stride=1, aff=None, stats_c=None, count=None, name=None):
-            """3x3x3 conv; with stats_c: returns the affine (scale, shift) of the InstanceNorm that follows (count values).
-            name: the layer's entry in VOLUME_IGEMM_PAIR_LAYERS, if it has one."""
-            st = ops.new_stats(qn, stats_c, dev) if stats_c else None
-            sc, sh = aff if aff is not None else (None, None)
-            # big calls of the fp32 path (the condition of volume_pair_route): a listed layer on the implicit-GEMM kernel's pair mode
-            # (_pair_rng: None with fp32_cores, during a fallback recompute and inside a 16-bit part)
-            r = self._pair_rng() if (qn >= F43_MIN_QUERIES and name in VOLUME_IGEMM_PAIR_LAYERS) else None
-            variant = VOLUME_IGEMM_PAIR_LAYERS[name] if (r is not None and isinstance(VOLUME_IGEMM_PAIR_LAYERS, dict)) else 3     # a plain list of names: 3
-            route = {"pairs": (r, r.slot(f"volume.{name}.igemm"), variant)} if r is not None else \
-                {"w_wino": getattr(wb, "u", None) if stride == 1 else None,
-                 "w_wino43": getattr(wb, "u43", None) if (stride == 1 and qn >= F43_MIN_QUERIES) else None}
-            return ops.conv(x, wb[0], wb[1], out, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh,
-                            in_relu=aff is not None, per_n=pn if aff is not None else 0, stats=st,
-                            rows_per_group=pn * (count or 0) if stats_c else 0, finalize=count if stats_c else None, **route)
-
-        def buf(s, c):
-            return torch.empty((qn, s, s, s, c), dtype=torch.float32, device=dev)
-
-        vox = sn ** 3
-        rng = self._pair_rng() if pairs_in else None
-        cat16 = pairs_in and "conv0" in VOLUME_PAIR_LAYERS
-        # the two embeds meet in `cat`: ONE 128-channel pair map (one exponent slot for both slices) when conv0 reads pairs, else fp32
-        cat = ops.new_map16(qn * sn, sn, sn, 128, 3, dev, rng=(rng, rng.slot("volume.cat"))) if cat16 else buf(sn, 128)
-
-        def embed(name, x, c_off):
-            if pairs_in:
-                return embed16(name, x, c_off)
-            y = buf(sn, 64)
-            aff = c3(x, pk[name][0], y, stats_c=64, count=vox)
-            c3(y, pk[name][1], cat[..., c_off:c_off + 64], aff=aff)
-
-        def embed16(name, x, c_off):
-            """conv, IN, ReLU, conv on pairs: the InstanceNorm affine + ReLU between the two layers is the elementwise pass that writes the
-            second layer's pairs (planes as images: sn planes per affine table); the second layer's fp32 map goes into its slice of `cat`
-            — directly (fp32 `cat`), or through the pass that splits it into the pair map conv0 reads."""
-            y0 = buf(sn, 64)
-            sc, sh = self._pair_conv(pk[name][0], x, y0, qn, vox, kd=3)
-            mid = ops.affine_split16(y0.view(qn * sn, 1, sn, sn, 64), sc, sh, sn, True, False, 3, rng=(rng, rng.slot(f"volume.{name[2:]}.mid")))
-            if not cat16:
-                self._pair_conv(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), cat[..., c_off:c_off + 64], 0, vox, kd=3)
-                return
-            y1 = buf(sn, 64)
-            self._pair_conv(pk[name][1], mid.view(qn, sn, sn, sn, 2, 64), y1, 0, vox, kd=3)
-            ops.affine_split16_to(y1.view(qn * sn, 1, sn, sn, 64), None, None, 0, False, 3, cat, c_off)
-
-        with self._mm("embed"):
-            embed("v_mean_embed", mean_in.view(qn, sn, sn, sn, 2, 256) if pairs_in else mean_in.view(qn, sn, sn, sn, 256), 0)
-            embed("v_var_embed", std.view(qn, sn, sn, sn, 2, 128) if pairs_in else std.view(qn, sn, sn, sn, 128), 64)
-        x, aff, s = cat, None, sn
-        with self._mm("stack"):
-            for name, co, stride in (("v_conv0", 64, 1), ("v_conv1", 128, 2), ("v_conv2", 128, 1), ("v_conv3", 256, 2),
-                                     ("v_conv4", 256, 1)):
-                s = s // stride
-                y = buf(s, co)
-                if name == "v_conv0" and cat16:
-                    # fp32 output with the sums: conv1 (stride 2, implicit GEMM) still takes the affine in its operand prologue
-                    x, aff = y, self._pair_conv(pk[name], cat.view(qn, sn, sn, sn, 2, 128), y, qn, vox, kd=3)
-                    continue
-                if name == "v_conv2" and pairs_in and "conv2" in VOLUME_PAIR_LAYERS:
-                    # conv1's InstanceNorm affine + ReLU is the pass that writes conv2's pairs (planes as images: s planes per table)
-                    xin = ops.affine_split16(x.view(qn * s, 1, s, s, 128), aff[0], aff[1], s, True, False, 3, rng=(rng, rng.slot("volume.conv2.in")))
-                    x, aff = y, self._pair_conv(pk[name], xin.view(qn, s, s, s, 2, 128), y, qn, s ** 3, kd=3)
-                    continue
-                x, aff = y, c3(x, pk[name], y, stride=stride, aff=aff, stats_c=co, count=s ** 3, name=name[2:])
-        s = s // 2
-        y = buf(s, 512)
-        with self._mm("tail"):
-            aff = c3(x, pk["v_conv5"][0], y, stride=2, aff=aff, stats_c=512, count=s ** 3, name="conv5.0")
-            code = buf(s, 512)
-            c3(y, pk["v_conv5"][1], code, aff=aff, name="conv5.3")
-        return code.view(qn, s ** 3, 512) if batched else code.view(s ** 3, 512)
+        vol = lambda t: t.view(qn, sn, sn, sn, *t.shape[(-2 if pairs_in else -1):])
+        maps = {"volume.mean_in": vol(mean_in), "volume.std": vol(std)}
+        code, _ = self._run_net(VOLUME, maps, qn, (sn,) * 3, qn >= F43_MIN_QUERIES, pairs_in, dev, fork=False)
+        return code.view(qn, -1, 512) if batched else code.view(-1, 512)
 
     def run_regressor(self, code):
         """code [v,512] (one query) or [qn,v,512] -> rotation [qn,4] (unit quaternion), offset [qn,2], scale [qn,1]; the 67 MB FC

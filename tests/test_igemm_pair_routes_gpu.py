@@ -1,5 +1,5 @@
 """The routes onto the implicit-GEMM kernel's fp16 hi / lo pair mode (ops.conv(pairs=...), conv_igemm_kernel<., MM = 3>):
-(1) VolumeRefiner.run_volume_net at 4 volumes with refiner.VOLUME_IGEMM_PAIR_LAYERS on, against the fp32_cores route on the same
+(1) VolumeRefiner.run_volume_net at 4 volumes with the "igemmV" entries of refiner.ROUTES on, against the fp32_cores route on the same
     features, at the bar test_refiner_volume_pairs_gpu uses for the same comparison (1e-4 absolute); the listed layers are booked as
     `conv16x3 igemm` launches and with fp32_cores none is;
 (2) the selector's logits at 2 queries x 8 references x 5 rotations against fp32_cores: same arg-max, difference under the selector
@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from gen6d_amd import synth
+from routes import forced_routes, igemm_layers, without
 from test_networks_gpu import _net
 from test_refiner_volume_pairs_gpu import _features, _volume_code
 
@@ -32,25 +33,23 @@ def volume_runs():
 
 
 def test_volume_net_igemm_pairs_against_fp32_cores(volume_runs):
-    from gen6d_amd.network import refiner
     _, (want, labels32), (got, labels), net = volume_runs
     assert not _igemm(labels32), labels32
     booked = _igemm(labels)
-    assert len(booked) == len(refiner.VOLUME_IGEMM_PAIR_LAYERS), labels
+    assert len(booked) == len(igemm_layers()), labels
     assert all("k=3x3x3" in l and "aff" in l for l in booked)
     assert net.range_check() is False
-    assert {f"volume.{n}.igemm" for n in refiner.VOLUME_IGEMM_PAIR_LAYERS} <= set(net.range_report())
+    assert {f"{n}.igemm" for n in igemm_layers()} <= set(net.range_report())
     err = float((got - want).abs().max())
     print(f"volume net, 4 volumes: igemm + halo-patch pair routes against fp32_cores, max abs difference {err:.3e} of codes up to "
           f"{float(want.abs().max()):.3e} (bar 1e-4)")
     assert err <= 1e-4, err
 
 
-def test_empty_list_restores_the_launches(volume_runs, monkeypatch):
-    from gen6d_amd.network import refiner
+def test_empty_list_restores_the_launches(volume_runs):
     args, _, (_, labels), _ = volume_runs
-    monkeypatch.setattr(refiner, "VOLUME_IGEMM_PAIR_LAYERS", ())
-    _, plain, _ = _volume_code(_net("refiner"), args)
+    with forced_routes(without("igemm")):
+        _, plain, _ = _volume_code(_net("refiner"), args)
     assert not _igemm(plain)
     # the same launches in the same order: a listed layer's label only gains the prefix
     assert [l[len("conv16x3 igemm "):] if l.startswith("conv16x3 igemm ") else l for l in labels] == plain

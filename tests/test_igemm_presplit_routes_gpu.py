@@ -1,5 +1,5 @@
-"""The volume net's routes onto the pre-split loader variants of the implicit-GEMM pair mode (refiner.VOLUME_IGEMM_PAIR_LAYERS: a dict
-layer -> variant, ops.conv(pairs=(table, slot, variant))), at 4 volumes on the features of test_refiner_volume_pairs_gpu:
+"""The volume net's routes onto the pre-split loader variants of the implicit-GEMM pair mode (the "igemmV" entries of refiner.ROUTES,
+ops.conv(pairs=(table, slot, variant))), at 4 volumes on the features of test_refiner_volume_pairs_gpu:
 (1) the default routes against fp32_cores at the bar of the existing route tests (1e-4 absolute);
 (2) against the parent's routing — every listed layer forced to variant 3 — the code is equal bit for bit with every layer on variant 4
     (same operands, same order).  The default routes (variant 5) were to stay within 1e-6 absolute, the issue's guess.  Measured on an
@@ -14,6 +14,7 @@ layer -> variant, ops.conv(pairs=(table, slot, variant))), at 4 volumes on the f
 import pytest
 import torch
 
+from routes import forced_routes, igemm_layers
 from test_networks_gpu import _net
 from test_refiner_volume_pairs_gpu import _features, _volume_code
 
@@ -22,20 +23,16 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def runs():
-    from gen6d_amd.network import refiner
     args = _features(4)
     want, _, _ = _volume_code(_net("refiner", fp32_cores=True), args)
-    default = dict(refiner.VOLUME_IGEMM_PAIR_LAYERS)
+    default = igemm_layers()
     codes = {}
     for key, routing in (("default", default), ("3", {n: 3 for n in default}), ("4", {n: 4 for n in default})):
-        refiner.VOLUME_IGEMM_PAIR_LAYERS = routing
-        try:
+        with forced_routes({n: (f"igemm{v}",) for n, v in routing.items()}):
             net = _net("refiner")
             code, labels, _ = _volume_code(net, args)
             assert net.range_check() is False
             codes[key] = (code, labels)
-        finally:
-            refiner.VOLUME_IGEMM_PAIR_LAYERS = default
     return want, codes, default
 
 

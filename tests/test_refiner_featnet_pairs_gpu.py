@@ -9,6 +9,7 @@ import torch
 
 from gen6d_amd import synth
 from oracle import gen6d_oracle as O
+from routes import forced_routes, with_pairs
 from test_networks_gpu import _accept, _net
 
 pytestmark = pytest.mark.gpu
@@ -39,16 +40,17 @@ def _profiled(net, imgs):
 
 
 ALL_BRANCHES = ("conv0", "conv1", "conv2", "conv_out")
+ALL_ON_PAIRS = [f"featnet.{b}.{i}" for b in ALL_BRANCHES for i in (0, 3)]
 
 
-def test_pair_route_books_conv16x3_and_meets_the_oracle(case, monkeypatch):
-    """All four branches on pairs (whatever subset the product routes, refiner.FEATNET_PAIR_BRANCHES: every branch's route stays tested)."""
+def test_pair_route_books_conv16x3_and_meets_the_oracle(case):
+    """All four branches on pairs (whatever subset the product routes, refiner.ROUTES: every branch's route stays tested)."""
     from gen6d_amd.network import refiner
     imgs, r32, r64 = case
-    product = refiner.FEATNET_PAIR_BRANCHES
-    monkeypatch.setattr(refiner, "FEATNET_PAIR_BRANCHES", ALL_BRANCHES)
-    net = _net("refiner")
-    out, labels = _profiled(net, imgs)
+    product = tuple(b for b in ALL_BRANCHES if all("pair" in refiner.ROUTES[f"featnet.{b}.{i}"] for i in (0, 3)))
+    with forced_routes(with_pairs(ALL_ON_PAIRS)):
+        net = _net("refiner")
+        out, labels = _profiled(net, imgs)
     layers = [l for l in labels if l.startswith("conv16x3 direct") and l.endswith(" stats")]      # (the trunk's launches carry no statistics)
     assert len(layers) == 8, labels
     assert not any("wino3x3" in l or "conv N=" in l for l in labels), labels                      # no Winograd / implicit-GEMM entry at all
@@ -57,7 +59,6 @@ def test_pair_route_books_conv16x3_and_meets_the_oracle(case, monkeypatch):
     want = {"featnet.f3", "featnet.f5", "featnet.f7", "featnet.cat"} | {f"featnet.{b}.mid" for b in ALL_BRANCHES}      # one slot per pair producer
     assert want <= set(net.range_report())
     if tuple(product) != ALL_BRANCHES:                          # the product's mix of routes: its branches on pairs, the others as before
-        monkeypatch.setattr(refiner, "FEATNET_PAIR_BRANCHES", product)
         net2 = _net("refiner")
         out2, labels2 = _profiled(net2, imgs)
         assert len([l for l in labels2 if l.startswith("conv16x3 direct") and l.endswith(" stats")]) == 2 * len(product), labels2
@@ -75,19 +76,17 @@ def test_fp32_cores_books_no_16_bit_launch(case):
     _accept(out, r32, r64, what="feature net on the fp32 cores, 7 crops")
 
 
-def test_batched_step_agrees_with_single_query_steps(monkeypatch):
+def test_batched_step_agrees_with_single_query_steps():
     c = synth.refiner_case()
     qn, rfn = 4, c["ref_imgs"].shape[1]
-    from gen6d_amd.network import refiner
-    monkeypatch.setattr(refiner, "FEATNET_PAIR_BRANCHES", ALL_BRANCHES)
-    net = _net("refiner")
     # four different queries: the case's crops, shifted by a few pixels per query
     que = torch.cat([torch.roll(c["que_imgs"], (3 * i, -2 * i), (2, 3)) for i in range(qn)], 0).cuda()
     refs = torch.stack([torch.roll(c["ref_imgs"][0], (-i, 2 * i), (2, 3)) for i in range(qn)], 0).cuda()
     rep = lambda t: t.expand(qn, *t.shape[1:]).contiguous().cuda()
     Ks, poses, rKs, rposes = rep(c["Ks_in"]), rep(c["poses_in"]), rep(c["ref_Ks"]), rep(c["ref_poses"])
     assert tuple(refs.shape) == (qn, rfn, 3, 128, 128)
-    with torch.no_grad():
+    with forced_routes(with_pairs(ALL_ON_PAIRS)), torch.no_grad():
+        net = _net("refiner")
         rot, off, scl = net._step(que, Ks, poses, refs, rKs, rposes)
         assert net.range_check() is False
         for q in range(qn):

@@ -107,7 +107,7 @@ def test_volume_net_pair_route_against_fp32_cores():
     assert not pairs32 and not any("conv16" in l for l in labels32), labels32
     net = _net("refiner")
     got, labels, pairs = _volume_code(net, args)
-    n16 = 4 + len({"conv0", "conv2"} & set(refiner.VOLUME_PAIR_LAYERS))           # two layers per embed, and conv0 / conv2 where they are listed
+    n16 = 4 + len([k for k in ("volume.conv0", "volume.conv2") if "pair" in refiner.ROUTES[k]])      # two layers per embed, and conv0 / conv2 where they are listed
     folded = [l for l in labels if l.startswith("conv16x3 direct") and "k=3x3x3" in l]
     assert pairs and len(folded) == n16, labels                 # the route is taken: every listed layer booked on the pair kernel
     assert net.range_check() is False

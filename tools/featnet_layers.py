@@ -1,9 +1,10 @@
 """The refiner's 2-D feature net per branch and per layer: today's fp32-core routes (F(4x4,3x3) / F(2x2,3x3) / implicit GEMM with the
 InstanceNorm affine in the operand prologue and the finalisation fused into the producing launch) against the fp16 hi / lo pair route
-(conv16w_kernel<3,.> + its hand-over passes), the launches of VolumeRefiner.run_feature_net timed one by one and as whole branches.
+(conv16w_kernel<3,.> + its hand-over passes), the launches of VolumeRefiner.run_feature_net timed one by one and as whole branches — each
+through the product's own layer runner, hand-over pass and join (VolumeRefiner.run_layer / to_pairs / join) on the shapes of refiner.FEATNET.
     python tools/featnet_layers.py [crops=112]
 us per launch, the best of three rounds of 10; a branch's time is its whole launch sequence back to back on one stream (what the step pays
-when the kernels serialise).  The table decides refiner.FEATNET_PAIR_BRANCHES (profiles/r16_featnet_pairs.md); run it with 7 crops for the
+when the kernels serialise).  The table decides the feature net's "pair" entries of refiner.ROUTES (profiles/r16_featnet_pairs.md); run it with 7 crops for the
 single-query times (recorded for a later decision, not routed on)."""
 import os
 import sys
@@ -16,8 +17,6 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import toolenv                                                  # noqa: E402,F401  (G6D_LIB_PATH / KNOBS)
 from gen6d_amd import lib, ops, synth                           # noqa: E402
 from gen6d_amd.network import name2network, refiner             # noqa: E402
-
-_K2, _P2 = (1, 3, 3), (0, 1, 1)
 
 
 def timed(fn, reps=10):
@@ -41,61 +40,52 @@ def main():
     net = name2network["refiner"]({"name": "featnet_layers"}).eval()
     net.load_state_dict(synth.synth_state_dict("refiner"))
     net.to(dev)
-    pk = net._pack()
+    size = (128, 128)
     big = n >= refiner.F43_MIN_QUERIES * 7
-    table = ops.RangeTable(dev)
+    cores = refiner.resolve_routes(refiner.FEATNET, refiner.ROUTES, size, big, False, False, {})      # the fp32 cores' kernel per layer
+    table = net.range_table()
     rng = lambda name: (table, table.slot(name))
     f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    cat32 = f32(n, 1, 32, 32, 192)
-    cat16 = ops.new_map16(n, 32, 32, 192, 3, dev, rng=rng("cat"))
+    reader = refiner.FEATNET.reader("featnet.cat")
+    cat32 = f32(n, 1, *reader.edge(size), reader.cin)
+    cat16 = ops.new_map16(n, *reader.edge(size), reader.cin, 3, dev, rng=rng("cat"))
     print(f"# {n} crops of 128x128: the feature net's launches, us per launch (best of 3 rounds of 10); convs with direct-form TFLOP/s")
     print("| branch | launch | fp32-core route | us | TFLOP/s | pair route | us | TFLOP/s |\n|---|---|---|---|---|---|---|---|")
-    # (branch, map side, Cin, c_off in cat, up-sampling factor)
     total = [0.0, 0.0]
-    for name, hw, ci, c_off, factor in (("conv0", 32, 256, 0, 1), ("conv1", 16, 512, 64, 2), ("conv2", 8, 512, 128, 4), ("conv_out", 32, 192, 0, 0)):
-        l0, l1 = pk[name]
-        cm, co = l0[0].shape[0], l1[0].shape[0]
+    for l0, l1 in refiner.FEATNET.chains():                     # a branch: its two layers; the second one's dst = (c_off in cat, up-sampling factor)
+        name, hw, ci, cm, co = l0.key.split(".")[1], l0.edge(size)[0], l0.cin, l0.cout, l1.cout
+        c_off, factor = l1.dst or (0, 0)
         x32 = torch.rand((n, 1, hw, hw, ci), device=dev) - 0.5
         y0, y1 = f32(n, 1, hw, hw, cm), f32(n, 1, hw, hw, co)
-        s0, s1 = ops.new_stats(n, cm, dev), ops.new_stats(n, co, dev)
+        s0, s1 = ops.new_stats(n, cm, dev), ops.new_stats(n, co, dev)             # (taken once: no zero-fill inside the timed launches)
         aff = {}
-        v = lambda l: l.u43 if (big and (name, 0 if l is l0 else 3) in refiner.FEATNET_F43_LAYERS) else None
 
         def old_c0():
-            aff["a0"] = ops.conv(x32, l0[0], l0[1], y0, ksize=_K2, pad=_P2, stats=s0, rows_per_group=hw * hw, w_wino=l0.u, w_wino43=v(l0), finalize=hw * hw)
+            aff["a0"] = net.run_layer(l0, cores[l0.key], x32, y0, None, s0)
 
         def old_c1():
-            aff["a1"] = ops.conv(y0, l1[0], l1[1], y1, ksize=_K2, pad=_P2, in_scale=aff["a0"][0], in_shift=aff["a0"][1], in_relu=True, per_n=True,
-                                 stats=s1, rows_per_group=hw * hw, w_wino=l1.u, w_wino43=v(l1), finalize=hw * hw)
+            aff["a1"] = net.run_layer(l1, cores[l1.key], y0, y1, aff["a0"], s1)
 
         def conv16(layer, xin, y, st, key):
-            ops.conv16_direct_multi([xin], layer.w16(3), layer[1], relu=False, full=torch.float32, stats=st, rows_per_group=hw * hw, out_full=[y[:, 0]])
-            aff[key] = ops.stats_finalize(st, hw * hw)
+            aff[key] = net.run_layer(layer, "pair", xin, y, None, st)
 
         x16 = {}
 
         def new_in():
+            # (the tap's pass is run_feature_net's own, not a layer's: spelled out)
             x16["x"] = ops.l2norm_split16(x32[:, 0], 3, rng=rng(name + ".in")) if factor else cat16
 
         def new_mid():
-            x16["mid"] = ops.affine_split16(y0, aff["a0"][0], aff["a0"][1], 1, True, False, 3, rng=rng(name + ".mid"))
+            x16["mid"] = net.to_pairs(y0, aff["a0"], l1.pass_slot)
 
         def old_end():
-            sc, sh = aff["a1"]
-            if factor == 1:
-                ops.affine_act_pool(y1, cat32[..., c_off:c_off + 64], sc, sh, per_n=True)
-            else:
-                ops.upsample_bilinear(y1, cat32[..., c_off:c_off + 64], factor, sc, sh, per_n=True)
+            net.join(y1, aff["a1"], cat32, c_off, factor)
 
         def new_end():
-            sc, sh = aff["a1"]
-            if factor == 1:
-                ops.affine_split16_to(y1, sc, sh, 1, False, 3, cat16, c_off)
-            else:
-                ops.upsample_bilinear_split16(y1, cat16, c_off, factor, sc, sh, 1, 3)
+            net.join(y1, aff["a1"], cat16, c_off, factor)
 
         fl0, fl1 = 2.0 * n * hw * hw * cm * 9 * ci, 2.0 * n * hw * hw * co * 9 * cm
-        kern = lambda l: "F(4x4)" if v(l) is not None else "F(2x2) / igemm"
+        kern = lambda l: "F(4x4)" if cores[l.key] == "f43" else "F(2x2) / igemm"
         rows = [("tap", "l2norm_rows (in place)" if factor else "-", (lambda: ops.l2norm_rows(x32)) if factor else None, 0.0,
                  "l2norm_split16" if factor else "-", new_in if factor else None),
                 (f"{name}.0 {ci}->{cm} @{hw}", kern(l0) + " +stats +finalize", old_c0, fl0, "conv16x3 +stats, stats_finalize",

@@ -1,14 +1,15 @@
 """The layers the halo-patch pair kernel cannot express — stride 2, small volumes that need split-K, 1x1 — launch by launch: today's
 fp32-core route (g6d_conv_igemm: conv_igemm_kernel<., MM = 0>, or F(2x2,3x3) for conv4) against the implicit-GEMM kernel's own fp16
-hi / lo pair mode (conv_igemm_kernel<., MM = 3>, ops.conv(pairs=...)), at the bench's shapes.
+hi / lo pair mode (conv_igemm_kernel<., MM = 3>, ops.conv(pairs=...)), at the bench's shapes — the volume layers (those of refiner.VOLUME
+the halo-patch kernel cannot express) through the product's own layer runner, VolumeRefiner.run_layer, with the route forced.
     python tools/igemm_pair_layers.py [volumes / queries = 16]
-us per launch, the best of three rounds of 10, with direct-form TFLOP/s.  The table decides refiner.VOLUME_IGEMM_PAIR_LAYERS and
+us per launch, the best of three rounds of 10, with direct-form TFLOP/s.  The table decides the "igemmV" entries of refiner.ROUTES and
 selector.SELECTOR_IGEMM_PAIR_LAYERS (profiles/r18_igemm_pairs.md): a layer is listed only where it is faster at 16; run it with 1 for
 the single-query times (recorded, not routed on).
 The five volume layers get a second table: the pair mode's three loader variants (ops.conv(pairs=(table, slot, variant))) — 3 splits both
 operands in the loader, 4 copies filters the weight pack split, 5 copies both operands behind ONE affine_split16 pass, whose time is
 included — each with the spread (max - min) of its three rounds.  A layer takes the fastest variant that beats its current route (the
-one refiner.VOLUME_IGEMM_PAIR_LAYERS names, else the fp32-core route) by more than the spread of the current route's rounds
+one refiner.ROUTES names, else the fp32-core route) by more than the spread of the current route's rounds
 (profiles/r22_igemm_presplit.md)."""
 import os
 import sys
@@ -20,10 +21,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import toolenv                                                  # noqa: E402,F401  (G6D_LIB_PATH / KNOBS)
 from gen6d_amd import lib, ops, synth                           # noqa: E402
-from gen6d_amd.network import name2network                      # noqa: E402
+from gen6d_amd.network import name2network, refiner             # noqa: E402
 from featnet_layers import timed                                # noqa: E402
-
-_K3, _P3 = (3, 3, 3), (1, 1, 1)
 
 
 def timed3(fn, reps=10):
@@ -48,7 +47,6 @@ def main():
     net = name2network["refiner"]({"name": "igemm_pair_layers"}).eval()
     net.load_state_dict(synth.synth_state_dict("refiner"))
     net.to(dev)
-    pk = net._pack()
     pn = 1 if qn > 1 else 0
     table = ops.RangeTable(dev)
     print(f"# {qn} volumes / queries: us per launch (best of 3 rounds of 10), direct-form TFLOP/s")
@@ -61,36 +59,32 @@ def main():
         print(f"| {name} | {shape} | {on} | {to:.1f} | {fl / to / 1e6:.0f} | conv_igemm pairs | {tn:.1f} | {fl / tn / 1e6:.0f} | "
               f"{'pairs faster' if tn < to else 'fp32 cores faster'} ({to / tn:.2f}x) |", flush=True)
 
-    # the volume net: (name, layer, input edge, Cin, Cout, stride); every layer takes the previous InstanceNorm's affine + ReLU in its
-    # operand prologue (a table per volume) and adds its own sums with the fused finalize, as run_volume_net launches it
-    for name, layer, s, ci, co, stride, stats in (("conv1", pk["v_conv1"], 32, 64, 128, 2, True), ("conv3", pk["v_conv3"], 16, 128, 256, 2, True),
-                                                  ("conv4", pk["v_conv4"], 8, 256, 256, 1, True), ("conv5.0", pk["v_conv5"][0], 8, 256, 512, 2, True),
-                                                  ("conv5.3", pk["v_conv5"][1], 4, 512, 512, 1, False)):
-        so = s // stride
+    # the volume net's candidates (stride 2, or 8^3 and below); every layer takes the previous InstanceNorm's affine + ReLU in its operand
+    # prologue (a table per volume) and adds its own sums with the fused finalize, as run_volume_net launches it
+    for L in (L for L in refiner.VOLUME.layers if L.igemm):
+        name, ci, co, stride, stats = L.key.split(".", 1)[1], L.cin, L.cout, L.stride, L.norm
+        s, so = L.edge((32,) * 3)[0], L.edge((32,) * 3, out=True)[0]
         x = torch.rand((qn, s, s, s, ci), device=dev) - 0.5
         y = torch.empty((qn, so, so, so, co), dtype=torch.float32, device=dev)
         sc, sh = torch.rand((qn if pn else 1, ci), device=dev) + 0.5, torch.rand((qn if pn else 1, ci), device=dev) - 0.5
-        st = ops.new_stats(qn, co, dev) if stats else None
+        st = ops.new_stats(qn, co, dev) if stats else None          # (taken once: no zero-fill inside the timed launches)
 
-        def launch(pairs, layer=layer, x=x, y=y, sc=sc, sh=sh, st=st, stride=stride, so=so):
-            kw = {"pairs": (table, table.slot(name), int(pairs))} if pairs else {"w_wino": getattr(layer, "u", None) if stride == 1 else None}
-            ops.conv(x, layer[0], layer[1], y, ksize=_K3, stride=(stride,) * 3, pad=_P3, in_scale=sc, in_shift=sh, in_relu=True, per_n=pn, stats=st,
-                     rows_per_group=pn * so ** 3 if st is not None else 0, finalize=so ** 3 if st is not None else None, **kw)
+        def launch(pairs, L=L, x=x, y=y, sc=sc, sh=sh, st=st):
+            net.run_layer(L, f"igemm{pairs}" if pairs else "cores", x, y, (sc, sh), st)
         fl = 2.0 * qn * so ** 3 * co * 27 * ci
-        old = "F(2x2,3x3)" if (stride == 1 and getattr(layer, "u", None) is not None) else "conv_igemm fp32"
+        old = "F(2x2,3x3)" if L.wino else "conv_igemm fp32"
         row(name, f"{s}^3 -> {so}^3, {ci} -> {co}, s{stride}, aff{' stats' if stats else ''}", old, lambda: launch(False), lambda: launch(3), fl)
-        ops.pair_filter_pack(layer[0])
         variants.append((name, old, {r: timed3(lambda r=r: launch(r)) for r in (0, 3, 4, 5)}))
         del x, y
 
-    from gen6d_amd.network.refiner import VOLUME_IGEMM_PAIR_LAYERS as routed
+    routed = {k.split(".", 1)[1]: int(r[5:]) for k, rs in refiner.ROUTES.items() for r in rs if r.startswith("igemm")}
     print(f"\n# {qn} volumes: loader variants of the pair mode, us per launch (best of 3 rounds of 10) +- spread (max - min of the rounds); "
           "variant 5 includes its affine_split16 pass")
     print("| layer | fp32-core route | us | pairs 3 (split in the loader) | pairs 4 (filters pre-split) | pairs 5 (both pre-split, + pass) | "
           "current route | decision |\n|---|---|---|---|---|---|---|---|")
     total = {"current": 0.0, "chosen": 0.0}
     for name, old, t in variants:
-        cur = (routed[name] if isinstance(routed, dict) else 3) if name in routed else 0
+        cur = routed.get(name, 0)
         best = min((4, 5, 3, 0), key=lambda r: t[r][0])
         take = best if (best != cur and t[cur][0] - t[best][0] > t[cur][1]) else cur
         total["current"] += t[cur][0]; total["chosen"] += t[take][0]

@@ -1,10 +1,11 @@
 """The 32^3 stage of the refiner's volume net launch by launch: today's fp32-core route (F(4x4,3x3) with the depth taps folded, the
 InstanceNorm affine in the operand prologue and the finalisation fused into the producing launch) against the fp16 hi / lo pair route
 (conv16w_kernel<3, ., 1, 3> with depth-folded filters + its hand-over passes), with the volume construction in front of both and conv2
-(16^3) as a candidate.
+(16^3) as a candidate — every layer through the product's own layer runner, hand-over pass and join (VolumeRefiner.run_layer / to_pairs /
+join) on the shapes of refiner.VOLUME.
     python tools/volume_layers.py [volumes=16]
-us per launch, the best of three rounds of 10, convs with direct-form TFLOP/s.  The table decides refiner.VOLUME_PAIR_LAYERS
-(profiles/r17_volume_pairs.md); run it with 1 volume for the single-query times (recorded, not routed on)."""
+us per launch, the best of three rounds of 10, convs with direct-form TFLOP/s.  The table decides the volume net's "pair" entries of
+refiner.ROUTES (profiles/r17_volume_pairs.md); run it with 1 volume for the single-query times (recorded, not routed on)."""
 import os
 import sys
 
@@ -18,8 +19,6 @@ from gen6d_amd import lib, ops, synth                           # noqa: E402
 from gen6d_amd.network import name2network, refiner             # noqa: E402
 from featnet_layers import timed                                # noqa: E402
 
-_K3, _P3 = (3, 3, 3), (1, 1, 1)
-
 
 def main():
     lib.load()
@@ -30,10 +29,10 @@ def main():
     net = name2network["refiner"]({"name": "volume_layers"}).eval()
     net.load_state_dict(synth.synth_state_dict("refiner"))
     net.to(dev)
-    pk = net._pack()
+    V = refiner.VOLUME
     big = qn >= refiner.F43_MIN_QUERIES
-    pn = 1 if qn > 1 else 0
-    table = ops.RangeTable(dev)
+    cores = refiner.resolve_routes(V, refiner.ROUTES, (sn,) * 3, big, False, False, {})               # the fp32 cores' kernel per layer
+    table = net.range_table()
     rng = lambda name: (table, table.slot(name))
     f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
     vox = sn ** 3
@@ -63,23 +62,18 @@ def main():
     total[0] += to; total[1] += tn
     mean32.uniform_(-0.5, 0.5); std32.uniform_(0.0, 0.5)
 
-    def conv32(x, layer, y, st=None, aff=None):
-        sc, sh = aff if aff is not None else (None, None)
-        return ops.conv(x, layer[0], layer[1], y, ksize=_K3, pad=_P3, in_scale=sc, in_shift=sh, in_relu=aff is not None, per_n=pn if aff is not None else 0,
-                        stats=st, rows_per_group=pn * vox if st is not None else 0, w_wino=layer.u, w_wino43=layer.u43 if big else None,
-                        finalize=vox if st is not None else None)
+    def conv32(x, layer, y, st=None, aff=None):                # (st: taken once, no zero-fill inside the timed launches)
+        return net.run_layer(layer, cores[layer.key], x, y, aff, st)
 
     def conv16(x, layer, y, st=None):
-        ops.conv16_direct_multi([x], layer.w16(3, layout=2), layer[1], relu=False, full=torch.float32, kd=3, stats=st, rows_per_group=vox if st is not None else 0,
-                                out_full=[y])
-        return ops.stats_finalize(st, vox) if st is not None else None
+        return net.run_layer(layer, "pair", x, y, None, st)
 
     kern = "F(4x4)" if big else "F(2x2)"
-    for name, ci, c_off, key in (("mean_embed", 256, 0, "mean"), ("var_embed", 128, 64, "std")):
-        l0, l1 = pk["v_" + name]
-        x32 = (mean32 if ci == 256 else std32).view(qn, sn, sn, sn, ci)
-        y0, y1 = f32(qn, sn, sn, sn, 64), f32(qn, sn, sn, sn, 64)
-        s0 = ops.new_stats(qn, 64, dev)
+    for (l0, l1), x32, key in zip(V.chains(), (mean32, std32), ("mean", "std")):           # the two embeds; l1.dst = (c_off in cat, 1)
+        name, ci, c_off = l0.key.split(".")[1], l0.cin, l1.dst[0]
+        x32 = x32.view(qn, sn, sn, sn, ci)
+        y0, y1 = f32(qn, sn, sn, sn, l0.cout), f32(qn, sn, sn, sn, l1.cout)
+        s0 = ops.new_stats(qn, l0.cout, dev)
         aff = {}
 
         def old_c0():
@@ -92,7 +86,7 @@ def main():
             aff["b"] = conv16(v16[key].view(qn, sn, sn, sn, 2, ci), l0, y0, st=s0)
 
         def new_mid():
-            v16["mid"] = ops.affine_split16(y0.view(qn * sn, 1, sn, sn, 64), aff["b"][0], aff["b"][1], sn, True, False, 3, rng=rng(name + ".mid"))
+            v16["mid"] = net.to_pairs(y0, aff["b"], l1.pass_slot)
 
         def new_c1():
             conv16(v16["mid"].view(qn, sn, sn, sn, 2, 64), l1, y1)
@@ -101,7 +95,7 @@ def main():
             conv16(v16["mid"].view(qn, sn, sn, sn, 2, 64), l1, cat32[..., c_off:c_off + 64])
 
         def new_end():
-            ops.affine_split16_to(y1.view(qn * sn, 1, sn, sn, 64), None, None, 0, False, 3, cat16, c_off)
+            net.join(y1, None, cat16, c_off, 1)
 
         fl0, fl1 = 2.0 * qn * vox * 64 * 27 * ci, 2.0 * qn * vox * 64 * 27 * 64
         rows = [(f"{name}.0 {ci}->64", f"{kern} +stats +finalize", old_c0, fl0, "conv16x3 folded +stats, stats_finalize", new_c0),
@@ -119,10 +113,10 @@ def main():
               f"into the fp32 cat: {tv:.0f} |", flush=True)
         del y0, y1
 
-    l = pk["v_conv0"]
+    l = V.layer("volume.conv0")
     y, st = f32(qn, sn, sn, sn, 64), ops.new_stats(qn, 64, dev)
     cat32.uniform_(-0.5, 0.5)
-    ops.affine_split16_to(cat32.view(qn * sn, 1, sn, sn, 128), None, None, 0, False, 3, cat16, 0)
+    net.join(cat32, None, cat16, 0, 1)
     fl = 2.0 * qn * vox * 64 * 27 * 128
     to, tn = row("conv0", "conv0 128->64", f"{kern} +stats +finalize", lambda: conv32(cat32, l, y, st=st), fl, "conv16x3 folded +stats, stats_finalize",
                  lambda: conv16(cat16.view(qn, sn, sn, sn, 2, 128), l, y, st=st))
@@ -131,24 +125,22 @@ def main():
 
     # candidate: conv2 (128 -> 128 at 16^3) — today it takes conv1's affine in its operand prologue; on pairs that is one more pass
     s2 = sn // 2
-    l = pk["v_conv2"]
+    l = V.layer("volume.conv2")
     x2, y2 = torch.rand((qn, s2, s2, s2, 128), device=dev) - 0.5, f32(qn, s2, s2, s2, 128)
     st1, st2 = ops.new_stats(qn, 128, dev), ops.new_stats(qn, 128, dev)
     sc = torch.rand((qn, 128), device=dev) + 0.5
     sh = torch.rand((qn, 128), device=dev) - 0.5
     fl = 2.0 * qn * s2 ** 3 * 128 * 27 * 128
-    if ops.conv16_direct_plan(qn, s2, s2, 128, 128, 3, stats_rows=s2 ** 3, D=s2) == 1:
+    N, H, W, ci, co, rows, D = refiner.admission_shapes(V, {l.key: ("pair",)}, qn, (sn,) * 3)[l.key]
+    if ops.conv16_direct_plan(N, H, W, ci, co, 3, stats_rows=rows, D=D) == 1:
         def old2():
-            ops.conv(x2, l[0], l[1], y2, ksize=_K3, pad=_P3, in_scale=sc, in_shift=sh, in_relu=True, per_n=pn, stats=st1, rows_per_group=pn * s2 ** 3,
-                     w_wino=l.u, w_wino43=None, finalize=s2 ** 3)
+            conv32(x2, l, y2, st1, (sc, sh))
 
         def new2_in():
-            v16["x2"] = ops.affine_split16(x2.view(qn * s2, 1, s2, s2, 128), sc, sh, s2, True, False, 3, rng=rng("conv2.in"))
+            v16["x2"] = net.to_pairs(x2, (sc, sh), l.pass_slot)
 
         def new2():
-            ops.conv16_direct_multi([v16["x2"].view(qn, s2, s2, s2, 2, 128)], l.w16(3, layout=2), l[1], relu=False, full=torch.float32, kd=3, stats=st2,
-                                    rows_per_group=s2 ** 3, out_full=[y2])
-            ops.stats_finalize(st2, s2 ** 3)
+            conv16(v16["x2"], l, y2, st2)
         row("conv2 (candidate)", "IN affine + ReLU", "(operand prologue)", None, 0.0, "affine_split16", new2_in)
         to, tn = row("conv2 (candidate)", "conv2 128->128 @16^3", "F(2x2) aff +stats +finalize", old2, fl, "conv16x3 folded +stats, stats_finalize", new2)
         tb = timed(lambda: [new2_in(), new2()])
