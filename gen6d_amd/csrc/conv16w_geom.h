@@ -1,5 +1,6 @@
-// conv16w_geom.h — the integer geometry of the halo-patch kernel (conv16w_kernel, conv16_direct.hip) in one place, for the device and
-// for the host (the launcher fills Tiling; tests/conv16w_geom_shim.cpp builds this header with g++ and checks it against plain division).
+// conv16w_geom.h — the integer geometry of the halo-patch kernel (conv16w_kernel, conv16w.hip) in one place, for the device and for the
+// host (c16w_admit fills Tiling through halo_tiling; tests/conv16w_geom_shim.cpp builds this header with g++ and checks it against plain
+// division and against a model of the tiling choice).
 //   tile index            -> (first tall-image row, first column, first image row, rows inside the image, interior?)
 //   (piece index, lane)   -> (patch row, patch column, band, row inside the band, LDS slot), validity, 32-bit buffer offset
 //   tile pixel            -> patch pixel of tap (0, 0) (the fragment base)
@@ -40,7 +41,7 @@ C16G_HD unsigned div31(unsigned n, unsigned m) { return mulhi(n << 1, m); }
 C16G_HD unsigned recip16(unsigned d) { return (65536u + d - 1) / d; }
 C16G_HD unsigned div16(unsigned n, unsigned m) { return (n * m) >> 16; }
 
-struct Tiling {       // one segment's halo tiling (c16_halo_tiling); h_: halo, beside the per-tap kernels' tiling in C16Seg
+struct Tiling {       // one segment's halo tiling (halo_tiling below); h_: halo, beside the per-tap kernels' tiling in C16Seg
   int h_tw_log2, h_tiles_x, h_tile0, h_tpi;      // tile width, tiles per row, first tile of the segment, tiles per image (0: tiles of whole small images)
   int h_segh_log2, h_bands;                // rows per band (min(H, TH): a power of two), bands per tile (TH / segh: > 1 when a tile holds several images)
   int h_swa, h_swd;                        // LDS slot swizzle: ((pcol >> swa) + prow * swd) & 3
@@ -58,6 +59,50 @@ C16G_HD bool finish(Tiling& t, long ntiles) {
   t.h_r_tx = recip31((unsigned)t.h_tiles_x); t.h_r_tpi = t.h_tpi > 0 ? recip31((unsigned)t.h_tpi) : 0u;
   if (ntiles >= (1L << 31)) return false;
   return recip31_ok((unsigned)t.h_tiles_x, (unsigned)ntiles) && (t.h_tpi <= 0 || recip31_ok((unsigned)t.h_tpi, (unsigned)ntiles));
+}
+
+// Tiling of one segment (N maps of H x W) for the halo-patch kernel: the tile width (32 / 16 / 8 / 4) with the least overhang; false if
+// none fits (a map lower than the tile must divide it: tiles of whole images).  pairs: the fp16 pair kernel's slot swizzle (its fragment
+// reads differ); in_image: only tilings whose tiles lie inside one image (depth-folded layers: N counts planes, and a tile must not span
+// two).  Fills o (all but h_tile0) and the segment's tile count.
+C16G_HD bool halo_tiling(int N, int H, int W, bool pairs, bool in_image, Tiling& o, int& tiles) {
+  double best = 1e30;
+  bool found = false;
+  for (int tw = 32; tw >= 4; tw >>= 1) {
+    const int th = BM / tw, tx = (W + tw - 1) / tw;
+    long nt; int tpi, segh, bands;
+    if (H >= th) { tpi = tx * ((H + th - 1) / th); nt = (long)N * tpi; segh = th; bands = 1; }
+    else {
+      if (th % H || in_image) continue;
+      tpi = 0; nt = (long)tx * (((long)N * H + th - 1) / th); segh = H; bands = th / H;
+    }
+    if (bands * (segh + 2) * (tw + 2) > 288) continue;
+    const double waste = (double)nt * BM / ((double)N * H * W);
+    if (waste < best - 1e-9) {
+      best = waste; found = true;
+      int l2 = 0; while ((1 << l2) < tw) ++l2;
+      int sl2 = 0; while ((1 << sl2) < segh) ++sl2;           // (segh = TH or a divisor of it: a power of two)
+      o.h_tw_log2 = l2; o.h_tiles_x = tx; o.h_tpi = tpi; o.h_segh_log2 = sl2; o.h_bands = bands;
+      tiles = (int)nt;
+      // conflict-free slot swizzles found by tools/ubench/conv16_swizzle.py: ((pcol >> a) + prow * d) & (slots - 1)  (64-byte patch rows:
+      // 4 slots).  The pair kernel reads 16 pixels x 4 slots per 16 lanes (16x16x32 fragments), the 16-bit modes 32 pixels x 2 slots;
+      // the pair kernel relies on d = 0 and a <= 2
+      if (pairs) { o.h_swa = tw >= 16 ? 1 : 0; o.h_swd = 0; }
+      else { o.h_swa = tw == 32 ? 2 : (tw == 16 ? 1 : 0); o.h_swd = tw <= 8 ? 1 : 0; }
+    }
+  }
+  // patch size and the reciprocals that replace the kernel's divisions (exact for every tile index of the segment, or no halo tiling)
+  return found && finish(o, tiles);
+}
+
+// The per-tap kernels' tile width for maps W wide: the power of two in 4 .. 64 with the least column overhang, ties -> the wider tile
+C16G_HD int pick_tw(int W) {
+  int best = 8; double bw = 1e9;
+  for (int tw = 64; tw >= 4; tw >>= 1) {
+    const double waste = (double)((W + tw - 1) / tw * tw) / W;
+    if (waste < bw - 1e-9) { bw = waste; best = tw; }
+  }
+  return best;
 }
 
 struct Tile {         // one 128-pixel tile (block-uniform)

@@ -72,7 +72,7 @@ __device__ __forceinline__ void store_pair(float* row, int seg, f32x4 u) {
 //     A lane's fragment of v_mfma_f32_32x32x16_f16 is 8 consecutive channels of one plane: ONE ds_read_b128 at row * 144 + 64 plane +
 //     32 ks + 16 (lane >> 5) — the address pattern of the fp32 fragments (row * 36 + 8 kc + 4 (lane >> 5) floats), so conflict-free the
 //     same way — and nothing is converted at the use site.  Per 16 channels and accumulator: hi x hi, hi x lo, lo x hi (lo x lo dropped,
-//     as around c16_mfma<3> (pair16.h) in conv16_direct.hip and corr16.hip).  The accumulators (and split partials) stay unscaled fp32 sums of the scaled operands; the
+//     as around c16_mfma<3> (pair16.h) in conv16_tap.hip and corr16.hip).  The accumulators (and split partials) stay unscaled fp32 sums of the scaled operands; the
 //     epilogue multiplies by 2^(e_in - w_exp).  The largest |activation| after the prologue is recorded (G6dRange16, one atomic per block).
 //     4 / 5 = the same LDS image, fragment reads, MFMA sequence, split-K finish and epilogue as 3 with operands that arrive PRE-SPLIT, so the
 //     loader copies instead of converting (the split costs ~25 vector instructions per 4-channel row piece, in every K step of every block):

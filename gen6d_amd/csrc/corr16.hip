@@ -1,6 +1,6 @@
 // corr16.hip — corr16_kernel: the detector's K x K correlation (K = 15, 7; reference network/detector.py:188-197,222-224: the query's
 // feature map correlated with the 32 reference-centre features) on 16-bit activations — the halo-patch scheme of conv16w_kernel
-// (conv16_direct.hip) with K^2 taps per patch.  Cout = 32 (the reference views), so a 128-pixel tile has ONE wave's worth of output
+// (conv16w.hip) with K^2 taps per patch.  Cout = 32 (the reference views), so a 128-pixel tile has ONE wave's worth of output
 // channels: the block's NW = 11 computing waves (three per SIMD with the loader, 150 registers each) split the TAPS of every slice (wave w:
 // taps w, w + NW, ...), each accumulates its partial 128 px x 32 ch sums over all slices, and the partials are added through LDS at the
 // end.  One more wave requests the patches (see inside).  Every index below comes from corr16_geom.h, which the host tests.

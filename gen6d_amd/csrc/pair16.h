@@ -14,7 +14,7 @@ template <> struct C16T<1> { typedef __bf16 T; typedef bf16x8 V; };
 template <> struct C16T<2> { typedef _Float16 T; typedef f16x8 V; };
 template <int MM> struct C16T3 { typedef typename C16T<MM == 3 ? 2 : MM>::T T; typedef typename C16T<MM == 3 ? 2 : MM>::V V; };
 
-// What the 16-bit kernels (conv16_direct.hip, corr16.hip) share: the 32x32x16 MFMA of a mode (pairs: of its fp16 planes), the buffer
+// What the 16-bit kernels (conv16_tap.hip, conv16w.hip, corr16.hip) share: the 32x32x16 MFMA of a mode (pairs: of its fp16 planes), the buffer
 // descriptor of their LDS-DMA and buffer loads, and the offset that always lies beyond it (the out-of-range zero fill).
 template <int MM>
 __device__ __forceinline__ f32x16 c16_mfma(typename C16T3<MM>::V a, typename C16T3<MM>::V b, f32x16 c) {

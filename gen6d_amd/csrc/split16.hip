@@ -1,4 +1,4 @@
-// split16.hip — the hand-over passes into the 16-bit activation formats of conv16_direct.hip's kernels (pair16.h: bf16 / fp16 maps and the
+// split16.hip — the hand-over passes into the 16-bit activation formats of the conv16_direct.hip family's kernels (conv16_tap.hip, conv16w.hip) (pair16.h: bf16 / fp16 maps and the
 // fp16 hi / lo pair maps of the fp32 path): four HBM-bound elementwise kernels that write an fp32 result ONCE in the format the next conv's
 // DMA loads take, and their launchers.  The three grid-stride kernels end in c16_store8; l2norm_split16_kernel keeps its paired-lane store.
 #include "g6d_common.h"

@@ -182,8 +182,8 @@ class TrunkLayer(tuple):
         key = ("direct", mode)
         if key not in self._u16:
             co, ci = self._w.shape[:2]
-            # bf16 / fp16: both operand tiles through LDS (measured 9 % faster than filters in registers: the register variant pulls every
-            # filter fragment once per wave instead of once per block, profiles/r06_conv16_bench.md); pairs: fragment-major filters in registers
+            # every mode: fragment-major filters (layout 1), which go straight into registers — the halo-patch kernel (csrc/conv16w.hip) where
+            # the map has a halo tiling, else the per-tap kernel that keeps the filters out of LDS (conv16r_kernel, csrc/conv16_tap.hip)
             self._u16[key] = ops.conv16_pack(self._w.permute(0, 2, 3, 1).reshape(co, 9, ci).contiguous(), mode, layout=1)
         return self._u16[key]
 

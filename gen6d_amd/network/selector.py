@@ -229,7 +229,7 @@ class ViewpointSelector(ParamBank):
                                                 out_full=[out[q0 * D:q1 * D, 0]])
                     res, fin = out, None
                 elif mode16:
-                    # round 6: the product layer on the direct 16-bit convolution (csrc/conv16_direct.hip): the normalised query x reference
+                    # round 6: the product layer on the direct 16-bit convolution (csrc/conv16_direct.hip, halo-patch kernel csrc/conv16w.hip): the normalised query x reference
                     # product is written once in the kernel's activation format (csrc/split16.hip; fp32 path: fp16 hi / lo pairs, fp32-class results), the conv
                     # adds this level's InstanceNorm sums in its epilogue, the affine of that norm comes from one small finalize launch
                     prod = ops.product_split16(cache.view(D, h * w, 512), q.view(qn, h * w, 512), scale, shift, mode16, **self._rng_kw(mode16, f"prod{l}"))

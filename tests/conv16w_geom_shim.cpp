@@ -4,7 +4,7 @@
 using namespace c16g;
 extern "C" {
 int g_sizeof_tiling() { return (int)sizeof(Tiling); }
-// a tiling as c16_halo_tiling fills it; returns finish()'s verdict for tile indices below ntiles
+// a tiling as halo_tiling fills it; returns finish()'s verdict for tile indices below ntiles
 int g_tiling(int tw_log2, int tiles_x, int tpi, int segh_log2, int bands, int swa, int swd, long ntiles, Tiling* out) {
   Tiling t = {};
   t.h_tw_log2 = tw_log2; t.h_tiles_x = tiles_x; t.h_tile0 = 0; t.h_tpi = tpi; t.h_segh_log2 = segh_log2; t.h_bands = bands; t.h_swa = swa; t.h_swd = swd;
@@ -13,6 +13,18 @@ int g_tiling(int tw_log2, int tiles_x, int tpi, int segh_log2, int bands, int sw
   return ok ? 1 : 0;
 }
 int g_patch_pixels(const Tiling* tl) { return tl->h_P; }
+// the launcher's own choice for a segment of N maps of H x W: halo_tiling's verdict, the tiling it filled, and
+// out8 = tw_log2, tiles_x, tpi, segh_log2, bands, swa, swd, tile count
+int g_halo_tiling(int N, int H, int W, int pairs, int in_image, Tiling* tl, int* out8) {
+  Tiling t = {};
+  int tiles = 0;
+  const bool ok = halo_tiling(N, H, W, pairs != 0, in_image != 0, t, tiles);
+  *tl = t;
+  out8[0] = t.h_tw_log2; out8[1] = t.h_tiles_x; out8[2] = t.h_tpi; out8[3] = t.h_segh_log2; out8[4] = t.h_bands; out8[5] = t.h_swa; out8[6] = t.h_swd;
+  out8[7] = tiles;
+  return ok ? 1 : 0;
+}
+int g_pick_tw(int W) { return pick_tw(W); }
 // tiles t0 .. t0 + n - 1 -> [n][5]: g0, x0, y0, ylim, interior
 void g_tiles(const Tiling* tl, int H, int W, int t0, int n, int* out) {
   for (int i = 0; i < n; ++i) {

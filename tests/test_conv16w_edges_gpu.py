@@ -29,7 +29,7 @@ def _rand(g, *shape, scale=1.0):
 
 
 def _halo_tw(N, H, W):
-    """The tile width c16_halo_tiling picks (least overhang, ties to the wider tile)."""
+    """The tile width c16g::halo_tiling picks (least overhang, ties to the wider tile)."""
     best, res = 1e30, None
     for tw in (32, 16, 8, 4):
         th, tx = 128 // tw, -(-W // tw)

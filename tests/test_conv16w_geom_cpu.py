@@ -2,7 +2,8 @@
 32-bit offset, tile pixel -> fragment base, all without run-time division), built for the host (tests/conv16w_geom_shim.cpp) and compared
 with the plain-division formulas the kernel used before, written out here with // and %.  Exhaustive over the tile widths 4 / 8 / 16 / 32,
 bands of 1 .. 32 rows and maps at least a tile high, every piece index a wave can hold and every lane, and every tile index of the
-headline launches (5120 maps of 16x16 for Cout = 64, the pyramid of 16 queries).  No GPU needed."""
+headline launches (5120 maps of 16x16 for Cout = 64, the pyramid of 16 queries).  The launcher's own choice of tile width, bands and slot
+swizzle (c16g::halo_tiling in the same header) is called through the shim and compared with the Python model below.  No GPU needed."""
 import ctypes as C
 import os
 import subprocess
@@ -26,15 +27,17 @@ def geo(tmp_path_factory):
     lib.g_pieces.argtypes = [C.c_void_p] + [C.c_int] * 6 + [I32]
     lib.g_frag.argtypes = [C.c_void_p, I32]
     lib.g_patch_pixels.argtypes = [C.c_void_p]
+    lib.g_halo_tiling.argtypes = [C.c_int] * 5 + [C.c_void_p, I32]
     lib.g_div31.argtypes = [U32, U32, C.c_int, U32, I32]
     lib.g_div16.argtypes = [U32, U32, C.c_int, U32]
     return lib
 
 
 class Tiling:
-    """One segment (N maps of H x W) tiled with tiles of width tw, as c16_halo_tiling lays it out; None if that width does not fit."""
+    """One segment (N maps of H x W) tiled with tiles of width tw, as c16g::halo_tiling lays it out; fits: that width is admissible
+    (in_image: only with tiles inside one image)."""
 
-    def __init__(self, N, H, W, tw, pairs=True):
+    def __init__(self, N, H, W, tw, pairs=True, in_image=False):
         th = BM // tw
         self.N, self.H, self.W, self.tw, self.th = N, H, W, tw, th
         self.tiles_x = -(-W // tw)
@@ -44,7 +47,7 @@ class Tiling:
         else:
             self.tpi = 0
             self.ntiles, self.segh, self.bands = self.tiles_x * -(-(N * H) // th), H, th // H
-        self.fits = (H >= th or th % H == 0) and self.bands * (self.segh + 2) * (tw + 2) <= 288
+        self.fits = (H >= th or (th % H == 0 and not in_image)) and self.bands * (self.segh + 2) * (tw + 2) <= 288
         if pairs:
             self.swa, self.swd = (1 if tw >= 16 else 0), 0
         else:
@@ -70,11 +73,11 @@ class Tiling:
         return ty * self.th, tx * self.tw, 0 * t, 0 * t + self.th
 
 
-def halo_tiling(N, H, W, pairs=True):
-    """c16_halo_tiling's choice: the width with the least overhang, ties to the wider tile."""
+def halo_tiling(N, H, W, pairs=True, in_image=False):
+    """The independent model of c16g::halo_tiling's choice: the width with the least overhang, ties to the wider tile."""
     best, res = 1e30, None
     for tw in (32, 16, 8, 4):
-        t = Tiling(N, H, W, tw, pairs)
+        t = Tiling(N, H, W, tw, pairs, in_image)
         if not t.fits:
             continue
         waste = t.ntiles * BM / (N * H * W)
@@ -167,6 +170,59 @@ def test_layouts_exhaustive(geo):
         assert _check_tiles(geo, tl, tl.make(geo)[0])[4, 4] == 1
         tl = Tiling(1, 2 * th, 2 * tw, tw)
         assert not _check_tiles(geo, tl, tl.make(geo)[0])[:, 4].any()
+
+
+def _real_choice(geo, N, H, W, pairs, in_image):
+    """c16g::halo_tiling itself (the function the launcher calls): None, or its tiling as a dict and the buffer it filled."""
+    buf = C.create_string_buffer(geo.g_sizeof_tiling())
+    out = np.zeros(8, np.int32)
+    if not geo.g_halo_tiling(N, H, W, int(pairs), int(in_image), buf, out.ctypes.data_as(I32)):
+        return None, buf
+    keys = ("tw_log2", "tiles_x", "tpi", "segh_log2", "bands", "swa", "swd", "tiles")
+    return dict(zip(keys, out.tolist())), buf
+
+
+def _assert_choice_matches_model(geo, N, H, W, pairs, in_image):
+    got, buf = _real_choice(geo, N, H, W, pairs, in_image)
+    want = halo_tiling(N, H, W, pairs, in_image)
+    # fits: the real function finds a tiling exactly where the model has a width that fits
+    assert (got is not None) == (want is not None), (N, H, W, pairs, in_image)
+    if want is None:
+        return 0
+    assert got == dict(tw_log2=want.tw.bit_length() - 1, tiles_x=want.tiles_x, tpi=want.tpi, segh_log2=want.segh.bit_length() - 1, bands=want.bands,
+                       swa=want.swa, swd=want.swd, tiles=want.ntiles), (N, H, W, pairs, in_image)
+    assert 1 << got["segh_log2"] == want.segh and geo.g_patch_pixels(buf) == want.P
+    if in_image:
+        assert got["tpi"] > 0 and got["bands"] == 1
+    return 1
+
+
+def test_real_chooser_matches_model(geo):
+    """The launcher's tiling choice (c16g::halo_tiling, through the shim) against the Python model above, over the shape set of
+    test_layouts_exhaustive and the headline shapes: width, bands, rows per band, tiles, swizzle, fits — pair and 16-bit mode, with and
+    without in_image."""
+    shapes = set(HEADLINE)
+    for tw in (4, 8, 16, 32):
+        th = BM // tw
+        heights = [h for h in (1, 2, 4, 8, 16, 32) if h < th] + [th, th + 1, 2 * th + 3, 3 * th, 4 * th - 1]
+        shapes |= {(N, H, W) for H in heights for W in (tw, tw + 1, 3 * tw - 1, 3 * tw, 3 * tw + 2) for N in (1, 5)}
+    shapes |= {(3, H, 8) for H in (3, 5, 6, 7, 12)}            # heights that divide no tile: banded forms must not be chosen
+    n = {}
+    for pairs in (True, False):
+        for in_image in (False, True):
+            n[pairs, in_image] = sum(_assert_choice_matches_model(geo, N, H, W, pairs, in_image) for N, H, W in sorted(shapes))
+    assert min(n.values()) > 250 and n[True, False] > n[True, True], n   # (in_image turns the banded tilings away)
+
+
+def test_choosers_under_sanitizers(tmp_path):
+    """The choosers are host code the launcher runs on caller-supplied sizes: a stand-alone program (no Python in the process) walks them
+    over small shapes exhaustively and over the extremes a launch admits, built with the address and undefined-behaviour sanitizers."""
+    exe = str(tmp_path / "geom_san")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "conv16w_geom_sanitize.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert " 0 broken" in r.stdout, r.stdout[-2000:]
 
 
 HEADLINE = [

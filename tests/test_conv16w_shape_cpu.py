@@ -1,8 +1,9 @@
 """The halo-patch kernel's instruction shapes and LDS swizzle, checked without a GPU.
 (1) conv16w_kernel<3, *> (fp16 hi / lo pairs) runs on v_mfma_f32_16x16x32_f16 only; the 16-bit modes (MM = 1 / 2) stay on the 32x32x16 forms.
 (2) A model of the ds_read_b128 lane groups: the pair kernel's slot swizzle is conflict-free for every tile width and banded layout of
-c16_halo_tiling and every tap shift, and the address the kernel reads (one swizzle term per tap column, shared by its eight m-tiles)
+c16g::halo_tiling and every tap shift, and the address the kernel reads (one swizzle term per tap column, shared by its eight m-tiles)
 finds the logical slot the patch fill put there."""
+import ctypes as C
 import itertools
 import os
 import re
@@ -20,7 +21,7 @@ GROUPS += [[l + 32 for l in g] for g in GROUPS]
 
 
 def _pair_swizzle(tw):
-    """(swa, swd) of c16_halo_tiling for the pair kernel."""
+    """(swa, swd) of c16g::halo_tiling for the pair kernel."""
     return (1 if tw >= 16 else 0), 0
 
 
@@ -61,16 +62,32 @@ def test_pair_swizzle_conflict_free_and_consistent():
     assert n == 12 * 8 * 9 * 4
 
 
-def test_halo_tiling_pair_swizzle_matches_model():
-    """The values the model checks are the ones c16_halo_tiling assigns in pair mode."""
-    src = open(os.path.join(ROOT, "gen6d_amd", "csrc", "conv16_direct.hip")).read()
-    assert re.search(r"if \(pairs\) \{ o\.h_swa = tw >= 16 \? 1 : 0; o\.h_swd = 0; \}", src)
+def test_halo_tiling_pair_swizzle_matches_model(tmp_path):
+    """The values the model checks are the ones the launcher's chooser (c16g::halo_tiling, called through tests/conv16w_geom_shim.cpp)
+    assigns in pair mode, for every tile width and banded layout of the model."""
+    so = str(tmp_path / "conv16w_geom.so")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", os.path.join(ROOT, "tests", "conv16w_geom_shim.cpp"), "-o", so], check=True)
+    geo = C.CDLL(so)
+    geo.g_halo_tiling.argtypes = [C.c_int] * 5 + [C.c_void_p, C.POINTER(C.c_int)]
+    buf = C.create_string_buffer(geo.g_sizeof_tiling())
+    seen = set()
+    for tw, segh in _layouts():
+        # maps exactly one tile wide and segh high, whole tiles of them: the chooser takes width tw (no overhang, ties to the wider tile)
+        out = (C.c_int * 8)()
+        assert geo.g_halo_tiling(2 * (128 // tw // segh), segh, tw, 1, 0, buf, out) == 1
+        tw_log2, segh_log2, swa, swd = out[0], out[3], out[5], out[6]
+        assert (1 << tw_log2, 1 << segh_log2) == (tw, segh)
+        assert (swa, swd) == _pair_swizzle(tw), (tw, segh)
+        assert swd == 0 and swa <= 2
+        seen.add(tw)
+    assert seen == {4, 8, 16, 32}
+    shutil.rmtree(tmp_path, ignore_errors=True)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_conv16w_mfma_shapes(tmp_path):
     out = tmp_path / "conv16.s"
-    src = os.path.join(ROOT, "gen6d_amd", "csrc", "conv16_direct.hip")
+    src = os.path.join(ROOT, "gen6d_amd", "csrc", "conv16w.hip")
     r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-w", "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
                         "-o", str(out), src], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

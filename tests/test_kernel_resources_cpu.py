@@ -16,7 +16,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_conv16w_has_no_spills(tmp_path):
     out = tmp_path / "conv16.s"
-    src = os.path.join(ROOT, "gen6d_amd", "csrc", "conv16_direct.hip")
+    src = os.path.join(ROOT, "gen6d_amd", "csrc", "conv16w.hip")
     r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-w", "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"),
                         "-o", str(out), src], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

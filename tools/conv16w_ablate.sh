@@ -6,9 +6,9 @@ cd "$(dirname "$0")/.."
 D=gen6d_amd/csrc/_abl
 if [ "$1" = build ]; then
   mkdir -p $D
-  OTHERS=$(ls gen6d_amd/csrc/*.o | grep -v conv16_direct.o)
+  OTHERS=$(ls gen6d_amd/csrc/*.o | grep -v conv16w.o)
   for a in ${ABL:-1 2 3 4 7}; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DC16W_ABLATE=$a -c gen6d_amd/csrc/conv16_direct.hip -o $D/conv16_abl$a.o &&
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DC16W_ABLATE=$a -c gen6d_amd/csrc/conv16w.hip -o $D/conv16_abl$a.o &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OTHERS $D/conv16_abl$a.o -o $D/libg6d_c16w_abl$a.so && rm $D/conv16_abl$a.o
   done
 else

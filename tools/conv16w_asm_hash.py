@@ -1,10 +1,10 @@
 """Per-kernel hashes of the conv16w_kernel instantiations in two device-assembly files, to show that a change left an instantiation's
 code as it was:
-    hipcc -O3 -std=c++17 --offload-arch=gfx950 -w -S --cuda-device-only -I include -o new.s gen6d_amd/csrc/conv16_direct.hip   (both trees)
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -w -S --cuda-device-only -I include -o new.s gen6d_amd/csrc/conv16w.hip   (both trees)
     python tools/conv16w_asm_hash.py old.s new.s [kernel-name pattern]
 The optional third argument is a regular expression for the kernels' (mangled) names, default conv16w_kernel: `kernel` covers every
-kernel of a translation unit, whichever file the two assembly files were built from.  The tool also serves gen6d_amd/csrc/corr16.hip
-(pattern corr16_kernel), and a kernel that moved between files: old.s and new.s need not come from the same source file.
+kernel of a translation unit, whichever file the two assembly files were built from.  The tool also serves gen6d_amd/csrc/conv16_tap.hip
+(pattern conv16r?_kernel) and gen6d_amd/csrc/corr16.hip (pattern corr16_kernel), and a kernel that moved between files: old.s and new.s need not come from the same source file.
 Instructions and directives only: comments, block-label numbering and the kernel's own mangled name are normalised, and a trailing
 KD = 1 template argument is dropped from the name, so that an instantiation keeps its key when the template gains that parameter."""
 import re, sys, hashlib

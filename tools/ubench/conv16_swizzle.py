@@ -1,6 +1,6 @@
 """LDS slot swizzle search for the halo-patch kernel (conv16w_kernel): patch rows of 64 B (4 slots of 16 B); physical slot s of patch
 (row, column) holds logical slot s ^ sw(row, column), sw = ((column >> a) + row * d) & 3.  For every tile width and banded layout of
-c16_halo_tiling, all nine tap shifts and every ds_read_b128 lane group (4 x 16 lanes, one LDS cycle each when the 16 lanes hit 16
+c16g::halo_tiling (csrc/conv16w_geom.h), all nine tap shifts and every ds_read_b128 lane group (4 x 16 lanes, one LDS cycle each when the 16 lanes hit 16
 distinct 16-byte bank slots), prints the LDS cycles per lane group (1 = conflict-free) of the best (a, d) for the two read patterns:
   16-bit modes (32x32x16 fragments): lane l reads tile pixel 32 mt + (l & 31), logical slot 2 ks + (l >> 5);
   fp16 pairs (16x16x32 fragments):   lane l reads tile pixel 16 mt + (l & 15), logical slot l >> 4."""
