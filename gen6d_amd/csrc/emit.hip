@@ -11,6 +11,8 @@
 // block-uniform.  A tile with an empty list (almost every tile) is a convert-and-copy: three dword loads per thread and row where the
 // canvas rows are dword-aligned, dword / dwordx4 stores where the sink's are.  Only listed primitives are tested per pixel.  A thread's
 // 8 pixels live in 8 scalar words (a byte array here was moved to LDS by the compiler); no scratch (tests/test_emit_cpu.py).
+// Sinks of the formats after NV12 (I420 / YV12, YUYV422 / UYVY422) and of the full-range matrices walk their tiles in a loop of their own
+// (block-uniform, ahead of the loop every other sink runs) and store through emit_common.h's store_rows_x.
 #include "emit_common.h"
 #include "pose_algebra.h"
 
@@ -31,6 +33,42 @@ __device__ __forceinline__ Row fill_row(const unsigned char* __restrict__ imgs, 
   return r;
 }
 
+// The tile walk of an extended sink (TWIN of frame_emit_kernel's prologue and loop: the same box, style, cull, fill and paint steps, with
+// emit_common.h's store_rows_x at the end; they must stay in step)
+__device__ __forceinline__ void ext_walk(const G6dSink& k, const unsigned char* __restrict__ imgs, int B, int H, int W, const int* __restrict__ pts,
+                                         const int* __restrict__ valid, int tile0, int tiles, int (*sp)[4], int* sn) {
+  const int t = threadIdx.x, slot = k.slot, sw = k.width, sh = k.height;
+  const int tiles_x = (sw + TW - 1) / TW, ntiles = tiles_x * ((sh + TH - 1) / TH);
+  const int pw = max(min(k.pic_w, W), 0), ph = max(min(k.pic_h, H), 0);
+  const int th = k.thickness, rad = k.dot_radius;
+  const bool draw = (k.box == 0 || k.box == 1) && valid[(size_t)k.box * B + slot] != 0;
+  const int* q = pts + (draw ? ((size_t)k.box * B + slot) * 16 : 0);
+  const long long th2 = (long long)th * th;
+  const int rad2 = rad * rad;
+  const unsigned line = swap1((unsigned)k.line_rgb & 0xffffffu), dot = swap1((unsigned)k.dot_rgb & 0xffffffu);
+  const FwdX fx = forward_matrix_x(k.matrix);
+  for (int tile = tile0; tile < ntiles; tile += tiles) {   // (block-uniform trip count)
+    const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
+    if (t < 64) cull_tile(sp, sn, t, draw, q, th, th2, rad, X0, Y0, pw, ph);
+    __syncthreads();
+    const int X = X0 + ((t & 31) << 2), Y = Y0 + ((t >> 5) << 1);
+    if (X < sw && Y < sh) {
+      const int ne = sn[0], n = sn[1];
+      Row r0 = fill_row(imgs, slot, H, W, X, Y, pw, ph), r1 = fill_row(imgs, slot, H, W, X, Y + 1, pw, ph);
+      if (n > 0) {
+        unsigned e0 = 0, e1 = 0, d0 = 0, d1 = 0;
+        cover(sp, ne, n, X, Y, th2, rad2, e0, e1, d0, d1);
+        const unsigned in = X + 4 <= pw ? 15u : (X < pw ? (1u << (pw - X)) - 1u : 0u);
+        const unsigned in0 = Y < ph ? in : 0u, in1 = Y + 1 < ph ? in : 0u;
+        paint(r0, e0 & in0, d0 & in0, line, dot);
+        paint(r1, e1 & in1, d1 & in1, line, dot);
+      }
+      store_rows_x(k, r0, r1, X, Y, fx);
+    }
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(256) frame_emit_kernel(const G6dSink* __restrict__ sinks, const unsigned char* __restrict__ imgs, int B,
                                                          int H, int W, const int* __restrict__ pts, const int* __restrict__ valid,
                                                          int tiles) {
@@ -40,6 +78,9 @@ __global__ void __launch_bounds__(256) frame_emit_kernel(const G6dSink* __restri
   const G6dSink& k = sinks[si];
   const int slot = k.slot, sw = k.width, sh = k.height;
   if (slot < 0 || slot >= B || sw < 1 || sh < 1) return;  // (block-uniform)
+  // (block-uniform) A sink of the formats after NV12 or of a full-range matrix: a tile walk of its own, entered before anything below is
+  // computed, so that the rest of this kernel is compiled from the lines and the live values it had before that walk existed
+  if (extended_sink(k)) { ext_walk(k, imgs, B, H, W, pts, valid, tile0, tiles, sp, sn); return; }
   const int t = threadIdx.x;
   const int tiles_x = (sw + TW - 1) / TW, ntiles = tiles_x * ((sh + TH - 1) / TH);
   const int pw = max(min(k.pic_w, W), 0), ph = max(min(k.pic_h, H), 0);

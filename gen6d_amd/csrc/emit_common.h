@@ -175,4 +175,90 @@ __device__ __forceinline__ void store_rows(const G6dSink& k, Row r0, Row r1, int
   }
 }
 
+// ---- sinks of the formats after NV12 and of the full-range matrices (header) ----
+// Both kernels send such a sink here on a block-uniform test and keep the code above, as it was measured, for everything else.
+__device__ __forceinline__ bool extended_sink(const G6dSink& k) { return k.format > G6D_FMT_NV12 || (k.format == G6D_FMT_NV12 && k.matrix > 1); }
+// sat8(v >> sh) clamped BEFORE the shift: the form emit_source.hip needs (see sat8s20 there), used for every conversion below
+__device__ __forceinline__ unsigned satsh(int v, int sh) { return (unsigned)(min(max(v, 0), (256 << sh) - 1) >> sh); }
+
+// a forward matrix and the constant of its Y row: 2^19 + 16 2^20 limited range, 2^19 full range
+struct FwdX { Fwd m; int yadd; };
+__device__ __forceinline__ FwdX forward_matrix_x(int matrix) {
+  if (matrix < 2) return FwdX{forward_matrix(matrix == 1), (1 << 19) + (16 << 20)};
+  const bool m709 = (matrix & 1) != 0;
+  return FwdX{Fwd{m709 ? 222927 : 313524, m709 ? 749942 : 615514, m709 ? 75707 : 119538,
+                  m709 ? -120138 : -176932, m709 ? -404150 : -347356, 524288,
+                  524288, m709 ? -476214 : -439026, m709 ? -48074 : -85262}, 1 << 19};
+}
+__device__ __forceinline__ unsigned luma_x(unsigned p, const FwdX& f) {
+  return satsh(f.m.cyr * (int)(p & 255u) + f.m.cyg * (int)((p >> 8) & 255u) + f.m.cyb * (int)(p >> 16) + f.yadd, 20);
+}
+__device__ __forceinline__ unsigned luma4_x(const Row& r, const FwdX& f) {
+  return luma_x(r.a, f) | (luma_x(r.b, f) << 8) | (luma_x(r.c, f) << 16) | (luma_x(r.d, f) << 24);
+}
+// Cb | Cr << 8 of one chroma block from its channel sums (rb = sR | sB << 16, g = sG); sh = 20 + log2(pixels of the block)
+__device__ __forceinline__ unsigned chroma_x(unsigned rb, unsigned g, const Fwd& m, int sh) {
+  const int sr = rb & 0xffff, sb = rb >> 16, add = (1 << (sh - 1)) + (128 << sh);
+  return satsh(m.cbr * sr + m.cbg * (int)g + m.cbb * sb + add, sh) | (satsh(m.crr * sr + m.crg * (int)g + m.crb * sb + add, sh) << 8);
+}
+// the chroma of a thread's pixels as U0 V0 U1 V1: of the two 2 x 2 blocks of two rows (4:2:0), of the two pairs of one row (4:2:2)
+__device__ __forceinline__ unsigned chroma420_x(const Row& r0, const Row& r1, const Fwd& m) {
+  const unsigned lo0 = (r0.a & 0xff00ffu) + (r0.b & 0xff00ffu) + (r1.a & 0xff00ffu) + (r1.b & 0xff00ffu);
+  const unsigned g0 = ((r0.a >> 8) & 255u) + ((r0.b >> 8) & 255u) + ((r1.a >> 8) & 255u) + ((r1.b >> 8) & 255u);
+  const unsigned lo1 = (r0.c & 0xff00ffu) + (r0.d & 0xff00ffu) + (r1.c & 0xff00ffu) + (r1.d & 0xff00ffu);
+  const unsigned g1 = ((r0.c >> 8) & 255u) + ((r0.d >> 8) & 255u) + ((r1.c >> 8) & 255u) + ((r1.d >> 8) & 255u);
+  return chroma_x(lo0, g0, m, 22) | (chroma_x(lo1, g1, m, 22) << 16);
+}
+__device__ __forceinline__ unsigned chroma422_x(const Row& r, const Fwd& m) {
+  return chroma_x((r.a & 0xff00ffu) + (r.b & 0xff00ffu), ((r.a >> 8) & 255u) + ((r.b >> 8) & 255u), m, 21) |
+         (chroma_x((r.c & 0xff00ffu) + (r.d & 0xff00ffu), ((r.c >> 8) & 255u) + ((r.d >> 8) & 255u), m, 21) << 16);
+}
+
+// neighbouring bytes swapped: Y0 U Y1 V <-> U Y0 V Y1
+__device__ __forceinline__ unsigned swap_bytes(unsigned w) { return ((w >> 8) & 0x00ff00ffu) | ((w << 8) & 0xff00ff00u); }
+// 2 bytes at o (the first `left` of them): one 16-bit store where the address allows
+__device__ __forceinline__ void put2(unsigned char* o, unsigned w, int left) {
+  if (left > 1 && (reinterpret_cast<uintptr_t>(o) & 1u) == 0) { *reinterpret_cast<unsigned short*>(o) = (unsigned short)w; return; }
+  if (left > 0) o[0] = (unsigned char)w;
+  if (left > 1) o[1] = (unsigned char)(w >> 8);
+}
+// A thread's 8-bit YUV samples -> a YUV sink in its layout: y0 / y1 the 4 Y bytes of rows Y / Y + 1, c0 / c1 the chroma U0 V0 U1 V1 of
+// those rows (4:2:0 sinks take c0: one block row).  Even widths: a pair of pixels is inside the sink whole or not at all.
+__device__ __forceinline__ void store_yuv8(const G6dSink& k, int X, int Y, unsigned y0, unsigned y1, unsigned c0, unsigned c1) {
+  const int fmt = k.format, sw = k.width, sh = k.height;
+  const bool full = X + 4 <= sw, two = Y + 1 < sh;
+  unsigned char* const p0 = static_cast<unsigned char*>(k.plane0);
+  unsigned char* const p1 = static_cast<unsigned char*>(k.plane1);
+  if (fmt > G6D_FMT_YV12) return;                          // P010 and GRAY8 are read-only formats: nothing is written
+  if (fmt == G6D_FMT_YUYV422 || fmt == G6D_FMT_UYVY422) {  // (block-uniform, as every format test here)
+    const bool uyvy = fmt == G6D_FMT_UYVY422;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j == 1 && !two) break;
+      const unsigned y = j ? y1 : y0, c = j ? c1 : c0;
+      unsigned w0 = (y & 255u) | ((c & 255u) << 8) | (((y >> 8) & 255u) << 16) | (((c >> 8) & 255u) << 24);
+      unsigned w1 = ((y >> 16) & 255u) | (((c >> 16) & 255u) << 8) | ((y >> 24) << 16) | ((c >> 24) << 24);
+      if (uyvy) { w0 = swap_bytes(w0); w1 = swap_bytes(w1); }
+      unsigned char* o = p0 + (size_t)(Y + j) * k.pitch0 + (size_t)X * 2;
+      put4(o, w0, true, 4);
+      if (full) put4(o + 4, w1, true, 4);
+    }
+    return;
+  }
+  put4(p0 + (size_t)Y * k.pitch0 + X, y0, full, sw - X);
+  if (!two) return;
+  put4(p0 + (size_t)(Y + 1) * k.pitch0 + X, y1, full, sw - X);
+  if (fmt == G6D_FMT_NV12) { put4(p1 + (size_t)(Y >> 1) * k.pitch1 + X, c0, full, sw - X); return; }
+  unsigned char* const second = p1 + (size_t)k.pitch1 * (sh >> 1);
+  const size_t o = (size_t)(Y >> 1) * k.pitch1 + (X >> 1);
+  put2((fmt == G6D_FMT_I420 ? p1 : second) + o, (c0 & 255u) | (((c0 >> 16) & 255u) << 8), full ? 2 : 1);
+  put2((fmt == G6D_FMT_I420 ? second : p1) + o, ((c0 >> 8) & 255u) | ((c0 >> 24) << 8), full ? 2 : 1);
+}
+// A thread's annotated RGB rows -> an extended sink (store_rows' counterpart)
+__device__ __forceinline__ void store_rows_x(const G6dSink& k, const Row& r0, const Row& r1, int X, int Y, const FwdX& f) {
+  const bool c422 = k.format == G6D_FMT_YUYV422 || k.format == G6D_FMT_UYVY422;
+  const unsigned c0 = c422 ? chroma422_x(r0, f.m) : chroma420_x(r0, r1, f.m);
+  store_yuv8(k, X, Y, luma4_x(r0, f), luma4_x(r1, f), c0, c422 ? chroma422_x(r1, f.m) : c0);
+}
+
 }  // namespace

@@ -9,6 +9,7 @@
 // magnifies the source neighbouring lanes read neighbouring source bytes.  rec[b], the record and the homography sit at block-uniform
 // addresses (scalar loads, once per block), so the has-source, format and rotation branches are block-uniform.  The canvas is sampled as
 // what it is, a same-size rgb24 picture of pitch 3 W: both branches run `taps_of` and `blend`, so they cannot drift apart.
+// A frame of the formats after NV12 or of a full-range matrix takes its taps from frame_src.h's `ext_taps` (block-uniform).
 #include "frame_src.h"
 
 namespace {
@@ -78,6 +79,7 @@ __global__ void __launch_bounds__(256) frame_crop_kernel(const G6dFrame* __restr
   const int r = rec[b];
   Src s;
   View v;
+  const bool ext = r >= 0 && extended(frames[r]);                     // (block-uniform) a format after NV12 or a full-range matrix
   if (r >= 0) {                                                       // (block-uniform)
     const G6dFrame& f = frames[r];
     s = source_of(f);
@@ -92,7 +94,12 @@ __global__ void __launch_bounds__(256) frame_crop_kernel(const G6dFrame* __restr
   if (x >= dw || y >= dh) return;
   const Taps t = taps_of(hinv + 9 * b, x, y, v);
   int r00, g00, b00, r01, g01, b01, r10, g10, b10, r11, g11, b11;
-  if (s.nv12) {                                                       // (block-uniform) a UV sample is loaded once for the taps that share it
+  if (ext) {                                                          // every tap is taken, as below: a weight-0 tap is clamped inside the source
+    Tap t00, t01, t10, t11;
+    ext_taps<false>(yuv_of(frames[r]), t.x0, t.x1, t.y0, t.y1, true, true, t00, t01, t10, t11);
+    r00 = t00.r; g00 = t00.g; b00 = t00.b; r01 = t01.r; g01 = t01.g; b01 = t01.b;
+    r10 = t10.r; g10 = t10.g; b10 = t10.b; r11 = t11.r; g11 = t11.g; b11 = t11.b;
+  } else if (s.nv12) {                                                       // (block-uniform) a UV sample is loaded once for the taps that share it
     const bool sx = (t.x1 >> 1) == (t.x0 >> 1), sy = (t.y1 >> 1) == (t.y0 >> 1);
     const Chroma k00 = chroma(s, t.x0 >> 1, t.y0 >> 1);
     const Chroma k01 = sx ? k00 : chroma(s, t.x1 >> 1, t.y0 >> 1);

@@ -11,6 +11,8 @@
 // NV12 sample are computed once for the taps of its 2 x 2 block (at 2:1 all four taps of a pixel share one).
 // g6d_frame_ingest_mesh (second half of the file) is the same launch with a lens per frame: blocks of a frame with a mesh take their
 // source coordinates from it (nodes in LDS, 64-bit integer interpolation), blocks of a frame without one run the plain tile.
+// Frames of the formats after NV12 and of the full-range matrices take a block-uniform branch to the same tiles on
+// frame_src.h's `Yuv` taps, in both kernels: a tick that mixes all eleven formats, with and without lenses, is one launch.
 #include "frame_src.h"
 
 namespace {
@@ -26,6 +28,11 @@ __device__ __forceinline__ unsigned sample_word(int t, int tgt, int src) {
   return i0 | ((i0 + 1 < (unsigned)src ? 1u : 0u) << 13) | (w << 14);
 }
 
+// one tile of a frame by the plain rule; EXT: a frame of the formats after NV12 or of a full-range matrix (frame_src.h `extended`)
+template <bool EXT>
+__device__ __forceinline__ void plain_tile(const G6dFrame& f, unsigned* cw, unsigned char* __restrict__ out, int slot, int H, int W, int X0,
+                                           int Y0);
+
 __global__ void __launch_bounds__(256) frame_ingest_kernel(const G6dFrame* __restrict__ frames, unsigned char* __restrict__ out, int B, int H,
                                                            int W, float* __restrict__ K_out, int tiles_x, int tiles) {
   __shared__ unsigned cw[TW + TH];
@@ -36,6 +43,7 @@ __global__ void __launch_bounds__(256) frame_ingest_kernel(const G6dFrame* __res
   const int t = threadIdx.x;
   if (tile == 0 && t < 9) K_out[(size_t)9 * slot + t] = f.K[t];
   const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
+  if (extended(f)) { plain_tile<true>(f, cw, out, slot, H, W, X0, Y0); return; }   // (block-uniform) the body below stays as measured
   const int ws = f.width, hs = f.height, rot = f.rotate;
   const int ow = min(f.out_w, W), oh = min(f.out_h, H);   // an empty or negative picture leaves a black canvas
   const bool swap = rot == 90 || rot == 270;
@@ -148,6 +156,20 @@ __device__ __forceinline__ void gather(const Src& s, int x0, int x1, int y0, int
   r = ar >> 22; g = ag >> 22; b = ab >> 22;
 }
 
+// the same for a frame of the extended formats: taps by frame_src.h's ext_taps (a tap of weight 0 is not loaded and counts as 0)
+__device__ __forceinline__ void gather(const Yuv& s, int x0, int x1, int y0, int y1, unsigned wa, unsigned wb, int& r, int& g, int& b) {
+  const unsigned w00 = (2048 - wa) * (2048 - wb), w01 = wa * (2048 - wb), w10 = (2048 - wa) * wb, w11 = wa * wb;
+  Tap t00, t01, t10, t11;
+  ext_taps<true>(s, x0, x1, y0, y1, wa != 0, wb != 0, t00, t01, t10, t11);
+  r = ((1u << 21) + w00 * t00.r + w01 * t01.r + w10 * t10.r + w11 * t11.r) >> 22;
+  g = ((1u << 21) + w00 * t00.g + w01 * t01.g + w10 * t10.g + w11 * t11.g) >> 22;
+  b = ((1u << 21) + w00 * t00.b + w01 * t01.b + w10 * t10.b + w11 * t11.b) >> 22;
+}
+template <bool EXT> __device__ __forceinline__ auto tap_source(const G6dFrame& f) {
+  if constexpr (EXT) return yuv_of(f);
+  else return source_of(f);
+}
+
 // a thread's 4 pixels -> canvas row Y of image `slot` from column X on
 __device__ __forceinline__ void store4(unsigned char* __restrict__ out, const unsigned char (&px)[12], int slot, int H, int W, int X, int Y) {
   unsigned char* o = out + (((size_t)slot * H + Y) * W + X) * 3;
@@ -165,6 +187,7 @@ __device__ __forceinline__ void store4(unsigned char* __restrict__ out, const un
 }
 
 // one tile of a frame by the plain rule (scaling + quarter turn); cw: TW + TH words of LDS
+template <bool EXT>
 __device__ __forceinline__ void plain_tile(const G6dFrame& f, unsigned* cw, unsigned char* __restrict__ out, int slot, int H, int W, int X0,
                                            int Y0) {
   const int t = threadIdx.x;
@@ -185,7 +208,7 @@ __device__ __forceinline__ void plain_tile(const G6dFrame& f, unsigned* cw, unsi
   __syncthreads();
   const int ry = t >> 5, X = X0 + ((t & 31) << 2), Y = Y0 + ry;
   if (Y >= H || X >= W) return;
-  const Src s = source_of(f);
+  const auto s = tap_source<EXT>(f);
   const unsigned rw = cw[TW + ry];
   unsigned char px[12];
 #pragma unroll
@@ -213,6 +236,7 @@ __device__ __forceinline__ Col column(const int2* nd, int at, int below, int g, 
 
 // one tile of a lens frame.  The canvas coordinates are those AFTER the quarter turn (the host undid it when it built the mesh), so there
 // is no rotation here.  nd: MESH_NX * MESH_NY nodes of LDS
+template <bool EXT>
 __device__ __forceinline__ void mesh_tile(const G6dFrame& f, const G6dMesh& m, int2* nd, unsigned char* __restrict__ out, int slot, int H, int W,
                                           int X0, int Y0) {
   const int t = threadIdx.x;
@@ -229,7 +253,7 @@ __device__ __forceinline__ void mesh_tile(const G6dFrame& f, const G6dMesh& m, i
   if (Y >= H || X >= W) return;
   const int ws = f.width, hs = f.height;
   const int ow = min(f.out_w, W), oh = min(f.out_h, H);
-  const Src s = source_of(f);
+  const auto s = tap_source<EXT>(f);
   // a thread's 4 pixels lie in one cell (two at step 2): the node columns they use, blended down the cell once
   const int j = Y & (g - 1), at = ((Y >> lg) - r0) * tnx + (X >> lg) - c0;
   const Col q0 = column(nd, at, tnx, g, j), q1 = column(nd, at + 1, tnx, g, j);
@@ -269,8 +293,11 @@ __global__ void __launch_bounds__(256) frame_ingest_lens_kernel(const G6dFrame* 
   if (tile == 0 && threadIdx.x < 9) K_out[(size_t)9 * slot + threadIdx.x] = f.K[threadIdx.x];
   const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
   const G6dMesh& m = meshes[fi];
-  if (m.nodes) mesh_tile(f, m, nd, out, slot, H, W, X0, Y0);     // (block-uniform)
-  else plain_tile(f, cw, out, slot, H, W, X0, Y0);
+  if (extended(f)) {                                             // (block-uniform, as every branch here)
+    if (m.nodes) mesh_tile<true>(f, m, nd, out, slot, H, W, X0, Y0);
+    else plain_tile<true>(f, cw, out, slot, H, W, X0, Y0);
+  } else if (m.nodes) mesh_tile<false>(f, m, nd, out, slot, H, W, X0, Y0);
+  else plain_tile<false>(f, cw, out, slot, H, W, X0, Y0);
 }
 
 }  // namespace

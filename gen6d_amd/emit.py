@@ -2,16 +2,18 @@
 batch with the object's projected 3-D box drawn on them (red corner discs, twelve blue edges on top), written in the format an encoder
 or a display takes, in ONE launch of g6d_frame_emit (csrc/emit.hip) for any number of destinations.  The output side of gen6d_amd.ingest.
 
-A `Sink` describes one destination the way `ingest.Frame` describes a source: packed rgb24 / bgr24 / rgba32 / bgra32 or NV12, any size up to
-8192 and any row pitch, in device memory or in pinned host memory.  The picture sits at the sink's top-left corner at working resolution:
+A `Sink` describes one destination the way `ingest.Frame` describes a source: packed rgb24 / bgr24 / rgba32 / bgra32, NV12, planar i420 /
+yv12 (a software encoder's input) or packed 4:2:2 yuyv422 / uyvy422 (a capture-card style display path), limited or full range, any
+size up to 8192 and any row pitch, in device memory or in pinned host memory.  The picture sits at the sink's top-left corner at working resolution:
 a larger sink (an encoder's aligned surface, an odd picture under NV12) is padded with black, a smaller one crops; nothing is scaled or
 rotated.  `project_corners` turns poses into integer pixel corners on the device (g6d_track_corners), `emit_frames` fills the sinks.
 The drawing and the colour conversion are the exact integer rules of include/gen6d_hip.h, not cv2's.
 
 A sink with view="source" shows the camera's own frame instead of the canvas: the `ingest.Frame` as it was delivered (full resolution,
 not turned) with the box drawn in its pixel grid, in ONE launch of g6d_frame_emit_source (csrc/emit_source.hip) that reads the frame
-table an ingest launch left on the device (`ingest_frames_keep`, `emit_source_frames`).  An NV12 frame
-into an NV12 sink of the same matrix passes through: bytes the box does not cover are the camera's bytes.
+table an ingest launch left on the device (`ingest_frames_keep`, `emit_source_frames`).  A frame into a sink of
+the same format among nv12 / i420 / yv12 / yuyv422 / uyvy422 and the same matrix passes through: bytes the box does not cover are the
+camera's bytes; every other pair goes through RGB.
 """
 import contextlib
 import ctypes as C
@@ -38,9 +40,11 @@ def _rgb(color, what):
 class Sink:
     """One destination.  data: a uint8 torch tensor, on the device or in PINNED host memory, [H,W,C] (C = 3 / 4 as the format says; sizes and
     the pitch are taken from it), [rows, row bytes] or a flat buffer (give width / height / pitch).  NV12: either one [H*3/2, pitch]
-    buffer (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV plane; even width and height.
-    pose: which pose's box is drawn, "smooth" or "raw" (predict.py writes both pictures of a frame).  matrix: "bt601" / "bt709" (limited
-    range), NV12 only.  Style: thickness, dot_radius, line_color / dot_color (R, G, B), box=False for the plain picture; the defaults are
+    buffer (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV plane; even width and height.  i420 / yv12 and
+    yuyv422 / uyvy422: the layouts of `ingest.Frame` (planar: one buffer of contiguous planes, or `uv` = the two chroma planes
+    stacked; 4:2:2: even width, any height).  p010 and gray8 cannot be written.
+    pose: which pose's box is drawn, "smooth" or "raw" (predict.py writes both pictures of a frame).  matrix (YUV formats): "bt601" /
+    "bt709" (limited range) or "bt601-full" / "bt709-full" (full range: black is Y = 0).  Style: thickness, dot_radius, line_color / dot_color (R, G, B), box=False for the plain picture; the defaults are
     draw_bbox_3d's.  A HOST sink's planes travel in one copy each, from the first row's first byte to the last row's last: the row padding
     in between is overwritten with zeros.  Host sinks therefore cannot share rows of one surface (two halves of a picture, a
     sub-rectangle of a larger image); device sinks, which the kernel writes pixel by pixel, can.
@@ -60,6 +64,9 @@ class Sink:
             raise ValueError(f"Sink: pose must be 'smooth' or 'raw', not {pose!r}")
         if not 0 <= int(thickness) <= MAX_STYLE or not 0 <= int(dot_radius) <= MAX_STYLE:
             raise ValueError(f"Sink: thickness and dot_radius must lie in 0..{MAX_STYLE}")
+        if fmt in I.READ_ONLY:
+            raise ValueError(f"Sink: a {fmt} picture cannot be written (p010 and gray8 are formats of a source Frame only); the written "
+                             f"formats are {sorted(f for f in I.FORMATS if f not in I.READ_ONLY)}")
         try:                                   # the plane, pitch and extent rules of a source picture are those of a destination
             f = I.Frame(data, fmt, width=width, height=height, pitch=pitch, uv=uv, uv_pitch=uv_pitch, matrix=matrix)
         except ValueError as e:

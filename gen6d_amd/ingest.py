@@ -1,7 +1,8 @@
 """Device-side frame ingest (reference prepare.py:16-42 `video2image` + predict.py:45,52-54): camera-native frames -> the uint8 RGB
 working-resolution images and intrinsics the networks take, in ONE launch of g6d_frame_ingest (csrc/ingest.hip) for any number of frames.
 
-A `Frame` describes one picture as a camera or a video decoder delivers it: packed rgb24 / bgr24 / rgba32 / bgra32 or NV12, any size up to
+A `Frame` describes one picture as a camera or a video decoder delivers it: packed rgb24 / bgr24 / rgba32 / bgra32, packed 4:2:2
+(yuyv422 / uyvy422), NV12, planar 4:2:0 (i420 / yv12), 10-bit P010 or 8-bit mono (gray8), limited or full range, any size up to
 8192, any row pitch, host or device memory, optionally turned by quarter turns.  `plan` places it in a canvas (scaled to fit, top-left
 corner) and maps its intrinsics; `ingest_frames` uploads what lives on the host through pinned memory without blocking and launches once.
 A Frame with a `Lens` (a calibrated distortion model beside its K) is undistorted in the same launch (g6d_frame_ingest_mesh): the host
@@ -20,9 +21,14 @@ from . import eval as EV
 from . import lib as _lib
 from . import ops
 
-FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4}
-MATRICES = {"bt601": 0, "bt709": 1}
-BPP = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1}
+FORMATS = {"rgb24": 0, "bgr24": 1, "rgba32": 2, "bgra32": 3, "nv12": 4, "yuyv422": 5, "uyvy422": 6, "i420": 7, "yv12": 8, "p010": 9, "gray8": 10}
+MATRICES = {"bt601": 0, "bt709": 1, "bt601-full": 2, "bt709-full": 3}     # limited range, full range
+BPP = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1, "yuyv422": 2, "uyvy422": 2, "i420": 1, "yv12": 1, "p010": 2,
+       "gray8": 1}                                       # bytes per luma sample (per pixel for the packed formats)
+PACKED_422 = ("yuyv422", "uyvy422")
+SEMI_PLANAR = ("nv12", "p010")                           # a Y plane and one plane of interleaved UV pairs
+PLANAR = ("i420", "yv12")                                # a Y plane and two chroma planes
+READ_ONLY = ("p010", "gray8")                            # formats a Frame can have and a Sink cannot
 MAX_SIZE = 8192
 RECORD_BYTES = C.sizeof(_lib.G6dFrame)                   # one record of a frame table
 LENS_MODELS = {"brown": (4, 5, 8), "fisheye": (4,)}      # model -> admissible numbers of coefficients
@@ -42,6 +48,18 @@ def _u8(a, what):
     if not 1 <= a.ndim <= 3:
         raise ValueError(f"Frame: {what} must have 1 to 3 dimensions")
     return a
+
+
+def _bytes(a, what, fmt):
+    """_u8 that also takes the uint16 samples of a p010 frame: the same memory as little-endian bytes (the last dimension doubles)."""
+    if not torch.is_tensor(a):
+        a = np.asarray(a)
+    if fmt == "p010" and a.dtype in (np.uint16, getattr(torch, "uint16", None)) and a.ndim >= 1:
+        if torch.is_tensor(a):
+            a = (a if a.stride(-1) == 1 else a.contiguous()).view(torch.uint8)
+        else:
+            a = (a if a.strides[-1] == 2 else np.ascontiguousarray(a)).astype("<u2", copy=False).view(np.uint8)
+    return _u8(a, what)
 
 
 def _rows(a, inner):
@@ -151,39 +169,51 @@ class Lens:
 
 
 class Frame:
-    """One source picture.  data: uint8 numpy array or torch tensor (host or device), [H,W,C] (C = 3 / 4 as the format says; sizes and
-    the pitch are taken from it), [rows, row bytes] or a flat buffer (give width / height / pitch).  NV12: either one [H*3/2, pitch] buffer
-    (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV plane ([H/2, bytes] or [H/2, W/2, 2]).
+    """One source picture.  data: uint8 numpy array or torch tensor (host or device), [H,W,C] (C = 3 / 4 / 2 / 1 as the format says; sizes
+    and the pitch are taken from it), [rows, row bytes] or a flat buffer (give width / height / pitch).  Formats:
+      rgb24 / bgr24 / rgba32 / bgra32   packed, 3 / 4 bytes per pixel;
+      yuyv422 / uyvy422                 packed 4:2:2, 2 bytes per pixel ([H,W,2] or rows of bytes); even width, any height;
+      nv12                              one [H*3/2, pitch] buffer (Y rows, then H/2 rows of interleaved UV) or `data` = Y plane and `uv` = UV
+                                        plane ([H/2, bytes] or [H/2, W/2, 2]); even sizes;
+      i420 / yv12                       planar 4:2:0, Y then U then V (yv12: V then U): one [H*3/2, pitch] buffer of contiguous planes (even
+                                        pitch, the chroma pitch is pitch / 2) or `data` = Y plane and `uv` = the two chroma planes stacked,
+                                        [H, uv_pitch]; even sizes.  Three separately allocated planes are out of scope;
+      p010                              nv12's layout with 16-bit little-endian samples (value = word >> 6): uint16 arrays, or uint8 byte
+                                        buffers with width / height / pitch; pitches are in BYTES and even;
+      gray8                             [H,W], or rows of bytes with a width.
     rotate: quarter turns clockwise applied after scaling (0 / 90 / 180 / 270).  K: the camera's intrinsics in SOURCE pixel coordinates, or
-    None for predict.py's pseudo intrinsics of the ingested picture.  matrix: "bt601" / "bt709" (limited range), NV12 only.  lens: the
-    camera's `Lens` (needs K): the ingested picture is the undistorted one, and its intrinsics come from the lens's new_K."""
+    None for predict.py's pseudo intrinsics of the ingested picture.  matrix (YUV formats): "bt601" / "bt709" (limited range),
+    "bt601-full" / "bt709-full" (full range, e.g. MJPEG-sourced YUV).  lens: the camera's `Lens` (needs K): the ingested picture is the
+    undistorted one, and its intrinsics come from the lens's new_K."""
 
     def __init__(self, data, fmt="rgb24", width=None, height=None, pitch=None, rotate=0, K=None, uv=None, uv_pitch=None, matrix="bt601",
                  lens=None):
         if fmt not in FORMATS:
             raise ValueError(f"Frame: unknown format {fmt!r} (one of {sorted(FORMATS)})")
         if matrix not in MATRICES:
-            raise ValueError(f"Frame: unknown matrix {matrix!r} (bt601 or bt709)")
+            raise ValueError(f"Frame: unknown matrix {matrix!r} (one of {sorted(MATRICES)})")
         if rotate not in (0, 90, 180, 270):
             raise ValueError(f"Frame: rotate must be 0, 90, 180 or 270, not {rotate!r}")
         if lens is not None and not isinstance(lens, Lens):
             raise ValueError("Frame: lens must be an ingest.Lens")
         if lens is not None and K is None:
             raise ValueError("Frame: a frame with a lens must carry the camera's K")
-        nv12, bpp = fmt == "nv12", BPP[fmt]
-        if uv is not None and not nv12:
-            raise ValueError("Frame: uv is the second plane of an nv12 frame")
-        d = _u8(data, "data")
+        bpp = BPP[fmt]
+        semi, planar = fmt in SEMI_PLANAR, fmt in PLANAR      # chroma beside the luma plane: one interleaved plane / two planes
+        two = semi or planar
+        if uv is not None and not two:
+            raise ValueError(f"Frame: uv is the chroma of an nv12 / p010 / i420 / yv12 frame; a {fmt} frame is one packed plane")
+        d = _bytes(data, "data", fmt)
         if d.ndim == 3:
-            if nv12 or d.shape[2] != bpp:
+            if two or d.shape[2] != bpp:
                 raise ValueError(f"Frame: a {fmt} frame cannot be a {tuple(d.shape)} array")
             d, p = _rows(d, bpp)
             h, w = d.shape[:2]
         elif d.ndim == 2:
             d, p = _rows(d, 1)
-            if nv12 and uv is None:
+            if two and uv is None:
                 if d.shape[0] % 3:
-                    raise ValueError("Frame: a one-buffer nv12 frame has H*3/2 rows")
+                    raise ValueError(f"Frame: a one-buffer {fmt} frame has H*3/2 rows")
                 h = d.shape[0] * 2 // 3
             else:
                 h = d.shape[0]
@@ -203,35 +233,46 @@ class Frame:
             raise ValueError(f"Frame: size {w} x {h} outside 1..{MAX_SIZE}")
         if p < w * bpp:
             raise ValueError(f"Frame: pitch {p} is smaller than a row of {w} {fmt} pixels")
+        if fmt in PACKED_422 and w % 2:
+            raise ValueError(f"Frame: a {fmt} frame has an even width, not {w}")
         self.fmt, self.width, self.height, self.pitch, self.rotate, self.matrix = fmt, w, h, p, int(rotate), matrix
         self.K = None if K is None else np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float64).reshape(3, 3)
         self.lens = lens
         self.plane0 = _span(d, w * bpp, h, p)
         self.plane1, self.uv_pitch = None, 0
-        if nv12:
+        if two:
             if w % 2 or h % 2:
-                raise ValueError(f"Frame: an nv12 frame has even width and height, not {w} x {h}")
+                raise ValueError(f"Frame: an {fmt} frame has even width and height, not {w} x {h}")
+            if fmt == "p010" and p % 2:
+                raise ValueError(f"Frame: a p010 pitch is in bytes and even, not {p}")
+            # plane1: h/2 rows of interleaved pairs, or the two chroma planes one after the other (h/2 + h/2 rows of w/2 bytes)
+            crow, crows = (w * bpp, h // 2) if semi else (w // 2, h)
             if uv is None:
-                if uv_pitch is not None and int(uv_pitch) != p:
-                    raise ValueError("Frame: a one-buffer nv12 frame has one pitch")
-                self.uv_pitch = p
-                self.plane1 = _span(d, w, h // 2, p, offset=p * h)
+                if planar and p % 2:
+                    raise ValueError(f"Frame: a one-buffer {fmt} frame has an even pitch (its chroma pitch is half of it), not {p}")
+                up = p if semi else p // 2
+                if uv_pitch is not None and int(uv_pitch) != up:
+                    raise ValueError(f"Frame: a one-buffer {fmt} frame has one pitch" + (" (the chroma pitch is half of it)" if planar else ""))
+                self.uv_pitch = up
+                self.plane1 = _span(d, crow, crows, up, offset=p * h)
             else:
-                u = _u8(uv, "uv")
+                u = _bytes(uv, "uv", fmt)
                 if type(u) is not type(d) or (torch.is_tensor(u) and u.device != d.device):
                     raise ValueError("Frame: data and uv must live in the same kind of memory")
                 if u.ndim == 1:
-                    up = int(uv_pitch) if uv_pitch is not None else w
+                    up = int(uv_pitch) if uv_pitch is not None else crow
                 else:
-                    u, up = _rows(u, 2)
-                    if u.shape[0] != h // 2 or (u.ndim == 3 and (u.shape[1] != w // 2 or u.shape[2] != 2)):
-                        raise ValueError(f"Frame: uv plane {tuple(u.shape)} does not belong to a {w} x {h} nv12 frame")
+                    u, up = _rows(u, 2 * bpp)
+                    if u.shape[0] != crows or (u.ndim == 3 and (planar or u.shape[1] != w // 2 or u.shape[2] != 2 * bpp)):
+                        raise ValueError(f"Frame: uv plane {tuple(u.shape)} does not belong to a {w} x {h} {fmt} frame")
                     if uv_pitch is not None and int(uv_pitch) != up and u.shape[0] > 1:
                         raise ValueError(f"Frame: uv_pitch {uv_pitch} given, the array's rows are {up} bytes apart")
-                if up < w:
-                    raise ValueError(f"Frame: uv pitch {up} is smaller than a row of {w // 2} UV pairs")
+                if up < crow:
+                    raise ValueError(f"Frame: uv pitch {up} is smaller than a chroma row of a {w} pixel wide {fmt} frame ({crow} bytes)")
+                if fmt == "p010" and up % 2:
+                    raise ValueError(f"Frame: a p010 pitch is in bytes and even, not {up}")
                 self.uv_pitch = up
-                self.plane1 = _span(u, w, h // 2, up)
+                self.plane1 = _span(u, crow, crows, up)
 
     @property
     def on_device(self):

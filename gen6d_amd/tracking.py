@@ -14,7 +14,7 @@ many streams (cameras or clients watching one object) at once:
     K and slot-map buffers that are filled on the lane's stream before each replay; unused slots (id -1) refine the parking pose
     (DeviceChain.ref_poses[0]) and are not committed;
   * per-stream state is device-resident: last raw and smoothed pose, and the ring of the last `smooth_num` frames' box corners;
-  * with `frame_size=(H, W)` the tracker takes camera-native frames (`gen6d_amd.ingest.Frame`: any size, packed RGB / BGR(A) or NV12,
+  * with `frame_size=(H, W)` the tracker takes camera-native frames (`gen6d_amd.ingest.Frame`: any size, any of its eleven pixel formats,
     pitched, rotated, with or without a calibrated `ingest.Lens`, mixed within one push): one g6d_frame_ingest launch per lane and tick
     (g6d_frame_ingest_mesh when a frame has a lens: it is undistorted on the way) scales them into the lane's static image
     slots and writes their intrinsics, in place of the per-slot copies (DESIGN.md §4.17);

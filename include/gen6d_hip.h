@@ -665,12 +665,14 @@ int g6d_track_verify(const float* det, const float* pose_table, const float* K, 
                      float* measures, int batch, g6d_stream_t stream);
 
 /* Frame ingest (gen6d_amd/ingest.py; reference prepare.py:16-42 video2image + predict.py:45,52-54); additive within ABI 12.  ONE launch
- * reads n camera-native frames (packed RGB / BGR / RGBA / BGRA or NV12, any size, row pitch and quarter-turn rotation), scales each to
+ * reads n camera-native frames (packed RGB / BGR / RGBA / BGRA or NV12, and the formats after NV12 listed at the enum below; any size, row
+ * pitch and quarter-turn rotation), scales each to
  * out_w x out_h with the integer bilinear below, and writes the RGB picture into the top-left corner of image `slot` of
  * out [B][H][W][3] uint8 (canvas pixels outside the picture are written as 0) and the frame's K into K_out [B][3][3].  Slots that no frame
  * names are not touched; a frame whose slot lies outside [0, B) is skipped; two frames must not name the same slot.
  * The table lives in DEVICE memory (it changes with every call, so the launch stays outside captured graphs); the caller validates its
- * contents: planes cover height rows of pitch bytes, 1 <= width, height <= 8192, even sizes for NV12, out_w <= W, out_h <= H.
+ * contents: planes cover height rows of pitch bytes, 1 <= width, height <= 8192, even sizes for the 4:2:0 formats and an even width for
+ * 4:2:2, out_w <= W, out_h <= H.
  * Arithmetic (exact integers, the numpy restatement in tests/test_ingest_cpu.py is bit-identical): with wt x ht the scaled
  * picture before rotation ((out_w, out_h) for rotate 0 / 180, (out_h, out_w) for 90 / 270) and ws x hs the source,
  *   fx = clamp(floor((2x+1) * ws * 1024 / wt) - 1024, 0, (ws-1) * 2048), x0 = fx >> 11, a = fx & 2047, x1 = min(x0+1, ws-1), y likewise (b);
@@ -679,15 +681,40 @@ int g6d_track_verify(const float* det, const float* pose_table, const float* K, 
  *   G = sat8((CY c - CUG d - CVG e + 2^19) >> 20), B = sat8((CY c + CUB d + 2^19) >> 20) with round(k * 2^20) constants of BT.601 / BT.709
  *   limited range; canvas pixel (X, Y) of a picture turned clockwise by 90 is the unrotated (Y, ht-1-X), 180: (wt-1-X, ht-1-Y),
  *   270: (wt-1-Y, X). */
-enum { G6D_FMT_RGB24 = 0, G6D_FMT_BGR24 = 1, G6D_FMT_RGBA32 = 2, G6D_FMT_BGRA32 = 3, G6D_FMT_NV12 = 4 };
+enum { G6D_FMT_RGB24 = 0, G6D_FMT_BGR24 = 1, G6D_FMT_RGBA32 = 2, G6D_FMT_BGRA32 = 3, G6D_FMT_NV12 = 4,
+       /* additive within ABI 12 (the numpy restatement in tests/test_pixel_formats_cpu.py is bit-identical) */
+       G6D_FMT_YUYV422 = 5,        /* packed 4:2:2, 2 bytes per pixel, a pair of pixels = Y0 U Y1 V; read and written */
+       G6D_FMT_UYVY422 = 6,        /* packed 4:2:2, a pair = U Y0 V Y1; read and written */
+       G6D_FMT_I420 = 7,           /* planar 4:2:0: Y, then U, then V; read and written */
+       G6D_FMT_YV12 = 8,           /* planar 4:2:0: Y, then V, then U; read and written */
+       G6D_FMT_P010 = 9,           /* NV12's layout with 16-bit little-endian samples, value = word >> 6; read only (G6dFrame) */
+       G6D_FMT_GRAY8 = 10 };       /* one byte per pixel; read only (G6dFrame) */
+/* The formats after NV12 and the full-range matrices.  Planar 4:2:0 (I420 / YV12) has two plane pointers: plane1 is the FIRST chroma
+ * plane, pitch1 the chroma row pitch, and the second chroma plane starts at plane1 + pitch1 * (height / 2).  Three separately allocated
+ * planes would need a third pointer, i.e. an ABI bump, and are out of scope.  matrix: 0 / 1 BT.601 / BT.709 limited range (constants and
+ * results as they were, bit for bit), 2 / 3 BT.601 / BT.709 FULL range; valid for every YUV format, NV12 included, in G6dFrame and G6dSink.
+ * Tap rules, exact integers; chroma is point-sampled as for NV12 (no siting interpolation); everything after a tap (the 11-bit blend,
+ * the rotation, the mesh rule, the crop's float32 blend) is as written for the five formats above:
+ *   4:2:2: luma at byte 2x of row y (YUYV) or 2x + 1 (UYVY), U and V from pair x >> 1 of the same row; even width, any height;
+ *   I420 / YV12: Y[y][x] and chroma [y>>1][x>>1] of the two chroma planes; even sizes;
+ *   limited range, 8 bit: the NV12 formula above with its constants, unchanged;
+ *   full range, 8 bit: c = Y, d = U-128, e = V-128, R = sat8((2^20 c + CVR e + 2^19) >> 20), G = sat8((2^20 c - CUG d - CVG e + 2^19) >> 20),
+ *     B = sat8((2^20 c + CUB d + 2^19) >> 20), (CVR, CUG, CVG, CUB) = round(k 2^20): BT.601 (1470104, 360853, 748826, 1858077) from
+ *     (1.402, 0.344136, 0.714136, 1.772), BT.709 (1651297, 196424, 490864, 1945738) from (1.5748, 0.187324, 0.468124, 1.8556);
+ *     every sum stays below 2^31 (2^20 255 + 1858077 128 + 2^19 = 5.06e8);
+ *   P010: y10 = word >> 6, c = max(y10 - 64, 0) (limited) or y10 (full), d = u10 - 512, e = v10 - 512, the 8-bit constants of the
+ *     matrix (CY = 1220542 limited, 2^20 full), >> 22 with rounding term 2^21.  c, d, e are four times their 8-bit values when the
+ *     samples are v8 << 8, so such a frame converts to the NV12 result bit for bit.  The limited-range sums pass 2^31
+ *     (1220542 959 + 2214593 511 + 2^21 = 2.30e9): they are EVALUATED IN 64-BIT, nothing is pre-shifted;
+ *   GRAY8: R = G = B = the byte. */
 typedef struct G6dFrame {          /* one per frame */
-  const void* plane0;              /* packed pixels, or the Y plane of NV12 */
-  const void* plane1;              /* NV12: interleaved UV plane; else NULL */
+  const void* plane0;              /* packed pixels (RGB, 4:2:2, GRAY8), or the Y plane */
+  const void* plane1;              /* NV12 / P010: interleaved UV plane; I420 / YV12: first chroma plane (above); else NULL */
   int32_t pitch0, pitch1;          /* bytes per source row */
   int32_t width, height;           /* source size in pixels, 1..8192 */
   int32_t format;                  /* G6D_FMT_* */
   int32_t rotate;                  /* 0 / 90 / 180 / 270 degrees clockwise */
-  int32_t matrix;                  /* NV12 only: 0 BT.601 limited range, 1 BT.709 limited range */
+  int32_t matrix;                  /* YUV formats: 0 BT.601, 1 BT.709 limited range; 2 BT.601, 3 BT.709 full range */
   int32_t slot;                    /* destination image index in `out`; outside [0, B): frame skipped */
   int32_t out_w, out_h;            /* size of the scaled AND rotated picture inside the canvas */
   float   K[9];                    /* intrinsics of the canvas picture, written to K_out[slot] */
@@ -751,13 +778,23 @@ int g6d_track_corners(const float* table, const float* K, const int* slot_stream
  *   its four annotated sink pixels (the division by 4 is folded into the shift);
  *   BT.601 (Kr, Kb) = (0.299, 0.114):   CY = (269262, 528618, 102662), CB = (-155423, -305128, 460551), CR = (460551, -385654, -74897)
  *   BT.709 (Kr, Kb) = (0.2126, 0.0722): CY = (191455, 644067, 65019),  CB = (-105533, -355018, 460551), CR = (460551, -418321, -42230) */
+/* Sinks of the formats after NV12 and of the full-range matrices (additive within ABI 12; restated in
+ * tests/test_pixel_formats_cpu.py), exact integers:
+ *   I420 / YV12 sinks hold exactly the Y, Cb, Cr values the NV12 sink of the same call would hold: the 2 x 2 channel-sum rule above with
+ *   planar stores.  4:2:2 sinks: Y per pixel as for NV12; Cb = sat8((CBR sR + CBG sG + CBB sB + 2^20 + 128 * 2^21) >> 21), Cr likewise,
+ *   once per horizontal pair from the channel sums of its two annotated sink pixels; even width, any height.
+ *   Full range (matrix 2 / 3), round(k * 2^20) of (Kr, Kg, Kb) without the 219 / 224 scaling and without the +16:
+ *   Y = sat8((CYR R + CYG G + CYB B + 2^19) >> 20), chroma as above with +128;
+ *   BT.601: CY = (313524, 615514, 119538), CB = (-176932, -347356, 524288), CR = (524288, -439026, -85262)
+ *   BT.709: CY = (222927, 749942, 75707),  CB = (-120138, -404150, 524288), CR = (524288, -476214, -48074)
+ *   (both Y rows sum to 2^20); black padding of a full-range sink is Y = 0, chroma 128. */
 typedef struct G6dSink {           /* one per destination */
-  void* plane0;                    /* packed pixels, or the Y plane of NV12 */
-  void* plane1;                    /* NV12: interleaved UV plane; else NULL */
+  void* plane0;                    /* packed pixels (RGB, 4:2:2), or the Y plane */
+  void* plane1;                    /* NV12: interleaved UV plane; I420 / YV12: first chroma plane, the second at plane1 + pitch1 * (height / 2); else NULL */
   int32_t pitch0, pitch1;          /* bytes per sink row */
-  int32_t width, height;           /* sink size in pixels, 1..8192 (even for NV12) */
-  int32_t format;                  /* G6D_FMT_* */
-  int32_t matrix;                  /* NV12 only: 0 BT.601 limited range, 1 BT.709 limited range */
+  int32_t width, height;           /* sink size in pixels, 1..8192 (4:2:0: even; 4:2:2: even width) */
+  int32_t format;                  /* G6D_FMT_* but P010 and GRAY8, which are read only: such a sink is not written */
+  int32_t matrix;                  /* YUV formats: 0 BT.601, 1 BT.709 limited range; 2 BT.601, 3 BT.709 full range */
   int32_t slot;                    /* source image index in `imgs`; outside [0, B): sink skipped */
   int32_t pic_w, pic_h;            /* the picture inside the canvas (top-left corner), <= W, H */
   int32_t thickness, dot_radius;   /* draw_bbox_3d: 2, 2 */
@@ -793,7 +830,11 @@ int g6d_sizeof_sink_desc(void);
  *   covered pixel comes from the forward formula on the channel sums of its four annotated pixels, the uncovered ones contributing
  *   their converted source RGB;
  *   outside the picture Y = 16 and UV = (128, 128), what the forward formulas make of black.  Both pictures have even sizes and share
- *   the origin, so no block straddles the picture's edge.  A pass-through sink without a box is a byte copy of the picture. */
+ *   the origin, so no block straddles the picture's edge.  A pass-through sink without a box is a byte copy of the picture.
+ * With the formats after NV12 the pass-through is this rule for a frame and a sink of the SAME format among NV12, I420,
+ * YV12, YUYV422, UYVY422 and the same `matrix` value, with the chroma block 2 x 2 for 4:2:0 and 2 x 1 (a horizontal pair of one row)
+ * for 4:2:2, and Y = 0 outside the picture under a full-range matrix.  Any other pair goes through RGB, YUYV <-> UYVY and I420 <-> NV12
+ * included.  For matrix values 0 / 1 on NV12 nothing changes. */
 int g6d_frame_emit_source(const G6dSink* sinks, int n, const G6dFrame* frames, int nf, const int32_t* pts, const int32_t* valid, int sets,
                           int B, int max_w, int max_h, g6d_stream_t stream);
 

@@ -4,13 +4,15 @@ crops="canvas", on device-resident camera frames (what a hardware decoder leaves
   nv12-1080p   1080x1920 NV12 (tools/track_bench.py's frames: the synthetic picture enlarged 2.25x in a grey full-HD frame)
   bgra-4k      2160x3840 BGRA (the same picture enlarged 4.5x)
 
-both into a 540x960 canvas.  Kernel part: one launch of each op fills B 128x128 crops under look-at-sized homographies (a crop pixel
+both into a 540x960 canvas; --formats a,b,.. adds <format>-1080p for each named pixel format (ingest.FORMATS): the nv12-1080p picture
+in that format (its BT.601 samples re-laid; bgr24 and the other packed RGB formats from the picture itself).  Kernel part: one launch of each op fills B 128x128 crops under look-at-sized homographies (a crop pixel
 steps 0.4 to 1.0 canvas pixels: an object of 50 to 130 canvas pixels, i.e. small in the frame); device events around `--launches`
 back-to-back calls, the two ops alternated `--repeats` times.  Tick part: tools/track_bench.py's timing (first frames and the capturing
 tick excluded, the rest between two synchronisations), the two modes alternated `--repeats` times.
 
   python tools/frame_crop_bench.py [--slots 8,32] [--launches 200] [--frames 30] [--repeats 3] [--out profiles/r19_frame_crop.md]
   python tools/frame_crop_bench.py --skip-ticks            (the kernel part alone)
+  python tools/frame_crop_bench.py --skip-ticks --slots 32 --formats nv12,bgr24,yuyv422,uyvy422,i420,yv12,p010,gray8
 """
 import argparse
 import os
@@ -36,8 +38,14 @@ def device_frames(frames, kind):
     yi = (torch.arange(h, device="cuda") / mul).long().clamp_(max=479)
     xi = (torch.arange(int(640 * mul), device="cuda") / mul).long().clamp_(max=639)
     out = []
+    fmt = kind[:-6] if kind.endswith("-1080p") else None      # a --formats source
     for f in frames[:8]:
         g = f[yi][:, xi]
+        if fmt in ("rgb24", "bgr24", "rgba32", "bgra32"):
+            buf = torch.full((h, w, 4 if fmt.endswith("32") else 3), 128, dtype=torch.uint8, device="cuda")
+            buf[:, :g.shape[1], :3] = g.flip(-1) if fmt.startswith("bgr") else g
+            out.append(Frame(buf, fmt))
+            continue
         if kind == "bgra-4k":
             buf = torch.full((h, w, 4), 128, dtype=torch.uint8, device="cuda")
             buf[:, :g.shape[1], :3] = g.flip(-1)
@@ -49,7 +57,22 @@ def device_frames(frames, kind):
         c = g[::2, ::2]
         buf[h:, 0:g.shape[1]:2] = (((-38 * c[..., 0] - 74 * c[..., 1] + 112 * c[..., 2] + 128) >> 8) + 128).to(torch.uint8)
         buf[h:, 1:g.shape[1]:2] = (((112 * c[..., 0] - 94 * c[..., 1] - 18 * c[..., 2] + 128) >> 8) + 128).to(torch.uint8)
-        out.append(Frame(buf, "nv12"))
+        if fmt in (None, "nv12"):
+            out.append(Frame(buf, "nv12"))
+            continue
+        Y, U, V = buf[:h], buf[h:, 0::2], buf[h:, 1::2]   # the same samples in the format's layout
+        if fmt == "gray8":
+            out.append(Frame(Y.contiguous(), fmt))
+        elif fmt == "p010":
+            out.append(Frame((buf.to(torch.int32) << 8).to(torch.uint16), fmt))
+        elif fmt in ("i420", "yv12"):
+            first, second = (U, V) if fmt == "i420" else (V, U)
+            out.append(Frame(torch.cat([Y.reshape(-1), first.reshape(-1), second.reshape(-1)]).reshape(h * 3 // 2, w), fmt))
+        else:
+            c = torch.stack([U, V], -1).repeat_interleave(2, 0).reshape(h, w // 2, 2)     # a chroma row per picture row
+            pair = torch.stack([Y[:, 0::2], c[..., 0], Y[:, 1::2], c[..., 1]], -1) if fmt == "yuyv422" else \
+                torch.stack([c[..., 0], Y[:, 0::2], c[..., 1], Y[:, 1::2]], -1)
+            out.append(Frame(pair.reshape(h, w, 2).contiguous(), fmt))
     return out
 
 
@@ -144,7 +167,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-ticks", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--formats", default=None, help="comma list of pixel formats: adds the source <format>-1080p for each")
     args = ap.parse_args()
+    for f in (args.formats.split(",") if args.formats else []):
+        SOURCES.setdefault(f"{f}-1080p", (1080, 1920, 2.25))
     args.slots = [int(s) for s in args.slots.split(",")]
     import torch
     if not torch.cuda.is_available():

@@ -5,14 +5,15 @@
 
 and with --lens two more, the same frames with a strong lens (brown -0.35 0.12 0.001 -0.0005 -0.02, f = 1000 / 333) through the mesh path
 of g6d_frame_ingest_mesh (nv12-1080p-lens, rgb-same-lens), and nv12-1080p-mixed: 31 plain frames and one lens frame, so that the plain
-frames take the plain tile of the lens kernel.  --rounds R runs the cases R times in turn (variants alternate; the table gives the
+frames take the plain tile of the lens kernel.  --formats a,b,.. adds one case per named pixel format (any of ingest.FORMATS):
+<format>-1080p, 32 x (1080x1920 frames of that format -> 540x960 canvas).  --rounds R runs the cases R times in turn (variants alternate; the table gives the
 spread of the rounds' medians).
 
 Bytes are counted from shapes: the source rows a launch touches (every row of every plane, pixel bytes only) plus the canvas bytes it
 writes.  Timing: device events around `--launches` back-to-back launches (includes the table upload of each call), or, under the profiler,
 the kernel's own durations:
 
-  python tools/ingest_bench.py [--launches 50] [--lens] [--rounds 3]
+  python tools/ingest_bench.py [--launches 50] [--lens] [--rounds 3] [--formats nv12,bgr24,yuyv422,uyvy422,i420,yv12,p010,gray8]
   rocprofv3 --kernel-trace -d DIR -o ingest --output-format csv -- python tools/ingest_bench.py [--lens] [--rounds 3]
   python tools/ingest_bench.py --trace-csv DIR/.../ingest_kernel_trace.csv [--lens] [--rounds 3] [--tick-ms T] [--out FILE.md]
 """
@@ -34,10 +35,22 @@ BROWN = (-0.35, 0.12, 0.001, -0.0005, -0.02)
 WARM = 3
 
 
+# source bytes per pixel: every sample of every plane
+SRC_BYTES = {"rgb24": 3, "bgr24": 3, "rgba32": 4, "bgra32": 4, "nv12": 1.5, "yuyv422": 2, "uyvy422": 2, "i420": 1.5, "yv12": 1.5, "p010": 3, "gray8": 1}
+
+
 def case_bytes(c):
     (h, w), (H, W) = c["src"], c["canvas"]
-    src = h * w * 3 // 2 if c["fmt"] == "nv12" else h * w * 3
-    return N * (src + H * W * 3)
+    return N * (int(h * w * SRC_BYTES[c["fmt"]]) + H * W * 3)
+
+
+def frame_array(rng, fmt, h, w):
+    """A noise picture of the format as the array ingest.Frame takes: [H,W,C] packed, [H*3/2, W] for the 4:2:0 formats (uint16 for p010)."""
+    if fmt == "p010":
+        return (rng.randint(0, 1024, (h * 3 // 2, w)) << 6).astype(np.uint16)
+    shape = {"nv12": (h * 3 // 2, w), "i420": (h * 3 // 2, w), "yv12": (h * 3 // 2, w), "yuyv422": (h, w, 2), "uyvy422": (h, w, 2),
+             "gray8": (h, w), "rgba32": (h, w, 4), "bgra32": (h, w, 4)}.get(fmt, (h, w, 3))
+    return rng.randint(0, 256, shape).astype(np.uint8)
 
 
 def trace_table(path, cases, launches, rounds, tick_ms):
@@ -67,11 +80,14 @@ def main():
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--lens", action="store_true", help="add the lens cases (g6d_frame_ingest_mesh)")
     ap.add_argument("--rounds", type=int, default=1, help="run the cases this many times in turn")
+    ap.add_argument("--formats", default=None, help="comma list of pixel formats: adds the case <format>-1080p for each")
     ap.add_argument("--trace-csv", default=None)
     ap.add_argument("--tick-ms", type=float, default=0.0, help="tick time of the 32-stream tracker the kernel time is set against")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    cases = dict(CASES, **LENS_CASES) if args.lens else CASES
+    cases = dict(CASES, **LENS_CASES) if args.lens else dict(CASES)
+    for fmt in (args.formats.split(",") if args.formats else []):
+        cases.setdefault(f"{fmt}-1080p", dict(src=(1080, 1920), fmt=fmt, canvas=(540, 960)))
     if args.trace_csv:
         txt = trace_table(args.trace_csv, cases, args.launches, args.rounds, args.tick_ms)
         print(txt)
@@ -88,10 +104,9 @@ def main():
     work = {}
     for name, c in cases.items():
         (h, w), (H, W) = c["src"], c["canvas"]
-        shape = (h * 3 // 2, w) if c["fmt"] == "nv12" else (h, w, 3)
         f = 1000.0 * w / 1920
         K = np.array([[f, 0, w / 2 - 0.5], [0, f, h / 2 - 0.5], [0, 0, 1]])
-        frames = [Frame(torch.from_numpy(rng.randint(0, 256, shape).astype(np.uint8)).cuda(), c["fmt"],
+        frames = [Frame(torch.from_numpy(frame_array(rng, c["fmt"], h, w)).cuda(), c["fmt"],
                         **(dict(K=K, lens=Lens("brown", BROWN)) if i < c.get("lens", 0) else {})) for i in range(N)]
         work[name] = (frames, torch.zeros((N, H, W, 3), dtype=torch.uint8, device="cuda"), torch.zeros((N, 3, 3), device="cuda"))
     for _ in range(args.rounds):
