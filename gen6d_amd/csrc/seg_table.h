@@ -7,7 +7,7 @@
 
 constexpr int G6D_MAX_SEG = 4;
 // How far (in floats) a launch reaches from its lowest input address
-constexpr long long G6D_REACH_BUFFER_LOAD = 1ll << 29;      // 2 GB: the bound of the buffer loads (wino_conv.hip, wino43_conv.hip)
+constexpr long long G6D_REACH_BUFFER_LOAD = 1ll << 29;      // 2 GB: the bound of the buffer loads (wino_conv.hip, wino16_conv.hip, wino43_conv.hip)
 constexpr long long G6D_REACH_CORR_PATCH = 1ll << 30;       // the bound of corr_patch.hip's addressing
 constexpr long long G6D_REACH_OUT = 1ll << 31;              // outputs: 32-bit float offsets
 // Hints of the bad-row message: tables that may give full outputs, pooled outputs or both; the Winograd correlations' rule on row lengths

@@ -1,5 +1,5 @@
 // 3x3 stride-1 pad-1 convolution as Winograd F(4x4,3x3) on the fp32 matrix cores of gfx950: 36 multiplications per 16 outputs —
-// 4x fewer than the direct form, 1.78x fewer than the F(2x2,3x3) kernel of wino_conv.hip.  Used where the parity budget has
+// 4x fewer than the direct form, 1.78x fewer than the F(2x2,3x3) kernels of wino_conv.hip / wino16_conv.hip.  Used where the parity budget has
 // room for the larger transform constants: the detector's image-pyramid trunk (reference
 // network/pretrain_models.py:9-31, network/detector.py:188-197), its 15x15 reference-as-filter correlation as 5x5 blocks of 3x3
 // (network/detector.py:222-224) and the refiner's 32^3 volume layers (network/refiner.py:88-143).
@@ -19,7 +19,7 @@
 // vector-ALU instructions never overlap with fp32 MFMAs, and 36 accumulator tiles of 32 tiles x 32 channels (576 registers) do not
 // fit one wave.
 //   block   = 256 threads = 4 waves = 8 "quarters" (8x8 output pixels = 2x2 Winograd tiles, the same flat quarter list as
-//             wino_conv.hip) x 16*NT output channels (NT = 4: 64 channels; NT = 2: 32, the correlation's 32 references).
+//             the F(2x2,3x3) kernels, built by wino_plan.h) x 16*NT output channels (NT = 4: 64 channels; NT = 2: 32, the correlation's 32 references).
 //   wave    = (pair pr, half hh): pair pr owns 16 tiles (4 quarters); the two waves of a pair split the 36 transform positions
 //             by ROW: wave hh holds rows a = 3hh..3hh+2, all 6 columns b, for all 16*NT channels: 18 x NT accumulators of 4
 //             registers (288 at NT = 4).  A 16-row A operand against a 64-column B operand halves the input-transform work per
@@ -40,7 +40,7 @@
 //             hand-off of g6d_common.h as in the other kernels.
 #include "g6d_common.h"
 #include "seg_table.h"
-#include <stdlib.h>
+#include "wino_plan.h"
 #include <stdio.h>
 #include <algorithm>
 #include <type_traits>
@@ -66,18 +66,18 @@ namespace {
 #define W43_QPIX 101                         // position stride between quarters (10 x 10 used); odd: conflict-free b64 reads
 #define W43_NQ 8                             // quarters per block
 #define W43_RAWF (28 * 64 * 4)               // floats of the raw patch region: 8 quarters x 101 positions x 8 channels, rounded up to 28 KB
-#define W43_MAX_SEG 4
+static_assert(W43_NQ == wplan::F4_NQ && W43_RAWF == wplan::F4_RAWF, "the limits and LDS sizes of wino_plan.h count these");
 
 constexpr float WA = 0.75f, WB = 1.5f;
 constexpr float WA2 = WA * WA, WB2 = WB * WB, WA3 = WA * WA * WA, WB3 = WB * WB * WB;
 constexpr float WC0 = WA2 * WB2, WC2 = WA2 + WB2;
 
-struct W43Seg { int qstart, N, H, W, QH, QW, in_off, full_off, pool_off, ld_in, ld_full, ld_pool; };
+typedef wplan::Seg W43Seg;
 
 struct W43Args {
   const float* in; const float* U; const float* bias; float* out_full; float* out_pool;
   int Cin, Cout, relu;
-  int nseg, qtotal; W43Seg seg[W43_MAX_SEG];
+  int nseg, qtotal; W43Seg seg[wplan::MAX_SEG];
   unsigned in_bytes;                             // extent of the input tensor(s) from `in` (< 2^31): bound of the buffer loads
   int splits, chunks_per_split; float* ws;
   int D;                                         // depth slices per image (1 for 2-D layers); KD = 3 pads in depth
@@ -129,7 +129,7 @@ __device__ __forceinline__ QGeo quarter_of(const W43Args& p, int bx, int q) {
   const int Q = bx * W43_NQ + q;
   int sidx = 0;
 #pragma unroll
-  for (int k = 1; k < W43_MAX_SEG; ++k) sidx = (k < p.nseg && Q >= p.seg[k].qstart) ? k : sidx;
+  for (int k = 1; k < wplan::MAX_SEG; ++k) sidx = (k < p.nseg && Q >= p.seg[k].qstart) ? k : sidx;
   const W43Seg& sg = p.seg[sidx];
   QGeo g;
   g.valid = Q < p.qtotal;
@@ -715,12 +715,11 @@ __global__ void __launch_bounds__(256, 1) wino43_kernel(const W43Args p) {
 #endif
 }
 
-// ---- launch: split over the chunks, instantiation
+// ---- launch: plan (wino_plan.h), instantiation
 template <int MODE, int KD, int NT>
 int w43_launch_t(W43Args& a, long long blocks, hipStream_t stream) {
-  const size_t lds_bytes = ((size_t)2 * W43_RAWF + 2 * (18 * 16 * NT * 8) + (MODE == 0 ? 0 : (MODE >= 2 ? 2 * W43_NQ : 2) * a.Cin)) * sizeof(float);
-  const size_t need = std::max(lds_bytes, (size_t)4 * 4096 * sizeof(float));      // the epilogue exchange: 16 KB per wave
-  g6d_allow_lds(reinterpret_cast<const void*>(&wino43_kernel<MODE, KD, NT>), 160 * 1024 - 512);      // (512 B of static LDS: the quarter table)
+  const size_t need = std::max(wplan::f4_lds_bytes(MODE, NT, a.Cin), (size_t)4 * 4096 * sizeof(float));      // the epilogue exchange: 16 KB per wave
+  g6d_allow_lds(reinterpret_cast<const void*>(&wino43_kernel<MODE, KD, NT>), (int)wplan::LDS_MAX - 512);      // (512 B of static LDS: the quarter table)
   a.gx = (int)blocks; a.gy = a.Cout / (16 * NT);
   a.map_mode = (int)g6d_knob(G6D_KNOB_W43_MAP);
   if (a.gy == 1 || (long long)a.gx * a.gy >= (1ll << 31)) a.map_mode = 0;
@@ -729,64 +728,21 @@ int w43_launch_t(W43Args& a, long long blocks, hipStream_t stream) {
   return g6d_check_launch("wino43_conv3x3");
 }
 
-// The hard size limits of a launch, shared by w43_run (error) and g6d_wino43_eligible (fall back to another kernel): 32-bit grid,
-// the 2^31-byte reach of the buffer loads on input and filter bank, the affine tables beside the stages in LDS.  nullptr = fits.
-const char* w43_limits(long long quarters, long long in_extent_floats, int kd, int Cin, int Cout, int mode) {
-  if ((quarters + W43_NQ - 1) / W43_NQ > 0x3fffffffll) return "wino43: grid too large";
-  if (in_extent_floats * 4 >= (1ll << 31)) return "wino43: input tensor exceeds 2^31 bytes";
-  if ((long long)kd * (Cin / 8) * 36 * Cout * 32 >= (1ll << 31)) return "wino43: filter bank exceeds 2^31 bytes";
-  const int nt = (Cout & 63) ? 2 : 4;
-  if (mode != 0 && (size_t)(mode >= 2 ? 2 * W43_NQ : 2) * Cin * 4 + ((size_t)2 * W43_RAWF + 2 * 18 * 16 * nt * 8) * 4 > 160 * 1024 - 512)
-    return "wino43: affine tables do not fit LDS";
-  return nullptr;
-}
-
 int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
-  long long quarters = 0, in_extent = 0;
-  double out_elems = 0.0;
-  for (int k = 0; k < a.nseg; ++k) {
-    W43Seg& g = a.seg[k];
-    in_extent = std::max(in_extent, (long long)g.in_off + (long long)g.N * g.H * g.W * g.ld_in);
-    g.QH = (g.H + 7) / 8; g.QW = (g.W + 7) / 8;
-    g.qstart = (int)quarters;
-    quarters += (long long)g.N * g.QH * g.QW;
-    out_elems += (double)g.N * g.H * g.W;
-  }
+  // (the model's constants can be overridden for measurements)
+  const wplan::F4Knobs knobs = {(int)g6d_knob(G6D_KNOB_W43_SPLIT_MAX), g6d_knob(G6D_KNOB_W43_SPLIT_GAIN), g6d_knob(G6D_KNOB_W43_CHUNK_US)};
+  const wplan::F4Plan pl = wplan::f4_plan(a.seg, a.nseg, mode, kd, a.Cin, a.Cout, wplan::room(workspace != nullptr, workspace_bytes, G6D_WS_COUNTER_BYTES),
+                                          G6D_WS_COUNTERS, knobs);
+  if (pl.error) { g6d_set_error(pl.error); return G6D_EINVAL; }
   a.H0 = a.seg[0].H; a.W0 = a.seg[0].W; a.ld0 = a.seg[0].ld_in;
-  const long long blocks = (quarters + W43_NQ - 1) / W43_NQ;
-  const int nt = (a.Cout & 63) ? 2 : 4;
-  if (const char* why = w43_limits(quarters, in_extent, kd, a.Cin, a.Cout, mode)) { g6d_set_error(why); return G6D_EINVAL; }
-  a.qtotal = (int)quarters;
-  a.in_bytes = (unsigned)(in_extent * 4);
-  // Split of the (kd, chunk) list over gridDim.z: one block per CU is resident and runs a serial loop of ~2.6 us per chunk (NT = 4;
-  // ~1.5 at NT = 2); pick the split count with the smallest modelled time, as wino_conv.hip does (constants overridable)
-  const int nchunks = kd * (a.Cin / 8);
-  int splits = 1;
-  const long long grid2 = blocks * (a.Cout / (16 * nt));
-  const int split_max = (int)g6d_knob(G6D_KNOB_W43_SPLIT_MAX);
-  const double m_gain = g6d_knob(G6D_KNOB_W43_SPLIT_GAIN);
-  const double m_chunk4 = g6d_knob(G6D_KNOB_W43_CHUNK_US);
-  const size_t room = workspace && workspace_bytes > G6D_WS_COUNTER_BYTES ? workspace_bytes - G6D_WS_COUNTER_BYTES : 0;
-  const double tile_bytes = (double)grid2 * 256 * nt * 32 * sizeof(float);
-  if (room > 0 && grid2 <= G6D_WS_COUNTERS && split_max > 1 && nchunks >= 4) {
-    const double out_bytes = out_elems * a.Cout * sizeof(float);
-    double best = 1e30;
-    for (int sp = 1; sp <= split_max && sp <= nchunks / 2; ++sp) {
-      if ((double)sp * tile_bytes > (double)room) break;
-      const int cps_ = (nchunks + sp - 1) / sp, real = (nchunks + cps_ - 1) / cps_;
-      if (real != sp) continue;
-      const double rounds = (double)((grid2 * sp + 255) / 256);
-      double t = rounds * (cps_ * (nt == 4 ? m_chunk4 : 0.55 * m_chunk4) + 6.0);
-      if (sp > 1) t += 2.0 + 0.6 * sp + (2 * sp + 1) * out_bytes / 2.5e6;
-      if (t < best * m_gain) { best = t; splits = sp; }
-    }
-  }
-  const int cps = (nchunks + splits - 1) / splits;
-  splits = (nchunks + cps - 1) / cps;
-  a.splits = splits; a.chunks_per_split = cps; a.ws = workspace;
-  const bool debug = g6d_knob(G6D_KNOB_WINO_DEBUG) == 1;
-  if (debug) fprintf(stderr, "wino43 %d seg, %dx%dx%d->%d kd=%d mode=%d: grid %lld x %d splits of %d chunks\n", a.nseg, a.seg[0].H, a.seg[0].W, a.Cin,
-                     a.Cout, kd, mode, grid2, splits, cps);
+  a.qtotal = (int)pl.q.quarters;
+  a.in_bytes = (unsigned)(pl.q.in_extent * 4);
+  a.splits = pl.split.splits; a.chunks_per_split = pl.split.chunks_per_split; a.ws = workspace;
+  if (g6d_knob(G6D_KNOB_WINO_DEBUG) == 1)
+    fprintf(stderr, "wino43 %d seg, %dx%dx%d->%d kd=%d mode=%d: grid %lld x %d splits of %d chunks\n", a.nseg, a.seg[0].H, a.seg[0].W, a.Cin,
+            a.Cout, kd, mode, pl.grid2, a.splits, a.chunks_per_split);
+  const long long blocks = pl.blocks;
+  const int nt = pl.nt;
   if (kd == 25) return nt == 4 ? w43_launch_t<0, 25, 4>(a, blocks, stream) : w43_launch_t<0, 25, 2>(a, blocks, stream);
   if (kd == 9) return nt == 4 ? w43_launch_t<0, 9, 4>(a, blocks, stream) : w43_launch_t<0, 9, 2>(a, blocks, stream);
   if (nt != 4) { g6d_set_error("wino43: Cout % 64 == 0 expected"); return G6D_EINVAL; }
@@ -794,15 +750,6 @@ int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_byt
   if (mode == 2) return w43_launch_t<2, 1, 4>(a, blocks, stream);
   if (mode == 1) return w43_launch_t<1, 1, 4>(a, blocks, stream);
   return w43_launch_t<0, 1, 4>(a, blocks, stream);
-}
-
-// The segment list and bases of a multi-map launch from its validated table (seg_table.h)
-void w43_segments(W43Args& a, const G6dSegTable& t) {
-  a.in = t.in; a.out_full = t.full; a.out_pool = t.pool; a.nseg = t.nseg;
-  for (int k = 0; k < t.nseg; ++k) {
-    const G6dSeg& g = t.seg[k];
-    a.seg[k] = W43Seg{0, g.N, g.H, g.W, 0, 0, g.in_off, g.full_off, g.pool_off, g.ld_in, g.ld_full, g.ld_pool};
-  }
 }
 
 }  // namespace
@@ -821,14 +768,14 @@ extern "C" int g6d_w43_timing_read(unsigned long long* out) {      // [4 waves][
 // Replaces features[4..27] of vgg11_bn on the detector's image pyramid (network/pretrain_models.py:17-25, network/detector.py:236-241).
 extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U43, const float* bias, int Cout, int relu,
                                         float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
-  if (!segs || nseg < 1 || nseg > W43_MAX_SEG || !U43 || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U43)) {
+  if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U43 || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U43)) {
     g6d_set_error("wino43_conv3x3_multi: bad args (1..4 segments, Cin % 8 == 0, Cout % 64 == 0)"); return G6D_EINVAL;
   }
   G6dSegTable t;
   if (int rc = g6d_seg_table("wino43_conv3x3_multi", "segment", G6D_SAME_KINDS, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
   W43Args a = {};
   a.U = U43; a.bias = bias; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1;
-  w43_segments(a, t);
+  wplan::segments(t, a.seg, a.nseg, a.in, a.out_full, a.out_pool);
   return w43_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -839,7 +786,7 @@ extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Ci
 // c * 25 + b = 8-channel chunk c of block b = 5 bi + bj holding w[:, 3bi..3bi+2, 3bj..3bj+2, :]; Cout % 32 == 0.
 extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin, const float* U43, int Cout, int kblocks, float* workspace,
                                        size_t workspace_bytes, g6d_stream_t stream) {
-  if (!segs || nseg < 1 || nseg > W43_MAX_SEG || !U43 || (kblocks != 5 && kblocks != 3) || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 31) || !g6d_aligned16(U43)) {
+  if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U43 || (kblocks != 5 && kblocks != 3) || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 31) || !g6d_aligned16(U43)) {
     g6d_set_error("corr2d_wino43_multi: bad args (1..4 map sizes, 15x15 = 5 blocks or 9x9 = 3 blocks, Cin % 8 == 0, Cout % 32 == 0)"); return G6D_EINVAL;
   }
   for (int k = 1; k < nseg; ++k)
@@ -848,7 +795,7 @@ extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin
   if (int rc = g6d_seg_table("corr2d_wino43_multi", "map", G6D_SHARED_LD_IN, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
   W43Args a = {};
   a.U = U43; a.bias = nullptr; a.Cin = Cin; a.Cout = Cout; a.relu = 0; a.D = 1;
-  w43_segments(a, t);
+  wplan::segments(t, a.seg, a.nseg, a.in, a.out_full, a.out_pool);
   return w43_run(a, 0, kblocks * kblocks, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -863,11 +810,11 @@ bool g6d_wino43_eligible(const G6dConv& d) {
   if (d.stats && d.stat_rows_per_group > 0 && d.stat_rows_per_group % (d.Do * d.Ho * d.Wo)) return false;
   if (d.in_scale && (d.Cin > 256 || (d.Cin & 3))) return false;      // affine prologue: tested up to 256 input channels
   if (!g6d_aligned16(d.weight_wino43)) return false;
-  // the launch's own hard limits (w43_run would refuse): such a layer falls through to the F(2x2,3x3) / implicit-GEMM kernels and
+  // the launch's own hard limits (wplan::f4_limits: w43_run would refuse): such a layer falls through to the F(2x2,3x3) / implicit-GEMM kernels and
   // g6d_conv_plan reports that family
   const long long quarters = (long long)d.N * d.Di * ((d.Hi + 7) / 8) * ((d.Wi + 7) / 8);
   const int mode = !d.in_scale ? 0 : (d.in_affine_per_n ? 2 : 1);
-  if (w43_limits(quarters, (long long)d.N * d.Di * d.Hi * d.Wi * d.ld_in, d.kd, d.Cin, d.Cout, mode)) return false;
+  if (wplan::f4_limits(quarters, (long long)d.N * d.Di * d.Hi * d.Wi * d.ld_in, d.kd, d.Cin, d.Cout, mode)) return false;
   if ((long long)d.N * d.Do * d.Ho * d.Wo * d.ld_out >= (1ll << 31)) return false;      // 32-bit output offsets
   return (long long)d.N * d.Di * d.Hi * d.Wi * d.ld_in < (1ll << 29);
 }

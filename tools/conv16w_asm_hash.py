@@ -4,9 +4,13 @@ code as it was:
     python tools/conv16w_asm_hash.py old.s new.s [kernel-name pattern]
 The optional third argument is a regular expression for the kernels' (mangled) names, default conv16w_kernel: `kernel` covers every
 kernel of a translation unit, whichever file the two assembly files were built from.  The tool also serves gen6d_amd/csrc/conv16_tap.hip
-(pattern conv16r?_kernel) and gen6d_amd/csrc/corr16.hip (pattern corr16_kernel), and a kernel that moved between files: old.s and new.s need not come from the same source file.
+(pattern conv16r?_kernel), gen6d_amd/csrc/corr16.hip (pattern corr16_kernel) and the Winograd family, gen6d_amd/csrc/wino_conv.hip,
+wino16_conv.hip and wino43_conv.hip (pattern kernel, built with -fno-slp-vectorize as the Makefile builds them), and a kernel that moved
+between files: old.s and new.s need not come from the same source file, and new.s may be several assembly files concatenated.
 Instructions and directives only: comments, block-label numbering and the kernel's own mangled name are normalised, and a trailing
-KD = 1 template argument is dropped from the name, so that an instantiation keeps its key when the template gains that parameter."""
+KD = 1 template argument is dropped from the name, so that an instantiation keeps its key when the template gains that parameter (a
+FOURTH argument equal to 1 only: of the Winograd family this shortens wino_conv3x3_kernel<0,1,4,1> alone, to a key no other
+instantiation has; the three-argument wino16_conv_kernel<MM,MODE,KD> and wino43_kernel<MODE,KD,NT> keep theirs)."""
 import re, sys, hashlib
 def bodies(path, pat):
     text = open(path).read()

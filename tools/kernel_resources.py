@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Register / scratch / occupancy summary of every kernel in a .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-Usage: python tools/kernel_resources.py gen6d_amd/csrc/wino_conv.hip [...]"""
+Usage: python tools/kernel_resources.py gen6d_amd/csrc/wino_conv.hip gen6d_amd/csrc/wino16_conv.hip [...]"""
 import re
 import subprocess
 import sys
