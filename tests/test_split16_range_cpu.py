@@ -24,6 +24,23 @@ def reparam(sd, gains, prefix="backbone.features"):
     return out
 
 
+def reparam_channels(sd, gains, prefix="backbone.features"):
+    """reparam with a vector of power-of-two gains per layer: channel c of the BatchNorm after VGG conv i scales by gains[i][c] (gamma[c]
+    and beta[c] times g[c]), conv i + 1 takes weight[:, c] / g[c].  ReLU and max-pool act per channel and are positively homogeneous, so
+    every scaling is exact and the network function is unchanged."""
+    convs = sorted((int(k.split(".")[-2]) for k, v in sd.items() if k.startswith(prefix) and k.endswith(".weight") and v.dim() == 4))
+    out = {k: v.clone() for k, v in sd.items()}
+    for i, g in gains.items():
+        g = torch.as_tensor(g, dtype=torch.float32)
+        assert bool((torch.frexp(g)[0] == 0.5).all()), "power-of-two gains only"
+        bn = f"{prefix}.{convs[i] + 1}"
+        assert g.shape == out[f"{bn}.weight"].shape
+        out[f"{bn}.weight"] *= g
+        out[f"{bn}.bias"] *= g
+        out[f"{prefix}.{convs[i + 1]}.weight"] /= g.view(1, -1, 1, 1)
+    return out
+
+
 @pytest.mark.parametrize("a,e", [
     (0.0, 0), (2.0 ** -4, 0), (1.0, 0), (math.nextafter(2.0 ** 14, 0), 0),
     (2.0 ** 14, 14), (2.0 ** 20 * 1.5, 20), (math.nextafter(2.0 ** -4, 0), -5), (2.0 ** -12, -12), (3e-40, -100), (3e38, 100)])
