@@ -130,17 +130,20 @@ class DeviceChain:
         the estimator-level counterpart of `TensorPipeline.query` with the data flow between the stages real.
         pose_init [B,3,4] (device; tracking, gen6d_amd/tracking.py): detection and selection are skipped ('det', 'sel', 'logits' and
         'crop' are None) and `refine_iter` steps (default 1) run from it; B <= refiner.MAX_BATCH then."""
-        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, None)
+        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, None, False)
 
-    def query_batch_source(self, que_imgs, que_Ks, source, pose_init=None, refine_iter=None):
+    def query_batch_source(self, que_imgs, que_Ks, source, pose_init=None, refine_iter=None, minify="point"):
         """`query_batch` with the two crops it cuts from que_imgs, the selector's after detection and the refiner's query crop of every
         step, cut from the camera-native pictures instead: source is the `ingest.SourceTable` of the B canvases, and one g6d_frame_crop
         launch stands in place of each of those warp launches.  A slot without a source record keeps its canvas crop.
         Reference crops, the detector's input and the intrinsics are what they are in `query_batch`: the composition happens inside the
-        sampler."""
-        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, source)
+        sampler.  minify="area": g6d_frame_crop_area with max_n = 8 stands there instead, which supersamples the crops of a slot that
+        shrinks its source; a slot that does not gets the same values."""
+        if minify not in ("point", "area"):
+            raise ValueError(f"query_batch_source: minify must be \"point\" or \"area\", not {minify!r}")
+        return self._query_batch(que_imgs, que_Ks, pose_init, refine_iter, source, minify == "area")
 
-    def _query_batch(self, que_imgs, que_Ks, pose_init, refine_iter, source):
+    def _query_batch(self, que_imgs, que_Ks, pose_init, refine_iter, source, area):
         est, size = self.est, self.size
         astep = est.refiner.angle_step() if est.refiner is not None else 0.0
         B = que_imgs.shape[0]
@@ -148,6 +151,8 @@ class DeviceChain:
             if source is None:
                 ar = torch.arange(B, dtype=torch.int32, device=self.dev)
                 cut = lambda hinv, n: ops.warp_batch(que_imgs, None, ar, hinv, n, n)
+            elif area:
+                cut = lambda hinv, n: ops.frame_crop_area(source.table, source.rec, que_imgs, hinv, n, n, max_n=8)
             else:
                 cut = lambda hinv, n: ops.frame_crop(source.table, source.rec, que_imgs, hinv, n, n)
             K9 = que_Ks.reshape(B, 9).contiguous()

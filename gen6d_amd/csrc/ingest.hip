@@ -13,6 +13,7 @@
 // source coordinates from it (nodes in LDS, 64-bit integer interpolation), blocks of a frame without one run the plain tile.
 // Frames of the formats after NV12 and of the full-range matrices take a block-uniform branch to the same tiles on
 // frame_src.h's `Yuv` taps, in both kernels: a tick that mixes all eleven formats, with and without lenses, is one launch.
+// g6d_frame_ingest_area (last part of the file) is the launch with an exact-integer area filter where a picture shrinks (§4.26).
 #include "frame_src.h"
 
 namespace {
@@ -300,6 +301,176 @@ __global__ void __launch_bounds__(256) frame_ingest_lens_kernel(const G6dFrame* 
   else plain_tile<false>(f, cw, out, slot, H, W, X0, Y0);
 }
 
+// ---- g6d_frame_ingest_area: the same launch with an area filter on every axis that shrinks (include/gen6d_hip.h) ----
+// The two kernels above stay as they were measured.  Same tiles, same flat block list; what differs is the thread's work.  A canvas pixel
+// of a shrinking axis owns the source stretch [t S, (t+1) S) / T, so the footprints of neighbouring pixels are disjoint but for the source
+// pixel a boundary cuts: a per-thread loop over the footprint reads every source byte once (twice at such a boundary, from the same
+// block or its tile neighbour) and converts it there, and a horizontal pass staged in LDS would have nothing left to share.  What decides
+// the speed is which lanes sit side by side: thread = one canvas COLUMN of the tile (4 of its 8 rows), so the 64 lanes of a wave walk 64
+// neighbouring footprints of one canvas row and each of their loads covers one contiguous stretch of a source row (at 4:1, 256 bytes of a
+// luma plane).  The 3-byte results go through LDS and leave as dwords, as the plain tile's do.  A turned frame (90 / 270) reads columns,
+// as it does in the plain tile.  The descriptors (first index, first weight, count) of the tile's 128 columns and 8 rows are built
+// once per tile with 32-bit divisions (t S < 2^26); the tap loops divide nothing.  Cost grows with the footprint: one thread sums
+// (S / T)^2 taps per pixel, which is the work there is for the ratios the ingest is meant for and slow for a thumbnail of a huge frame.
+
+// canvas coordinate t of an axis with `tgt` picture pixels over `src` source pixels -> (i0 | w0 << 13, count): the taps i0 .. i0 + count - 1;
+// the first weighs w0, every later one min(step, what is left of D), step = tgt and D = src where the axis shrinks, else 2048 and 2048
+__device__ __forceinline__ uint2 area_word(int t, int tgt, int src) {
+  if (src <= tgt) {                                       // no shrink: the plain rule's two taps (2048 - a, a), one when a == 0
+    const unsigned v = sample_word(t, tgt, src), a = v >> 14;
+    return make_uint2((v & 8191u) | ((2048u - a) << 13), a ? 2u : 1u);
+  }
+  const unsigned lo = (unsigned)t * (unsigned)src;        // t < tgt < src <= 8192: below 2^26
+  const unsigned i0 = lo / (unsigned)tgt, i1 = (lo + (unsigned)src - 1u) / (unsigned)tgt;
+  return make_uint2(i0 | (((i0 + 1u) * (unsigned)tgt - lo) << 13), i1 - i0 + 1u);   // (i0 + 1) tgt <= lo + tgt < lo + src: the min of the rule
+}
+
+// floor((2 sigma + D) / (2 D)) with d2 = 2 D <= 2^27 and sigma <= 255 D: the quotient is at most 255, so a float estimate (relative error
+// below 2^-21, absolute below 2^-13) is the floor or one beside it, and one exact 64-bit remainder settles which
+__device__ __forceinline__ int area_round(unsigned long long sigma, unsigned d2, float inv) {
+  const unsigned long long n = 2ull * sigma + (d2 >> 1);
+  int q = (int)((float)n * inv);
+  const long long r = (long long)n - (long long)q * (long long)d2;
+  if (r < 0) --q;
+  else if (r >= (long long)d2) ++q;
+  return q;
+}
+
+// KIND: 0 packed RGB, 1 NV12 under matrix 0 / 1 (both on `Src`), 2 the 8-bit YUV layouts on `Yuv`, 3 P010, 4 GRAY8
+template <int KIND, typename S>
+__device__ __forceinline__ void area_sum(const S& s, uint2 xd, uint2 yd, unsigned xstep, unsigned xD, unsigned ystep, unsigned yD,
+                                         unsigned long long& R, unsigned long long& G, unsigned long long& Bl) {
+  const int x0 = xd.x & 8191, y0 = yd.x & 8191, nx = (int)xd.y, ny = (int)yd.y;
+  const unsigned xw0 = xd.x >> 13;
+  unsigned wy = yd.x >> 13, ly = yD - wy;
+  R = G = Bl = 0;
+  for (int j = 0; j < ny; ++j) {
+    const int y = y0 + j;
+    unsigned rr = 0, gg = 0, bb = 0, wx = xw0, lx = xD - xw0;   // a row's sums: at most 255 * 2^13
+    int r1, g1, b1;
+    if constexpr (KIND == 1) {                            // a UV sample is loaded and converted once for the taps of a row that share it
+      int cx = -1;
+      Chroma k;
+      for (int i = 0; i < nx; ++i) {
+        const int x = x0 + i;
+        if ((x >> 1) != cx) { cx = x >> 1; k = chroma(s, cx, y >> 1); }
+        tap_nv12(s, k, x, y, r1, g1, b1);
+        rr += wx * r1; gg += wx * g1; bb += wx * b1;
+        wx = min(xstep, lx); lx -= wx;
+      }
+    } else if constexpr (KIND == 2 || KIND == 3) {
+      using T = typename std::conditional<KIND == 3, long long, int>::type;
+      int cx = -1;
+      Kc<T> k;
+      for (int i = 0; i < nx; ++i) {
+        const int x = x0 + i;
+        if ((x >> 1) != cx) { cx = x >> 1; k = yuv_chroma<T>(s, cx, y >> s.csy); }
+        yuv_tap<T>(s, k, x, y, r1, g1, b1);
+        rr += wx * r1; gg += wx * g1; bb += wx * b1;
+        wx = min(xstep, lx); lx -= wx;
+      }
+    } else {
+      for (int i = 0; i < nx; ++i) {
+        if constexpr (KIND == 0) tap_packed(s, x0 + i, y, r1, g1, b1);
+        else { const Tap t = gray_tap(s, x0 + i, y); r1 = t.r; g1 = t.g; b1 = t.b; }
+        rr += wx * r1; gg += wx * g1; bb += wx * b1;
+        wx = min(xstep, lx); lx -= wx;
+      }
+    }
+    R += (unsigned long long)wy * rr; G += (unsigned long long)wy * gg; Bl += (unsigned long long)wy * bb;   // at most 255 * 2^26
+    wy = min(ystep, ly); ly -= wy;
+  }
+}
+
+// one tile of a frame by the area rule; aw: TW + TH descriptors, stage: the tile's TW x TH x 3 result bytes (LDS both)
+template <int KIND, typename S>
+__device__ __forceinline__ void area_tile(const G6dFrame& f, const S& s, uint2* aw, unsigned* stage, unsigned char* __restrict__ out, int slot,
+                                          int H, int W, int X0, int Y0) {
+  const int t = threadIdx.x;
+  const int rot = f.rotate;
+  const int ow = min(f.out_w, W), oh = min(f.out_h, H);   // an empty or negative picture leaves a black canvas
+  const bool swap = rot == 90 || rot == 270;
+  const int csrc = swap ? f.height : f.width, rsrc = swap ? f.width : f.height;   // the source extent a canvas column / row index runs over
+  if (t < TW + TH) {
+    uint2 v = make_uint2(0u, 0u);
+    if (t < TW) {
+      const int X = X0 + t;
+      if (X < ow) v = area_word((rot == 90 || rot == 180) ? f.out_w - 1 - X : X, f.out_w, csrc);
+    } else {
+      const int Y = Y0 + t - TW;
+      if (Y < oh) v = area_word((rot == 180 || rot == 270) ? f.out_h - 1 - Y : Y, f.out_h, rsrc);
+    }
+    aw[t] = v;
+  }
+  __syncthreads();
+  const bool cshrink = csrc > f.out_w, rshrink = rsrc > f.out_h;
+  const unsigned cstep = cshrink ? (unsigned)f.out_w : 2048u, cD = cshrink ? (unsigned)csrc : 2048u;
+  const unsigned rstep = rshrink ? (unsigned)f.out_h : 2048u, rD = rshrink ? (unsigned)rsrc : 2048u;
+  const unsigned d2 = 2u * cD * rD;                       // 2 D <= 2^27
+  const float inv = 1.f / (float)d2;
+  const int col = t & (TW - 1), X = X0 + col;
+  unsigned char* st = reinterpret_cast<unsigned char*>(stage);
+  const uint2 c = aw[col];
+#pragma unroll 1
+  for (int ry = t >> 7; ry < TH; ry += 2) {
+    int r = 0, g = 0, b = 0;
+    if (X < ow && Y0 + ry < oh) {
+      const uint2 rw = aw[TW + ry];
+      unsigned long long sr, sg, sb;
+      if (swap) area_sum<KIND>(s, rw, c, rstep, rD, cstep, cD, sr, sg, sb);
+      else area_sum<KIND>(s, c, rw, cstep, cD, rstep, rD, sr, sg, sb);
+      r = area_round(sr, d2, inv); g = area_round(sg, d2, inv); b = area_round(sb, d2, inv);
+    }
+    unsigned char* p = st + (ry * TW + col) * 3;
+    p[0] = (unsigned char)r; p[1] = (unsigned char)g; p[2] = (unsigned char)b;
+  }
+  __syncthreads();
+  // the tile's rows leave as dwords where the canvas row is dword-aligned (3 TW bytes of a row = 96 dwords), as bytes elsewhere
+  const int nb = 3 * min(TW, W - X0);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int idx = t + 256 * j, ry = idx / 96, b0 = 4 * (idx - ry * 96), Y = Y0 + ry;
+    if (Y >= H || b0 >= nb) continue;
+    unsigned char* o = out + (((size_t)slot * H + Y) * W + X0) * 3 + b0;
+    const unsigned v = stage[idx];
+    if (b0 + 4 <= nb && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) *reinterpret_cast<unsigned*>(o) = v;
+    else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (b0 + e < nb) o[e] = (unsigned char)(v >> (8 * e));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) frame_ingest_area_kernel(const G6dFrame* __restrict__ frames, const G6dMesh* __restrict__ meshes,
+                                                                unsigned char* __restrict__ out, int B, int H, int W,
+                                                                float* __restrict__ K_out, int tiles_x, int tiles) {
+  __shared__ uint2 aw[TW + TH];
+  __shared__ unsigned stage[TW * TH * 3 / 4];
+  __shared__ int2 nd[MESH_NX * MESH_NY];
+  const int fi = blockIdx.x / tiles, tile = blockIdx.x - fi * tiles;
+  const G6dFrame& f = frames[fi];
+  const int slot = f.slot;
+  if (slot < 0 || slot >= B) return;                      // (block-uniform, as every branch below)
+  if (tile == 0 && threadIdx.x < 9) K_out[(size_t)9 * slot + threadIdx.x] = f.K[threadIdx.x];
+  const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
+  if (meshes && meshes[fi].nodes) {                       // the lens fallback: a footprint that varies over a mesh is out of scope
+    if (extended(f)) mesh_tile<true>(f, meshes[fi], nd, out, slot, H, W, X0, Y0);
+    else mesh_tile<false>(f, meshes[fi], nd, out, slot, H, W, X0, Y0);
+    return;
+  }
+  if (extended(f)) {
+    const Yuv s = yuv_of(f);
+    if (s.kind == 0) area_tile<2>(f, s, aw, stage, out, slot, H, W, X0, Y0);
+    else if (s.kind == 1) area_tile<3>(f, s, aw, stage, out, slot, H, W, X0, Y0);
+    else area_tile<4>(f, s, aw, stage, out, slot, H, W, X0, Y0);
+  } else {
+    const Src s = source_of(f);
+    if (s.nv12) area_tile<1>(f, s, aw, stage, out, slot, H, W, X0, Y0);
+    else area_tile<0>(f, s, aw, stage, out, slot, H, W, X0, Y0);
+  }
+}
+
 }  // namespace
 
 extern "C" int g6d_sizeof_frame_desc(void) { return (int)sizeof(G6dFrame); }
@@ -329,4 +500,17 @@ extern "C" int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* mesh
   hipLaunchKernelGGL(frame_ingest_lens_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
                      meshes, out, B, H, W, K_out, tiles_x, tiles);
   return g6d_check_launch("frame_ingest_mesh");
+}
+
+extern "C" int g6d_frame_ingest_area(const G6dFrame* frames, const G6dMesh* meshes, int n, uint8_t* out, int B, int H, int W, float* K_out,
+                                     g6d_stream_t stream) {
+  if (!frames || n < 0 || !out || !K_out || B < 1 || H < 1 || W < 1) {
+    g6d_set_error("frame_ingest_area: bad args (null table / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
+  }
+  if (n == 0) return G6D_OK;
+  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
+  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_area: too many tiles for one launch"); return G6D_EINVAL; }
+  hipLaunchKernelGGL(frame_ingest_area_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
+                     meshes, out, B, H, W, K_out, tiles_x, tiles);
+  return g6d_check_launch("frame_ingest_area");
 }

@@ -405,23 +405,34 @@ def _mesh_key(frame, out_h, out_w, dev):
     return (dev, frame.lens, frame.K.tobytes(), frame.width, frame.height, frame.rotate, out_w, out_h)
 
 
+MINIFY = ("point", "area")                               # how a picture that shrinks is sampled
+
+
 def ingest_frames(frames, out, K_out, slots=None, stream=None):
     """frames (Frame objects) -> out[slot] uint8 [B,H,W,3] and K_out[slot] float32 [B,3,3], slot i by default; one launch on `stream` (the
     current stream if None).  Host-resident planes and the descriptor table are gathered in one pinned staging buffer and travel in one
     non-blocking copy (copying planes that already are pinned one by one was measured slower); device-resident planes
     are recorded on the stream.  Frames with a lens make it one launch of g6d_frame_ingest_mesh instead: a camera's mesh is built on its
-    first frame, travels in the same copy and stays on the device.  Does not synchronise.  Slots no frame names keep their content."""
+    first frame, travels in the same copy and stays on the device.  Does not synchronise.  Slots no frame names keep their content.
+    The scaling is the point-sampled bilinear rule; `ingest_frames_keep(..., minify="area")` filters a picture that shrinks."""
     return _ingest(frames, out, K_out, slots, stream, False)
 
 
-def ingest_frames_keep(frames, out, K_out, slots=None, stream=None):
+def ingest_frames_keep(frames, out, K_out, slots=None, stream=None, minify="point"):
     """`ingest_frames` that returns (out, staged): `staged` (a `Staged`) holds the device-resident frame table of this call and keeps the
     staging buffer and the device planes alive, so that a later launch on the same stream can read the source pictures again
-    (emit.emit_source_frames).  The launch is the same."""
-    return _ingest(frames, out, K_out, slots, stream, True)
+    (emit.emit_source_frames).  The launch is the same.
+    minify: "point" is the bilinear rule, which reads two source pixels per axis however far the picture shrinks; "area" makes it one
+    launch of g6d_frame_ingest_area, with or without lenses: every axis that shrinks is box-filtered with exact integer weights, a frame
+    that does not shrink gets the same bytes as under "point", and a frame with a lens keeps the mesh rule (the lens fallback).
+    (`ingest_frames` keeps its parameters as they are, the default tracker's recorded launch schedule lists them: a caller that wants
+    the filtered ingest and not the table takes `ingest_frames_keep(..., minify="area")[0]`; keeping the table costs nothing.)"""
+    return _ingest(frames, out, K_out, slots, stream, True, minify)
 
 
-def _ingest(frames, out, K_out, slots, stream, keep):
+def _ingest(frames, out, K_out, slots, stream, keep, minify="point"):
+    if minify not in MINIFY:
+        raise ValueError(f"ingest_frames_keep: minify must be \"point\" or \"area\", not {minify!r}")
     frames = list(frames)
     n = len(frames)
     if out.dim() != 4 or out.shape[3] != 3:
@@ -515,7 +526,9 @@ def _ingest(frames, out, K_out, slots, stream, keep):
                 if m.stream != cur:                                   # uploaded on another lane's stream: this launch waits for it on the device
                     cur.wait_event(m.event)
                     m.nodes.record_stream(cur)
-        if meshes:
+        if minify == "area":
+            ops.frame_ingest_area(buf[toff:moff], buf[moff:] if meshes else None, n, out, K_out)
+        elif meshes:
             ops.frame_ingest_mesh(buf[toff:moff], buf[moff:], n, out, K_out)
         else:
             ops.frame_ingest(buf[toff:], n, out, K_out)

@@ -164,6 +164,8 @@ SIGNATURES = {
     "g6d_sizeof_sink_desc": [],
     "g6d_frame_emit_source": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P],
     "g6d_frame_crop": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _P],
+    "g6d_frame_ingest_area": [_P, _P, _I, _P, _I, _I, _I, _P, _P],
+    "g6d_frame_crop_area": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P],
 }
 
 _lib = None

@@ -1829,22 +1829,55 @@ def frame_crop(table, rec, imgs, hinv, dh, dw, out=None):
     of lib.G6dFrame records, built and validated by gen6d_amd.ingest.ingest_frames_keep; the caller vouches that rec indexes it), or
     its canvas when rec[b] < 0 -> float32 [B,3,dh,dw] in [0,1] (uint8-rounded); `out`: optional contiguous destination.  rec and the
     table are read on the device when the kernel runs."""
-    _track_same_device("frame_crop", table, rec, imgs, hinv)
+    B, H, W, dh, dw, dst = _frame_crop_args("frame_crop", table, rec, imgs, hinv, dh, dw, out)
+    _lib.check(_lib.load().g6d_frame_crop(_ptr(table), _ptr(rec), _ptr(imgs), B, H, W, _ptr(hinv), _ptr(dst), dh, dw, _stream()),
+               "g6d_frame_crop")
+    return dst
+
+
+# ------------------------------------------------------------------------------------------------ area-filtered minification
+def frame_ingest_area(table, meshes, n, out, K_out):
+    """One launch of g6d_frame_ingest_area: frame_ingest_mesh (`meshes` None: no frame has a lens) with the exact-integer area rule on
+    every axis a plain frame shrinks on; a frame that does not shrink gets frame_ingest's bytes, a lens frame frame_ingest_mesh's."""
+    _track_same_device("frame_ingest_area", table, out, K_out, *(() if meshes is None else (meshes,)))
+    n, B, H, W = _frame_ingest_args("frame_ingest_area", table, n, out, K_out)
+    size = C.sizeof(_lib.G6dMesh)
+    if meshes is not None and (meshes.dtype != torch.uint8 or meshes.dim() != 1 or not meshes.is_contiguous() or meshes.numel() < n * size or
+                               meshes.data_ptr() % 8):
+        raise ValueError(f"frame_ingest_area: meshes must be None or a contiguous, 8-byte aligned uint8 tensor of n * {size} bytes")
+    _lib.check(_lib.load().g6d_frame_ingest_area(_ptr(table), None if meshes is None else _ptr(meshes), n, _ptr(out), B, H, W, _ptr(K_out),
+                                                 _stream()), "g6d_frame_ingest_area")
+    return out
+
+
+def _frame_crop_args(what, table, rec, imgs, hinv, dh, dw, out):
+    _track_same_device(what, table, rec, imgs, hinv)
     size = C.sizeof(_lib.G6dFrame)
     if table.dtype != torch.uint8 or table.dim() != 1 or not table.is_contiguous() or table.numel() < size or table.data_ptr() % 8:
-        raise ValueError(f"frame_crop: table must be a contiguous, 8-byte aligned uint8 tensor of at least one {size}-byte record")
+        raise ValueError(f"{what}: table must be a contiguous, 8-byte aligned uint8 tensor of at least one {size}-byte record")
     if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3 or not imgs.is_contiguous():
-        raise ValueError("frame_crop: imgs must be a contiguous uint8 [B,H,W,3] tensor")
+        raise ValueError(f"{what}: imgs must be a contiguous uint8 [B,H,W,3] tensor")
     B, H, W = imgs.shape[:3]
     if rec.dtype != torch.int32 or tuple(rec.shape) != (B,) or not rec.is_contiguous():
-        raise ValueError("frame_crop: rec must be a contiguous int32 [B] tensor")
+        raise ValueError(f"{what}: rec must be a contiguous int32 [B] tensor")
     _f32c(hinv)
     dh, dw = int(dh), int(dw)
     if hinv.numel() != 9 * B or dh < 1 or dw < 1:
-        raise ValueError("frame_crop: hinv [B,9] and a crop of at least 1 x 1 expected")
+        raise ValueError(f"{what}: hinv [B,9] and a crop of at least 1 x 1 expected")
     dst = out if out is not None else torch.empty((B, 3, dh, dw), dtype=torch.float32, device=imgs.device)
     if tuple(dst.shape) != (B, 3, dh, dw) or dst.dtype != torch.float32 or not dst.is_contiguous() or dst.device != imgs.device:
-        raise ValueError("frame_crop: out must be a contiguous float32 [B,3,dh,dw] tensor")
-    _lib.check(_lib.load().g6d_frame_crop(_ptr(table), _ptr(rec), _ptr(imgs), B, H, W, _ptr(hinv), _ptr(dst), dh, dw, _stream()),
-               "g6d_frame_crop")
+        raise ValueError(f"{what}: out must be a contiguous float32 [B,3,dh,dw] tensor")
+    return B, H, W, dh, dw, dst
+
+
+def frame_crop_area(table, rec, imgs, hinv, dh, dw, max_n=8, out=None):
+    """One launch of g6d_frame_crop_area: `frame_crop` with every crop pixel supersampled n x n, n per slot from how many source pixels
+    (canvas pixels for a slot with rec[b] < 0) a crop pixel of that slot covers, at most max_n (1..8).  A slot whose crop does not shrink
+    its source (n = 1) gets frame_crop's values bit for bit."""
+    B, H, W, dh, dw, dst = _frame_crop_args("frame_crop_area", table, rec, imgs, hinv, dh, dw, out)
+    max_n = int(max_n)
+    if not 1 <= max_n <= 8:
+        raise ValueError(f"frame_crop_area: max_n must lie in 1..8, not {max_n}")
+    _lib.check(_lib.load().g6d_frame_crop_area(_ptr(table), _ptr(rec), _ptr(imgs), B, H, W, _ptr(hinv), _ptr(dst), dh, dw, max_n, _stream()),
+               "g6d_frame_crop_area")
     return dst

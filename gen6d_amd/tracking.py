@@ -31,6 +31,11 @@ many streams (cameras or clients watching one object) at once:
     its frame table, the tick copies it into a static table beside a slot -> record map, and ONE g6d_frame_crop launch stands where
     each of those warp launches stood, inside the tick's graph.  Frames with a lens keep their canvas crops.  The
     default `crops="canvas"` launches what it always launched;
+  * with `minify="area"` (needs `frame_size`) what shrinks is filtered instead of point-sampled: the tick's and the
+    first frames' ingest is g6d_frame_ingest_area (an exact-integer box filter on every axis that shrinks; frames with a lens keep the
+    mesh rule), and with `crops="source"` the crops are g6d_frame_crop_area (n x n samples per crop pixel, n per slot from the crop's
+    own footprint, at most 8), in the same places of the same graph; with `crops="canvas"` the crops stay g6d_warp_batch.  The default
+    `minify="point"` launches what it always launched;
   * with `health=HealthPolicy(...)` every stream carries a status (TRACKING / SUSPECT / LOST) that the device keeps: a gate parks lost
     streams and non-finite table rows before the gather, a health launch judges every refined pose before the commit (a bad frame is
     not committed), the detector can check the committed poses every n-th tick, and the host, which sees the status with a fixed lag,
@@ -208,7 +213,7 @@ class _HealthMirror:
 
 class StreamTracker:
     def __init__(self, estimator, max_streams, batch=8, lanes=2, track_iter=1, smooth_num=5, smooth_std=2.5, object_pts=None,
-                 graphs=True, frame_size=None, health=None, crops="canvas"):
+                 graphs=True, frame_size=None, health=None, crops="canvas", minify="point"):
         if estimator.refiner is None:
             raise ValueError("StreamTracker: the estimator has no refiner (tracking refines every frame)")
         self.max_streams, self.batch, self.nlanes = int(max_streams), int(batch), int(lanes)
@@ -258,6 +263,12 @@ class StreamTracker:
             raise ValueError("StreamTracker: crops=\"source\" needs a tracker with frame_size (without it the canvas is the only source "
                              "there is)")
         self.source_crops = crops == "source"  # the query crops are cut from the camera-native pictures (g6d_frame_crop)
+        if minify not in I.MINIFY:
+            raise ValueError(f"StreamTracker: minify must be \"point\" or \"area\", not {minify!r}")
+        if minify == "area" and self.frame_size is None:
+            raise ValueError("StreamTracker: minify=\"area\" needs a tracker with frame_size (without it nothing is scaled: the frames "
+                             "arrive at the canvas size)")
+        self.minify = minify                   # "area": the ingest and the source crops filter where they shrink
         self._records = None                   # track_streams: [_Record]
         self._sinks = {}                       # the running push: stream id -> [Sink, ...]
         for net in self._nets():               # maps of earlier unchecked calls do not count against the tracker
@@ -506,6 +517,14 @@ class StreamTracker:
                 lane.eff, lane.commit, lane.draw = (torch.full((B,), -1, dtype=torch.int32, device=self.dev) for _ in range(3))
                 lane.pic = torch.tensor([[w, h]] * B, dtype=torch.int32, device=self.dev)
 
+    def _ingest(self, frames, out, K_out, slots=None):
+        """The ingest of a tick or of first frames whose frame table nobody reads afterwards: `ingest_frames` as always, or with
+        minify="area" the filtered launch (`ingest_frames_keep` carries the switch; its table is dropped)."""
+        if self.minify == "area":
+            I.ingest_frames_keep(frames, out, K_out, slots=slots, minify=self.minify)
+        else:
+            I.ingest_frames(frames, out, K_out, slots=slots)
+
     def _judge(self, prev, pose, K9, pic, size, slot_map, commit=None, draw=None):
         """The health step between a refinement from the gathered poses `prev` (None: an acquisition) and its commit -> (slot_commit,
         slot_draw): a frame that fails its gates is not committed, a LOST stream is not drawn.  Without a policy: the slot map itself."""
@@ -525,7 +544,8 @@ class StreamTracker:
         if lane.source is None:
             r = self.chain.query_batch(lane.img, lane.K, pose_init=pose0, refine_iter=self.track_iter)
         else:
-            r = self.chain.query_batch_source(lane.img, lane.K, lane.source, pose_init=pose0, refine_iter=self.track_iter)
+            r = self.chain.query_batch_source(lane.img, lane.K, lane.source, pose_init=pose0, refine_iter=self.track_iter,
+                                              minify=self.minify)
         commit, draw = self._judge(pose0, r["pose"], K9, lane.pic, None, eff, lane.commit, lane.draw)
         return ops.track_commit(r["pose"], K9, commit, False, self.box, self.num, self.std, self.pose_table, self.hist, self.hist_count,
                                 self.smooth_table), commit, draw
@@ -554,9 +574,10 @@ class StreamTracker:
         staged = None
         if self.frame_size is not None:        # one launch fills the named slots of the static image and K buffers
             if self.source_crops or self._wants_source(ents):      # ... and leaves its frame table on the device for the source-view
-                staged = I.ingest_frames_keep([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])[1]     # emit and crops
+                staged = I.ingest_frames_keep([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents],
+                                              minify=self.minify)[1]                                           # emit and crops
             else:
-                I.ingest_frames([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
+                self._ingest([e.frame for e in ents], lane.img, lane.K, slots=[e.slot for e in ents])
         else:
             for e in ents:
                 lane.img[e.slot].copy_(e.frame)
@@ -602,13 +623,14 @@ class StreamTracker:
             imgs = torch.empty((n,) + self._shape, dtype=torch.uint8, device=self.dev)
             Ks = torch.empty((n, 3, 3), dtype=torch.float32, device=self.dev)
             if self.source_crops or self._wants_source(ents):
-                staged = I.ingest_frames_keep([e.frame for e in ents], imgs, Ks)[1]
+                staged = I.ingest_frames_keep([e.frame for e in ents], imgs, Ks, minify=self.minify)[1]
             else:
-                I.ingest_frames([e.frame for e in ents], imgs, Ks)
+                self._ingest([e.frame for e in ents], imgs, Ks)
         else:
             imgs = torch.stack([e.frame for e in ents], 0)
             Ks = torch.stack([e.K for e in ents], 0)
-        r = self.chain.query_batch_source(imgs, Ks, I.SourceTable.of(staged)) if self.source_crops else self.chain.query_batch(imgs, Ks)
+        r = (self.chain.query_batch_source(imgs, Ks, I.SourceTable.of(staged), minify=self.minify) if self.source_crops else
+             self.chain.query_batch(imgs, Ks))
         pose, K9 = r["pose"].reshape(n, 12), Ks.reshape(n, 9)
         ids = self._upload(np.asarray([e.stream for e in ents], np.int32))
         pic = self._upload(self._pic(ents, n)) if native and self.policy is not None else None
@@ -681,13 +703,18 @@ def _stream_Ks(Ks, seqs):
     return out
 
 
-def _ingest_to_host(frames, frame_size, device):
-    """Frames of any format -> ([H,W,3] uint8 arrays, [3,3] float32 Ks) through the device ingest (track_streams' rare fallback path)."""
+def _ingest_to_host(frames, frame_size, device, minify="point"):
+    """Frames of any format -> ([H,W,3] uint8 arrays, [3,3] float32 Ks) through the device ingest (track_streams' rare fallback path),
+    by the tracker's own `minify` rule, so that a recomputed sequence sees the pictures the tracker saw."""
     imgs, Ks = [], []
     for f in frames:
         img = torch.empty((1, int(frame_size[0]), int(frame_size[1]), 3), dtype=torch.uint8, device=device)
         K = torch.empty((1, 3, 3), dtype=torch.float32, device=device)
-        I.ingest_frames([f if isinstance(f, I.Frame) else I.Frame(StreamTracker._rgb(f))], img, K)
+        frame = [f if isinstance(f, I.Frame) else I.Frame(StreamTracker._rgb(f))]
+        if minify == "area":
+            I.ingest_frames_keep(frame, img, K, minify=minify)
+        else:
+            I.ingest_frames(frame, img, K)
         imgs.append(img[0].cpu().numpy())
         Ks.append(K[0].cpu().numpy())
     return imgs, Ks
@@ -716,7 +743,8 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
     """S frame sequences (possibly of different lengths; uint8 [H,W,3] frames of one shape) -> per stream (poses [T,3,4], smoothed
     [T,3,4]) float32 for every frame.  Ks: None (predict.py's pseudo K) or per stream one [3,3] or one per frame [T,3,3].  With
     `frame_size=(H, W)` the frames are `ingest.Frame`s (or [h,w,3] arrays) of any size and format, carry their own K, and Ks stays None;
-    `crops="source"` then cuts the networks' query crops from them (StreamTracker), also when the sequences are recomputed.  Frame t of
+    `crops="source"` then cuts the networks' query crops from them (StreamTracker), also when the sequences are recomputed, and
+    `minify="area"` filters what shrinks, in the ticks and in the recomputation alike.  Frame t of
     every stream that has one is pushed in tick t; one synchronisation at the end.  Runs under the estimator's range guard: if an fp16
     pair map left the window, the sequences are recomputed by the host-driven loop (`host_track`) with those networks on fp32.
     With `health=HealthPolicy(...)` every stream's tuple is (poses, smoothed, status [T] int32): the status after each frame; a frame
@@ -740,7 +768,8 @@ def track_streams(estimator, streams, Ks=None, **tracker_kw):
     def recompute():
         box = None if kw.get("object_pts") is None else G.box_corners(kw["object_pts"])
         # the host loop takes plain arrays: native frames are ingested on the device one by one and read back
-        host = [_ingest_to_host(frames, kw["frame_size"], estimator.device) for frames in seqs] if native else zip(seqs, Kss)
+        host = ([_ingest_to_host(frames, kw["frame_size"], estimator.device, kw.get("minify", "point")) for frames in seqs] if native
+                else zip(seqs, Kss))
         return [host_track(estimator, fr, Kh, kw.get("track_iter", 1), kw.get("smooth_num", 5), kw.get("smooth_std", 2.5), box)
                 for fr, Kh in host]
     if kw.get("crops", "canvas") == "source":

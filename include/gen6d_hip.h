@@ -745,6 +745,26 @@ int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* meshes, int n, 
                           g6d_stream_t stream);
 int g6d_sizeof_mesh_desc(void);
 
+/* Area-filtered ingest (gen6d_amd/ingest.py minify="area"); additive within ABI 12, no struct changes.
+ * g6d_frame_ingest_area is g6d_frame_ingest_mesh (the table, the slot rules, K_out, the black canvas outside the picture) with `meshes`
+ * optional (NULL: no frame has a lens) and a filter where a picture shrinks.  The lens fallback: a frame whose mesh has nodes takes the mesh
+ * rule above unchanged, bit for bit (a footprint that varies over a mesh is out of scope); lens and plain frames still mix in one launch.
+ * Every other frame takes this rule per axis of the scaled picture before rotation (target extent T = wt or ht, source extent S = ws or
+ * hs; the quarter turn maps canvas (X, Y) to the unrotated (tx, ty) as above), exact integers, restated bit-identically in
+ * tests/test_minify_cpu.py:
+ *   S <= T (the axis does not shrink): the plain rule's two taps (i0, 2048 - a) and (i1, a), D_axis = 2048;
+ *   S >  T: target coordinate t covers [t S, (t+1) S) in units of 1/T source pixel, source pixel i covers [i T, (i+1) T): the taps are
+ *     i = floor(t S / T) .. floor(((t+1) S - 1) / T) (the last is at most S - 1), w_i = min((i+1) T, (t+1) S) - max(i T, t S) in 1..T;
+ *     the weights sum to S: D_axis = S;
+ *   each tap is converted to 8-bit RGB by its format's tap rule above (all eleven formats, the four matrices, P010 in 64-bit);
+ *   per channel Sigma = sum_y sum_x wy wx p, D = Dx Dy, v = floor((2 Sigma + D) / (2 D)): the weighted mean, rounded half up.
+ * Two consequences.  1: with no shrinking axis D = 2^22 and v = (Sigma + 2^21) >> 22: a frame that does not shrink gives
+ * g6d_frame_ingest's bytes exactly.  2: with S = k T on both axes every canvas pixel is the round-half-up mean of its k x k block of
+ * converted source pixels; the box's centre is the bilinear rule's centre ((t + 0.5) S / T - 0.5), so the picture's K does not change.
+ * Magnitudes: Sigma <= 255 * 2^26; a row's inner sum sum_x wx p <= 255 * 2^13 fits 32 bits; the sum over rows and 2 Sigma + D need 64. */
+int g6d_frame_ingest_area(const G6dFrame* frames, const G6dMesh* meshes /* may be NULL */, int n, uint8_t* out, int B, int H, int W,
+                          float* K_out, g6d_stream_t stream);
+
 /* Annotated frame output (gen6d_amd/emit.py; reference predict.py:60-72 + utils/draw_utils.py draw_bbox_3d); additive within ABI 12.
  * g6d_track_corners, one 64-thread block per slot: the box (box[8][3], corner order of pts_range_to_bbox_pts) projected in float64 (the
  * projection of g6d_track_commit) under row slot_stream[b] of `table` (pose_table or smooth_table, [streams][12]) and K[b][9]; every
@@ -858,9 +878,24 @@ int g6d_frame_emit_source(const G6dSink* sinks, int n, const G6dFrame* frames, i
  *   5. each tap becomes RGB by the ingest's tap rules: packed formats by channel order (alpha ignored), NV12 through the integer
  *      conversion above with chroma UV[y>>1][x>>1] and the frame's matrix;
  *   6. per channel v = sum of weight * tap, dst = clamp(rint(v), 0, 255) / 255.
- * The sampler is the point-sampled bilinear of every warp here: a crop pixel that covers several source pixels aliases. */
+ * The sampler is the point-sampled bilinear of every warp here: a crop pixel that covers several source pixels aliases
+ * (g6d_frame_crop_area below filters such a crop). */
 int g6d_frame_crop(const G6dFrame* frames, const int32_t* rec, const uint8_t* imgs, int B, int H, int W, const float* hinv, float* dst,
                    int dh, int dw, g6d_stream_t stream);
+
+/* g6d_frame_crop_area, g6d_frame_crop supersampled where the crop shrinks its source (chain.py query_batch_source minify="area",
+ * DESIGN.md §4.26); additive within ABI 12.  g6d_frame_crop's arguments plus max_n in 1..8; everything is read from device memory when
+ * the kernel runs, so the launch sits in a captured graph where g6d_frame_crop sits.
+ * Per slot b, with the slot's view as above (the source record, or the identity on the canvas when rec[b] < 0: such slots are filtered
+ * over their canvas), float32: P(.) = steps 1 - 3 of the rule above, the source position before the clamp; c = ((dw-1)/2, (dh-1)/2);
+ *   m = max(|P(c + (1,0)) - P(c)|, |P(c + (0,1)) - P(c)|), Euclidean lengths in source pixels: how far a crop pixel reaches;
+ *   n = min(floor(m + 0.5), max_n) if m is finite and m >= 1.5, else n = 1 (a NaN or infinite m of a degenerate map: one sample).
+ * Per crop pixel (x, y), for i, j in 0 .. n-1: the sample at (x + (2i + 1 - n) / (2n), y + (2j + 1 - n) / (2n)) (offsets 0 when n = 1)
+ * goes through steps 1 - 5 unchanged and gives the unrounded weighted sum v_ij per channel; dst = clamp(rint(sum v_ij / n^2), 0, 255) / 255.
+ * With n = 1 the result is g6d_frame_crop's, bit for bit.  The order of the n^2 sum is not part of the contract.  max_n = 8 bounds the
+ * work at 256 taps per crop pixel; beyond 8x the crop still aliases, at an eighth of the rate. */
+int g6d_frame_crop_area(const G6dFrame* frames, const int32_t* rec, const uint8_t* imgs, int B, int H, int W, const float* hinv, float* dst,
+                        int dh, int dw, int max_n, g6d_stream_t stream);
 
 #ifdef __cplusplus
 }
