@@ -166,6 +166,10 @@ SIGNATURES = {
     "g6d_frame_crop": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _P],
     "g6d_frame_ingest_area": [_P, _P, _I, _P, _I, _I, _I, _P, _P],
     "g6d_frame_crop_area": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P],
+    "g6d_corr_fft_plan": [_P, _I, _I, _I, _I, _I, _P],
+    "g6d_corr_fft_fwd": [_P, _I, _I, _I, _I, _P, _P],
+    "g6d_corr_fft_gemm": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "g6d_corr_fft_inv": [_P, _I, _I, _I, _I, _P, _P],
 }
 
 _lib = None

@@ -8,7 +8,9 @@ For the 4 detection scales of a batch of queries at once (reference detect_impl,
                                     (F.conv2d(que_x, ref_x, padding=7/3/1), detector.py:222-224), on the kernel Detector.corr_routes names:
                                     at 32 references the 15x15 and 7x7 levels on g6d_corr16_multi (the trunk hands them over in its
                                     pair format), otherwise as blocks of 3x3 in the F(4x4,3x3) domain (g6d_corr2d_wino43_multi; the 7x7
-                                    filters zero-extended to 9x9); the 3x3 level on g6d_corr2d_patch_multi
+                                    filters zero-extended to 9x9); the 3x3 level on g6d_corr2d_patch_multi; calls of at least
+                                    CORR_FFT_MIN_QUERIES queries run the 15x15 level in the frequency domain on the fp32 tap
+                                    (route "fft": ops.corr_fft_multi, csrc/corr_fft.hip)
     g6d_detector_assemble           nearest up-sampling, (x-mu)/sigma, clip, bilinear resize to (h/8,w/8), stack
 then g6d_detector_score_mlp_max     score_conv MLP + max over references, never materialising [64,rfn,hs,ws]
      g6d_conv_igemm x7              the three 3x3 heads (first layers merged into one 64->192 conv)
@@ -27,6 +29,10 @@ _TAPS = ("c5", "c7_pre", "p7")   # the trunk taps of the three correlation level
 MAX_BATCH = 16       # most queries that share one set of launches; _detect_impl_fp cuts the chunk further for larger images (the pyramid's
                      # first layers address all scales of the batch with 32-bit offsets from one base, < 2^29 floats: 16 images of
                      # 480x640 at 64 channels; 32 would not fit)
+CORR_FFT_MIN_QUERIES = 4     # queries per call from which the 15x15 level runs in the frequency domain (ops.corr_fft_multi).  Its three
+                             # launches beat the one corr16 launch by more than that launch's own spread at every batch measured, 1 included
+                             # (profiles/r29_corr_fft.md); the floor of 4 keeps the tracker's two-query acquisition chunks and single
+                             # queries on the launches they have
 
 
 class Detector(ParamBank):
@@ -47,6 +53,7 @@ class Detector(ParamBank):
         self.ref_wino15_43 = None        # the 15x15 level's filters for the F(4x4,3x3) kernel (winograd43_corr_filters), rfn % 32 == 0
         self.ref_wino7_43 = None         # the 7x7 level's filters, zero-extended to 9x9, for the F(4x4,3x3) kernel
         self._corr16 = {}                # (level, mode) -> the level's filters for g6d_corr16_multi, built on first use
+        self._corr_fft = None            # the 15x15 level's filter spectra for ops.corr_fft_multi, built on first use
         self.ref_shape = None
         self.rank, self.world, self.group = 0, 1, None
         self.sharded = False
@@ -99,6 +106,7 @@ class Detector(ParamBank):
         self.ref_center_feats = [f.reshape(f.shape[0], f.shape[2] * f.shape[3], 512).contiguous() for f in feats]
         self.ref_ksize = [f.shape[2] for f in feats]               # 15, 7, 3
         self._corr16 = {}
+        self._corr_fft = None
         self.ref_shape = [120, 120]
         # F(4x4,3x3)-domain filters of the 15x15 and 7x7 levels for the "wino43" route (the reference views used as filters: transformed
         # once per object; whether a call takes the route depends on its math mode and pair setting, so they exist whenever it can)
@@ -112,9 +120,18 @@ class Detector(ParamBank):
             self._corr16[level, mode] = ops.corr16_pack(self.ref_center_feats[level], mode)
         return self._corr16[level, mode]
 
-    def corr_routes(self, hq, wq):
+    def _corr_fft_filters(self):
+        """The 15x15 level's filter spectra (ops.corr_fft_spectra), built on first use: reference state, the same for every query."""
+        if self._corr_fft is None:
+            self._corr_fft = ops.corr_fft_spectra(self.ref_center_feats[0])
+        return self._corr_fft
+
+    def corr_routes(self, hq, wq, qn=1):
         """The kernel that correlates each level (15x15, 7x7, 3x3 filters) with the references for [qn,3,hq,wq] queries in the current math
         mode and pair setting:
+          "fft"     ops.corr_fft_multi, the 15x15 level in the frequency domain (32 x 32 windows, fp32): where "corr16" would be taken on
+                    the fp32 path (pairs on, 32 references, not sharded) for calls of at least CORR_FFT_MIN_QUERIES queries; the trunk hands
+                    the level over as its fp32 tap.  cfg key 'corr_fft': None = that rule, False = never, True = at any batch (tools, tests)
           "corr16"  g6d_corr16_multi: the pyramid trunk runs on the direct kernel and hands the level over in its 16-bit / pair format
                     (32 references)
           "wino43"  blocks of 3x3 in the F(4x4,3x3) domain (fp32, rfn % 32 == 0: 20.25 instead of 49 multiplications per output at 7x7)
@@ -126,7 +143,9 @@ class Detector(ParamBank):
         routes = []
         for k in self.ref_ksize:
             if k in (15, 7) and trunk16 and rfn == 32:
-                routes.append("corr16")
+                want = self.cfg.get("corr_fft")
+                fft = k == 15 and not ops.MATH_MODE and not self.sharded and want is not False and (want or qn >= CORR_FFT_MIN_QUERIES)
+                routes.append("fft" if fft else "corr16")
             elif k in (15, 7) and rfn % 32 == 0 and not ops.MATH_MODE:
                 routes.append("wino43")
             else:
@@ -156,6 +175,13 @@ class Detector(ParamBank):
                 filt = self._corr16_filters(l, mode)
                 outs = [torch.empty((qn, 1, x.shape[1], x.shape[2], rfn), dtype=torch.float32, device=dev) for x in xs]
                 ops.corr16_multi(xs, filt, outs)
+                for i, o in enumerate(outs):
+                    maps[i][l] = o.reshape(qn * o.shape[2] * o.shape[3], rfn)
+                continue
+            if route == "fft":
+                # the fp32 tap through forward FFT, per-bin products on the fp32 matrix cores and inverse FFT (csrc/corr_fft.hip)
+                outs = [torch.empty((qn, 1, x.shape[2], x.shape[3], rfn), dtype=torch.float32, device=dev) for x in xs]
+                ops.corr_fft_multi([x.contiguous() for x in xs], self._corr_fft_filters(), outs)
                 for i, o in enumerate(outs):
                     maps[i][l] = o.reshape(qn * o.shape[2] * o.shape[3], rfn)
                 continue
@@ -232,7 +258,7 @@ class Detector(ParamBank):
             # over); the correlations of the scales then run side by side
             # the image pyramid in ONE launch (g6d_resize_bilinear_pyramid; the scale of the query's own size is the query itself)
             pyr = ops.resize_bilinear_pyramid(que_imgs, [self._scale_size(hq, wq, sc) for _, sc in order])
-            routes = self.corr_routes(hq, wq)
+            routes = self.corr_routes(hq, wq, qn)
             t16 = tuple(tap for tap, r in zip(_TAPS, routes) if r == "corr16")     # taps handed over in the trunk's 16-bit / pair format
             feats = trunk_features_multi(pk["vgg"], pyr, _TAPS, f43=True, taps16=t16, rng=self._pair_rng(), pairs=self.pairs_on)
             self._scores_from_pyramid(feats, routes, [si for si, _ in order], stacked, hs, ws)

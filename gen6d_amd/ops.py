@@ -1170,6 +1170,148 @@ def corr16_multi(xs, filt, outs):
     return outs
 
 
+CORR_FFT_T = 32            # window side of the frequency-domain correlation (the kernels of csrc/corr_fft.hip are built for 32)
+CORR_FFT_CHUNK = 4         # queries per set of launches at most (the plan cuts it further where the spectrum would pass 2^31 bytes); measured at
+                           # batch 16 on the headline's pyramid: chunks of 2 / 4 / 8 / 13 take 4.2 / 2.60 / 2.71 / 2.74 ms (profiles/r29_corr_fft.md)
+
+
+def _corr_fft_segs(xs, outs, Cin, what):
+    """G6dCorrSeg table of fp32 channels-last maps [N,(1,)H,W,Cin] and / or dense outputs [N,(1,)H,W,32] (either list may be None)."""
+    n = len(xs if xs is not None else outs)
+    if not 1 <= n <= 4:
+        raise ValueError(f"{what}: 1..4 segments expected")
+    segs = (_lib.G6dCorrSeg * n)()
+    for i in range(n):
+        x = xs[i] if xs is not None else None
+        o = outs[i] if outs is not None else None
+        for t, ch in ((x, Cin), (o, 32)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.dim() not in (4, 5) or t.shape[-1] != ch
+                                  or (t.dim() == 5 and t.shape[1] != 1)):
+                raise ValueError(f"{what}: dense fp32 channels-last maps [N,(1,)H,W,{ch}] expected")
+        ref = x if x is not None else o
+        N, H, W = ref.shape[0], ref.shape[-3], ref.shape[-2]
+        if x is not None and o is not None and (o.shape[0], o.shape[-3], o.shape[-2]) != (N, H, W):
+            raise ValueError(f"{what}: output shape mismatch")
+        segs[i] = _lib.G6dCorrSeg(in_=x.data_ptr() if x is not None else None, out=o.data_ptr() if o is not None else None, H=H, W=W,
+                                  ld_in=Cin, ld_out=32, N=N, reserved_=0)
+    return segs
+
+
+def corr_fft_plan(sizes, Cin, Cout=32, k=15, T=CORR_FFT_T):
+    """The plan of the frequency-domain correlation (csrc/corr_fft_plan.h) for segments sizes = [(N, H, W)]: tiles, bins, V, the bytes of
+    the spectrum, of the product and of the filter spectra, the tiles of one query and the most queries one set of launches takes.  Host only."""
+    segs = (_lib.G6dCorrSeg * len(sizes))()
+    for i, (N, H, W) in enumerate(sizes):
+        segs[i] = _lib.G6dCorrSeg(in_=None, out=None, H=H, W=W, ld_in=Cin, ld_out=Cout, N=N, reserved_=0)
+    out = (C.c_int64 * 8)()
+    _lib.check(_lib.load().g6d_corr_fft_plan(segs, len(sizes), Cin, Cout, k, T, out), "g6d_corr_fft_plan")
+    keys = ("tiles", "bins", "V", "spectrum_bytes", "product_bytes", "filter_bytes", "tiles_per_query", "max_queries")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+class CorrFftSpectra:
+    """B' of g6d_corr_fft_gemm ([bins][2 Cin][64] fp32) with the sizes it was built for."""
+
+    def __init__(self, data, Cin, k, T):
+        self.data, self.Cin, self.k, self.T = data, Cin, k, T
+
+
+def corr_fft_spectra(w_taps, T=CORR_FFT_T):
+    """[32, k*k, Cin] fp32 correlation filters (tap = ky*k + kx) -> their conjugate spectra as the real matrices B' of g6d_corr_fft_gemm:
+    float64 rfft2 of the filters zero-extended to T x T, rounded to fp32 once.  Row c = [Wr | -Wi], row Cin + c = [Wi | Wr] over the 32
+    references.  Reference state: built once per object (on the host: 16 K transforms of 32 x 32, then one upload of 142 MB at Cin = 512)."""
+    R, taps, Cin = w_taps.shape
+    k = int(round(taps ** 0.5))
+    if R != 32 or k * k != taps or k >= T:
+        raise ValueError("corr_fft_spectra: [32, k*k, Cin] filters with k < T expected")
+    w = w_taps.detach().to("cpu", torch.float64).reshape(R, k, k, Cin).permute(0, 3, 1, 2)               # r, c, ky, kx
+    Wf = torch.fft.rfft2(torch.nn.functional.pad(w, (0, T - k, 0, T - k)))                                # r, c, T, T/2+1
+    Wr = Wf.real.permute(2, 3, 1, 0).reshape(-1, Cin, R)                                                  # bin, c, r
+    Wi = Wf.imag.permute(2, 3, 1, 0).reshape(-1, Cin, R)
+    B = torch.cat([torch.cat([Wr, -Wi], 2), torch.cat([Wi, Wr], 2)], 1).to(torch.float32).contiguous()    # bin, 2 Cin, 2 R
+    return CorrFftSpectra(B.to(w_taps.device), Cin, k, T)
+
+
+def corr_fft_fwd(xs, X, k=15, T=CORR_FFT_T):
+    """Windows of the maps xs -> their spectra X [bins][tiles][2][Cin] (g6d_corr_fft_fwd)."""
+    Cin = xs[0].shape[-1]
+    _need_gpu(X, *xs)
+    segs = _corr_fft_segs(xs, None, Cin, "corr_fft_fwd")
+    plan = corr_fft_plan([(s.N, s.H, s.W) for s in segs], Cin, 32, k, T)
+    if X.dtype != torch.float32 or not X.is_contiguous() or X.numel() * 4 < plan["spectrum_bytes"]:
+        raise ValueError("corr_fft_fwd: the spectrum buffer is smaller than [bins][tiles][2][Cin] fp32")
+    _lib.check(_lib.load().g6d_corr_fft_fwd(segs, len(xs), Cin, k, T, _ptr(X), _stream()), "g6d_corr_fft_fwd")
+    return X
+
+
+def corr_fft_gemm(X, B, Y, tiles, Cin, T=CORR_FFT_T):
+    """Y [bins][tiles][64] = X [bins][tiles][2 Cin] . B' [bins][2 Cin][64] per bin (g6d_corr_fft_gemm)."""
+    _need_gpu(X, B, Y)
+    bins = T * (T // 2 + 1)
+    if X.numel() < bins * tiles * 2 * Cin or B.numel() != bins * 2 * Cin * 64 or Y.numel() < bins * tiles * 64 \
+            or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (X, B, Y)):
+        raise ValueError("corr_fft_gemm: fp32 X [bins][tiles][2 Cin], B' [bins][2 Cin][64], Y [bins][tiles][64] expected")
+    _lib.check(_lib.load().g6d_corr_fft_gemm(_ptr(X), _ptr(B), _ptr(Y), int(tiles), int(Cin), 32, T, _stream()), "g6d_corr_fft_gemm")
+    return Y
+
+
+def corr_fft_inv(Y, outs, k=15, T=CORR_FFT_T):
+    """Products Y [bins][tiles][2][32] -> the maps outs [N,(1,)H,W,32] (g6d_corr_fft_inv)."""
+    _need_gpu(Y, *outs)
+    segs = _corr_fft_segs(None, outs, 32, "corr_fft_inv")
+    plan = corr_fft_plan([(s.N, s.H, s.W) for s in segs], 32, 32, k, T)
+    if Y.dtype != torch.float32 or not Y.is_contiguous() or Y.numel() * 4 < plan["product_bytes"]:
+        raise ValueError("corr_fft_inv: the product buffer is smaller than [bins][tiles][2][32] fp32")
+    _lib.check(_lib.load().g6d_corr_fft_inv(segs, len(outs), 32, k, T, _ptr(Y), _stream()), "g6d_corr_fft_inv")
+    return outs
+
+
+def corr_fft_multi(xs, spectra, outs, chunk=None):
+    """The detector's 15 x 15 correlation in the frequency domain: xs 1..4 dense fp32 channels-last maps [N,(1,)H,W,Cin] with one N (the
+    queries of a batch at the scales of the pyramid), spectra = corr_fft_spectra(...), outs fp32 [N,(1,)H,W,32] dense.  The queries go
+    through in chunks of at most `chunk` (default CORR_FFT_CHUNK; never more than the plan allows): three launches per chunk over the
+    segments of all scales, on spectrum and product buffers from torch's allocator (stream-ordered, and part of the graph's pool under
+    capture).  PROFILE: one record per launch, booked with the FLOPs executed."""
+    Cin, k, T = spectra.Cin, spectra.k, spectra.T
+    N = xs[0].shape[0]
+    if any(x.shape[0] != N or x.shape[-1] != Cin for x in xs) or len(xs) != len(outs):
+        raise ValueError("corr_fft_multi: every segment holds the same queries and Cin channels")
+    _need_gpu(spectra.data, *xs, *outs)
+    _corr_fft_segs(xs, outs, Cin, "corr_fft_multi")             # layout checks of the whole call
+    one = corr_fft_plan([(1, x.shape[-3], x.shape[-2]) for x in xs], Cin, 32, k, T)
+    qc = min(N, one["max_queries"], int(chunk or CORR_FFT_CHUNK))
+    if qc < 1:
+        raise ValueError("corr_fft_multi: one query's spectrum passes 2^31 bytes")
+    dev = xs[0].device
+    tiles_max = one["tiles_per_query"] * qc
+    bins = one["bins"]
+    X = torch.empty(bins * tiles_max * 2 * Cin, dtype=torch.float32, device=dev)
+    Y = torch.empty(bins * tiles_max * 64, dtype=torch.float32, device=dev)
+    on = PROFILE is not None
+    log2t = math.log2(T)
+    for q0 in range(0, N, qc):
+        q1 = min(N, q0 + qc)
+        tiles = one["tiles_per_query"] * (q1 - q0)
+        xc, oc = [x[q0:q1] for x in xs], [o[q0:q1] for o in outs]
+        sizes = "+".join(f"{q1 - q0}x{x.shape[-3]}x{x.shape[-2]}" for x in xs)
+        # FLOPs executed: 5 T log2 T per complex T-point FFT; T/2 + (T/2 + 1) of them per window and channel (two real rows per FFT, the real
+        # columns 0 and T/2 as one); the products as the real GEMM; the inverse side keeps V of the T rows
+        f_fft = 5.0 * T * log2t
+        fl_fwd = tiles * Cin * (T / 2 + T / 2) * f_fft
+        fl_gemm = 2.0 * bins * tiles * (2 * Cin) * 64
+        fl_inv = tiles * 32 * (T / 2 + (T - k + 1) / 2) * f_fft
+        act = sum(x.numel() for x in xc) * 4.0
+        _timed(on, lambda: corr_fft_fwd(xc, X, k, T),
+               lambda e0, e1: PROFILE.append((fl_fwd, e0, e1, f"corr_fft fwd in={sizes}x{Cin} T={T}", act + 4.0 * bins * tiles * 2 * Cin, fl_fwd)))
+        _timed(on, lambda: corr_fft_gemm(X, spectra.data, Y, tiles, Cin, T),
+               lambda e0, e1: PROFILE.append((fl_gemm, e0, e1, f"corr_fft gemm bins={bins} M={tiles} K={2 * Cin} N=64",
+                                              4.0 * (bins * tiles * (2 * Cin + 64) + spectra.data.numel()), fl_gemm)))
+        _timed(on, lambda: corr_fft_inv(Y, oc, k, T),
+               lambda e0, e1: PROFILE.append((fl_inv, e0, e1, f"corr_fft inv out={sizes}x32 T={T}",
+                                              4.0 * bins * tiles * 64 + sum(o.numel() for o in oc) * 4.0, fl_inv)))
+    return outs
+
+
 def l2norm_rows(x):
     """In-place F.normalize over the last axis of a channels-last tensor whose rows are dense (ld = C), or of a 2-D row-strided
     view [rows, C] (ld = x.stride(0))."""

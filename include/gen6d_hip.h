@@ -897,6 +897,23 @@ int g6d_frame_crop(const G6dFrame* frames, const int32_t* rec, const uint8_t* im
 int g6d_frame_crop_area(const G6dFrame* frames, const int32_t* rec, const uint8_t* imgs, int B, int H, int W, const float* hinv, float* dst,
                         int dh, int dw, int max_n, g6d_stream_t stream);
 
+/* The detector's 15x15 correlation in the frequency domain (csrc/corr_fft.hip; network/detector.py:222-224 for batched
+ * calls on the fp32 path); additive within ABI 12.  Overlap-save over T x T windows, T = 32, k = 15, V = T - k + 1 = 18: tile (ty, tx) of
+ * a map owns output pixels (ty V .., tx V ..), its window starts k/2 pixels before them and is zero outside the map; a window has
+ * bins = T (T/2 + 1) Hermitian bins, bin = ky (T/2 + 1) + kx.  The tiles of all segments form one flat list in segment, image, row, column
+ * order (csrc/corr_fft_plan.h).  fp32 everywhere: three launches, each an entry point of its own, so that each is testable:
+ *   g6d_corr_fft_fwd   segs[i].in [N][H][W][ld_in] (>= Cin channels, Cin % 32 == 0)  ->  X [bins][tiles][2][Cin], re plane then im plane
+ *   g6d_corr_fft_gemm  Y [bins][tiles][2][32] = X' . B' per bin, B' [bins][2 Cin][64] = the conjugate filter spectrum as a real matrix:
+ *                      row c (of Xr) = [Wr[.][c] | -Wi[.][c]], row Cin + c (of Xi) = [Wi[.][c] | Wr[.][c]] over the 32 references, with
+ *                      W = rfft2 of the k x k filter zero-extended to T x T (tap (0, 0) at the origin)
+ *   g6d_corr_fft_inv   Y  ->  inverse real FFT / T^2, positions [0, V)^2 of every tile to segs[i].out [N][H*W][ld_out] inside the map.
+ * One launch addresses less than 2^31 bytes of X (G6D_ENOSPC beyond): g6d_corr_fft_plan answers, for the segments given, out[0..7] =
+ * tiles, bins, V, bytes of X, bytes of Y, bytes of B', the tiles of one query (one map per segment) and the most queries a launch takes. */
+int g6d_corr_fft_plan(const G6dCorrSeg* segs, int nseg, int Cin, int Cout, int k, int T, int64_t* out);
+int g6d_corr_fft_fwd(const G6dCorrSeg* segs, int nseg, int Cin, int k, int T, float* X, g6d_stream_t stream);
+int g6d_corr_fft_gemm(const float* X, const float* B, float* Y, int tiles, int Cin, int Cout, int T, g6d_stream_t stream);
+int g6d_corr_fft_inv(const G6dCorrSeg* segs, int nseg, int Cout, int k, int T, const float* Y, g6d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
