@@ -126,24 +126,57 @@ __global__ __launch_bounds__(NT) void corrfft_fwd_kernel(const CfftParams p) {
   }
 }
 
-// ---- products: block = (bin, 128 rows), wave = 64 rows x 64 columns = 4 accumulators.  Lane (r = lane & 31, h = lane >> 5) takes, per
-// step of 32 k, its rows' 16 consecutive values k0 + 16 h .. + 15 straight from memory (64 contiguous bytes) and the same k of B': the
-// order of k inside the sum is free as long as both operands agree.  Blocks of one bin run back to back on ONE XCD (bins % 8 == 0), so
-// B'[bin] (256 KB at Cin = 512) is fetched into one L2 once.
-constexpr int GEMM_NT = 128, GEMM_BM = 128;
-struct CfftGemm { const float* X; const float* B; float* Y; int M, bins, K2, mblocks; };
+// ---- products: block = (bin, WAVES x 64 rows), wave = 64 rows x 64 columns = 4 accumulators, over a ring of STAGES LDS stages of 32 k
+// each (corr_fft_plan.h holds the integers).  Per stage a wave requests its own 64 rows of X as 8 LDS-DMA pieces of 8 rows x 128 bytes
+// (every 128-byte line is asked for once, whole) and its share of the stage's 8 KB of B', which the block's waves share: B' goes
+// through the vector memory path once per block, not once per wave.  Lane (r = lane & 31, h = lane >> 5) then takes k = 16 h .. 16 h + 15
+// of the stage for both operands: four 16-byte reads per row tile from the slot-swizzled X image, 32 single values of B' (32
+// consecutive banks per half wave): the order of k inside the sum is free as long as both operands agree.
+// One barrier per step: it publishes every wave's pieces of step t (each wave first retires its own with a counted vmcnt that leaves
+// the later steps' requests in flight) and frees the stage that step t - 1 read, into which step t + STAGES - 1 is requested next.
+// A bin's rows are spread evenly over its blocks in whole waves; a wave left without rows asks for its share of B' only.
+// Rows beyond M are clamped to M - 1 in the request and never stored; the buffer descriptors end at the bin's last byte of X and B'.
+// Blocks of one bin run back to back on ONE XCD (bins % 8 == 0), so B'[bin] (256 KB at Cin = 512) is fetched into one L2 once.
+struct CfftGemm { const float* X; const float* B; float* Y; int M, bins, K2, mblocks, rows; };
+typedef __attribute__((address_space(3))) void* cfft_lds_ptr;
 
-__global__ __launch_bounds__(GEMM_NT) void corrfft_gemm_kernel(const CfftGemm p) {
-  const int b = blockIdx.x, xcd = b & 7, s = b >> 3;
-  const int bin = xcd + 8 * (s / p.mblocks), mb = s % p.mblocks;
-  if (bin >= p.bins) return;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-  const int m0 = mb * GEMM_BM + wv * 64;
-  if (m0 >= p.M) return;
-  const int K2 = p.K2;
-  const float* A0 = p.X + ((size_t)bin * p.M + min(m0 + r, p.M - 1)) * K2 + 16 * h;
-  const float* A1 = p.X + ((size_t)bin * p.M + min(m0 + 32 + r, p.M - 1)) * K2 + 16 * h;
-  const float* Bp = p.B + ((size_t)bin * K2 + 16 * h) * 64 + r;
+template <bool V> struct CfftBool { static constexpr bool value = V; };
+template <int N> __device__ __forceinline__ void cfft_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+template <int WAVES, int STAGES>
+__global__ __launch_bounds__(WAVES * 64) void corrfft_gemm_kernel(const CfftGemm p) {
+  extern __shared__ __attribute__((aligned(16))) char gl[];
+  constexpr int ASTG = cfft::gemm_a_stage_bytes(WAVES), STG = cfft::gemm_stage_bytes(WAVES);
+  constexpr int PB = cfft::gemm_b_pieces_per_wave(WAVES);
+  constexpr int WIMG = cfft::GEMM_WAVE_ROWS * cfft::GEMM_ROW_BYTES;      // a wave's X image of one stage
+  static_assert(STAGES == cfft::gemm_stages(WAVES) && (STAGES == 2 || STAGES == 3), "the waits below are written for rings of two and three");
+  int bin, mb;
+  cfft::gemm_block_of(blockIdx.x, p.mblocks, bin, mb);
+  if (bin >= p.bins) return;                                   // (the whole block)
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, h = lane >> 5;
+  const int m0 = cfft::gemm_wave_row0(mb, wv, p.rows), K2 = p.K2, nsteps = K2 / cfft::GEMM_KSTEP;
+  const bool active = !cfft::gemm_wave_idle(mb, wv, p.rows, p.M);      // a wave without rows still stages its share of B' and meets the barriers
+  const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X) + (size_t)bin * p.M * K2, 0, p.M * K2 * 4, 0x00020000);
+  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B) + (size_t)bin * K2 * cfft::GEMM_COLS, 0, K2 * cfft::GEMM_COLS * 4, 0x00020000);
+  unsigned aoff[cfft::GEMM_A_PIECES];
+#pragma unroll
+  for (int c = 0; c < cfft::GEMM_A_PIECES; ++c)
+    aoff[c] = (unsigned)min(m0 + cfft::gemm_a_src_row(c, lane), p.M - 1) * (unsigned)(K2 * 4) + 16u * cfft::gemm_a_src_seg(c, lane);
+  const unsigned boff = (unsigned)(wv * PB) * cfft::GEMM_PIECE + 16u * lane;
+
+  auto issue = [&](int t, int st, bool with_a) {
+    char* sa = gl + st * STG;
+    const unsigned ka = (unsigned)t * cfft::GEMM_ROW_BYTES, kb = (unsigned)t * cfft::GEMM_B_STAGE;
+    if (with_a)
+#pragma unroll
+      for (int c = 0; c < cfft::GEMM_A_PIECES; ++c)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (cfft_lds_ptr)(sa + wv * WIMG + c * cfft::GEMM_PIECE), 16, aoff[c] + ka, 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < PB; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (cfft_lds_ptr)(sa + ASTG + (wv * PB + q) * cfft::GEMM_PIECE), 16,
+                                               boff + q * cfft::GEMM_PIECE + kb, 0, 0, 0);
+  };
+
   f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -151,18 +184,24 @@ __global__ __launch_bounds__(GEMM_NT) void corrfft_gemm_kernel(const CfftGemm p)
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][n][q] = 0.f;
-  f32x4 a0[2][4], a1[2][4];
-  float b0[2][16], b1[2][16];
-  auto load = [&](int k0, f32x4 (&x0)[4], f32x4 (&x1)[4], float (&y0)[16], float (&y1)[16]) {
+  // the step's fragments: all 24 LDS reads are requested first, in the order the MFMAs use them, and the next stage's pieces behind them
+  f32x4 x0[4], x1[4];
+  float y0[16], y1[16];
+  auto fetch = [&](int st) {
+    const char* sa = gl + st * STG + wv * WIMG;
+    const char* sb = gl + st * STG + ASTG + cfft::gemm_b_lds_offset(16 * h, r);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      x0[j] = *reinterpret_cast<const f32x4*>(A0 + k0 + 4 * j);
-      x1[j] = *reinterpret_cast<const f32x4*>(A1 + k0 + 4 * j);
-    }
+      x0[j] = *reinterpret_cast<const f32x4*>(sa + cfft::gemm_a_lds_offset(r, 4 * h + j));
+      x1[j] = *reinterpret_cast<const f32x4*>(sa + cfft::gemm_a_lds_offset(32 + r, 4 * h + j));
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { y0[e] = Bp[(size_t)(k0 + e) * 64]; y1[e] = Bp[(size_t)(k0 + e) * 64 + 32]; }
+      for (int e = 4 * j; e < 4 * j + 4; ++e) {
+        y0[e] = *reinterpret_cast<const float*>(sb + cfft::gemm_b_lds_offset(e, 0));
+        y1[e] = *reinterpret_cast<const float*>(sb + cfft::gemm_b_lds_offset(e, 32));
+      }
+    }
   };
-  auto mac = [&](const f32x4 (&x0)[4], const f32x4 (&x1)[4], const float (&y0)[16], const float (&y1)[16]) {
+  auto mac = [&]() {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const float u0 = x0[e >> 2][e & 3], u1 = x1[e >> 2][e & 3];
@@ -172,14 +211,30 @@ __global__ __launch_bounds__(GEMM_NT) void corrfft_gemm_kernel(const CfftGemm p)
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(u1, y1[e], acc[1][1], 0, 0, 0);
     }
   };
-  load(0, a0[0], a1[0], b0[0], b1[0]);
+
+#pragma unroll
+  for (int t = 0; t < STAGES - 1; ++t) issue(t, t, active);    // nsteps >= 2 >= STAGES - 1 (K2 >= 64)
+  // the K loop, once for a wave with rows and once for an idle wave (so that the accumulators never cross a branch)
+  auto run = [&](auto act) {
+    constexpr int LOADS = cfft::gemm_loads_per_stage(WAVES, !decltype(act)::value);
+    int st = 0;
 #pragma unroll 1
-  for (int k0 = 0; k0 < K2; k0 += 64) {                      // K2 % 64 == 0: two steps per turn, the next step's operands requested first
-    load(k0 + 32, a0[1], a1[1], b0[1], b1[1]);
-    mac(a0[0], a1[0], b0[0], b1[0]);
-    if (k0 + 64 < K2) load(k0 + 64, a0[0], a1[0], b0[0], b1[0]);
-    mac(a0[1], a1[1], b0[1], b1[1]);
-  }
+    for (int t = 0; t < nsteps; ++t) {
+      // in flight here: steps t .. min(t + STAGES - 2, nsteps - 1); requests return in order, so leaving the later step's pieces retires step t's
+      if (cfft::gemm_ahead(STAGES, t, nsteps) == 1) cfft_wait_vm<LOADS>(); else cfft_wait_vm<0>();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wave's reads of step t - 1 have returned
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      if (decltype(act)::value) { fetch(st); __builtin_amdgcn_sched_barrier(0); }
+      const int sn = st == 0 ? STAGES - 1 : st - 1;            // (st + STAGES - 1) % STAGES: the stage step t - 1 read
+      if (t + STAGES - 1 < nsteps) issue(t + STAGES - 1, sn, decltype(act)::value);
+      __builtin_amdgcn_sched_barrier(0);
+      if (decltype(act)::value) mac();
+      st = st + 1 == STAGES ? 0 : st + 1;
+    }
+  };
+  if (!active) { run(CfftBool<false>{}); return; }
+  run(CfftBool<true>{});
   float* Yb = p.Y + (size_t)bin * p.M * 64 + r;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -188,6 +243,13 @@ __global__ __launch_bounds__(GEMM_NT) void corrfft_gemm_kernel(const CfftGemm p)
       const int row = m0 + 32 * i + (q & 3) + 8 * (q >> 2) + 4 * h;
       if (row < p.M) { Yb[(size_t)row * 64] = acc[i][0][q]; Yb[(size_t)row * 64 + 32] = acc[i][1][q]; }
     }
+}
+
+template <int WAVES>
+void cfft_gemm_launch(const CfftGemm& p, hipStream_t stream) {
+  constexpr int STAGES = cfft::gemm_stages(WAVES), LDS = cfft::gemm_lds_bytes(WAVES);
+  g6d_allow_lds(reinterpret_cast<const void*>(&corrfft_gemm_kernel<WAVES, STAGES>), LDS);
+  hipLaunchKernelGGL((corrfft_gemm_kernel<WAVES, STAGES>), dim3(p.bins * p.mblocks), dim3(WAVES * 64), LDS, stream, p);
 }
 
 // ---- inverse: block = tile, thread = (g, reference): first spectrum column g (thread 0: columns 0 and 16, whose inverse transforms are
@@ -300,9 +362,11 @@ extern "C" int g6d_corr_fft_gemm(const float* X, const float* B, float* Y, int t
     g6d_set_error("corr_fft_gemm: T = 32, 32 references, Cin % 32 == 0 expected"); return G6D_EINVAL;
   }
   if (cfft::spectrum_bytes(Tw, tiles, Cin) >= (1ll << 31)) { g6d_set_error("corr_fft_gemm: spectrum beyond 2 GB"); return G6D_ENOSPC; }
-  CfftGemm p = {X, B, Y, tiles, cfft::bins(Tw), 2 * Cin, (tiles + GEMM_BM - 1) / GEMM_BM};
+  if (!g6d_aligned16(B)) { g6d_set_error("corr_fft_gemm: the filter spectrum is staged in 16-byte pieces, a 16-byte aligned B' expected"); return G6D_EINVAL; }
+  const CfftGemm p = {X, B, Y, tiles, cfft::bins(Tw), 2 * Cin, cfft::gemm_mblocks(tiles), cfft::gemm_rows_per_block(tiles)};
   static_assert(cfft::bins(T) % 8 == 0, "blocks of a bin stay on one XCD");
-  hipLaunchKernelGGL(corrfft_gemm_kernel, dim3(p.bins * p.mblocks), dim3(GEMM_NT), 0, static_cast<hipStream_t>(stream), p);
+  if (cfft::gemm_waves(tiles) == 2) cfft_gemm_launch<2>(p, static_cast<hipStream_t>(stream));
+  else cfft_gemm_launch<4>(p, static_cast<hipStream_t>(stream));
   return g6d_check_launch("corr_fft_gemm");
 }
 

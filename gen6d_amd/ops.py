@@ -1171,8 +1171,9 @@ def corr16_multi(xs, filt, outs):
 
 
 CORR_FFT_T = 32            # window side of the frequency-domain correlation (the kernels of csrc/corr_fft.hip are built for 32)
-CORR_FFT_CHUNK = 4         # queries per set of launches at most (the plan cuts it further where the spectrum would pass 2^31 bytes); measured at
-                           # batch 16 on the headline's pyramid: chunks of 2 / 4 / 8 / 13 take 4.2 / 2.60 / 2.71 / 2.74 ms (profiles/r29_corr_fft.md)
+CORR_FFT_CHUNK = 8         # queries per set of launches at most (the plan cuts it further where the spectrum would pass 2^31 bytes); measured at
+                           # batch 16 on the headline's pyramid: chunks of 2 / 4 / 8 / 13 take 2.68 / 2.36 / 2.05 / 1.97 ms (profiles/r31_corr_fft_gemm.md);
+                           # 8 holds 1.3 GB of spectrum, 13 would hold 2.1 GB for 0.08 ms
 
 
 def _corr_fft_segs(xs, outs, Cin, what):

@@ -905,7 +905,7 @@ int g6d_frame_crop_area(const G6dFrame* frames, const int32_t* rec, const uint8_
  *   g6d_corr_fft_fwd   segs[i].in [N][H][W][ld_in] (>= Cin channels, Cin % 32 == 0)  ->  X [bins][tiles][2][Cin], re plane then im plane
  *   g6d_corr_fft_gemm  Y [bins][tiles][2][32] = X' . B' per bin, B' [bins][2 Cin][64] = the conjugate filter spectrum as a real matrix:
  *                      row c (of Xr) = [Wr[.][c] | -Wi[.][c]], row Cin + c (of Xi) = [Wi[.][c] | Wr[.][c]] over the 32 references, with
- *                      W = rfft2 of the k x k filter zero-extended to T x T (tap (0, 0) at the origin)
+ *                      W = rfft2 of the k x k filter zero-extended to T x T (tap (0, 0) at the origin); X and B' 16-byte aligned
  *   g6d_corr_fft_inv   Y  ->  inverse real FFT / T^2, positions [0, V)^2 of every tile to segs[i].out [N][H*W][ld_out] inside the map.
  * One launch addresses less than 2^31 bytes of X (G6D_ENOSPC beyond): g6d_corr_fft_plan answers, for the segments given, out[0..7] =
  * tiles, bins, V, bytes of X, bytes of Y, bytes of B', the tiles of one query (one map per segment) and the most queries a launch takes. */
