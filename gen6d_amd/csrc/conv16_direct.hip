@@ -27,6 +27,7 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
                int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream,
                bool plan_only) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("conv16_direct: 1..4 segments and filters expected"); return G6D_EINVAL; }
+  if (Cin < 1 || Cout < 1 || !g6d_aligned16(W16)) { g6d_set_error("conv16_direct: bad args (Cin, Cout >= 1, 16-byte aligned filters)"); return G6D_EINVAL; }
   // w_layout 2: fragment-major filters of a 3x3x3 layer packed as the 2-D bank [Cout][9][3 Cin], channel order (dz, ci) — the pair
   // kernel folds the depth taps into its reduction (conv16w_kernel<3, ., 1, 3>)
   const bool folded = w_layout == 2;

@@ -747,7 +747,7 @@ int conv_narrow_launch(const G6dConv& d, hipStream_t stream) {
 // 3 F(4x4,3x3) kernel, 4 the narrow-output kernel on the vector ALUs, 5 the implicit GEMM on fp16 hi / lo pairs (math_mode 3: no hand-off)
 // (no launch; bench.py uses it to book the executed FLOPs of a launch in the right roofline family).
 extern "C" int g6d_conv_plan(const G6dConv* desc) {
-  if (!desc) return G6D_EINVAL;
+  if (!desc) { g6d_set_error("conv_plan: null descriptor"); return G6D_EINVAL; }
   if (desc->math_mode >= 3 && desc->math_mode <= 5) return 5;
   if (conv_narrow_eligible(*desc)) return 4;
   if (g6d_wino43_eligible(*desc)) return 3;
@@ -759,7 +759,7 @@ extern "C" int g6d_conv_plan(const G6dConv* desc) {
 extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) { return g6d_conv_igemm_ex(desc, nullptr, stream_); }
 
 extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g6d_stream_t stream_) {
-  if (!desc) return G6D_EINVAL;
+  if (!desc) { g6d_set_error("conv: null descriptor"); return G6D_EINVAL; }
   const G6dConv& d = *desc;
   const G6dRange16 rng = range ? *range : G6dRange16{nullptr, nullptr, -1, -1};
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -789,6 +789,9 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
   } else if (range) { g6d_set_error("conv: a G6dRange16 applies to math_mode 3 only"); return G6D_EINVAL; }
   if (d.N <= 0 || d.Cin <= 0 || d.Cout <= 0 || d.Do <= 0 || d.Ho <= 0 || d.Wo <= 0 || d.kd <= 0 || d.kh <= 0 || d.kw <= 0) {
     g6d_set_error("conv: bad shape"); return G6D_EINVAL;
+  }
+  if (d.Di <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.sd <= 0 || d.sh <= 0 || d.sw <= 0 || d.pd < 0 || d.ph < 0 || d.pw < 0 || d.out_act < 0 || d.out_act > 2) {
+    g6d_set_error("conv: bad shape (positive input sizes and strides, non-negative padding, out_act 0 / 1 / 2)"); return G6D_EINVAL;
   }
   if ((d.Cin & 3) || (d.ld_in & 3) || d.ld_in < d.Cin || d.ld_out < d.Cout) { g6d_set_error("conv: Cin/ld_in must be multiples of 4"); return G6D_EINVAL; }
   if (!g6d_aligned16(d.in) || !g6d_aligned16(d.weight) || (d.mul && !g6d_aligned16(d.mul)) ||

@@ -228,6 +228,7 @@ __global__ __launch_bounds__(64 * (cg::NW + 1), 1) void corr16_kernel(const Corr
 extern "C" int g6d_corr16_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
                                    const G6dRange16* range, g6d_stream_t stream) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("corr16: 1..4 segments and filters expected"); return G6D_EINVAL; }
+  if (Cin < 1 || !g6d_aligned16(W16)) { g6d_set_error("corr16: bad args (Cin >= 1, 16-byte aligned filters)"); return G6D_EINVAL; }
   if (math_mode < 1 || math_mode > 3 || Cout != 32 || (k != 15 && k != 7) || Cin % 32) {
     g6d_set_error("corr16: math_mode 1 (bf16) / 2 (fp16) / 3 (fp16 pairs), Cout = 32, k in {7, 15}, Cin % 32 == 0 expected"); return G6D_EINVAL;
   }

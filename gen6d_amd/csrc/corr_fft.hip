@@ -349,7 +349,7 @@ extern "C" int g6d_corr_fft_plan(const G6dCorrSeg* segs, int nseg, int Cin, int 
 extern "C" int g6d_corr_fft_fwd(const G6dCorrSeg* segs, int nseg, int Cin, int k, int Tw, float* X, g6d_stream_t stream) {
   CfftParams p = {};
   if (int rc = cfft_params(p, "corr_fft_fwd: bad segment (fp32 channels-last maps, 16-byte aligned, ld_in % 4 == 0)", segs, nseg, Cin, k, Tw, true)) return rc;
-  if (!X || !g6d_aligned16(X) || Cin % CG) { g6d_set_error("corr_fft_fwd: Cin % 32 == 0 and an aligned spectrum expected"); return G6D_EINVAL; }
+  if (!X || !g6d_aligned16(X) || Cin < CG || Cin % CG) { g6d_set_error("corr_fft_fwd: Cin % 32 == 0 and an aligned spectrum expected"); return G6D_EINVAL; }
   if (cfft::spectrum_bytes(Tw, p.plan.tiles, Cin) >= (1ll << 31)) { g6d_set_error("corr_fft_fwd: spectrum beyond 2 GB, launch fewer queries"); return G6D_ENOSPC; }
   p.Cin = Cin; p.X = X;
   g6d_allow_lds(reinterpret_cast<const void*>(&corrfft_fwd_kernel), FWD_LDS);

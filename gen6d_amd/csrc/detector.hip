@@ -202,6 +202,9 @@ extern "C" int g6d_detector_assemble(const float* s0, const float* s1, const flo
       scale_idx < 0 || 3 * scale_idx + 3 > nch || batch < 1 || batch > 65535) {
     g6d_set_error("detector_assemble: bad args (level-0 map must be a multiple of 4, hs and ws positive)"); return G6D_EINVAL;
   }
+  if ((long long)hs * ws > 0x7fffffffLL || ((long long)hs * ws * rfn + 255) / 256 > 0x7fffffffLL) {
+    g6d_set_error("detector_assemble: bad args (hs * ws within an int, hs * ws * rfn within one grid)"); return G6D_EINVAL;
+  }
   LevelStats st;
   for (int l = 0; l < 3; ++l) { st.mu[l] = mu_sigma[2 * l]; st.sigma[l] = mu_sigma[2 * l + 1]; }
   const long long total = (long long)hs * ws * rfn;
@@ -215,6 +218,7 @@ extern "C" int g6d_detector_score_mlp_max(const float* stacked, int P, int rfn, 
   if (!stacked || !w0 || !b0 || !w1 || !b1 || !out || P <= 0 || rfn <= 0 || rfn > 256 || nch != 12) {
     g6d_set_error("detector_score_mlp_max: bad args (rfn <= 256, nch == 12)"); return G6D_EINVAL;
   }
+  if (P > 0x7fffffff - 255) { g6d_set_error("detector_score_mlp_max: bad args (P + 255 within an int)"); return G6D_EINVAL; }
   const int ppb = 256 / rfn;
   hipLaunchKernelGGL(score_mlp_max_kernel<12>, dim3((P + ppb - 1) / ppb), dim3(256), (size_t)ppb * 64 * sizeof(int),
                      STREAM(stream), stacked, P, rfn, w0, b0, w1, b1, out, ppb);
@@ -224,6 +228,9 @@ extern "C" int g6d_detector_score_mlp_max(const float* stacked, int P, int rfn, 
 extern "C" int g6d_detector_decode(const float* scores, int ld_s, const float* offset, int ld_o, const float* scale,
                                    int ld_c, int hs, int ws, int pool_ratio, float* result, int batch, g6d_stream_t stream) {
   if (!scores || !offset || !scale || !result || hs <= 0 || ws <= 0 || batch < 1) { g6d_set_error("detector_decode: bad args"); return G6D_EINVAL; }
+  if (ld_s < 1 || ld_o < 2 || ld_c < 1 || (long long)hs * ws > 0x7fffffffLL) {
+    g6d_set_error("detector_decode: bad args (ld_s >= 1, ld_o >= 2, ld_c >= 1, hs * ws within an int)"); return G6D_EINVAL;
+  }
   hipLaunchKernelGGL(decode_kernel, dim3(batch), dim3(256), 0, STREAM(stream), scores, ld_s, offset, ld_o, scale, ld_c, hs, ws,
                      (float)pool_ratio, result);
   return g6d_check_launch("detector_decode");

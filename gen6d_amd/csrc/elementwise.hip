@@ -601,7 +601,7 @@ inline int grid_for(long long total, int block) {
 
 extern "C" int g6d_stats_finalize(const double* stats, int n, double count, double eps, float* scale, float* shift,
                                   g6d_stream_t stream) {
-  if (!stats || !scale || !shift || n <= 0 || count <= 0) { g6d_set_error("stats_finalize: bad args"); return G6D_EINVAL; }
+  if (!stats || !scale || !shift || n <= 0 || n > 0x7fffffff - 255 || !(count > 0)) { g6d_set_error("stats_finalize: bad args (n + 255 within an int, count > 0)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(stats_finalize_kernel, dim3((n + 255) / 256), dim3(256), 0, STREAM(stream), stats, n, 1.0 / count,
                      eps, scale, shift);
   return g6d_check_launch("stats_finalize");
@@ -613,6 +613,9 @@ extern "C" int g6d_affine_act_pool(const float* in, int ld_in, const float* scal
   if (!in || !out || (C & 3) || (ld_in & 3) || (ld_out & 3) || N <= 0 || H <= 0 || W <= 0 || pool < 0 || pool > 2 ||
       (pool == 1 && ((H | W) & 1)) || !g6d_aligned16(in) || !g6d_aligned16(out) || (scale && (!shift || !g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("affine_act_pool: bad args"); return G6D_EINVAL;
+  }
+  if (C <= 0 || ld_in < C || ld_out < C || per_n < 0 || (pool == 2 && (long long)H * W > 0x7fffffffLL)) {
+    g6d_set_error("affine_act_pool: bad args (C > 0, ld_in >= C, ld_out >= C, affine_per_n >= 0, H * W of the mean within an int)"); return G6D_EINVAL;
   }
   if (pool == 2) {
     long long total = (long long)N * (C / 4);
@@ -631,6 +634,9 @@ extern "C" int g6d_upsample_bilinear(const float* in, int ld_in, const float* sc
   if (!in || !out || (C & 3) || (ld_in & 3) || (ld_out & 3) || factor < 1 || N <= 0 || H <= 0 || W <= 0 || !g6d_aligned16(in) ||
       !g6d_aligned16(out) || (scale && (!shift || !g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("upsample_bilinear: bad args"); return G6D_EINVAL;
+  }
+  if (C <= 0 || ld_in < C || ld_out < C || per_n < 0 || (long long)H * factor > 0x7fffffffLL || (long long)W * factor > 0x7fffffffLL) {
+    g6d_set_error("upsample_bilinear: bad args (C > 0, ld_in >= C, ld_out >= C, affine_per_n >= 0, H * factor and W * factor within an int)"); return G6D_EINVAL;
   }
   long long total = (long long)N * H * factor * W * factor * (C / 4);
   hipLaunchKernelGGL(upsample_bilinear_kernel, dim3(grid_for(total, 256)), dim3(256), 0, STREAM(stream), in, ld_in, scale,
@@ -662,6 +668,9 @@ extern "C" int g6d_nchw_to_nhwc(const float* in, int N, int C, int H, int W, int
       (l2norm && ((C & 3) || (ld_out & 3) || !g6d_aligned16(out)))) {
     g6d_set_error("nchw_to_nhwc: bad args (l2norm needs C and ld_out multiples of 4)"); return G6D_EINVAL;
   }
+  if ((long long)H * W > 0x7fffffffLL - 63 || (long long)N * H * W > 0x7fffffffLL - 3 || C > 0x7fffffff - 63) {
+    g6d_set_error("nchw_to_nhwc: bad args (H * W + 63, C + 63 and N * H * W + 3 within an int)"); return G6D_EINVAL;
+  }
   const int HW = H * W;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((HW + 63) / 64, (C + 63) / 64, N), dim3(256), 0, STREAM(stream), in, C, HW,
                      out, ld_out);
@@ -676,12 +685,14 @@ extern "C" int g6d_l2norm_rows(float* x, int rows, int C, int ld, g6d_stream_t s
   if (!x || rows <= 0 || C <= 0 || ld < C || (!(ld & 3) && g6d_aligned16(x) && (C & 3))) {
     g6d_set_error("l2norm_rows: bad args (C a multiple of 4 on the 16-byte aligned path)"); return G6D_EINVAL;
   }
+  if (rows > 0x7fffffff - 3) { g6d_set_error("l2norm_rows: bad args (rows + 3 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(l2norm_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, STREAM(stream), x, rows, C, ld);
   return g6d_check_launch("l2norm_rows");
 }
 
 extern "C" int g6d_vps_norm(const float* vps, int D, float* feats, int ld, int c_off, int batch, g6d_stream_t stream) {
   if (!vps || !feats || D <= 0 || batch < 1 || batch > 65535) { g6d_set_error("vps_norm: bad args"); return G6D_EINVAL; }
+  if (c_off < 0 || (long long)c_off + 3 > ld) { g6d_set_error("vps_norm: bad args (c_off >= 0, c_off + 3 <= ld)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(vps_norm_kernel, dim3(3, batch), dim3(256), 0, STREAM(stream), vps, D, feats, ld, c_off);
   return g6d_check_launch("vps_norm");
 }
@@ -689,6 +700,9 @@ extern "C" int g6d_vps_norm(const float* vps, int D, float* feats, int ld, int c
 extern "C" int g6d_max_an_add(const float* in, int ld_in, int rfn, int an, int C, const float* embed, float* out,
                               int ld_out, int batch, g6d_stream_t stream) {
   if (!in || !embed || !out || rfn <= 0 || an <= 0 || C <= 0 || batch < 1 || batch > 65535) { g6d_set_error("max_an_add: bad args"); return G6D_EINVAL; }
+  if (ld_in < C || ld_out < C || (long long)rfn * C > 0x7fffffffLL - 255 || (long long)rfn * an > 0x7fffffffLL) {
+    g6d_set_error("max_an_add: bad args (ld_in >= C, ld_out >= C, rfn * C + 255 and rfn * an within an int)"); return G6D_EINVAL;
+  }
   hipLaunchKernelGGL(max_an_add_kernel, dim3((rfn * C + 255) / 256, batch), dim3(256), 0, STREAM(stream), in, ld_in, rfn, an, C,
                      embed, out, ld_out);
   return g6d_check_launch("max_an_add");
@@ -699,6 +713,7 @@ extern "C" int g6d_attention(const float* q, const float* k, const float* v, int
   if (!q || !k || !v || !out || n <= 0 || heads <= 0 || C <= 0 || C % heads || ld < C || ld_out < C || batch < 1 || batch > 65535) {
     g6d_set_error("attention: bad args (ld >= C, ld_out >= C)"); return G6D_EINVAL;
   }
+  if ((long long)n * heads > 0x7fffffffLL) { g6d_set_error("attention: bad args (n * heads within an int)"); return G6D_EINVAL; }
   size_t lds = (size_t)(C / heads + n) * sizeof(float);
   if (lds > 60000) { g6d_set_error("attention: n too large"); return G6D_EINVAL; }
   if (n <= ATT_N && C / heads <= ATT_N)
@@ -711,6 +726,7 @@ extern "C" int g6d_attention(const float* q, const float* k, const float* v, int
 extern "C" int g6d_layernorm(const float* in, int ld_in, int n, int C, const float* gamma, const float* beta, float eps,
                              float* out, int ld_out, g6d_stream_t stream) {
   if (!in || !out || !gamma || !beta || n <= 0 || C <= 0) { g6d_set_error("layernorm: bad args"); return G6D_EINVAL; }
+  if (ld_in < C || ld_out < C) { g6d_set_error("layernorm: bad args (ld_in >= C, ld_out >= C)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(layernorm_kernel, dim3(n), dim3(64), 0, STREAM(stream), in, ld_in, C, gamma, beta, eps, out, ld_out);
   return g6d_check_launch("layernorm");
 }
@@ -719,6 +735,9 @@ extern "C" int g6d_affine_act_add(const float* in, int ld_in, const float* scale
                                   const float* residual, int ld_res, int n, int C, float* out, int ld_out,
                                   int rows_per_group, g6d_stream_t stream) {
   if (!in || !out || n <= 0 || C <= 0 || (scale && !shift) || rows_per_group < 0) { g6d_set_error("affine_act_add: bad args"); return G6D_EINVAL; }
+  if (ld_in < C || ld_out < C || (residual && ld_res < C) || (long long)n * C > 0x7fffffffLL - 255) {
+    g6d_set_error("affine_act_add: bad args (ld_in >= C, ld_out >= C, ld_res >= C with a residual, n * C + 255 within an int)"); return G6D_EINVAL;
+  }
   hipLaunchKernelGGL(affine_act_add_kernel, dim3((n * C + 255) / 256), dim3(256), 0, STREAM(stream), in, ld_in, scale,
                      shift, relu, residual, ld_res, n, C, out, ld_out, rows_per_group);
   return g6d_check_launch("affine_act_add");
@@ -729,6 +748,7 @@ extern "C" int g6d_linear_gemv_batch(const float* x, int B, int K, const float* 
   if (!x || !W || !out || B <= 0 || K <= 0 || (K & 3) || O <= 0 || !g6d_aligned16(x) || !g6d_aligned16(W)) {
     g6d_set_error("linear_gemv_batch: bad args"); return G6D_EINVAL;
   }
+  if (act < 0 || act > 2) { g6d_set_error("linear_gemv_batch: bad args (act 0 none, 1 ReLU, 2 LeakyReLU)"); return G6D_EINVAL; }
   constexpr int KL = GEMVB_THREADS * 4 * 2;                 // KV = 2: K slices of 2048 floats
   const bool rows_ok = O % GEMVB_R == 0 && K % KL == 0 && O / GEMVB_R <= G6D_WS_COUNTERS;
   const int KS = rows_ok ? K / KL : 0;
@@ -775,6 +795,7 @@ extern "C" int g6d_linear_gemv(const float* x, int B, int K, const float* W, con
   if (!x || !W || !out || B <= 0 || B > 8 || K <= 0 || (K & 3) || O <= 0 || !g6d_aligned16(x) || !g6d_aligned16(W)) {
     g6d_set_error("linear_gemv: bad args"); return G6D_EINVAL;
   }
+  if (act < 0 || act > 2) { g6d_set_error("linear_gemv: bad args (act 0 none, 1 ReLU, 2 LeakyReLU)"); return G6D_EINVAL; }
   if (K >= GEMV_THREADS * 4 * 16)
     hipLaunchKernelGGL(linear_gemv_kernel<16>, dim3(O), dim3(GEMV_THREADS), 0, STREAM(stream), x, B, K, W, bias, act, out, O);
   else

@@ -191,8 +191,9 @@ extern "C" int g6d_frame_emit(const G6dSink* sinks, int n, const uint8_t* imgs, 
     g6d_set_error("frame_emit: bad args (null table / imgs / pts / valid, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
   }
   if (n == 0) return G6D_OK;
-  const int tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_emit: too many tiles for one launch"); return G6D_EINVAL; }
+  const long long tiles_ll = (((long long)W + TW - 1) / TW) * (((long long)H + TH - 1) / TH);      // (in 64 bits: the product of two ints)
+  if ((long long)W + TW - 1 > 0x7fffffffLL || (long long)H + TH - 1 > 0x7fffffffLL || tiles_ll * n > 0x7fffffffLL) { g6d_set_error("frame_emit: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles = (int)tiles_ll;
   hipLaunchKernelGGL(frame_emit_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), sinks, imgs, B, H, W,
                      pts, valid, tiles);
   return g6d_check_launch("frame_emit");

@@ -230,9 +230,9 @@ extern "C" int g6d_frame_crop(const G6dFrame* frames, const int32_t* rec, const 
     g6d_set_error("frame_crop: bad args (null table / rec / imgs / hinv / dst, B outside 1..65535, a non-positive canvas or crop)");
     return G6D_EINVAL;
   }
-  const int tiles_x = (dw + CW - 1) / CW;
-  const long long tiles = (long long)tiles_x * ((dh + CH - 1) / CH);
-  if (tiles > 0x7fffffffLL) { g6d_set_error("frame_crop: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles_x = (int)(((long long)dw + CW - 1) / CW);
+  const long long tiles = (long long)tiles_x * (((long long)dh + CH - 1) / CH);
+  if ((long long)dw + CW - 1 > 0x7fffffffLL || (long long)dh + CH - 1 > 0x7fffffffLL || tiles > 0x7fffffffLL) { g6d_set_error("frame_crop: too many tiles for one launch"); return G6D_EINVAL; }
   hipLaunchKernelGGL(frame_crop_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames, rec,
                      imgs, H, W, hinv, dst, dh, dw, tiles_x);
   return g6d_check_launch("frame_crop");
@@ -245,9 +245,9 @@ extern "C" int g6d_frame_crop_area(const G6dFrame* frames, const int32_t* rec, c
                   "max_n outside 1..8)");
     return G6D_EINVAL;
   }
-  const int tiles_x = (dw + CW - 1) / CW;
-  const long long tiles = (long long)tiles_x * ((dh + CH - 1) / CH);
-  if (tiles > 0x7fffffffLL) { g6d_set_error("frame_crop_area: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles_x = (int)(((long long)dw + CW - 1) / CW);
+  const long long tiles = (long long)tiles_x * (((long long)dh + CH - 1) / CH);
+  if ((long long)dw + CW - 1 > 0x7fffffffLL || (long long)dh + CH - 1 > 0x7fffffffLL || tiles > 0x7fffffffLL) { g6d_set_error("frame_crop_area: too many tiles for one launch"); return G6D_EINVAL; }
   hipLaunchKernelGGL(frame_crop_area_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
                      rec, imgs, H, W, hinv, dst, dh, dw, tiles_x, max_n);
   return g6d_check_launch("frame_crop_area");

@@ -480,8 +480,9 @@ extern "C" int g6d_frame_ingest(const G6dFrame* frames, int n, uint8_t* out, int
     g6d_set_error("frame_ingest: bad args (null table / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
   }
   if (n == 0) return G6D_OK;
-  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest: too many tiles for one launch"); return G6D_EINVAL; }
+  const long long tiles_ll = (((long long)W + TW - 1) / TW) * (((long long)H + TH - 1) / TH);      // (in 64 bits: the product of two ints)
+  if ((long long)W + TW - 1 > 0x7fffffffLL || (long long)H + TH - 1 > 0x7fffffffLL || tiles_ll * n > 0x7fffffffLL) { g6d_set_error("frame_ingest: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles_x = (W + TW - 1) / TW, tiles = (int)tiles_ll;
   hipLaunchKernelGGL(frame_ingest_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames, out, B, H,
                      W, K_out, tiles_x, tiles);
   return g6d_check_launch("frame_ingest");
@@ -495,8 +496,9 @@ extern "C" int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* mesh
     g6d_set_error("frame_ingest_mesh: bad args (null table / meshes / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
   }
   if (n == 0) return G6D_OK;
-  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_mesh: too many tiles for one launch"); return G6D_EINVAL; }
+  const long long tiles_ll = (((long long)W + TW - 1) / TW) * (((long long)H + TH - 1) / TH);      // (in 64 bits: the product of two ints)
+  if ((long long)W + TW - 1 > 0x7fffffffLL || (long long)H + TH - 1 > 0x7fffffffLL || tiles_ll * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_mesh: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles_x = (W + TW - 1) / TW, tiles = (int)tiles_ll;
   hipLaunchKernelGGL(frame_ingest_lens_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
                      meshes, out, B, H, W, K_out, tiles_x, tiles);
   return g6d_check_launch("frame_ingest_mesh");
@@ -508,8 +510,9 @@ extern "C" int g6d_frame_ingest_area(const G6dFrame* frames, const G6dMesh* mesh
     g6d_set_error("frame_ingest_area: bad args (null table / out / K_out, n < 0 or a non-positive canvas)"); return G6D_EINVAL;
   }
   if (n == 0) return G6D_OK;
-  const int tiles_x = (W + TW - 1) / TW, tiles = tiles_x * ((H + TH - 1) / TH);
-  if ((long long)tiles * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_area: too many tiles for one launch"); return G6D_EINVAL; }
+  const long long tiles_ll = (((long long)W + TW - 1) / TW) * (((long long)H + TH - 1) / TH);      // (in 64 bits: the product of two ints)
+  if ((long long)W + TW - 1 > 0x7fffffffLL || (long long)H + TH - 1 > 0x7fffffffLL || tiles_ll * n > 0x7fffffffLL) { g6d_set_error("frame_ingest_area: too many tiles for one launch"); return G6D_EINVAL; }
+  const int tiles_x = (W + TW - 1) / TW, tiles = (int)tiles_ll;
   hipLaunchKernelGGL(frame_ingest_area_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
                      meshes, out, B, H, W, K_out, tiles_x, tiles);
   return g6d_check_launch("frame_ingest_area");

@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(64) track_commit_kernel(const float* __restric
 #define CHAIN_STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" int g6d_chain_crop_from_detection(const float* det, float size, float* hinv, int batch, g6d_stream_t stream) {
-  if (!det || !hinv || size <= 0 || batch < 1) { g6d_set_error("chain_crop_from_detection: bad args"); return G6D_EINVAL; }
+  if (!det || !hinv || !(size > 0) || batch < 1) { g6d_set_error("chain_crop_from_detection: bad args"); return G6D_EINVAL; }
   hipLaunchKernelGGL(crop_from_detection_kernel, dim3(batch), dim3(64), 0, CHAIN_STREAM(stream), det, size, hinv);
   return g6d_check_launch("chain_crop_from_detection");
 }
@@ -220,7 +220,7 @@ extern "C" int g6d_chain_pose_from_selection(const float* det, const float* logi
 extern "C" int g6d_chain_refine_prepare(const float* pose_in, const float* que_K, const float* norm, float size, float margin,
                                         const float* sub_poses, const float* sub_Ks, int n_sub, int ref_num, float* geo,
                                         int* ref_idx, float angle_step, int* ref_bucket, int batch, g6d_stream_t stream) {
-  if (!pose_in || !que_K || !norm || size <= 0 || !sub_poses || !sub_Ks || n_sub <= 0 || n_sub > 128 || ref_num <= 0 ||
+  if (!pose_in || !que_K || !norm || !(size > 0) || !sub_poses || !sub_Ks || n_sub <= 0 || n_sub > 128 || ref_num <= 0 ||
       ref_num > 8 || ref_num > n_sub || !geo || !ref_idx || batch < 1) {
     g6d_set_error("chain_refine_prepare: bad args (n_sub <= 128, ref_num <= 8)"); return G6D_EINVAL;
   }
@@ -242,6 +242,7 @@ extern "C" int g6d_warp_batch(const unsigned char* stack, const unsigned char* s
       (!idx && !single)) {
     g6d_set_error("warp_batch: bad args"); return G6D_EINVAL;
   }
+  if ((long long)dh * dw > 0x7fffffffLL - 255) { g6d_set_error("warp_batch: bad args (dh * dw + 255 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(warp_batch_kernel, dim3((dh * dw + 255) / 256, B), dim3(256), 0, CHAIN_STREAM(stream), stack, single, idx, sh, sw,
                      ch, hinv, dst, dh, dw);
   return g6d_check_launch("warp_batch");

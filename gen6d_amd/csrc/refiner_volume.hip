@@ -189,6 +189,7 @@ extern "C" int g6d_refiner_volume(const float* feats, const float* projs, const 
       !g6d_aligned16(stdv)) {
     g6d_set_error("refiner_volume: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
   }
+  if ((long long)fh * fw * C > 0x7fffffffLL) { g6d_set_error("refiner_volume: bad args (fh * fw * C within an int: the tap offsets)"); return G6D_EINVAL; }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {projs, nullptr, nullptr, nullptr, nullptr, rot_in, 3};
   hipLaunchKernelGGL(refiner_volume_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
@@ -208,6 +209,7 @@ extern "C" int g6d_refiner_volume_kp(const float* feats, const float* ref_Ks, co
       !g6d_aligned16(mean_in) || !g6d_aligned16(stdv)) {
     g6d_set_error("refiner_volume_kp: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
   }
+  if ((long long)fh * fw * C > 0x7fffffffLL) { g6d_set_error("refiner_volume_kp: bad args (fh * fw * C within an int: the tap offsets)"); return G6D_EINVAL; }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {nullptr, ref_Ks, ref_poses, K_in, pose_in, pose_in, 4};
   hipLaunchKernelGGL(refiner_volume_kernel<false>, dim3((unsigned)((threads + 255) / 256), batch), dim3(256), 0,
@@ -228,6 +230,7 @@ extern "C" int g6d_refiner_volume_kp_pairs(const float* feats, const float* ref_
       !g6d_aligned16(mean_in16) || !g6d_aligned16(std16)) {
     g6d_set_error("refiner_volume_kp_pairs: bad args (1 <= rfn <= 8, C a positive multiple of 4, positive map and image sizes)"); return G6D_EINVAL;
   }
+  if ((long long)fh * fw * C > 0x7fffffffLL) { g6d_set_error("refiner_volume_kp_pairs: bad args (fh * fw * C within an int: the tap offsets)"); return G6D_EINVAL; }
   const long long threads = (long long)sn * sn * sn * 32;
   const VolViews vw = {nullptr, ref_Ks, ref_poses, K_in, pose_in, pose_in, 4};
   VolPairs vp = {};

@@ -277,6 +277,11 @@ extern "C" int g6d_selector_levels(int nlev, int qn, const float* const* que, co
       D <= 0 || Dg <= 0 || C <= 0 || (C & 3)) {
     g6d_set_error("selector_levels: bad args (1 <= qn <= 8, score_maps required)"); return G6D_EINVAL;
   }
+  long long scan_ll = 0;                  // the grid and the block ranges of the levels are ints
+  for (int l = 0; l < nlev; ++l) scan_ll += (long long)D * (((long long)(HW[l] > 0 ? HW[l] : 0) + 63) / 64);
+  if (C > 0x7fffffff - 15 || scan_ll + (long long)qn * nlev * ((C + 15) / 16) > 0x7fffffffLL || (long long)qn * nlev * D + 3 > 0x7fffffffLL) {
+    g6d_set_error("selector_levels: bad args (D * ceil(HW / 64) blocks over the levels and qn * nlev * D + 3 within an int)"); return G6D_EINVAL;
+  }
   SelArgs a = {};
   a.nlev = nlev; a.qn = qn; a.D = D; a.C = C; a.inv_dg = 1.0 / (double)Dg; a.eps = eps; a.vps = vps; a.scale = scale; a.shift = shift;
   int blk = 0;
@@ -326,6 +331,7 @@ extern "C" int g6d_selector_levels(int nlev, int qn, const float* const* que, co
 
 extern "C" int g6d_selector_ref_sums(const float* refs, int D, int HW, int C, double* r1, double* r2, g6d_stream_t stream) {
   if (!refs || !r1 || !r2 || D <= 0 || HW <= 0 || C <= 0) { g6d_set_error("selector_ref_sums: bad args"); return G6D_EINVAL; }
+  if ((long long)HW * C > 0x7fffffffLL - 255) { g6d_set_error("selector_ref_sums: bad args (HW * C + 255 within an int)"); return G6D_EINVAL; }
   const int n = HW * C;
   hipLaunchKernelGGL(ref_sums_kernel, dim3((n + 255) / 256), dim3(256), 0, STREAM(stream), refs, D, n, r1, r2);
   return g6d_check_launch("selector_ref_sums");
@@ -333,7 +339,7 @@ extern "C" int g6d_selector_ref_sums(const float* refs, int D, int HW, int C, do
 
 extern "C" int g6d_selector_prod_affine(const float* que, const double* r1, const double* r2, int D, int HW, int C,
                                         double eps, float* scale, float* shift, g6d_stream_t stream) {
-  if (!que || !r1 || !r2 || !scale || !shift || D <= 0 || HW <= 0 || C <= 0) { g6d_set_error("selector_prod_affine: bad args"); return G6D_EINVAL; }
+  if (!que || !r1 || !r2 || !scale || !shift || D <= 0 || HW <= 0 || C <= 0 || C > 0x7fffffff - 63) { g6d_set_error("selector_prod_affine: bad args (C + 63 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(prod_affine_kernel, dim3((C + 63) / 64), dim3(256), 0, STREAM(stream), que, r1, r2, HW, C,
                      1.0 / ((double)D * HW), eps, scale, shift);
   return g6d_check_launch("selector_prod_affine");

@@ -267,6 +267,9 @@ extern "C" int g6d_upsample_bilinear_split16(const float* in, int ld_in, const f
       math_mode < 1 || math_mode > 3 || !g6d_aligned16(in) || (scale && (!g6d_aligned16(scale) || !g6d_aligned16(shift)))) {
     g6d_set_error("upsample_bilinear_split16: bad args (C % 8 == 0, 16-byte aligned rows, factor >= 1, math_mode 1..3)"); return G6D_EINVAL;
   }
+  if ((long)H * factor > 0x7fffffffL || (long)W * factor > 0x7fffffffL) {
+    g6d_set_error("upsample_bilinear_split16: bad args (H * factor and W * factor within an int)"); return G6D_EINVAL;
+  }
   char* o = c16_slice_out(out, C, ld_out, plane, c_off, math_mode);
   if (!o) { g6d_set_error("upsample_bilinear_split16: the channel slice does not fit the output rows (multiples of 8, c_off + C <= plane, plane + c_off + C <= ld_out)"); return G6D_EINVAL; }
   const long total = (long)N * H * factor * W * factor * (C >> 3);
@@ -281,6 +284,7 @@ extern "C" int g6d_l2norm_split16(const float* in, int ld_in, int rows, int C, v
   if (!in || !out || rows < 1 || (C != 256 && C != 512) || ld_in < C || (ld_in & 3) || math_mode < 1 || math_mode > 3 || !g6d_aligned16(in) || !g6d_aligned16(out)) {
     g6d_set_error("l2norm_split16: bad args (C = 256 or 512, 16-byte aligned rows, math_mode 1..3)"); return G6D_EINVAL;
   }
+  if (rows > 0x7fffffff - 3) { g6d_set_error("l2norm_split16: bad args (rows + 3 within an int)"); return G6D_EINVAL; }
   const dim3 grid((rows + 3) / 4);
   char* o = static_cast<char*>(out);
   split16_dispatch(math_mode, range, stream, [&](auto mm, hipStream_t st, const G6dRange16& rng) {

@@ -97,6 +97,7 @@ __global__ void __launch_bounds__(64) track_verify_kernel(const float* __restric
 extern "C" int g6d_track_gate(const float* pose_table, int32_t* health, const int* slot_stream, int* slot_eff, int batch,
                               g6d_stream_t stream) {
   if (!pose_table || !health || !slot_stream || !slot_eff || batch < 1) { g6d_set_error("track_gate: bad args"); return G6D_EINVAL; }
+  if (batch > 0x7fffffff - 63) { g6d_set_error("track_gate: bad args (batch + 63 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(track_gate_kernel, dim3((batch + 63) / 64), dim3(64), 0, HEALTH_STREAM(stream), pose_table, health, slot_stream,
                      slot_eff, batch);
   return g6d_check_launch("track_gate");
@@ -111,6 +112,7 @@ extern "C" int g6d_track_health(const float* pose_prev, const float* pose_new, c
     g6d_set_error("track_health: bad args (pose_prev unless reset, pic or W, H >= 1, diameter > 0, patience >= 1)"); return G6D_EINVAL;
   }
   const pa::HealthGates g{min_px, max_px, margin, max_rot_deg, max_shift, max_log2_scale};
+  if (batch > 0x7fffffff - 63) { g6d_set_error("track_health: bad args (batch + 63 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(track_health_kernel, dim3((batch + 63) / 64), dim3(64), 0, HEALTH_STREAM(stream), pose_prev, pose_new, K, pic, W, H,
                      slot_eff, reset ? 1 : 0, center, diameter, patience, g, health, measures, slot_commit, slot_draw, batch);
   return g6d_check_launch("track_health");
@@ -123,6 +125,7 @@ extern "C" int g6d_track_verify(const float* det, const float* pose_table, const
       !measures || batch < 1) {
     g6d_set_error("track_verify: bad args (diameter, ref_px > 0, verify_patience >= 1)"); return G6D_EINVAL;
   }
+  if (batch > 0x7fffffff - 63) { g6d_set_error("track_verify: bad args (batch + 63 within an int)"); return G6D_EINVAL; }
   hipLaunchKernelGGL(track_verify_kernel, dim3((batch + 63) / 64), dim3(64), 0, HEALTH_STREAM(stream), det, pose_table, K, slot_commit,
                      center, diameter, ref_px, verify_shift, verify_log2_scale, verify_patience, health, measures, batch);
   return g6d_check_launch("track_verify");

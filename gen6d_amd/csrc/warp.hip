@@ -49,6 +49,7 @@ extern "C" int g6d_warp_perspective(const unsigned char* src, int sh, int sw, in
   if (!src || !hinv || !dst || sh <= 0 || sw <= 0 || ch <= 0 || ch > 4 || dh <= 0 || dw <= 0) {
     g6d_set_error("warp_perspective: bad args"); return G6D_EINVAL;
   }
+  if ((long long)dh * dw > 0x7fffffffLL - 255) { g6d_set_error("warp_perspective: bad args (dh * dw + 255 within an int)"); return G6D_EINVAL; }
   Mat3 m;
   for (int i = 0; i < 9; ++i) m.m[i] = hinv[i];
   const int n = dh * dw;

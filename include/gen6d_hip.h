@@ -31,6 +31,16 @@ enum {
   G6D_ENOSPC = -2,   /* workspace too small */
   G6D_ELAUNCH = -3   /* hipLaunch error (hipGetLastError != success) */
 };
+/* Refusals.  Every launcher checks its arguments on the host BEFORE the first HIP call and refuses with G6D_EINVAL (G6D_ENOSPC for a
+ * workspace or spectrum that is too small) and a message in g6d_last_error(): a NULL required pointer; a dimension or count < 1 (or beyond
+ * its documented maximum); a row stride smaller than the row it holds (ld < C), or off the vector width where rows are read in 16-byte
+ * pieces; a pointer that is not 16-byte aligned where the kernel reads or writes 8- / 16-byte pieces; an enumeration outside its values;
+ * and sizes whose element offsets, work-item counts or grid sizes leave the type the launcher or the kernel computes them in (products
+ * such as n * C, HW * C, hs * ws, dh * dw, rfn * C, N * H * W, fh * fw * C that pass 2^31 - 1 where they are formed as int; where a grid
+ * is such a count rounded up to whole blocks, count + block - 1 must fit as well, e.g. n * C <= 2^31 - 256).  A refused call has
+ * launched nothing.  The entry points the table reaches are those of elementwise, selector, detector, refiner_volume, warp, pose_chain,
+ * track_health, split16 and the frame launchers, whose integer arithmetic was read line by line; the convolution, Winograd and correlation
+ * families keep the byte and element bounds they state in their own messages (2^29 / 2^30 / 2^31 floats, 2 GB of filters).  tests/launch_contract.py holds the rules per entry point as a table, tests/test_launch_contract_cpu.py runs it. */
 
 int g6d_abi_version(void);
 /* last HIP error string of this thread ("" if none) */
@@ -94,7 +104,9 @@ typedef struct G6dConv {
   int32_t in_relu;              /* apply ReLU after the input affine */
   int32_t in_affine_per_n;      /* 0: one affine table for all N; k >= 1: image n uses table n / k (1 = a table per image; k = the
                                    hypothesis count D when N = qn * D images of a batched selector call share one table per query) */
-  int32_t out_act;              /* 0 none, 1 ReLU, 2 LeakyReLU(0.1) */
+  int32_t out_act;              /* 0 none, 1 ReLU, 2 LeakyReLU(0.1); anything else is refused.  Sizes: N, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, the
+                                   kernel extents (<= 32) and the strides sd, sh, sw are >= 1, the paddings >= 0; Cin % 4 == 0,
+                                   ld_in % 4 == 0, ld_in >= Cin, ld_out >= Cout; in, weight, mul and the affine tables 16-byte aligned */
   int32_t stat_rows_per_group;  /* output rows per statistics group (0 = all rows in one group) */
   int32_t split_k;              /* 0 = choose automatically; 1 = never split; >1 = force */
   int32_t math_mode;            /* 0 = fp32 MFMA (default, the parity path); 1 = bf16, 2 = fp16 operands with fp32 accumulation:
@@ -223,18 +235,21 @@ int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin, const flo
 
 /* InstanceNorm finalisation: stats[g][c] = (sum, sumsq) over `count` elements ->
  * scale = 1/sqrt(var+eps), shift = -mean*scale (biased variance; torch InstanceNorm{1,2,3}d, eps 1e-5,
- * network/selector.py:28-77, network/refiner.py:27-50,93-133). n = groups*channels. */
+ * network/selector.py:28-77, network/refiner.py:27-50,93-133). n = groups*channels, 1 <= n <= 2^31 - 256;
+ * count > 0. */
 int g6d_stats_finalize(const double* stats, int n, double count, double eps, float* scale, float* shift, g6d_stream_t stream);
 
 /* y = pool2x2?( relu?( x*scale[c] + shift[c] ) ) on [N][H][W][C] channels-last rows (D folded into N).
  * pool: 0 none, 1 = 2x2 max (MaxPool3d (1,2,2), network/selector.py:34,41,56), 2 = full-window mean over HxW
- * (AvgPool3d (1,4,4), selector.py:76).  scale/shift may be NULL (identity); affine_per_n = k >= 1: image n uses table n / k
- * (as G6dConv.in_affine_per_n), 0: one table. */
+ * (AvgPool3d (1,4,4), selector.py:76).  scale/shift may be NULL (identity; both or neither); affine_per_n = k >= 1: image n uses table n / k
+ * (as G6dConv.in_affine_per_n), 0: one table.  C > 0 and C, ld_in, ld_out multiples of 4, ld_in >= C, ld_out >= C; in, out and the tables
+ * 16-byte aligned; pool 1 needs even H and W; pool 2: H * W <= 2^31 - 1. */
 int g6d_affine_act_pool(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n, int relu,
                         int pool, int N, int H, int W, int C, float* out, int ld_out, g6d_stream_t stream);
 
 /* Bilinear up-sampling by an integer factor (align_corners=False, F.interpolate in network/refiner.py:74-75) of
- * relu?(x*scale+shift) on [N][H][W][C] -> [N][H*f][W*f][C] written with channel stride ld_out.  N, H, W > 0, factor >= 1. */
+ * relu?(x*scale+shift) on [N][H][W][C] -> [N][H*f][W*f][C] written with channel stride ld_out.  N, H, W > 0, factor >= 1; C, strides,
+ * alignment and affine_per_n as g6d_affine_act_pool; H * factor and W * factor <= 2^31 - 1. */
 int g6d_upsample_bilinear(const float* in, int ld_in, const float* scale, const float* shift, int affine_per_n,
                           int N, int H, int W, int C, int factor, float* out, int ld_out, g6d_stream_t stream);
 
@@ -329,7 +344,8 @@ int g6d_wino16_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const vo
  *        images do, and where a tile holds several small images (8 x 8: two) a group may also be whole 64-pixel epilogue passes of the
  *        tile — one 8 x 8 image per group.  Groups smaller than a pass, or not aligned to one, are rejected (G6D_EINVAL)
  * Up to 4 map sizes per launch (the scales of the detector's pyramid) like g6d_wino_conv3x3_multi; all segments share D and the
- * kinds of output.  No workspace: the K loop is never split. */
+ * kinds of output.  No workspace: the K loop is never split.  Cin, Cout >= 1; W16 16-byte aligned (g6d_corr16_multi too); ld_in, ld_full,
+ * ld_pool multiples of 8 elements. */
 typedef struct G6dConv16Seg {
   const void* in;
   void* out_full;
@@ -427,11 +443,12 @@ int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const fl
 
 /* In-place L2 normalisation over C of channels-last rows x[rows][ld] (F.normalize eps 1e-12, network/selector.py:118,
  * network/refiner.py:69-71,165).  16-byte accesses when x is 16-byte aligned and ld % 4 == 0 (then C % 4 == 0 is required),
- * scalar accesses otherwise (the [qn][7] rows of the regressor output). */
+ * scalar accesses otherwise (the [qn][7] rows of the regressor output).  ld >= C, rows <= 2^31 - 4. */
 int g6d_l2norm_rows(float* x, int rows, int C, int ld, g6d_stream_t stream);
 
 /* NCHW (backbone output) -> channels-last, optionally L2-normalised over C (F.normalize eps 1e-12,
- * network/selector.py:118, network/refiner.py:69-71). out [N][H][W][ld_out]. */
+ * network/selector.py:118, network/refiner.py:69-71). out [N][H][W][ld_out], ld_out >= C; with l2norm C and ld_out are multiples of 4 and
+ * out is 16-byte aligned; H * W <= 2^31 - 64, C <= 2^31 - 64, N * H * W <= 2^31 - 4 (grids of rounded-up counts). */
 int g6d_nchw_to_nhwc(const float* in, int N, int C, int H, int W, int l2norm, float* out, int ld_out, g6d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -446,6 +463,7 @@ int g6d_nchw_to_nhwc(const float* in, int N, int C, int H, int W, int l2norm, fl
  * g6d_selector_scan       (query time) one coalesced streaming pass over refs, wavefront shuffle reductions:
  *                                      score_map[d][hw] = sum_c que*ref ;  vps[d] = sum_hw S^2 / max_hw S
  * ---------------------------------------------------------------------------------------------------------------- */
+/* D, HW, C >= 1.  g6d_selector_ref_sums: HW * C <= 2^31 - 256 (the grid is formed as (HW * C + 255) / 256 in int).  g6d_selector_scan: C % 4 == 0, que and refs 16-byte aligned, D * HW <= 2^30. */
 int g6d_selector_ref_sums(const float* refs, int D, int HW, int C, double* r1, double* r2, g6d_stream_t stream);
 int g6d_selector_prod_affine(const float* que, const double* r1, const double* r2, int D, int HW, int C, double eps,
                              float* scale, float* shift, g6d_stream_t stream);
@@ -470,6 +488,7 @@ int g6d_selector_levels(int nlev, int qn, const float* const* que, const float* 
  *   lin       [sn]                torch.linspace(-1,1,sn)
  *   mean_in   [sn^3][2C]          cat[mean over refs, query sample]   (input of mean_embed)
  *   std       [sn^3][C]           1 <= rfn <= 8
+ * fh * fw * C <= 2^31 - 1 (the tap offsets inside a view are ints).
  * C is any positive multiple of 4 (also below 4 * (rfn + 1) and off the 128-channel trips of a half-wave: every lane walks every
  * trip, lanes beyond C store nothing); fh, fw, h_in, w_in > 0, sn <= 256.  Anything else is refused with G6D_EINVAL.
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -495,20 +514,23 @@ int g6d_refiner_volume_kp_pairs(const float* feats, const float* ref_Ks, const f
  * correlation maps (level l at 1/(8*2^l) resolution, channels-last [h_l*w_l][rfn]), nearest-upsample levels 1,2 to
  * level-0 size, normalise ((x-mu_l)/sigma_l), clip to +-clip, bilinear-resize (align_corners=False) to (hs,ws) and
  * write channels [3*scale_idx .. 3*scale_idx+2] of stacked [hs*ws][rfn][nch].  batch >= 1 queries (network/detector.py:291-304
- * takes [qn,H,W,3]): s_l [batch][h_l*w_l][rfn], stacked [batch][hs*ws][rfn][nch].  hc, wc multiples of 4; hs, ws > 0.
+ * takes [qn,H,W,3]): s_l [batch][h_l*w_l][rfn], stacked [batch][hs*ws][rfn][nch].  hc, wc multiples of 4; hs, ws > 0; 0 <= scale_idx and
+ * 3 * scale_idx + 3 <= nch; batch <= 65535; hs * ws <= 2^31 - 1 (the kernel's pixel index is an int) and ceil(hs * ws * rfn / 256) <= 2^31 - 1
+ * (one grid).
  * ---------------------------------------------------------------------------------------------------------------- */
 int g6d_detector_assemble(const float* s0, const float* s1, const float* s2, int hc, int wc, int rfn,
                           const float* mu_sigma /* HOST pointer: {mu0,sigma0,mu1,sigma1,mu2,sigma2} */, float clip, int hs, int ws,
                           int scale_idx, int nch, float* stacked, int batch, g6d_stream_t stream);
 
 /* score_conv + max over references (network/detector.py:159-163,246-247): per (pixel, ref) MLP nch->64 (ReLU) ->64,
- * then max over rfn.  w0 [64][nch], b0[64], w1[64][64], b1[64]; out [P][64]. */
+ * then max over rfn.  w0 [64][nch], b0[64], w1[64][64], b1[64]; out [P][64].  rfn <= 256, nch == 12, P <= 2^31 - 256. */
 int g6d_detector_score_mlp_max(const float* stacked, int P, int rfn, int nch, const float* w0, const float* b0,
                                const float* w1, const float* b1, float* out, g6d_stream_t stream);
 
 /* arg-max + decode (network/detector.py:84-121): scores [hs*ws], offset [hs*ws][2], scale [hs*ws] (channels-last);
  * result[0..1] = position (x,y) px, result[2] = 2^scale, result[3..4] = (x,y) cell of the peak (as float).
- * batch >= 1 queries: the maps of query b start b*hs*ws rows after those of query 0, result [batch][5]. */
+ * batch >= 1 queries: the maps of query b start b*hs*ws rows after those of query 0, result [batch][5].  Row strides in floats: ld_s >= 1,
+ * ld_o >= 2, ld_c >= 1 (three dense maps of their own: 1, 2, 1); hs * ws <= 2^31 - 1. */
 int g6d_detector_decode(const float* scores, int ld_s, const float* offset, int ld_o, const float* scale, int ld_c,
                         int hs, int ws, int pool_ratio, float* result, int batch, g6d_stream_t stream);
 /* (ABI v10) The detector's image pyramid in one launch: F.interpolate(que_imgs, size=(h_k, w_k), mode='bilinear') (align_corners False;
@@ -524,9 +546,11 @@ int g6d_zero_bytes(void* ptr, size_t bytes, g6d_stream_t stream);
  * Selector tail helpers (network/selector.py:201-214, network/attention.py:4-17,50-68).
  * ---------------------------------------------------------------------------------------------------------------- */
 /* The tail helpers take `batch` >= 1 queries (selector.py:165-175 takes [qn,...]): row blocks of the queries follow each other.
- * InstanceNorm2d(3) of vps [batch][3][D] over D, written to channels c_off..c_off+2 of feats [batch*D][ld] (selector.py:201-202) */
+ * InstanceNorm2d(3) of vps [batch][3][D] over D, written to channels c_off..c_off+2 of feats [batch*D][ld] (selector.py:201-202);
+ * c_off >= 0, c_off + 3 <= ld, batch <= 65535 */
 int g6d_vps_norm(const float* vps, int D, float* feats, int ld, int c_off, int batch, g6d_stream_t stream);
-/* x[b*rfn+r][c] = max_a in[(b*rfn+r)*an+a][c] + embed[r][c]   (selector.py:204-205) */
+/* x[b*rfn+r][c] = max_a in[(b*rfn+r)*an+a][c] + embed[r][c]   (selector.py:204-205); ld_in >= C, ld_out >= C, batch <= 65535,
+ * rfn * C <= 2^31 - 256, rfn * an <= 2^31 - 1 */
 int g6d_max_an_add(const float* in, int ld_in, int rfn, int an, int C, const float* embed, float* out, int ld_out, int batch,
                    g6d_stream_t stream);
 /* multi-head attention over n tokens with the reference's head split c -> (d=c/heads, head=c%heads), scale
@@ -534,11 +558,12 @@ int g6d_max_an_add(const float* in, int ld_in, int rfn, int an, int C, const flo
  * query (attention.py:4-17,60-64) */
 int g6d_attention(const float* q, const float* k, const float* v, int ld, int n, int C, int heads, float* out,
                   int ld_out, int batch, g6d_stream_t stream);
-/* LayerNorm over C per token with affine (attention.py:19-26): out may alias in */
+/* LayerNorm over C per token with affine (attention.py:19-26): out may alias in; ld_in >= C, ld_out >= C */
 int g6d_layernorm(const float* in, int ld_in, int n, int C, const float* gamma, const float* beta, float eps,
                   float* out, int ld_out, g6d_stream_t stream);
 /* out = relu?(x*scale+shift) (+ residual) elementwise on [n][C] rows (selector.py:209); rows_per_group = k > 0: row r uses
- * table r / k of scale / shift [n/k][C] (one InstanceNorm1d per query of a batch), 0: one table */
+ * table r / k of scale / shift [n/k][C] (one InstanceNorm1d per query of a batch), 0: one table.  scale and shift both or neither;
+ * ld_in >= C, ld_out >= C, ld_res >= C when residual is given (not read otherwise); n * C <= 2^31 - 256 */
 int g6d_affine_act_add(const float* in, int ld_in, const float* scale, const float* shift, int relu,
                        const float* residual, int ld_res, int n, int C, float* out, int ld_out, int rows_per_group,
                        g6d_stream_t stream);
@@ -550,6 +575,7 @@ int g6d_affine_act_add(const float* in, int ld_in, const float* scale, const flo
  * src uint8 [sh][sw][ch] (device); hinv: HOST pointer, row-major 3x3 destination->source pixel map (inverse of the
  * cv2 `M`/`H`); dst [dh][dw][ch] uint8 (out_float=0, round-to-nearest) or float32 * out_scale (out_float=1).
  * Bilinear, zero outside the source.  Exact float weights: cv2 quantises them to 1/32 px (<= 1-2 grey levels apart).
+ * 1 <= ch <= 4; dh * dw <= 2^31 - 256 (g6d_warp_batch too).
  * ---------------------------------------------------------------------------------------------------------------- */
 int g6d_warp_perspective(const unsigned char* src, int sh, int sw, int ch, const float* hinv, void* dst, int dh, int dw,
                          int out_float, float out_scale, g6d_stream_t stream);
@@ -595,7 +621,8 @@ int g6d_warp_batch(const unsigned char* stack, const unsigned char* single, cons
                    const float* hinv, float* dst, int dh, int dw, g6d_stream_t stream);
 
 /* Small-batch linear layer, weight-streaming GEMV (network/refiner.py:153-166): out[b][o] = act(W[o].x[b] + bias[o]);
- * W [O][K] row-major, x [B][K], B <= 8; act as G6dConv.out_act. */
+ * W [O][K] row-major, x [B][K], B <= 8; act as G6dConv.out_act (0, 1 or 2).  K % 4 == 0; x and W 16-byte aligned (g6d_linear_gemv_batch
+ * too). */
 int g6d_linear_gemv(const float* x, int B, int K, const float* W, const float* bias, int O, int act, float* out,
                     g6d_stream_t stream);
 
