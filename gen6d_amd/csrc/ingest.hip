@@ -13,7 +13,8 @@
 // source coordinates from it (nodes in LDS, 64-bit integer interpolation), blocks of a frame without one run the plain tile.
 // Frames of the formats after NV12 and of the full-range matrices take a block-uniform branch to the same tiles on
 // frame_src.h's `Yuv` taps, in both kernels: a tick that mixes all eleven formats, with and without lenses, is one launch.
-// g6d_frame_ingest_area (last part of the file) is the launch with an exact-integer area filter where a picture shrinks (§4.26).
+// g6d_frame_ingest_area (last part of the file) is the launch with an exact-integer area filter where a picture shrinks (§4.26); its lens
+// frames that ask for it are supersampled through their mesh by a second kernel behind it (§4.28).
 #include "frame_src.h"
 
 namespace {
@@ -442,6 +443,158 @@ __device__ __forceinline__ void area_tile(const G6dFrame& f, const S& s, uint2* 
   }
 }
 
+// ---- lens frames of g6d_frame_ingest_area: n x n sub-samples per canvas pixel through the mesh (header) ----
+// The mesh tile's launch shape (thread = 4 consecutive pixels of a canvas row, store4) with a loop over the pixel's sub-samples around
+// its body.  A pixel's sub-samples lie within half a canvas pixel of its centre, so those of a pixel on a cell's first column / row fall
+// into the cell before it: the tile's node array has one more column at the left and one more row at the top than mesh_tile's.
+// 60 VGPRs, no scratch, 3168 bytes of LDS; 0.50 ms for 32 1080p NV12 frames at n = 2 and 4.3 ms for 32 2160p frames at n = 4
+// (profiles/r33_lens_area.md): 4 n^2 taps per pixel, each converted where it is read.
+
+constexpr int MESHA_NX = TW / 2 + 2, MESHA_NY = TH / 2 + 2;   // a tile's nodes at the finest step, 2
+
+// (TWINS of the two `gather` above: the same taps and weights, the sum neither rounded nor shifted.  A change of the blend goes into both;
+// tests/test_ingest_lens_area_gpu.py holds them together: samples_log2 = 0 through mesh_tile against the restatement of this rule)
+__device__ __forceinline__ void gather_sum(const Src& s, int x0, int x1, int y0, int y1, unsigned wa, unsigned wb, unsigned& ar, unsigned& ag,
+                                           unsigned& ab) {
+  const unsigned w00 = (2048 - wa) * (2048 - wb), w01 = wa * (2048 - wb), w10 = (2048 - wa) * wb, w11 = wa * wb;
+  int r1, g1, b1;
+  ar = ag = ab = 0;
+#define G6D_ACC(w) { ar += (w) * r1; ag += (w) * g1; ab += (w) * b1; }
+  if (s.nv12) {                                           // (block-uniform) a UV sample is loaded once for the taps that share it
+    const bool sx = (x1 >> 1) == (x0 >> 1), sy = (y1 >> 1) == (y0 >> 1);
+    const Chroma k00 = chroma(s, x0 >> 1, y0 >> 1);
+    tap_nv12(s, k00, x0, y0, r1, g1, b1); G6D_ACC(w00)
+    Chroma k01 = k00;
+    if (wa) { if (!sx) k01 = chroma(s, x1 >> 1, y0 >> 1); tap_nv12(s, k01, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+    if (wb) {
+      const Chroma k10 = sy ? k00 : chroma(s, x0 >> 1, y1 >> 1);
+      tap_nv12(s, k10, x0, y1, r1, g1, b1); G6D_ACC(w10)
+      if (wa) {
+        const Chroma k11 = sx ? k10 : (sy ? k01 : chroma(s, x1 >> 1, y1 >> 1));
+        tap_nv12(s, k11, x1, y1, r1, g1, b1); G6D_ACC(w11)
+      }
+    }
+  } else {
+    tap_packed(s, x0, y0, r1, g1, b1); G6D_ACC(w00)
+    if (wa) { tap_packed(s, x1, y0, r1, g1, b1); G6D_ACC(w01) }
+    if (wb) { tap_packed(s, x0, y1, r1, g1, b1); G6D_ACC(w10) }
+    if (wa && wb) { tap_packed(s, x1, y1, r1, g1, b1); G6D_ACC(w11) }
+  }
+#undef G6D_ACC
+}
+// the extended formats: frame_src.h's yuv_taps (a chroma sample loaded once for the taps that share it, a tap of weight 0 not loaded) with
+// every tap summed as it arrives.  What is kept of a chroma sample is (d, e), not its three products (yuv_chroma's Kc, 64-bit for P010):
+// the products are formed again at each tap, which costs multiplies and saves the registers that decide how many waves the plain tiles
+// of this launch run with
+struct De { int d, e; };
+template <typename T> __device__ __forceinline__ De yuv_de(const Yuv& s, int cx, int cy) {
+  constexpr int mid = sizeof(T) == 8 ? 512 : 128;
+  const size_t o = (size_t)cy * s.cpitch + (size_t)cx * s.cstep;
+  return De{sample<T>(s.pu + o) - mid, sample<T>(s.pv + o) - mid};
+}
+template <typename T> __device__ __forceinline__ void yuv_tap_de(const Yuv& s, De q, int x, int y, int& r, int& g, int& b) {   // yuv_chroma's terms
+  constexpr T rnd = sizeof(T) == 8 ? (T)1 << 21 : (T)1 << 19;
+  const T d = q.d, e = q.e;
+  yuv_tap<T>(s, Kc<T>{s.cvr * e + rnd, -s.cug * d - s.cvg * e + rnd, s.cub * d + rnd}, x, y, r, g, b);
+}
+template <typename T>
+__device__ __forceinline__ void yuv_gather_sum(const Yuv& s, int x0, int x1, int y0, int y1, unsigned wa, unsigned wb, unsigned& ar,
+                                               unsigned& ag, unsigned& ab) {
+  int r1, g1, b1;
+  ar = ag = ab = 0;
+#define G6D_ACC(w) { const unsigned w_ = (w); ar += w_ * r1; ag += w_ * g1; ab += w_ * b1; }
+  const bool sx = (x1 >> 1) == (x0 >> 1), sy = (y1 >> s.csy) == (y0 >> s.csy);
+  De k0 = yuv_de<T>(s, x0 >> 1, y0 >> s.csy), k1 = k0;    // the chroma of the row's x0 tap and of its x1 tap
+  yuv_tap_de<T>(s, k0, x0, y0, r1, g1, b1); G6D_ACC((2048 - wa) * (2048 - wb))
+  if (wa) { if (!sx) k1 = yuv_de<T>(s, x1 >> 1, y0 >> s.csy); yuv_tap_de<T>(s, k1, x1, y0, r1, g1, b1); G6D_ACC(wa * (2048 - wb)) }
+  if (wb) {
+    if (!sy) k0 = yuv_de<T>(s, x0 >> 1, y1 >> s.csy);
+    yuv_tap_de<T>(s, k0, x0, y1, r1, g1, b1); G6D_ACC((2048 - wa) * wb)
+    if (wa) {
+      if (sx) k1 = k0;
+      else if (!sy) k1 = yuv_de<T>(s, x1 >> 1, y1 >> s.csy);
+      yuv_tap_de<T>(s, k1, x1, y1, r1, g1, b1); G6D_ACC(wa * wb)
+    }
+  }
+#undef G6D_ACC
+}
+__device__ __forceinline__ void gather_sum(const Yuv& s, int x0, int x1, int y0, int y1, unsigned wa, unsigned wb, unsigned& ar, unsigned& ag,
+                                           unsigned& ab) {
+  if (s.kind == 0) yuv_gather_sum<int>(s, x0, x1, y0, y1, wa, wb, ar, ag, ab);                   // (block-uniform)
+  else if (s.kind == 1) yuv_gather_sum<long long>(s, x0, x1, y0, y1, wa, wb, ar, ag, ab);
+  else {
+    const unsigned v = (2048 - wa) * (2048 - wb) * gray_tap(s, x0, y0).r + (wa ? wa * (2048 - wb) * gray_tap(s, x1, y0).r : 0u) +
+                       (wb ? (2048 - wa) * wb * gray_tap(s, x0, y1).r : 0u) + (wa && wb ? wa * wb * gray_tap(s, x1, y1).r : 0u);
+    ar = ag = ab = v;
+  }
+}
+
+// one tile of a lens frame with 2^L x 2^L sub-samples per pixel, L = 1..3.  nd: MESHA_NX * MESHA_NY nodes of LDS.  Positions are in units
+// of 1 / (2n) canvas pixel (U, V of the header), a cell is G = 2 n g of them wide.  The header's upper clamp of the cell index (nx - 2) is
+// not computed: inside the picture nx >= ceil(out_w / g) + 1 keeps the index below it, and the LDS index depends on the position alone.
+template <bool EXT>
+__device__ __forceinline__ void mesh_area_tile(const G6dFrame& f, const G6dMesh& m, int L, int2* nd, unsigned char* __restrict__ out, int slot,
+                                               int H, int W, int X0, int Y0) {
+  const int t = threadIdx.x;
+  const int lg = min(max(m.step_log2, 1), 4), n = 1 << L, lG = 1 + L + lg, G = 1 << lG, sh = 2 * lG + 5;
+  const int tnx = (TW >> lg) + 2, tny = max(TH >> lg, 1) + 2;   // mesh_tile's nodes and the column / row before them
+  const int c0 = (X0 >> lg) - 1, r0 = (Y0 >> lg) - 1;           // -1 at the picture's edge: loaded as a copy of 0 and not used (cells clamp at 0)
+  for (int k = t; k < tnx * tny; k += 256) {              // columns / rows past the mesh's edge are read only by pixels outside the picture
+    const int r = k / tnx, c = k - r * tnx;
+    const int* p = m.nodes + 2 * ((size_t)max(min(r0 + r, m.ny - 1), 0) * m.nx + max(min(c0 + c, m.nx - 1), 0));
+    nd[k] = make_int2(p[0], p[1]);
+  }
+  __syncthreads();
+  const int ry = t >> 5, X = X0 + ((t & 31) << 2), Y = Y0 + ry;
+  if (Y >= H || X >= W) return;
+  const int ws = f.width, hs = f.height;
+  const int ow = min(f.out_w, W), oh = min(f.out_h, H);
+  const auto s = tap_source<EXT>(f);
+  const long long half = 1ll << (sh - 1);
+  const int xhi = (ws - 1) * 2048, yhi = (hs - 1) * 2048;
+  const int fs = 22 + 2 * L;
+  // One pixel at a time, its sums in 6 registers (sums for 4 pixels at once cost 24 and the kernel half the waves the plain tiles of this
+  // launch run with); the loop is not unrolled, so its 3 bytes go into the thread's 12 by shifts, not by an index
+  unsigned o0 = 0, o1 = 0, o2 = 0;
+#pragma unroll 1
+  for (int kk = 0; kk < 4; ++kk) {
+    const int P = X + kk;
+    if (P >= ow || Y >= oh) break;                        // the rest of the 4 lies outside the picture: 0
+    unsigned long long sr = 0, sg = 0, sb = 0;            // sums of A: below 2^37
+#pragma unroll 1
+    for (int q = 0; q < n * n; ++q) {                     // sub-sample (k, l) = (q mod n, q / n): one loop, one counter
+      // r: the pixel's cell row or, on that cell's first row and for l < n / 2, the one above; j < 0 at the top edge.  Columns likewise
+      const int V = 2 * n * Y + 2 * (q >> L) + 1 - n, r = max(V >> lG, 0), j = V - (r << lG);
+      const int U = 2 * n * P + 2 * (q & (n - 1)) + 1 - n, c = max(U >> lG, 0), i = U - (c << lG);
+      // the four nodes of the cell straight from LDS: each term of S is one 32 x 32 -> 64-bit multiply-add (|weight| < 2^18), where node
+      // columns blended once per sub-row are 64-bit factors, and 12 registers that stay live across the taps
+      const int2* row = nd + (r - r0) * tnx - c0;
+      const int2 m00 = row[c], m01 = row[c + 1], m10 = row[c + tnx], m11 = row[c + tnx + 1];
+      const int w00 = (G - i) * (G - j), w01 = i * (G - j), w10 = (G - i) * j, w11 = i * j;
+      int fx = (int)(((long long)w00 * m00.x + (long long)w01 * m01.x + (long long)w10 * m10.x + (long long)w11 * m11.x + half) >> sh);
+      int fy = (int)(((long long)w00 * m00.y + (long long)w01 * m01.y + (long long)w10 * m10.y + (long long)w11 * m11.y + half) >> sh);
+      if (fx >= -1024 && fx <= xhi + 1024 && fy >= -1024 && fy <= yhi + 1024) {   // else: the constant border, A = 0
+        fx = min(max(fx, 0), xhi); fy = min(max(fy, 0), yhi);
+        const int x0 = fx >> 11, y0 = fy >> 11;
+        unsigned ar, ag, ab;
+        gather_sum(s, x0, min(x0 + 1, ws - 1), y0, min(y0 + 1, hs - 1), fx & 2047, fy & 2047, ar, ag, ab);
+        sr += ar; sg += ag; sb += ab;
+      }
+    }
+    const unsigned long long rnd = 1ull << (fs - 1);
+    const unsigned v = (unsigned)((sr + rnd) >> fs) | ((unsigned)((sg + rnd) >> fs) << 8) | ((unsigned)((sb + rnd) >> fs) << 16);
+    o0 |= kk == 0 ? v : (kk == 1 ? v << 24 : 0u);
+    o1 |= kk == 1 ? v >> 8 : (kk == 2 ? v << 16 : 0u);
+    o2 |= kk == 2 ? v >> 16 : (kk == 3 ? v << 8 : 0u);
+  }
+  unsigned char px[12];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    px[e] = (unsigned char)(o0 >> (8 * e)); px[4 + e] = (unsigned char)(o1 >> (8 * e)); px[8 + e] = (unsigned char)(o2 >> (8 * e));
+  }
+  store4(out, px, slot, H, W, X, Y);
+}
+
 __global__ void __launch_bounds__(256) frame_ingest_area_kernel(const G6dFrame* __restrict__ frames, const G6dMesh* __restrict__ meshes,
                                                                 unsigned char* __restrict__ out, int B, int H, int W,
                                                                 float* __restrict__ K_out, int tiles_x, int tiles) {
@@ -454,7 +607,8 @@ __global__ void __launch_bounds__(256) frame_ingest_area_kernel(const G6dFrame* 
   if (slot < 0 || slot >= B) return;                      // (block-uniform, as every branch below)
   if (tile == 0 && threadIdx.x < 9) K_out[(size_t)9 * slot + threadIdx.x] = f.K[threadIdx.x];
   const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
-  if (meshes && meshes[fi].nodes) {                       // the lens fallback: a footprint that varies over a mesh is out of scope
+  if (meshes && meshes[fi].nodes) {                       // a lens frame: samples_log2 = 0 is the mesh rule itself (header, consequence 1);
+    if (meshes[fi].samples_log2 > 0) return;              // more samples: frame_ingest_lens_area_kernel's frame
     if (extended(f)) mesh_tile<true>(f, meshes[fi], nd, out, slot, H, W, X0, Y0);
     else mesh_tile<false>(f, meshes[fi], nd, out, slot, H, W, X0, Y0);
     return;
@@ -469,6 +623,24 @@ __global__ void __launch_bounds__(256) frame_ingest_area_kernel(const G6dFrame* 
     if (s.nv12) area_tile<1>(f, s, aw, stage, out, slot, H, W, X0, Y0);
     else area_tile<0>(f, s, aw, stage, out, slot, H, W, X0, Y0);
   }
+}
+
+// The lens frames of a g6d_frame_ingest_area call that ask for more than one sample, in a launch of their own behind
+// frame_ingest_area_kernel's (same grid; every other block leaves at once).  As a branch of that kernel the tile made its plain tiles 16 to
+// 23 % slower at unchanged register and LDS figures (profiles/r33_lens_area.md), so that kernel keeps the code it was measured with.
+__global__ void __launch_bounds__(256) frame_ingest_lens_area_kernel(const G6dFrame* __restrict__ frames, const G6dMesh* __restrict__ meshes,
+                                                                     unsigned char* __restrict__ out, int B, int H, int W, int tiles_x,
+                                                                     int tiles) {
+  __shared__ int2 nd[MESHA_NX * MESHA_NY];
+  const int fi = blockIdx.x / tiles, tile = blockIdx.x - fi * tiles;
+  const G6dMesh& m = meshes[fi];
+  if (!m.nodes || m.samples_log2 <= 0) return;            // (block-uniform, as every branch below) frame_ingest_area_kernel's frame
+  const G6dFrame& f = frames[fi];
+  const int slot = f.slot;
+  if (slot < 0 || slot >= B) return;                      // (K_out[slot] is written by frame_ingest_area_kernel, for every frame)
+  const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH, L = min(m.samples_log2, 3);
+  if (extended(f)) mesh_area_tile<true>(f, m, L, nd, out, slot, H, W, X0, Y0);
+  else mesh_area_tile<false>(f, m, L, nd, out, slot, H, W, X0, Y0);
 }
 
 }  // namespace
@@ -515,5 +687,10 @@ extern "C" int g6d_frame_ingest_area(const G6dFrame* frames, const G6dMesh* mesh
   const int tiles_x = (W + TW - 1) / TW, tiles = (int)tiles_ll;
   hipLaunchKernelGGL(frame_ingest_area_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
                      meshes, out, B, H, W, K_out, tiles_x, tiles);
+  const int rc = g6d_check_launch("frame_ingest_area");
+  if (rc != G6D_OK || !meshes) return rc;
+  // the lens frames with samples_log2 > 0 (which frames those are is known on the device only: the mesh table lives there)
+  hipLaunchKernelGGL(frame_ingest_lens_area_kernel, dim3((unsigned)(tiles * n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), frames,
+                     meshes, out, B, H, W, tiles_x, tiles);
   return g6d_check_launch("frame_ingest_area");
 }

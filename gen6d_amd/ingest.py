@@ -93,15 +93,21 @@ class Lens:
         xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2), yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y;
       "fisheye", coeffs k1 k2 k3 k4: t = atan(r), td = t (1 + k1 t^2 + k2 t^4 + k3 t^6 + k4 t^8), (xd, yd) = (td / r) (x, y) (factor 1 at r = 0).
     The ingested picture is the scaled virtual pinhole picture of the source's size with intrinsics new_K (default: the frame's K, as
-    cv2.undistort); pixels that look past the source's edge are black.  tol: the mesh's largest distance to the model in canvas pixels."""
+    cv2.undistort); pixels that look past the source's edge are black.  tol: the mesh's largest distance to the model in canvas pixels.
+    minify: "point" samples the source once per canvas pixel in every call; "area" makes a call that is itself minify="area"
+    (ingest_frames_keep, StreamTracker, track_streams) average n x n sub-samples per canvas pixel through the mesh, n = 1 / 2 / 4 / 8 chosen
+    per mesh by `samples_log2` (include/gen6d_hip.h), and changes nothing in a point call."""
     model: str
     coeffs: tuple
     new_K: tuple = None
     tol: float = 1 / 16
+    minify: str = "point"
 
     def __post_init__(self):
         if self.model not in LENS_MODELS:
             raise ValueError(f"Lens: unknown model {self.model!r} (one of {sorted(LENS_MODELS)})")
+        if self.minify not in ("point", "area"):
+            raise ValueError(f"Lens: minify must be \"point\" or \"area\", not {self.minify!r}")
         c = tuple(float(v) for v in np.asarray(self.coeffs, np.float64).reshape(-1))
         if len(c) not in LENS_MODELS[self.model]:
             raise ValueError(f"Lens: a {self.model} lens takes {' / '.join(map(str, LENS_MODELS[self.model]))} coefficients, not {len(c)}")
@@ -166,6 +172,21 @@ class Lens:
                 return np.ascontiguousarray(fixed.astype(np.int32)), g.bit_length() - 1
         raise ValueError(f"{self!r}: a mesh of step 2 misses the model by {miss:.3g} source pixels at a {ws} x {hs} source in a {out_w} x "
                          f"{out_h} picture, more than tol allows ({bound:.3g})")
+
+    @staticmethod
+    def samples_log2(nodes, step_log2, ws, hs):
+        """-> L: a minify="area" lens averages 2^L x 2^L sub-samples per canvas pixel of this mesh (int32 nodes [ny, nx, 2], `mesh`).
+        Over the horizontally and vertically adjacent node pairs whose two nodes lie inside [-0.5, ws - 0.5] x [-0.5, hs - 0.5], M is the
+        largest max(|dx|, |dy|) / (65536 g): the source pixels one canvas pixel spans.  n = 1 for M < 1.5, 2 for M < 3, 4 for M < 6, else
+        8; 1 when there is no such pair.  Exact integers."""
+        m = np.asarray(nodes).astype(np.int64)
+        inside = (m[..., 0] >= -32768) & (m[..., 0] <= ws * 65536 - 32768) & (m[..., 1] >= -32768) & (m[..., 1] <= hs * 65536 - 32768)
+        span = 0
+        for a, b, ok in ((m[:, :-1], m[:, 1:], inside[:, :-1] & inside[:, 1:]), (m[:-1], m[1:], inside[:-1] & inside[1:])):
+            if ok.any():
+                span = max(span, int(np.abs(b - a).max(-1)[ok].max()))
+        unit = 65536 << step_log2                                    # M = span / unit
+        return sum(2 * span >= k * unit for k in (3, 6, 12))
 
 
 class Frame:
@@ -394,11 +415,12 @@ _meshes = collections.OrderedDict()     # (device, lens, K, ws, hs, rotate, out_
 
 
 class _Mesh:
-    """A lens mesh on its way to / in device memory: host (int32 [ny, nx, 2], until uploaded), nodes (the device tensor), step_log2, and
-    the stream and event of the upload (a launch on another stream waits for the event on the device)."""
+    """A lens mesh on its way to / in device memory: host (int32 [ny, nx, 2], until uploaded), nodes (the device tensor), step_log2,
+    samples_log2 (what an area call writes into the mesh record: 0 for a lens with minify="point") and the stream and event of the
+    upload (a launch on another stream waits for the event on the device)."""
 
-    def __init__(self, host, step_log2):
-        self.host, self.step_log2, self.nodes, self.stream, self.event = host, step_log2, None, None, None
+    def __init__(self, host, step_log2, samples_log2=0):
+        self.host, self.step_log2, self.samples_log2, self.nodes, self.stream, self.event = host, step_log2, samples_log2, None, None, None
 
 
 def _mesh_key(frame, out_h, out_w, dev):
@@ -424,7 +446,8 @@ def ingest_frames_keep(frames, out, K_out, slots=None, stream=None, minify="poin
     (emit.emit_source_frames).  The launch is the same.
     minify: "point" is the bilinear rule, which reads two source pixels per axis however far the picture shrinks; "area" makes it one
     launch of g6d_frame_ingest_area, with or without lenses: every axis that shrinks is box-filtered with exact integer weights, a frame
-    that does not shrink gets the same bytes as under "point", and a frame with a lens keeps the mesh rule (the lens fallback).
+    that does not shrink gets the same bytes as under "point", a frame whose `Lens` has minify="area" is supersampled through its mesh
+    (n x n sub-samples per canvas pixel, `Lens.samples_log2`), and a frame whose lens keeps the default keeps the mesh rule's bytes.
     (`ingest_frames` keeps its parameters as they are, the default tracker's recorded launch schedule lists them: a caller that wants
     the filtered ingest and not the table takes `ingest_frames_keep(..., minify="area")[0]`; keeping the table costs nothing.)"""
     return _ingest(frames, out, K_out, slots, stream, True, minify)
@@ -469,7 +492,8 @@ def _ingest(frames, out, K_out, slots, stream, keep, minify="point"):
             key = _mesh_key(f, out_h, out_w, dev)
             m = _meshes.get(key) or fresh.get(key)
             if m is None:
-                m = fresh[key] = _Mesh(*f.lens.mesh(f.K, f.width, f.height, f.rotate, out_w, out_h))
+                nodes, lg = f.lens.mesh(f.K, f.width, f.height, f.rotate, out_w, out_h)
+                m = fresh[key] = _Mesh(nodes, lg, Lens.samples_log2(nodes, lg, f.width, f.height) if f.lens.minify == "area" else 0)
             elif key in _meshes:
                 _meshes.move_to_end(key)                             # most recently used
             meshes[i] = m
@@ -507,6 +531,7 @@ def _ingest(frames, out, K_out, slots, stream, keep, minify="point"):
             m.nodes = torch.empty(m.host.shape, dtype=torch.int32, device=dev)
         for i, m in meshes.items():
             mtable[i].nodes, mtable[i].ny, mtable[i].nx, mtable[i].step_log2 = m.nodes.data_ptr(), m.nodes.shape[0], m.nodes.shape[1], m.step_log2
+            mtable[i].samples_log2 = m.samples_log2 if minify == "area" else 0
         hn[toff:moff] = np.frombuffer(table, np.uint8, n * size)
         if meshes:
             hn[moff:] = np.frombuffer(mtable, np.uint8, total - moff)

@@ -45,6 +45,11 @@ class G6dMesh(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("step_log2", C.c_int32), ("reserved", C.c_int32)]
 
 
+# The header names the former reserved field samples_log2 (read by g6d_frame_ingest_area alone).  As for G6dConv.w_exp below, the binding
+# keeps the field's earlier name in _fields_ and exposes the header's as a property.
+G6dMesh.samples_log2 = property(lambda self: self.reserved, lambda self, v: setattr(self, "reserved", int(v)))
+
+
 class G6dSink(C.Structure):
     """include/gen6d_hip.h: one destination of g6d_frame_emit (the table lives in device memory)."""
     _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("pitch0", C.c_int32), ("pitch1", C.c_int32), ("width", C.c_int32),

@@ -33,7 +33,7 @@ many streams (cameras or clients watching one object) at once:
     default `crops="canvas"` launches what it always launched;
   * with `minify="area"` (needs `frame_size`) what shrinks is filtered instead of point-sampled: the tick's and the
     first frames' ingest is g6d_frame_ingest_area (an exact-integer box filter on every axis that shrinks; frames with a lens keep the
-    mesh rule), and with `crops="source"` the crops are g6d_frame_crop_area (n x n samples per crop pixel, n per slot from the crop's
+    mesh rule unless the lens is Lens(minify="area"): n x n sub-samples per canvas pixel through the mesh), and with `crops="source"` the crops are g6d_frame_crop_area (n x n samples per crop pixel, n per slot from the crop's
     own footprint, at most 8), in the same places of the same graph; with `crops="canvas"` the crops stay g6d_warp_batch.  The default
     `minify="point"` launches what it always launched;
   * with `health=HealthPolicy(...)` every stream carries a status (TRACKING / SUSPECT / LOST) that the device keeps: a gate parks lost

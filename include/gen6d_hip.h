@@ -766,7 +766,7 @@ typedef struct G6dMesh {           /* one per frame */
   const int32_t* nodes;            /* [ny][nx][2] (x, y), device memory; NULL: the plain rule */
   int32_t nx, ny;                  /* nodes per row, rows */
   int32_t step_log2;               /* 1..4 */
-  int32_t reserved;
+  int32_t samples_log2;            /* the former `reserved` (0 everywhere before): read by g6d_frame_ingest_area alone, 0..3 (clamped), below */
 } G6dMesh;
 int g6d_frame_ingest_mesh(const G6dFrame* frames, const G6dMesh* meshes, int n, uint8_t* out, int B, int H, int W, float* K_out,
                           g6d_stream_t stream);
@@ -774,9 +774,11 @@ int g6d_sizeof_mesh_desc(void);
 
 /* Area-filtered ingest (gen6d_amd/ingest.py minify="area"); additive within ABI 12, no struct changes.
  * g6d_frame_ingest_area is g6d_frame_ingest_mesh (the table, the slot rules, K_out, the black canvas outside the picture) with `meshes`
- * optional (NULL: no frame has a lens) and a filter where a picture shrinks.  The lens fallback: a frame whose mesh has nodes takes the mesh
- * rule above unchanged, bit for bit (a footprint that varies over a mesh is out of scope); lens and plain frames still mix in one launch.
- * Every other frame takes this rule per axis of the scaled picture before rotation (target extent T = wt or ht, source extent S = ws or
+ * optional (NULL: no frame has a lens) and a filter where a picture shrinks.  A frame whose mesh has nodes is supersampled through the
+ * mesh by the rule at the end of this comment; with samples_log2 = 0 (every caller before the field had a name) that is the mesh rule
+ * above, bit for bit.  Lens and plain frames still mix in one call (with a mesh table the call is two kernels on `stream`: the second
+ * takes the frames with samples_log2 > 0, and which those are is known on the device only).
+ * Every frame without a mesh takes this rule per axis of the scaled picture before rotation (target extent T = wt or ht, source extent S = ws or
  * hs; the quarter turn maps canvas (X, Y) to the unrotated (tx, ty) as above), exact integers, restated bit-identically in
  * tests/test_minify_cpu.py:
  *   S <= T (the axis does not shrink): the plain rule's two taps (i0, 2048 - a) and (i1, a), D_axis = 2048;
@@ -788,7 +790,26 @@ int g6d_sizeof_mesh_desc(void);
  * Two consequences.  1: with no shrinking axis D = 2^22 and v = (Sigma + 2^21) >> 22: a frame that does not shrink gives
  * g6d_frame_ingest's bytes exactly.  2: with S = k T on both axes every canvas pixel is the round-half-up mean of its k x k block of
  * converted source pixels; the box's centre is the bilinear rule's centre ((t + 0.5) S / T - 0.5), so the picture's K does not change.
- * Magnitudes: Sigma <= 255 * 2^26; a row's inner sum sum_x wx p <= 255 * 2^13 fits 32 bits; the sum over rows and 2 Sigma + D need 64. */
+ * Magnitudes: Sigma <= 255 * 2^26; a row's inner sum sum_x wx p <= 255 * 2^13 fits 32 bits; the sum over rows and 2 Sigma + D need 64.
+ * A frame whose mesh has nodes (gen6d_amd/ingest.py Lens(minify="area"); restated bit-identically in
+ * tests/test_ingest_lens_area_cpu.py): L = clamp(samples_log2, 0, 3), n = 2^L, g = 2^step_log2, G = 2 n g, s = 2 (1 + L + step_log2) + 5.
+ * Canvas pixel (X, Y) of the picture is the mean of n x n sub-samples (k, l), k, l = 0 .. n-1, placed at canvas position
+ * (X + (2k+1-n) / (2n), Y + (2l+1-n) / (2n)), centred on the pixel; exact integers:
+ *   U = 2nX + 2k + 1 - n, V = 2nY + 2l + 1 - n (the position in units of 1/(2n) canvas pixel);
+ *   c = clamp(floor(U / G), 0, nx - 2), i = U - c G; r = clamp(floor(V / G), 0, ny - 2), j = V - r G.  i and j are negative only at the
+ *     picture's left / top edge, where the first cell is extrapolated over less than half a canvas pixel; nx >= ceil(out_w / g) + 1
+ *     keeps floor(U / G) <= nx - 2 inside the picture (ny likewise);
+ *   m00 m01 / m10 m11 the nodes (c, r), (c+1, r), (c, r+1), (c+1, r+1):
+ *   S = (G-i)(G-j) m00 + i (G-j) m01 + (G-i) j m10 + i j m11 (64-bit), f = (S + 2^(s-1)) >> s (arithmetic): fx, fy in 1/2048 source pixels;
+ *   the mesh rule's black test, clamp and four taps, unchanged; each tap converted by its format's tap rule (all eleven formats, the four
+ *     matrices, P010 in 64-bit); per channel A = sum of the four 11-bit weight products w p.  The weights sum to 2^22 and A is NOT rounded;
+ *     a black sample has A = 0;
+ *   v = (sum_{k,l} A + 2^(21 + 2L)) >> (22 + 2L).
+ * Magnitudes: A < 2^30, sum A < 2^37 (64-bit), |S| < 2^52.  Two consequences.  1: L = 0 gives U = 2X, G = 2g: S is four times the mesh
+ * rule's S and s two more, so the result is the mesh rule's, bit for bit.  2: a lens that maps every canvas position to itself (a brown
+ * lens with zero coefficients, new_K = K) over a source exactly k times the picture, k in {1, 2, 4, 8}, with n = k puts every sub-sample
+ * on one source pixel with fraction 0: the result is the round-half-up mean of the k x k block, the bytes the rule above writes for the
+ * same frame without a lens. */
 int g6d_frame_ingest_area(const G6dFrame* frames, const G6dMesh* meshes /* may be NULL */, int n, uint8_t* out, int B, int H, int W,
                           float* K_out, g6d_stream_t stream);
 

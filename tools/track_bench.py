@@ -7,7 +7,7 @@ clock starts (the upload of a user's numpy frames is not part of the tick).  Gra
 each; the table gives the median and the spread (max - min) / median.
 
   python tools/track_bench.py [--streams 1,8,32] [--frames 30] [--repeats 3] [--out profiles/r08_track_bench.md]
-  python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p[,nv12-1080p-lens]   (graphs only, the variants alternated)
+  python tools/track_bench.py --streams 32 --ingest none,same,nv12-1080p[,nv12-1080p-lens][,nv12-1080p-area,nv12-1080p-lens-area]   (graphs only, the variants alternated)
   python tools/track_bench.py --streams 32 --emit nv12 [--emit-host]            (graphs only: no sinks / device sinks / pinned host sinks
                                                                                  of the working-resolution picture, alternated)
   python tools/track_bench.py --streams 32 --ingest nv12-1080p --emit nv12 --emit-source [--emit-host]   (the same plus one SOURCE-view sink
@@ -55,12 +55,15 @@ def native_frames(frames, K, mode):
     nv12-1080p: host-resident 1080x1920 NV12 frames (numpy) into a 540x960 canvas: each synthetic
     frame enlarged 2.25x (nearest) into the left 1440 columns of a grey full-HD picture, BT.601; intrinsics: predict.py's pseudo K.
     nv12-1080p-lens: the same frames as pictures of a camera with f = 1000 and the lens brown (-0.35, 0.12, 0.001, -0.0005, -0.02),
-    undistorted by the ingest launch (one mesh for all streams, built and uploaded in the first tick)."""
+    undistorted by the ingest launch (one mesh for all streams, built and uploaded in the first tick).
+    nv12-1080p-area / nv12-1080p-lens-area: the nv12-1080p / nv12-1080p-lens frames for a tracker with minify="area" (`run` sets it), the
+    lens with minify="area": n x n sub-samples per canvas pixel through the mesh."""
     import torch
     from gen6d_amd.ingest import Frame, Lens
     cam = {}
-    if mode == "nv12-1080p-lens":
-        cam = dict(K=np.array([[1000.0, 0, 959.5], [0, 1000.0, 539.5], [0, 0, 1]]), lens=Lens("brown", (-0.35, 0.12, 0.001, -0.0005, -0.02)))
+    if mode in ("nv12-1080p-lens", "nv12-1080p-lens-area"):
+        cam = dict(K=np.array([[1000.0, 0, 959.5], [0, 1000.0, 539.5], [0, 0, 1]]),
+                   lens=Lens("brown", (-0.35, 0.12, 0.001, -0.0005, -0.02), minify="area" if mode.endswith("-area") else "point"))
     if mode == "same":
         return [Frame(f, K=K) for f in frames], tuple(frames[0].shape[:2])
     out = []
@@ -114,7 +117,7 @@ def run(est, frames, K, S, F, batch, graphs, ingest=None, emit=None, emit_host=F
         canvas = tuple(frames[0].shape[:2])
     else:
         frames, canvas = native_frames(frames, K, ingest)
-        tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas, **hk)
+        tr = StreamTracker(est, S, batch=batch, graphs=graphs, frame_size=canvas, minify="area" if ingest.endswith("-area") else "point", **hk)
         Ks = None
     frame = lambda s, t: frames[(7 * s + t) % len(frames)]
     if emit and emit_view == "source":
@@ -186,7 +189,7 @@ def main():
     ap.add_argument("--profile", type=int, default=0, help="one graphs run of this many streams (for a rocprofv3 trace)")
     ap.add_argument("--stats-csv", default=None)
     ap.add_argument("--ticks", type=int, default=0)
-    ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p / nv12-1080p-lens: graphs runs of these frame "
+    ap.add_argument("--ingest", default=None, help="comma list of none / same / nv12-1080p / nv12-1080p-lens / nv12-1080p-area / nv12-1080p-lens-area: graphs runs of these frame "
                     "sources, alternated (with --profile: the one source of the profiled run)")
     ap.add_argument("--batch", type=int, default=0, help="--profile: slots per lane (default min(streams, 8))")
     ap.add_argument("--emit", default=None, choices=["nv12", "rgb24"], help="graphs runs without sinks and with one device sink of this "
