@@ -37,6 +37,10 @@ int g6d_wino43_launch(const G6dConv& d, hipStream_t stream);
 // conv_patch.hip: 3x3 / 3x3x3 stride-1 layers with Cout <= 64: spatial output tile, input patch reused by all taps
 bool g6d_conv_patch_eligible(const G6dConv& d);
 int g6d_conv_patch_launch(const G6dConv& d, int M, hipStream_t stream);
+// what the three launchers above choose on the host for `d` (no launch): their kernel's prologue mode and the split count
+void g6d_wino_route(const G6dConv& d, int* mode, int* splits);
+void g6d_wino43_route(const G6dConv& d, int* mode, int* splits);
+void g6d_conv_patch_route(const G6dConv& d, int* mode, int* splits);
 
 namespace {
 
@@ -588,11 +592,26 @@ bool igemm_position_major(const G6dConv& d, int bm, int splits) {
          d.N >= 4 * bm;
 }
 
+// The grid's split count: `splits` ranges of ips = ceil(total / splits) K steps each can leave the last ranges empty, so the count is
+// rounded back down to the ranges that hold work.  Returns ips.
+int igemm_round_splits(int total, int& splits) {
+  const int ips = (total + splits - 1) / splits;
+  splits = (total + ips - 1) / ips;
+  return ips;
+}
+
+// Loader prologue (the kernel's MODE): 0 none, 1 affine with one table, 2 affine with a table per image group, 3 multiplier + affine,
+// 4 multiplier + affine with a table per image group
+int igemm_mode(const G6dConv& d) {
+  if (d.mul) return d.in_affine_per_n ? 4 : 3;
+  if (!d.in_scale) return 0;
+  return d.in_affine_per_n ? 2 : 1;
+}
+
 template <int BM, int BN, int WGM, int WGN, int MODE, int MM>
 int launch_mm(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks, int splits, hipStream_t stream) {
   const int total = T * nChunks;
-  const int ips = (total + splits - 1) / splits;
-  splits = (total + ips - 1) / ips;
+  const int ips = igemm_round_splits(total, splits);
   const bool pm = igemm_position_major(d, BM, splits);
   const int pm_hw = pm ? d.Ho * d.Wo : 0, pm_tiles = pm ? (d.N + BM - 1) / BM : 0;
   const int ny = (d.Cout + BN - 1) / BN;
@@ -643,11 +662,13 @@ int launch_mode(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChun
 
 template <int BM, int BN, int WGM, int WGN>
 int launch_cfg(const G6dConv& d, const G6dRange16& rng, int M, int T, int nChunks, int splits, hipStream_t stream) {
-  if (d.mul) return d.in_affine_per_n ? launch_mode<BM, BN, WGM, WGN, 4>(d, rng, M, T, nChunks, splits, stream)
-                                      : launch_mode<BM, BN, WGM, WGN, 3>(d, rng, M, T, nChunks, splits, stream);
-  if (!d.in_scale) return launch_mode<BM, BN, WGM, WGN, 0>(d, rng, M, T, nChunks, splits, stream);
-  if (d.in_affine_per_n) return launch_mode<BM, BN, WGM, WGN, 2>(d, rng, M, T, nChunks, splits, stream);
-  return launch_mode<BM, BN, WGM, WGN, 1>(d, rng, M, T, nChunks, splits, stream);
+  switch (igemm_mode(d)) {
+    case 4: return launch_mode<BM, BN, WGM, WGN, 4>(d, rng, M, T, nChunks, splits, stream);
+    case 3: return launch_mode<BM, BN, WGM, WGN, 3>(d, rng, M, T, nChunks, splits, stream);
+    case 2: return launch_mode<BM, BN, WGM, WGN, 2>(d, rng, M, T, nChunks, splits, stream);
+    case 1: return launch_mode<BM, BN, WGM, WGN, 1>(d, rng, M, T, nChunks, splits, stream);
+    default: return launch_mode<BM, BN, WGM, WGN, 0>(d, rng, M, T, nChunks, splits, stream);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -741,28 +762,26 @@ int conv_narrow_launch(const G6dConv& d, hipStream_t stream) {
   return g6d_check_launch("conv_narrow");
 }
 
-}  // namespace
-
-// Which kernel family g6d_conv_igemm will run this descriptor on: 0 generic implicit GEMM, 1 LDS-patch kernel, 2 Winograd kernel,
-// 3 F(4x4,3x3) kernel, 4 the narrow-output kernel on the vector ALUs, 5 the implicit GEMM on fp16 hi / lo pairs (math_mode 3: no hand-off)
-// (no launch; bench.py uses it to book the executed FLOPs of a launch in the right roofline family).
-extern "C" int g6d_conv_plan(const G6dConv* desc) {
-  if (!desc) { g6d_set_error("conv_plan: null descriptor"); return G6D_EINVAL; }
-  if (desc->math_mode >= 3 && desc->math_mode <= 5) return 5;
-  if (conv_narrow_eligible(*desc)) return 4;
-  if (g6d_wino43_eligible(*desc)) return 3;
-  if (g6d_wino_eligible(*desc)) return 2;
+// Kernel family of a descriptor (the values of g6d_conv_plan), in the order the launcher tries them
+int conv_family(const G6dConv& d) {
+  if (d.math_mode >= 3 && d.math_mode <= 5) return 5;      // the pair modes are the implicit-GEMM kernel itself: no hand-off
+  if (conv_narrow_eligible(d)) return 4;
+  if (g6d_wino43_eligible(d)) return 3;
+  if (g6d_wino_eligible(d)) return 2;
   const bool use_patch = g6d_knob(G6D_KNOB_CONV_PATCH) != 0;
-  return (use_patch && g6d_conv_patch_eligible(*desc)) ? 1 : 0;
+  return (use_patch && g6d_conv_patch_eligible(d)) ? 1 : 0;
 }
 
-extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) { return g6d_conv_igemm_ex(desc, nullptr, stream_); }
+// The whole host decision of g6d_conv_igemm(_ex) for one descriptor — validation, kernel family and, for the implicit GEMM, tile, loader
+// prologue, split count and row order — in ONE copy: the launcher runs what this fills in, g6d_conv_route reports it.
+struct ConvRoute {
+  int family, bm, bn, mode, splits, split_source, position_major;      // as G6dConvRoute (include/gen6d_hip.h)
+  int M, T, nChunks;
+};
 
-extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g6d_stream_t stream_) {
-  if (!desc) { g6d_set_error("conv: null descriptor"); return G6D_EINVAL; }
-  const G6dConv& d = *desc;
-  const G6dRange16 rng = range ? *range : G6dRange16{nullptr, nullptr, -1, -1};
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+// report: also ask the launcher of family 1 - 3 for its prologue mode and split count (g6d_conv_route; the launch itself leaves that to it)
+int conv_route(const G6dConv& d, const G6dRange16* range, ConvRoute& r, bool report) {
+  r = ConvRoute{0, 0, 0, -1, 1, 0, 0, 0, 0, 0};
   if (!d.in || !d.weight || !d.out) { g6d_set_error("conv: null pointer"); return G6D_EINVAL; }
   if (d.math_mode < 0 || d.math_mode > 5) {
     g6d_set_error("conv: math_mode must be 0 (fp32), 1 (bf16), 2 (fp16), 3 (fp16 pairs), 4 (pairs, pre-split filters) or 5 (pairs, pre-split operands)");
@@ -799,6 +818,8 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
     g6d_set_error("conv: operand pointers must be 16-byte aligned"); return G6D_EINVAL;
   }
   if (d.mul && !d.in_scale) { g6d_set_error("conv: mul requires in_scale/in_shift"); return G6D_EINVAL; }
+  // (every kernel of the family applies the ReLU inside its affine prologue, the narrow one has none: alone the flag would be dropped)
+  if (d.in_relu && !d.in_scale) { g6d_set_error("conv: in_relu requires in_scale/in_shift (the ReLU follows the input affine)"); return G6D_EINVAL; }
   if (d.in_affine_per_n < 0 || d.in_image_mod < 0 || d.mul_group_images < 0 || (d.mul_group_images > 0 && !d.mul) ||
       d.in_image_mod > d.N) {
     g6d_set_error("conv: in_affine_per_n / in_image_mod / mul_group_images must be >= 0 (mul_group_images needs mul; in_image_mod <= N)");
@@ -816,16 +837,19 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
   }
   const long long Mll = (long long)d.N * d.Do * d.Ho * d.Wo;
   if (Mll > (1ll << 30)) { g6d_set_error("conv: M too large"); return G6D_EINVAL; }
-  const int M = (int)Mll;
-  if (!pairs) {      // math_mode 3 is the implicit-GEMM kernel itself: no hand-off
-    if (conv_narrow_eligible(d)) return conv_narrow_launch(d, stream);
-    if (g6d_wino43_eligible(d)) return g6d_wino43_launch(d, stream);
-    if (g6d_wino_eligible(d)) return g6d_wino_launch(d, stream);
-    const bool use_patch = g6d_knob(G6D_KNOB_CONV_PATCH) != 0;
-    if (use_patch && g6d_conv_patch_eligible(d)) return g6d_conv_patch_launch(d, M, stream);
+  const int M = r.M = (int)Mll;
+  r.family = conv_family(d);
+  if (r.family >= 1 && r.family <= 4) {      // handed to another launcher: the prologue mode and split count that one chooses
+    if (!report) return G6D_OK;
+    if (r.family == 4) r.mode = 0;
+    else if (r.family == 3) g6d_wino43_route(d, &r.mode, &r.splits);
+    else if (r.family == 2) g6d_wino_route(d, &r.mode, &r.splits);
+    else g6d_conv_patch_route(d, &r.mode, &r.splits);
+    r.split_source = r.splits > 1 ? 2 : 0;
+    return G6D_OK;
   }
-  const int T = d.kd * d.kh * d.kw;
-  const int nChunks = (d.Cin + BK - 1) / BK;
+  const int T = r.T = d.kd * d.kh * d.kw;
+  const int nChunks = r.nChunks = (d.Cin + BK - 1) / BK;
   const int total = T * nChunks;
 
   // tile configuration
@@ -861,6 +885,7 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
     }
   }
   if (splits > total) splits = total;
+  bool clamped = false;
   if (splits > 1) {     // workspace = tile counters + [split][tile] partial tiles (g6d_common.h)
     const size_t per = (size_t)blocks * bm * bn * sizeof(float);
     const size_t room = d.workspace && d.workspace_bytes > G6D_WS_COUNTER_BYTES ? d.workspace_bytes - G6D_WS_COUNTER_BYTES : 0;
@@ -868,10 +893,58 @@ extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g
       if (d.split_k > 1) { g6d_set_error("conv: workspace too small for forced split_k"); return G6D_ENOSPC; }
       splits = blocks > G6D_WS_COUNTERS ? 1 : (int)(room / per);
       if (splits < 2) splits = 1;
+      clamped = true;
     }
   }
-  if (bm == 64) return launch_cfg<64, 64, 2, 2>(d, rng, M, T, nChunks, splits, stream);
-  if (bn == 32) return launch_cfg<128, 32, 4, 1>(d, rng, M, T, nChunks, splits, stream);
-  if (bn == 64) return launch_cfg<128, 64, 2, 2>(d, rng, M, T, nChunks, splits, stream);
-  return launch_cfg<128, 128, 2, 2>(d, rng, M, T, nChunks, splits, stream);
+  igemm_round_splits(total, splits);      // (what launch_mm makes of the count)
+  r.bm = bm; r.bn = bn; r.mode = igemm_mode(d); r.splits = splits;
+  r.split_source = clamped ? 3 : (splits == 1 ? 0 : (d.split_k > 1 ? 1 : 2));
+  r.position_major = igemm_position_major(d, bm, splits) ? 1 : 0;
+  return G6D_OK;
+}
+
+}  // namespace
+
+// Which kernel family g6d_conv_igemm will run this descriptor on: 0 generic implicit GEMM, 1 LDS-patch kernel, 2 Winograd kernel,
+// 3 F(4x4,3x3) kernel, 4 the narrow-output kernel on the vector ALUs, 5 the implicit GEMM on fp16 hi / lo pairs (math_mode 3: no hand-off)
+// (no launch; bench.py uses it to book the executed FLOPs of a launch in the right roofline family).  = g6d_conv_route's `family`.
+extern "C" int g6d_conv_plan(const G6dConv* desc) {
+  if (!desc) { g6d_set_error("conv_plan: null descriptor"); return G6D_EINVAL; }
+  return conv_family(*desc);
+}
+
+// What g6d_conv_igemm will do with this descriptor under the current knobs (no launch, no operand read): conv_route's answer, or its
+// refusal — G6D_EINVAL / G6D_ENOSPC with the launcher's own message — for a descriptor the launch would refuse.
+extern "C" int g6d_conv_route(const G6dConv* desc, G6dConvRoute* route) {
+  if (!desc || !route) { g6d_set_error("conv_route: null descriptor or route"); return G6D_EINVAL; }
+  ConvRoute r;
+  const int rc = conv_route(*desc, nullptr, r, true);
+  const bool igemm = r.family == 0 || r.family == 5;
+  *route = G6dConvRoute{r.family, igemm ? r.bm : 0, igemm ? r.bn : 0, r.mode, igemm ? desc->math_mode : 0, r.splits, r.split_source,
+                        r.position_major};
+  return rc;
+}
+
+extern "C" int g6d_sizeof_conv_route(void) { return (int)sizeof(G6dConvRoute); }
+
+extern "C" int g6d_conv_igemm(const G6dConv* desc, g6d_stream_t stream_) { return g6d_conv_igemm_ex(desc, nullptr, stream_); }
+
+extern "C" int g6d_conv_igemm_ex(const G6dConv* desc, const G6dRange16* range, g6d_stream_t stream_) {
+  if (!desc) { g6d_set_error("conv: null descriptor"); return G6D_EINVAL; }
+  const G6dConv& d = *desc;
+  const G6dRange16 rng = range ? *range : G6dRange16{nullptr, nullptr, -1, -1};
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  ConvRoute r;
+  if (const int rc = conv_route(d, range, r, false)) return rc;
+  switch (r.family) {
+    case 4: return conv_narrow_launch(d, stream);
+    case 3: return g6d_wino43_launch(d, stream);
+    case 2: return g6d_wino_launch(d, stream);
+    case 1: return g6d_conv_patch_launch(d, r.M, stream);
+    default: break;
+  }
+  if (r.bm == 64) return launch_cfg<64, 64, 2, 2>(d, rng, r.M, r.T, r.nChunks, r.splits, stream);
+  if (r.bn == 32) return launch_cfg<128, 32, 4, 1>(d, rng, r.M, r.T, r.nChunks, r.splits, stream);
+  if (r.bn == 64) return launch_cfg<128, 64, 2, 2>(d, rng, r.M, r.T, r.nChunks, r.splits, stream);
+  return launch_cfg<128, 128, 2, 2>(d, rng, r.M, r.T, r.nChunks, r.splits, stream);
 }

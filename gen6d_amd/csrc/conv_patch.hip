@@ -337,12 +337,12 @@ __global__ void __launch_bounds__(256) conv_patch_kernel(const G6dConv p, const 
   }
 }
 
-template <int KIND, int MODE>
-int launch_patch(const G6dConv& d, int M, hipStream_t stream) {
-  using G = TileGeo<KIND>;
-  constexpr int NPOS = G::TN * (G::TD + G::KD - 1) * (G::TH + 2) * (G::TW + 2);
-  const int tiles_n = (d.N + G::TN - 1) / G::TN;
-  const int tiles_d = (d.Di + G::TD - 1) / G::TD, tiles_h = (d.Hi + G::TH - 1) / G::TH, tiles_w = (d.Wi + G::TW - 1) / G::TW;
+// Grid of one launch: the tiles of a kind's geometry and the split of the channel chunks over blocks (launch_patch; g6d_conv_patch_route)
+struct PatchGrid { int tiles_d, tiles_h, tiles_w, tiles, ntn, total_chunks, splits, cps; };
+
+PatchGrid patch_grid(const G6dConv& d, int TN, int TD, int TH, int TW) {
+  const int tiles_n = (d.N + TN - 1) / TN;
+  const int tiles_d = (d.Di + TD - 1) / TD, tiles_h = (d.Hi + TH - 1) / TH, tiles_w = (d.Wi + TW - 1) / TW;
   const int tiles = tiles_n * tiles_d * tiles_h * tiles_w, ntn = (d.Cout + BN - 1) / BN;
   const int total_chunks = (d.Cin + 31) / 32;
   int splits = 1;
@@ -356,6 +356,16 @@ int launch_patch(const G6dConv& d, int M, hipStream_t stream) {
   }
   const int cps = (total_chunks + splits - 1) / splits;
   splits = (total_chunks + cps - 1) / cps;
+  return PatchGrid{tiles_d, tiles_h, tiles_w, tiles, ntn, total_chunks, splits, cps};
+}
+
+template <int KIND, int MODE>
+int launch_patch(const G6dConv& d, int M, hipStream_t stream) {
+  using G = TileGeo<KIND>;
+  constexpr int NPOS = G::TN * (G::TD + G::KD - 1) * (G::TH + 2) * (G::TW + 2);
+  const PatchGrid pg = patch_grid(d, G::TN, G::TD, G::TH, G::TW);
+  const int tiles_d = pg.tiles_d, tiles_h = pg.tiles_h, tiles_w = pg.tiles_w, tiles = pg.tiles, ntn = pg.ntn;
+  const int total_chunks = pg.total_chunks, splits = pg.splits, cps = pg.cps;
   const size_t lds_bytes = (size_t)(NPOS * LDS_K + 2 * BN * LDS_K) * sizeof(float);
   const bool pipe = g6d_knob(G6D_KNOB_PATCH_PIPE) != 0;
   const int var = d.math_mode == 1 ? 2 : d.math_mode == 2 ? 3 : (pipe ? 0 : 1);
@@ -375,10 +385,15 @@ int launch_patch(const G6dConv& d, int M, hipStream_t stream) {
   return rc;
 }
 
+// Prologue of the kernel (its MODE): 0 none, 1 affine (one table or one per image group), 3 multiplier + affine (2-D kinds only:
+// g6d_conv_patch_eligible keeps a multiplier off the 3-D kind)
+int patch_mode(const G6dConv& d, int kind) { return kind != 1 && d.mul ? 3 : (d.in_scale ? 1 : 0); }
+
 template <int KIND>
 int launch_kind(const G6dConv& d, int M, hipStream_t stream) {
-  if constexpr (KIND != 1) { if (d.mul) return launch_patch<KIND, 3>(d, M, stream); }
-  return d.in_scale ? launch_patch<KIND, 1>(d, M, stream) : launch_patch<KIND, 0>(d, M, stream);
+  const int mode = patch_mode(d, KIND);
+  if constexpr (KIND != 1) { if (mode == 3) return launch_patch<KIND, 3>(d, M, stream); }
+  return mode == 1 ? launch_patch<KIND, 1>(d, M, stream) : launch_patch<KIND, 0>(d, M, stream);
 }
 
 // tile kind with the best fill for this layer, or -1
@@ -433,4 +448,15 @@ int g6d_conv_patch_launch(const G6dConv& d, int M, hipStream_t stream) {
     case 1: return launch_kind<1>(d, M, stream);
     default: return launch_kind<2>(d, M, stream);
   }
+}
+
+// The prologue mode and the split count g6d_conv_patch_launch runs `d` with (no launch)
+void g6d_conv_patch_route(const G6dConv& d, int* mode, int* splits) {
+  double eff; long long tiles;
+  const int kind = pick_kind(d, &eff, &tiles);
+  if (kind < 0) { *mode = -1; *splits = -1; return; }
+  *mode = patch_mode(d, kind);
+  using G0 = TileGeo<0>; using G1 = TileGeo<1>; using G2 = TileGeo<2>;
+  *splits = kind == 0 ? patch_grid(d, G0::TN, G0::TD, G0::TH, G0::TW).splits
+          : kind == 1 ? patch_grid(d, G1::TN, G1::TD, G1::TH, G1::TW).splits : patch_grid(d, G2::TN, G2::TD, G2::TH, G2::TW).splits;
 }

@@ -728,11 +728,16 @@ int w43_launch_t(W43Args& a, long long blocks, hipStream_t stream) {
   return g6d_check_launch("wino43_conv3x3");
 }
 
-int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+// The plan of one launch under the current knobs (w43_run; g6d_wino43_route)
+wplan::F4Plan w43_plan_of(W43Args& a, int mode, int kd, bool has_workspace, size_t workspace_bytes) {
   // (the model's constants can be overridden for measurements)
   const wplan::F4Knobs knobs = {(int)g6d_knob(G6D_KNOB_W43_SPLIT_MAX), g6d_knob(G6D_KNOB_W43_SPLIT_GAIN), g6d_knob(G6D_KNOB_W43_CHUNK_US)};
-  const wplan::F4Plan pl = wplan::f4_plan(a.seg, a.nseg, mode, kd, a.Cin, a.Cout, wplan::room(workspace != nullptr, workspace_bytes, G6D_WS_COUNTER_BYTES),
-                                          G6D_WS_COUNTERS, knobs);
+  return wplan::f4_plan(a.seg, a.nseg, mode, kd, a.Cin, a.Cout, wplan::room(has_workspace, workspace_bytes, G6D_WS_COUNTER_BYTES),
+                        G6D_WS_COUNTERS, knobs);
+}
+
+int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const wplan::F4Plan pl = w43_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
   if (pl.error) { g6d_set_error(pl.error); return G6D_EINVAL; }
   a.H0 = a.seg[0].H; a.W0 = a.seg[0].W; a.ld0 = a.seg[0].ld_in;
   a.qtotal = (int)pl.q.quarters;
@@ -819,8 +824,8 @@ bool g6d_wino43_eligible(const G6dConv& d) {
   return (long long)d.N * d.Di * d.Hi * d.Wi * d.ld_in < (1ll << 29);
 }
 
-int g6d_wino43_launch(const G6dConv& d, hipStream_t stream) {
-  W43Args a = {};
+// The argument block and the prologue mode of a conv descriptor on this family (g6d_wino43_launch; g6d_wino43_route)
+static int w43_args_of(const G6dConv& d, W43Args& a) {
   a.in = d.in; a.U = d.weight_wino43; a.bias = d.bias; a.out_full = d.out; a.out_pool = nullptr;
   a.D = d.Di; a.Cin = d.Cin; a.Cout = d.Cout; a.relu = d.out_act == 1;
   a.nseg = 1;
@@ -830,6 +835,19 @@ int g6d_wino43_launch(const G6dConv& d, hipStream_t stream) {
   a.aff_div = d.in_affine_per_n;
   if (d.fin_scale)
     a.fin = G6dFin{d.fin_scale, d.fin_shift, reinterpret_cast<int*>(d.fin_counter), d.stats, 1.0 / d.fin_count, d.fin_eps, d.fin_groups * d.Cout};
-  const int mode = !d.in_scale ? 0 : (d.in_affine_per_n ? 2 : 1);
+  return !d.in_scale ? 0 : (d.in_affine_per_n ? 2 : 1);
+}
+
+int g6d_wino43_launch(const G6dConv& d, hipStream_t stream) {
+  W43Args a = {};
+  const int mode = w43_args_of(d, a);
   return w43_run(a, mode, d.kd, d.workspace, d.workspace_bytes, stream);
+}
+
+// The prologue mode and the split count g6d_wino43_launch runs `d` with (no launch; splits -1: the plan refuses the layer)
+void g6d_wino43_route(const G6dConv& d, int* mode, int* splits) {
+  W43Args a = {};
+  *mode = w43_args_of(d, a);
+  const wplan::F4Plan pl = w43_plan_of(a, *mode, d.kd, d.workspace != nullptr, d.workspace_bytes);
+  *splits = pl.error ? -1 : pl.split.splits;
 }

@@ -484,8 +484,8 @@ int wino_launch_w(WinoArgs& a, long long blocks, int nwn, hipStream_t stream) {
   return nwn == 1 ? wino_launch_t<MODE, KD, 1>(a, blocks, stream) : wino_launch_t<MODE, KD, 2>(a, blocks, stream);
 }
 
-// Fills the geometry / split fields of `a` and launches.  kd = 1, 3 or 25; mode as the kernel's MODE.
-int wino_run(WinoArgs& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+// The plan of one launch under the current knobs (wino_run; g6d_wino_route): completes a one-map argument block's segment list first
+wplan::F2Plan wino_plan_of(WinoArgs& a, int mode, int kd, bool has_workspace, size_t workspace_bytes) {
   if (a.nseg == 0) {          // one map size: the launch's own fields
     a.nseg = 1;
     a.seg[0] = WinoSeg{0, a.N, a.H, a.W, 0, 0, 0, 0, 0, a.ld_in, a.ld_full, a.ld_pool};
@@ -493,8 +493,13 @@ int wino_run(WinoArgs& a, int mode, int kd, float* workspace, size_t workspace_b
   // (the model's constants can be overridden for measurements)
   const wplan::F2Knobs knobs = {(int)g6d_knob(G6D_KNOB_WINO_WIDE), (int)g6d_knob(G6D_KNOB_WINO_SPLIT_MAX), g6d_knob(G6D_KNOB_WINO_SPLIT_GAIN),
                                 g6d_knob(G6D_KNOB_WINO_SPLIT_FIX), g6d_knob(G6D_KNOB_WINO_SPLIT_PER)};
-  const wplan::F2Plan pl = wplan::f2_plan(a.seg, a.nseg, a.img_mod > 0 ? (long long)a.img_mod * a.D : 0, a.mm, mode, kd, a.Cin, a.Cout,
-                                          wplan::room(workspace != nullptr, workspace_bytes, G6D_WS_COUNTER_BYTES), G6D_WS_COUNTERS, knobs);
+  return wplan::f2_plan(a.seg, a.nseg, a.img_mod > 0 ? (long long)a.img_mod * a.D : 0, a.mm, mode, kd, a.Cin, a.Cout,
+                        wplan::room(has_workspace, workspace_bytes, G6D_WS_COUNTER_BYTES), G6D_WS_COUNTERS, knobs);
+}
+
+// Fills the geometry / split fields of `a` and launches.  kd = 1, 3 or 25; mode as the kernel's MODE.
+int wino_run(WinoArgs& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+  const wplan::F2Plan pl = wino_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
   if (pl.error) { g6d_set_error(pl.error); return G6D_EINVAL; }
   a.QH = a.seg[0].QH; a.QW = a.seg[0].QW;
   a.qtotal = (int)pl.q.quarters;
@@ -632,8 +637,8 @@ bool g6d_wino_eligible(const G6dConv& d) {
   return (long long)(d.in_image_mod > 0 ? d.in_image_mod : d.N) * d.Di * d.Hi * d.Wi * d.ld_in < (1ll << 29);      // 2^31 bytes: the bound of the buffer loads
 }
 
-int g6d_wino_launch(const G6dConv& d, hipStream_t stream) {
-  WinoArgs a = {};
+// The argument block and the prologue mode of a conv descriptor on this family (g6d_wino_launch; g6d_wino_route)
+static int wino_args_of(const G6dConv& d, WinoArgs& a) {
   a.in = d.in; a.U = d.math_mode ? reinterpret_cast<const float*>(d.weight_wino16) : d.weight_wino; a.mm = d.math_mode;
   a.bias = d.bias; a.out_full = d.out; a.out_pool = nullptr;
   a.D = d.Di; a.N = d.N * d.Di; a.H = d.Hi; a.W = d.Wi; a.Cin = d.Cin; a.ld_in = d.ld_in; a.Cout = d.Cout; a.ld_full = d.ld_out;
@@ -644,6 +649,19 @@ int g6d_wino_launch(const G6dConv& d, hipStream_t stream) {
   a.aff_div = d.in_affine_per_n; a.img_mod = d.in_image_mod; a.mul_div = d.mul_group_images > 0 ? d.mul_group_images * d.Di : 0;
   if (d.fin_scale)
     a.fin = G6dFin{d.fin_scale, d.fin_shift, reinterpret_cast<int*>(d.fin_counter), d.stats, 1.0 / d.fin_count, d.fin_eps, d.fin_groups * d.Cout};
-  const int mode = d.mul ? 3 : (!d.in_scale ? 0 : (d.in_affine_per_n ? 2 : 1));
+  return d.mul ? 3 : (!d.in_scale ? 0 : (d.in_affine_per_n ? 2 : 1));
+}
+
+int g6d_wino_launch(const G6dConv& d, hipStream_t stream) {
+  WinoArgs a = {};
+  const int mode = wino_args_of(d, a);
   return wino_run(a, mode, d.kd, d.workspace, d.workspace_bytes, stream);
+}
+
+// The prologue mode and the split count g6d_wino_launch runs `d` with (no launch; splits -1: the plan refuses the layer)
+void g6d_wino_route(const G6dConv& d, int* mode, int* splits) {
+  WinoArgs a = {};
+  *mode = wino_args_of(d, a);
+  const wplan::F2Plan pl = wino_plan_of(a, *mode, d.kd, d.workspace != nullptr, d.workspace_bytes);
+  *splits = pl.error ? -1 : pl.split.splits;
 }

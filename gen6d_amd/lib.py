@@ -58,6 +58,12 @@ class G6dSink(C.Structure):
                 ("box", C.c_int32)]
 
 
+class G6dConvRoute(C.Structure):
+    """include/gen6d_hip.h: what g6d_conv_route reports about a G6dConv descriptor."""
+    _fields_ = [("family", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("mode", C.c_int32), ("math_mode", C.c_int32),
+                ("splits", C.c_int32), ("split_source", C.c_int32), ("position_major", C.c_int32)]
+
+
 class G6dConv(C.Structure):
     _fields_ = [
         ("in_", C.c_void_p), ("mul", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p),
@@ -98,6 +104,7 @@ SIGNATURES = {
     "g6d_conv_igemm": [C.POINTER(G6dConv), _P],
     "g6d_conv_igemm_ex": [C.POINTER(G6dConv), _P, _P],
     "g6d_conv_plan": [C.POINTER(G6dConv)],
+    "g6d_conv_route": [C.POINTER(G6dConv), C.POINTER(G6dConvRoute)],
     "g6d_corr2d_patch": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, C.c_size_t, _I, _P],
     "g6d_corr2d_patch_multi": [_P, _I, _I, _P, _I, _I, _I, _P, C.c_size_t, _I, _P],
     "g6d_corr2d_wino_multi": [_P, _I, _I, _P, _I, _I, _P, C.c_size_t, _P],
@@ -200,6 +207,9 @@ def load():
     lib.g6d_sizeof_conv_desc.restype = C.c_int
     if lib.g6d_sizeof_conv_desc() != C.sizeof(G6dConv):
         raise RuntimeError("libgen6d_hip.so: G6dConv layout differs from the ctypes binding (stale build?)")
+    lib.g6d_sizeof_conv_route.restype = C.c_int
+    if lib.g6d_sizeof_conv_route() != C.sizeof(G6dConvRoute):
+        raise RuntimeError("libgen6d_hip.so: G6dConvRoute layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
         raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_mesh_desc() != C.sizeof(G6dMesh):

@@ -48,6 +48,8 @@ class math_mode:
 PROFILE = None
 # Same for the HBM-bound kernels: a dict name -> list of (algorithmic bytes, start, end).
 PROFILE_HBM = None
+# When set to a list, conv() appends the route report of every descriptor (conv_route below) just before it launches it (tests).
+ROUTE = None
 
 
 _T16 = {1: torch.bfloat16, 2: torch.float16, 3: torch.float16}       # math / filter mode -> the 16-bit operand type
@@ -126,6 +128,13 @@ def fork_join(fns, device):
     return results
 
 
+def conv_route(d):
+    """g6d_conv_route: what g6d_conv_igemm will do with the descriptor `d` under the current knobs, as a lib.G6dConvRoute (no launch)."""
+    r = _lib.G6dConvRoute()
+    _lib.check(_lib.load().g6d_conv_route(C.byref(d), C.byref(r)), "g6d_conv_route")
+    return r
+
+
 def _cl5(t, name):
     """Validate a channels-last 5-D view; return (N, D, H, W, C, ld)."""
     if t.dim() != 5 or t.dtype != torch.float32:
@@ -175,6 +184,8 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
             raise ValueError("conv: pairs variant must be 3, 4 or 5")
     if MATH_MODE:
         pairs = None
+    if in_relu and in_scale is None:
+        raise ValueError("conv: in_relu needs in_scale / in_shift (the ReLU of the prologue follows the input affine; G6dConv.in_relu)")
     x16 = None
     if isinstance(x, PairMap):
         if pairs is None or mul is not None or in_scale is not None or in_mod:
@@ -188,7 +199,7 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
         _need_gpu(x)
         n5, d5, h5, w5, c5, _ = _cl5(x, "conv.x")
         x16 = affine_split16(x.view(n5 * d5, 1, h5, w5, c5), in_scale, in_shift, int(per_n) * d5 if in_scale is not None else 0,
-                             in_relu and in_scale is not None, False, 3, rng=pairs).view(n5, d5, h5, w5, 2, c5)
+                             bool(in_relu), False, 3, rng=pairs).view(n5, d5, h5, w5, 2, c5)
     label_aff = in_scale is not None            # the layer's label names its affine whichever launch applies it
     if x16 is not None:
         x, slot_in = x16.data, x16.slot
@@ -282,6 +293,8 @@ def conv(x, w, bias, out, ksize=(1, 1, 1), stride=(1, 1, 1), pad=(0, 0, 0), mul=
                         f"{' mul' if mul is not None else ''}{' aff' if label_aff else ''}{' stats' if stats is not None else ''}",
                         # algorithmic bytes: every operand once (input images, multiplier maps, filters, output)
                         4.0 * ((in_mod or N) * Di * Hi * Wi * Cin + (mul.numel() if mul is not None else 0) + w.numel() + N * Do * Ho * Wo * Cout), fl))
+    if ROUTE is not None:
+        ROUTE.append(conv_route(d))
     if pairs is not None:
         ra = C.byref(pairs[0].arg(slot_in, -1) if variant == 5 else pairs[0].arg(-1, pairs[1]))
         _timed(PROFILE is not None, lambda: _lib.check(_lib.load().g6d_conv_igemm_ex(C.byref(d), ra, _stream()), "g6d_conv_igemm_ex"), book)

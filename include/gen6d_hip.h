@@ -75,7 +75,8 @@ int g6d_marker(int id, g6d_stream_t stream);
  * Fused into the epilogue: bias, activation, per-(group,channel) sum / sum-of-squares for the FOLLOWING
  * InstanceNorm (fp64 accumulators).
  *   out[m][co] = act( bias[co] + sum_{tap,ci} X(m,tap,ci) * weight[co][tap][ci] )
- *   X = relu?( (in * mul?) * in_scale + in_shift ), 0 outside the input
+ *   X = relu?( (in * mul?) * in_scale + in_shift ), 0 outside the input; mul and relu only together with in_scale / in_shift (the ReLU is
+ *   the one that follows the InstanceNorm affine: in_relu or mul without in_scale is refused with G6D_EINVAL)
  * ---------------------------------------------------------------------------------------------------------------- */
 /* Workspace (g6d_conv_igemm, g6d_corr2d_patch, g6d_wino_conv3x3): layers whose grid would not fill 256 CUs split their
  * reduction over more blocks.  The workspace holds G6D_WORKSPACE_COUNTER_BYTES of per-tile arrival counters followed by the
@@ -101,7 +102,7 @@ typedef struct G6dConv {
   int32_t kd, kh, kw;
   int32_t sd, sh, sw;
   int32_t pd, ph, pw;
-  int32_t in_relu;              /* apply ReLU after the input affine */
+  int32_t in_relu;              /* apply ReLU after the input affine; non-zero needs in_scale / in_shift (G6D_EINVAL without them) */
   int32_t in_affine_per_n;      /* 0: one affine table for all N; k >= 1: image n uses table n / k (1 = a table per image; k = the
                                    hypothesis count D when N = qn * D images of a batched selector call share one table per query) */
   int32_t out_act;              /* 0 none, 1 ReLU, 2 LeakyReLU(0.1); anything else is refused.  Sizes: N, Di, Hi, Wi, Do, Ho, Wo, Cin, Cout, the
@@ -186,6 +187,26 @@ int g6d_conv_igemm_ex(const G6dConv* desc, const struct G6dRange16* range, g6d_s
 int g6d_conv_plan(const G6dConv* desc);
 /* sizeof(G6dConv) as compiled into the library: bindings check their struct layout against it */
 int g6d_sizeof_conv_desc(void);
+/* The route g6d_conv_igemm will take with `desc` under the current knobs (additive to ABI v12; launches nothing, reads no operand, and is
+   the launcher's own decision code, not a restatement of it).  Returns G6D_OK, or what the launch would refuse the descriptor with
+   (G6D_EINVAL / G6D_ENOSPC and its message; the fields are then not meaningful).  tests/conv_sweep.py files its descriptors by it. */
+typedef struct G6dConvRoute {
+  int32_t family;          /* as g6d_conv_plan */
+  int32_t bm, bn;          /* families 0 and 5: the tile, 128x128 / 128x64 / 128x32 / 64x64 output rows x channels; otherwise 0 */
+  int32_t mode;            /* the loader prologue of the kernel that runs.  Families 0 and 5: 0 none, 1 affine with one table, 2 affine with a
+                              table per image group, 3 multiplier + affine, 4 multiplier + affine per image group.  Families 1 - 3: the mode
+                              their own launcher chooses (0 none, 1 affine, 2 affine per image group, 3 multiplier + affine; the LDS-patch
+                              kernel reads one or many tables in mode 1).  Family 4: 0 */
+  int32_t math_mode;       /* families 0 and 5: the descriptor's; otherwise 0 */
+  int32_t splits;          /* blocks that share one output tile's reduction, after every clamp and rounding (1 = no split); families 1 - 3:
+                              the count their launcher's own rule chooses, -1 if that launcher would refuse the layer */
+  int32_t split_source;    /* 0 none (splits == 1), 1 forced by split_k > 1, 2 automatic, 3 automatic and then clamped by the workspace's
+                              room or by the tile-counter limit (splits may be 1).  Families 1 - 3: 0 or 2 only — their launchers fold
+                              the workspace's room into their own count and do not say whether it cut it */
+  int32_t position_major;  /* families 0 and 5: 1 = position-major row order (knob conv_pm), 0 = row order */
+} G6dConvRoute;
+int g6d_conv_route(const G6dConv* desc, G6dConvRoute* route);
+int g6d_sizeof_conv_route(void);
 
 /* Stride-1 2-D cross-correlation without bias for Cout <= 32 with input-patch reuse in LDS: the detector's
  * F.conv2d(que_x0, ref_x0, padding=7) (network/detector.py:224), where the generic kernel is bound by re-loading the

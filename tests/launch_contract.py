@@ -135,7 +135,7 @@ CONV_FIELDS = {
     "workspace_bytes": ("X", "0 with a NULL workspace disables splitting; any size is meaningful"),
     "N": "N", "Di": "N", "Hi": "N", "Wi": "N", "Cin": "N", "ld_in": "N", "Do": "N", "Ho": "N", "Wo": "N", "Cout": "N", "ld_out": "N",
     "kd": "N", "kh": "N", "kw": "N", "sd": "N", "sh": "N", "sw": "N",
-    "pd": "I", "ph": "I", "pw": "I", "in_relu": ("X", FLAG), "in_affine_per_n": "I", "out_act": "I",
+    "pd": "I", "ph": "I", "pw": "I", "in_relu": "I", "in_affine_per_n": "I", "out_act": "I",
     "stat_rows_per_group": ("X", "not read while stats is NULL (the baseline)"),
     "split_k": ("X", "<= 0 chooses automatically, 1 never splits, > 1 forces: every value is meaningful"), "math_mode": "I",
     "weight_wino": "ON", "fin_scale": "ON", "fin_shift": "ON", "fin_counter": "ON",
@@ -161,6 +161,11 @@ def conv_cases():
         rejk("mode", "in_affine_per_n=-1", {d + "in_affine_per_n": -1}),
         rejk("mode", "in_image_mod=-1", {d + "in_image_mod": -1}), rejk("mode", "mul_group_images=-1", {d + "mul_group_images": -1}),
         rejk("pairing", "in_scale without in_shift", {d + "in_scale": dev(50)}),
+        # the ReLU of the prologue is the one after the InstanceNorm affine: every kernel applies it inside its affine branch (the narrow
+        # kernel has no prologue at all), so the flag alone would be dropped; with the affine any non-zero value means "on"
+        rejk("pairing", "in_relu without in_scale", {d + "in_relu": 1}),
+        acck("pairing", "in_relu with in_scale and in_shift", {d + "in_relu": 1, d + "in_scale": dev(50), d + "in_shift": dev(51)}),
+        acck("pairing", "in_relu=-3 (any non-zero value) with the affine", {d + "in_relu": -3, d + "in_scale": dev(50), d + "in_shift": dev(51)}),
         acck("pairing", "in_scale with in_shift", {d + "in_scale": dev(50), d + "in_shift": dev(51)}),
         rejk("pairing", "fin_scale without stats", {d + "fin_scale": dev(50), d + "fin_shift": dev(51), d + "fin_counter": dev(52), d + "fin_groups": 1, d + "fin_count": 64.0}),
         rejk("pairing", "fin_scale without fin_shift", {d + "stats": dev(53), d + "fin_scale": dev(50), d + "fin_counter": dev(52), d + "fin_groups": 1, d + "fin_count": 64.0}),
@@ -178,6 +183,13 @@ E("g6d_conv_igemm_ex", [T("desc", lib.G6dConv, conv_row(), CONV_FIELDS), R("rang
 PLAN_WHY = "g6d_conv_plan launches nothing and reads no operand: the descriptor is validated by g6d_conv_igemm"
 PLAN_FIELDS = {f: ("ON" if t is C.c_void_p else ("X", PLAN_WHY)) for f, t in lib.G6dConv._fields_}
 E("g6d_conv_plan", [T("desc", lib.G6dConv, conv_row(), PLAN_FIELDS)])
+# g6d_conv_route is the launcher's own decision code run without the launch: it dereferences no operand either.  What it answers for a
+# descriptor the launch refuses is that refusal (one example below); the rules themselves are stated once, in the launchers' tables above.
+ROUTE_WHY = "g6d_conv_route launches nothing and reads no operand: it answers with g6d_conv_igemm's own verdict on the descriptor"
+ROUTE_FIELDS = {f: ("ON" if t is C.c_void_p else ("X", ROUTE_WHY)) for f, t in lib.G6dConv._fields_}
+E("g6d_conv_route", [T("desc", lib.G6dConv, conv_row(), ROUTE_FIELDS), H("route", C.c_int32, [0] * 8)],
+  [rejk("pairing", "in_relu without in_scale: the launcher's refusal", {"desc[0].in_relu": 1}),
+   acck("pairing", "in_relu with in_scale and in_shift", {"desc[0].in_relu": 1, "desc[0].in_scale": dev(50), "desc[0].in_shift": dev(51)})])
 
 # ---------------------------------------------------------------------------------------------------------- correlations
 WS = [ON("workspace"), X("workspace_bytes", 0, "0 with a NULL workspace disables splitting; any size is meaningful")]

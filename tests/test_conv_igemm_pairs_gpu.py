@@ -170,18 +170,23 @@ def test_position_major_tiles(pm, knob):
     """512 images of 4x4, 3x3 stride 1 with an affine prologue, split_k = 1: the shape meets every condition of the library's
     position-major rule (igemm_position_major in conv_igemm.hip: 2-D, stride 1, "same" padding, map <= 8x8, an affine prologue under knob
     conv_pm 1, un-split, N >= 4 tiles of 128 images — a forced split_k skips the tile policy, so the tile stays 128x64), so knob 1 runs the
-    pair mode in position-major order and knob 0 in row order; both hold the bar.  The library reports no row order
-    (g6d_conv_plan gives the kernel family only), so the test cannot tell that the order was taken: the conditions are asserted here on
-    the shape, and a change of the rule has to be followed here by hand."""
-    N_, HW = 512, 16
-    assert N_ >= 4 * 128 and HW <= 64                      # the rule's size conditions for the 128-row tile
+    pair mode in position-major order and knob 0 in row order; both hold the bar.  g6d_conv_route (the launcher's own decision code)
+    says which order the launch takes."""
+    from gen6d_amd import ops
     knob("conv_pm", pm)
     g = torch.Generator().manual_seed(5)
     x = _rand(g, 512, 1, 4, 4, 32)
     sc, sh = _rand(g, 32) + 1.5, _rand(g, 32) * 0.5
     w = _rand(g, 64, 9, 32, scale=(1.0 / (9 * 32)) ** 0.5 * 3)
     ref, _ = _reference(x, w, None, (1, 3, 3), (1, 1, 1), (0, 1, 1), aff=(sc, sh), relu=True)
-    out, _, _ = _run(x, w, None, (1, 3, 3), (1, 1, 1), (0, 1, 1), _table(), "a", aff=(sc, sh), relu=True, split_k=1)
+    ops.ROUTE = []
+    try:
+        out, _, _ = _run(x, w, None, (1, 3, 3), (1, 1, 1), (0, 1, 1), _table(), "a", aff=(sc, sh), relu=True, split_k=1)
+        route, = ops.ROUTE
+    finally:
+        ops.ROUTE = None
+    assert (route.family, route.bm, route.bn, route.splits) == (5, 128, 64, 1)
+    assert route.position_major == pm, "the launch did not take the row order this case is about"
     e = _err(out, ref)
     print(f"conv_pm {pm}: error / range {e:.3e}")
     assert e <= BAR, e

@@ -162,7 +162,7 @@ FRAMES = "byte-pixel frame kernel: its own tests run unaligned bases and odd pit
 TWIN = "the _ex form is in the case table"
 
 EXEMPT = {
-    "g6d_marker": NO_MAPS, "g6d_zero_bytes": NO_MAPS, "g6d_conv_plan": NO_MAPS, "g6d_conv16_direct_plan": NO_MAPS, "g6d_corr_fft_plan": NO_MAPS,
+    "g6d_marker": NO_MAPS, "g6d_zero_bytes": NO_MAPS, "g6d_conv_plan": NO_MAPS, "g6d_conv_route": NO_MAPS, "g6d_conv16_direct_plan": NO_MAPS, "g6d_corr_fft_plan": NO_MAPS,
     "g6d_stats_finalize": NO_MAPS, "g6d_sizeof_frame_desc": NO_MAPS, "g6d_sizeof_mesh_desc": NO_MAPS, "g6d_sizeof_sink_desc": NO_MAPS,
     "g6d_chain_crop_from_detection": TABLES, "g6d_chain_pose_from_selection": TABLES, "g6d_chain_refine_prepare": TABLES,
     "g6d_chain_refine_update": TABLES, "g6d_track_gather": TABLES, "g6d_track_commit": TABLES, "g6d_track_gate": TABLES,
@@ -176,7 +176,7 @@ EXEMPT = {
 
 def _allowed(name, reason, covered):
     if reason == NO_MAPS:
-        return name in ("g6d_marker", "g6d_zero_bytes", "g6d_stats_finalize") or name.endswith("_plan") or name.startswith("g6d_sizeof_") or \
+        return name in ("g6d_marker", "g6d_zero_bytes", "g6d_stats_finalize") or name.endswith(("_plan", "_route")) or name.startswith("g6d_sizeof_") or \
             bool(re.search(r"knob|abi|error", name))
     if reason == TABLES:
         return name.startswith(("g6d_chain_", "g6d_track_"))

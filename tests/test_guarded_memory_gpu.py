@@ -161,7 +161,7 @@ def _ws():
 
 
 # ================================================================================================ implicit GEMM (g6d_conv_igemm[_ex])
-# Bars: tests/test_kernels_gpu.py::_run_conv_case — 2e-5 rel-to-max for the map and both statistics (4e-5 on the Winograd kernel);
+# Bars: tests/test_kernels_gpu.py::_run_conv_case (= tests/conv_case.py::run_conv_case) — 2e-5 rel-to-max for the map and both statistics (4e-5 on the Winograd kernel);
 # tests/test_wino43_gpu.py::test_conv_on_wino43_kernel — 1e-5 map, 2e-5 statistics on the F(4x4,3x3) kernel.
 def _conv(id, c, entries=("g6d_conv_igemm",), bar=2e-5, sbar=None, wino=None, label=None, hbm=None, knobs=(), mode=0):
     sbar = sbar if sbar is not None else bar

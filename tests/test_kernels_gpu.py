@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_case
 import ref_ops
 
 pytestmark = pytest.mark.gpu
@@ -178,57 +179,8 @@ def test_conv_on_winograd_kernel(ops, case, knob):
 
 
 def _run_conv_case(ops, case, wino):
-    g = torch.Generator().manual_seed(17)
-    c = case
-    N, D, H, W, Cin, Cout = c["N"], c["D"], c["H"], c["W"], c["Cin"], c["Cout"]
-    k, s, p = c["k"], c["s"], c["p"]
-    ld_in, ld_out = c.get("ld_in", Cin), c.get("ld_out", Cout)
-    Do, Ho, Wo = [(i + 2 * pp - kk) // ss + 1 for i, kk, ss, pp in zip((D, H, W), k, s, p)]
-    in_mod, mul_group, per_n = c.get("in_mod", 0), c.get("mul_group", 0), int(c.get("per_n", 0))
-    xbuf = _rand(g, in_mod or N, D, H, W, ld_in)
-    off = 64 if ld_in >= Cin + 64 else 0
-    x = xbuf[..., off:off + Cin]
-    T = k[0] * k[1] * k[2]
-    w = _rand(g, Cout, T, Cin, scale=(1.0 / (T * Cin)) ** 0.5)
-    bias = _rand(g, Cout, scale=0.1)
-    mul = (_rand(g, (N + mul_group - 1) // mul_group, H, W, Cin) if mul_group else _rand(g, H, W, Cin)) if c.get("mul") else None
-    groups_in = (N + per_n - 1) // per_n if per_n else 1
-    sc = (0.5 + torch.rand((groups_in, Cin), generator=g)) if c.get("aff") else None
-    sh = _rand(g, groups_in, Cin, scale=0.3) if c.get("aff") else None
-    M = N * Do * Ho * Wo
-    rpg = c.get("rpg", 0)
-    G = M // rpg if rpg else 1
-    dev = "cuda"
-    xg = xbuf.to(dev)
-    xv = xg[..., off:off + Cin]
-    outbuf = torch.full((N, Do, Ho, Wo, ld_out), -777.0, device=dev)
-    out = outbuf[..., :Cout]
-    stats = ops.new_stats(G, Cout, dev) if c.get("stats") else None
-    count = float(rpg if rpg else M)
-    res = ops.conv(xv, w.to(dev), bias.to(dev), out, ksize=k, stride=s, pad=p, mul=mul.to(dev) if mul is not None else None,
-                   in_scale=sc.to(dev) if sc is not None else None, in_shift=sh.to(dev) if sh is not None else None,
-                   in_relu=bool(c.get("relu")), per_n=per_n, out_act=c.get("act", 0), stats=stats,
-                   rows_per_group=rpg, split_k=c.get("split", 0), w_wino=_wino_u(w, k).to(dev) if wino else None,
-                   finalize=count if stats is not None else None,          # InstanceNorm affine from the launch's last block
-                   in_mod=in_mod, mul_group=mul_group)
-    torch.cuda.synchronize()
-    ref = torch.empty((N, Do, Ho, Wo, Cout), dtype=torch.float64)
-    rstats = torch.zeros((G, Cout, 2), dtype=torch.float64) if c.get("stats") else None
-    ref_ops.conv(_d(x), _d(w), _d(bias), ref, ksize=k, stride=s, pad=p, mul=_d(mul), in_scale=_d(sc), in_shift=_d(sh),
-                 in_relu=bool(c.get("relu")), per_n=per_n, out_act=c.get("act", 0), stats=rstats,
-                 rows_per_group=rpg, in_mod=in_mod, mul_group=mul_group)
-    _check(out, ref, 4e-5 if wino else 2e-5, "conv out")
-    if ld_out != Cout:
-        assert (outbuf[..., Cout:] == -777.0).all(), "conv wrote outside its channel slice"
-    if stats is not None:
-        _check(stats[..., 0], rstats[..., 0], 4e-5 if wino else 2e-5, "stats sum")
-        _check(stats[..., 1], rstats[..., 1], 4e-5 if wino else 2e-5, "stats sumsq")
-        # the fused finalisation equals the stand-alone kernel on the same table, and the reference formula
-        sc_f, sh_f = res
-        sc_k, sh_k = ops.stats_finalize(stats, count)
-        assert torch.equal(sc_f, sc_k) and torch.equal(sh_f, sh_k), "fused InstanceNorm finalisation differs from g6d_stats_finalize"
-        rsc, rsh = ref_ops.stats_finalize(rstats, count)
-        _check(sc_f, rsc.double(), 1e-4, "finalised scale"); _check(sh_f, rsh.double(), 1e-4, "finalised shift")
+    """(the helper lives in tests/conv_case.py, shared with the descriptor sweep of tests/test_conv_sweep_gpu.py)"""
+    conv_case.run_conv_case(ops, case, wino)
 
 
 def _wino_u(w_taps, k):
