@@ -29,6 +29,10 @@ struct Params {
   int ablate;                                                // knob c16_ablate (timing experiments)
   G6dRange16 rng;                                            // pair exponents / range record (zero: unscaled, not recorded)
 };
+// The grids of the two launches (blocks of 256 threads; whole groups of 8 tile blocks per channel block), in one copy for the launch and
+// for g6d_conv16_direct_route: the halo-patch kernel on blocks of wm pixel tiles, the per-tap kernels on single tiles
+inline int halo_grid(const Params& p, int wm) { return ((p.ptiles + wm - 1) / wm + 7) / 8 * 8 * p.nN; }
+inline int tap_grid(const Params& p) { return (p.ptiles + 7) / 8 * 8 * p.nN; }
 }  // namespace c16
 
 // The per-tap kernels (conv16_tap.hip): chooses the instantiation for (w_layout, math_mode) and launches it on p.ptiles tiles.

@@ -22,10 +22,24 @@
 #include "conv16_common.h"
 
 namespace {
-// g6d_conv16_direct_multi_ex; plan_only: validate and choose the kernel, launch nothing (g6d_conv16_direct_plan's return value)
+// What g6d_conv16_direct_route reports, filled from the parameter block the launch would carry (kernel: the plan's answer)
+void c16_report(G6dConv16Route* r, const c16::Params& p, int kernel, int w_layout, int math_mode, int wm, bool half_tile, bool folded, int blocks) {
+  if (!r) return;
+  *r = G6dConv16Route{};
+  r->kernel = kernel; r->w_layout = w_layout; r->math_mode = math_mode; r->kd = p.kd; r->wm = wm; r->half_tile = half_tile; r->folded = folded;
+  r->tiles = p.ptiles; r->nN = p.nN; r->blocks = blocks;
+  for (int i = 0; i < p.nseg; ++i) {
+    const C16Seg& s = p.seg[i];
+    if (kernel) r->seg[i] = {s.h_tile0, s.h_tw_log2, s.h_tiles_x, s.h_tpi, s.h_segh_log2, s.h_bands};
+    else r->seg[i] = {s.tile0, s.tw_log2, s.tiles_x, 0, 0, 0};
+  }
+}
+
+// g6d_conv16_direct_multi_ex; plan_only: validate and choose the kernel, launch nothing (g6d_conv16_direct_plan's return value; route: also
+// report the choice, g6d_conv16_direct_route)
 int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale, const float* bias, int Cout, int kd, int relu,
                int full_type, int pool_type, int math_mode, double* stats, int stat_rows_per_group, const G6dRange16* range, g6d_stream_t stream,
-               bool plan_only) {
+               bool plan_only, G6dConv16Route* route = nullptr) {
   if (!segs || nseg < 1 || nseg > 4 || !W16) { g6d_set_error("conv16_direct: 1..4 segments and filters expected"); return G6D_EINVAL; }
   if (Cin < 1 || Cout < 1 || !g6d_aligned16(W16)) { g6d_set_error("conv16_direct: bad args (Cin, Cout >= 1, 16-byte aligned filters)"); return G6D_EINVAL; }
   // w_layout 2: fragment-major filters of a 3x3x3 layer packed as the 2-D bank [Cout][9][3 Cin], channel order (dz, ci) — the pair
@@ -96,6 +110,7 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
       const int wm = Cout % (4 * cw) == 0 ? 1 : 2;
       p.ptiles = a.tiles;
       p.nN = Cout / (cw * (4 / wm));
+      c16_report(route, p, a.per_pass ? 2 : 1, w_layout, math_mode, wm, half_tile, folded, c16::halo_grid(p, wm));
       if (plan_only) return a.per_pass ? 2 : 1;
       return c16w_launch(p, math_mode, wm, half_tile, folded, st);
     }
@@ -103,6 +118,7 @@ int c16_direct(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int
   if (folded) { g6d_set_error("conv16_direct: depth-folded filters run on the halo-patch kernel only (planes at least one tile high, statistics groups of whole volumes)"); return G6D_EINVAL; }
   if (half_tile) { g6d_set_error("conv16_direct: Cout = 64 runs on the halo-patch kernel only (knob conv16_halo, tile shapes)"); return G6D_EINVAL; }
   if (!pertap_stats_ok) { g6d_set_error("conv16_direct: statistics groups must be whole tile rows (small maps: whole 64-pixel epilogue passes)"); return G6D_EINVAL; }
+  c16_report(route, p, 0, w_layout, math_mode, 1, false, false, c16::tap_grid(p));
   if (plan_only) return 0;
   return c16tap_launch(p, w_layout, math_mode, st);
 }
@@ -120,6 +136,16 @@ extern "C" int g6d_conv16_direct_plan(const G6dConv16Seg* segs, int nseg, int Ci
   return c16_direct(segs, nseg, Cin, W16, w_layout, 1.f, nullptr, Cout, kd, 0, full_type, pool_type, math_mode, stats, stat_rows_per_group, nullptr,
                     nullptr, true);
 }
+
+extern "C" int g6d_conv16_direct_route(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, int Cout, int kd, int full_type,
+                                       int pool_type, int math_mode, double* stats, int stat_rows_per_group, G6dConv16Route* route) {
+  if (!route) { g6d_set_error("conv16_direct_route: route expected"); return G6D_EINVAL; }
+  const int rc = c16_direct(segs, nseg, Cin, W16, w_layout, 1.f, nullptr, Cout, kd, 0, full_type, pool_type, math_mode, stats, stat_rows_per_group, nullptr,
+                            nullptr, true, route);
+  return rc < 0 ? rc : G6D_OK;
+}
+
+extern "C" int g6d_sizeof_conv16_route(void) { return (int)sizeof(G6dConv16Route); }
 
 extern "C" int g6d_conv16_direct_multi(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, float acc_scale,
                                        const float* bias, int Cout, int kd, int relu, int full_type, int pool_type, int math_mode, double* stats,

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256, 2) void conv16r_kernel(const C16Params p) {
 
 void c16tap_go(void (*kern)(const C16Params), int lds_bytes, const c16::Params& p, hipStream_t st) {
   g6d_allow_lds(reinterpret_cast<const void*>(kern), lds_bytes);
-  hipLaunchKernelGGL(kern, dim3((p.ptiles + 7) / 8 * 8 * p.nN), dim3(256), lds_bytes, st, C16Params{p});
+  hipLaunchKernelGGL(kern, dim3(c16::tap_grid(p)), dim3(256), lds_bytes, st, C16Params{p});
 }
 
 }  // namespace

@@ -574,7 +574,7 @@ C16wAdmit c16w_admit(c16::Params& p, const G6dConv16Seg* segs, bool pairs, bool 
 }
 
 int c16w_launch(const c16::Params& p, int math_mode, int wm, bool half_tile, bool folded, hipStream_t stream) {
-  const int blocks = ((p.ptiles + wm - 1) / wm + 7) / 8 * 8 * p.nN;
+  const int blocks = c16::halo_grid(p, wm);
   if (half_tile && math_mode != 3) {                           // Cout = 64 in a 16-bit mode: 32-channel waves
     if (math_mode == 1) c16w_go<1, 2, 1>(p, blocks, stream);
     else c16w_go<2, 2, 1>(p, blocks, stream);

@@ -64,6 +64,18 @@ class G6dConvRoute(C.Structure):
                 ("splits", C.c_int32), ("split_source", C.c_int32), ("position_major", C.c_int32)]
 
 
+class G6dConv16RouteSeg(C.Structure):
+    _fields_ = [("tile0", C.c_int32), ("tw_log2", C.c_int32), ("tiles_x", C.c_int32), ("tpi", C.c_int32), ("segh_log2", C.c_int32),
+                ("bands", C.c_int32)]
+
+
+class G6dConv16Route(C.Structure):
+    """include/gen6d_hip.h: what g6d_conv16_direct_route reports about a 16-bit direct launch."""
+    _fields_ = [("kernel", C.c_int32), ("w_layout", C.c_int32), ("math_mode", C.c_int32), ("kd", C.c_int32), ("wm", C.c_int32),
+                ("half_tile", C.c_int32), ("folded", C.c_int32), ("tiles", C.c_int32), ("nN", C.c_int32), ("blocks", C.c_int32),
+                ("seg", G6dConv16RouteSeg * 4)]
+
+
 class G6dConv(C.Structure):
     _fields_ = [
         ("in_", C.c_void_p), ("mul", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p),
@@ -126,6 +138,7 @@ SIGNATURES = {
     "g6d_product_split16_ex": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "g6d_affine_split16_ex": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
     "g6d_conv16_direct_plan": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I],
+    "g6d_conv16_direct_route": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, C.POINTER(G6dConv16Route)],
     "g6d_affine_split16_to": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
     "g6d_upsample_bilinear_split16": [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
     "g6d_l2norm_split16": [_P, _I, _I, _I, _P, _I, _P, _P],
@@ -210,6 +223,9 @@ def load():
     lib.g6d_sizeof_conv_route.restype = C.c_int
     if lib.g6d_sizeof_conv_route() != C.sizeof(G6dConvRoute):
         raise RuntimeError("libgen6d_hip.so: G6dConvRoute layout differs from the ctypes binding (stale build?)")
+    lib.g6d_sizeof_conv16_route.restype = C.c_int
+    if lib.g6d_sizeof_conv16_route() != C.sizeof(G6dConv16Route):
+        raise RuntimeError("libgen6d_hip.so: G6dConv16Route layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
         raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_mesh_desc() != C.sizeof(G6dMesh):

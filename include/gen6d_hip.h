@@ -422,6 +422,26 @@ int g6d_conv16_direct_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, cons
  * kernel with statistics groups of whole epilogue passes inside a tile of several small images. */
 int g6d_conv16_direct_plan(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, int Cout, int kd, int full_type, int pool_type,
                            int math_mode, double* stats, int stat_rows_per_group);
+/* The whole choice behind g6d_conv16_direct_plan's answer (additive to ABI v12; launches nothing, reads no operand, and is the launcher's
+   own decision code under the current knobs, not a restatement of it).  Returns G6D_OK, or G6D_EINVAL with the launch's message (the
+   fields are then not meaningful).  tests/conv16_sweep.py files its cases by it. */
+typedef struct G6dConv16Route {
+  int32_t kernel;          /* g6d_conv16_direct_plan's answer: 0 per-tap kernels, 1 halo-patch kernel, 2 halo-patch with per-pass statistics */
+  int32_t w_layout, math_mode, kd;     /* as passed */
+  int32_t wm;              /* pixel tiles per block: 1 or 2 (per-tap kernels: 1) */
+  int32_t half_tile;       /* 1: Cout = 64 packed as half of a 128-channel tile */
+  int32_t folded;          /* 1: depth-folded 3x3x3 layer (w_layout 2) */
+  int32_t tiles, nN, blocks;           /* 128-pixel tiles of the launch, channel blocks, blocks of the grid */
+  struct {
+    int32_t tile0;         /* first tile of the segment */
+    int32_t tw_log2, tiles_x;          /* tile width and tiles per map row (halo-patch: c16g::halo_tiling's; per-tap: c16g::pick_tw's) */
+    int32_t tpi;           /* halo-patch: tiles per image, 0 = banded tiles of whole small images; per-tap: 0 */
+    int32_t segh_log2, bands;          /* halo-patch: rows per band and bands per tile (1 = tiles inside one image); per-tap: 0 */
+  } seg[4];                /* segments past nseg: zeros */
+} G6dConv16Route;
+int g6d_conv16_direct_route(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, int w_layout, int Cout, int kd, int full_type, int pool_type,
+                            int math_mode, double* stats, int stat_rows_per_group, G6dConv16Route* route);
+int g6d_sizeof_conv16_route(void);
 int g6d_corr16_multi_ex(const G6dConv16Seg* segs, int nseg, int Cin, const void* W16, float acc_scale, int Cout, int k, int math_mode,
                         const G6dRange16* range, g6d_stream_t stream);
 int g6d_product_split16_ex(const float* ref, const float* que, const float* scale, const float* shift, void* out, int qn, int D, int P, int C,

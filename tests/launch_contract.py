@@ -343,6 +343,10 @@ E("g6d_conv16_direct_multi", [T("segs", lib.G6dConv16Seg, c16_rows(64, 128), C16
 E("g6d_conv16_direct_multi_ex",
   [T("segs", lib.G6dConv16Seg, c16_rows(64, 128), C16_FIELDS), *C16, F("acc_scale", 0.0), *C16_TAIL, X("relu", 1, FLAG), *C16_TYPES, R("range"), S()], c16_cases())
 E("g6d_conv16_direct_plan", [T("segs", lib.G6dConv16Seg, c16_rows(64, 128), C16_FIELDS), *C16, *C16_TAIL[1:], *C16_TYPES], c16_cases())
+# g6d_conv16_direct_route is g6d_conv16_direct_plan with the whole choice written out: the same decision code, so the same refusals; it launches
+# nothing and reads no operand (the pointers are only tested for NULL and alignment, as the launch tests them), and it needs its out struct.
+E("g6d_conv16_direct_route", [T("segs", lib.G6dConv16Seg, c16_rows(64, 128), C16_FIELDS), *C16, *C16_TAIL[1:], *C16_TYPES, H("route", C.c_int32, [0] * 34)],
+  c16_cases())
 
 
 def corr16_cases():

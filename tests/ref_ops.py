@@ -589,13 +589,15 @@ def conv16_direct_multi(xs, filt, bias, relu=True, full=None, pool=None, kd=1, s
         else:
             w = filt.w.to(dt).reshape(filt.Cout, 3, 3, 3, filt.Cin).permute(0, 4, 1, 2, 3)
             y = F.conv3d(v.permute(0, 4, 1, 2, 3), w, None if bias is None else bias.to(dt), padding=1).permute(0, 2, 3, 4, 1)
-        if stats is not None:
-            g = y.reshape(-1, y.shape[-1]) if rows_per_group <= 0 else y.reshape(-1, rows_per_group, y.shape[-1])
-            g = g[None] if rows_per_group <= 0 else g
-            stats[:g.shape[0], :, 0] += g.double().sum(1)
-            stats[:g.shape[0], :, 1] += (g.double() ** 2).sum(1)
         if relu:
             y = F.relu(y)
+        if stats is not None:          # of the stored values (after the ReLU, as the kernels' epilogue sums them); a last group may be short
+            g = y.reshape(-1, y.shape[-1])
+            if rows_per_group > 0 and g.shape[0] % rows_per_group:
+                g = torch.cat([g, g.new_zeros((rows_per_group - g.shape[0] % rows_per_group, g.shape[1]))])
+            g = g[None] if rows_per_group <= 0 else g.reshape(-1, rows_per_group, g.shape[-1])
+            stats[:g.shape[0], :, 0] += g.double().sum(1)
+            stats[:g.shape[0], :, 1] += (g.double() ** 2).sum(1)
 
         def coded(t, kind):
             if kind is None:

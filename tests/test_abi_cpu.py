@@ -25,7 +25,7 @@ def test_header_symbols_exported():
         assert hasattr(l, n), f"{n} declared in gen6d_hip.h but not exported by libgen6d_hip.so"
     assert l.g6d_abi_version() == 12
     # every typed binding corresponds to a declared symbol and vice versa
-    assert set(lib.SIGNATURES) | {"g6d_abi_version", "g6d_last_error", "g6d_sizeof_conv_desc", "g6d_sizeof_conv_route", "g6d_set_knob", "g6d_get_knob",
+    assert set(lib.SIGNATURES) | {"g6d_abi_version", "g6d_last_error", "g6d_sizeof_conv_desc", "g6d_sizeof_conv_route", "g6d_sizeof_conv16_route", "g6d_set_knob", "g6d_get_knob",
                                   "g6d_reset_knobs"} == set(names)
 
 
@@ -63,6 +63,8 @@ def test_struct_layout_matches_header():
     assert lib.G6dConv.math_mode.offset == 80 + 25 * 4 and lib.G6dConv.weight_wino.offset == 80 + 26 * 4
     # g6d_conv_route's report: eight int32
     assert C.sizeof(lib.G6dConvRoute) == 8 * 4 == lib.load().g6d_sizeof_conv_route()
+    # g6d_conv16_direct_route's report: ten int32 for the launch, six for each of four segments
+    assert C.sizeof(lib.G6dConv16Route) == (10 + 4 * 6) * 4 == lib.load().g6d_sizeof_conv16_route()
 
 
 def test_null_descriptor_is_rejected_without_gpu():
