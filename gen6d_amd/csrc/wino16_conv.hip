@@ -679,18 +679,30 @@ int w16_go(Wino16Kernel kernel, const WinoArgs& a, dim3 grid, int threads, size_
 
 }  // namespace
 
+// The kernel of a planned launch (a.splits set): the trunk kernels (mode 0, 2-D, no statistics; buffer loads) — two waves per SIMD for
+// un-split launches — or the conv-family one
+wino::Pick16 wino16_pick(const wino::Args& a, int mode, int kd) {
+  wino::Pick16 p = {};
+  if ((p.error = wplan::w16_limits(a.Cout, mode, a.Cin))) return p;
+  p.trunk = mode == 0 && kd == 1 && !a.stats;
+  // knob wino16_2w (tests run both kernels): 0 = the one-wave-per-SIMD kernel only
+  p.two_waves = p.trunk && g6d_knob(G6D_KNOB_WINO16_2W) != 0 && a.splits == 1;
+  p.threads = p.two_waves ? 512 : 256;
+  p.lds_bytes = p.two_waves ? wplan::w16b_lds_bytes() : wplan::w16_lds_bytes(mode, a.Cin);
+  if (!p.trunk && kd == 3 && (mode & 3) == 3) p.error = "wino16: no multiplier prologue for 3x3x3";
+  return p;
+}
+
 int wino16_launch(const wino::Args& args, int mode, int kd, long long blocks, hipStream_t stream) {
-  if (const char* why = wplan::w16_limits(args.Cout, mode, args.Cin)) { g6d_set_error(why); return G6D_EINVAL; }
+  const wino::Pick16 pick = wino16_pick(args, mode, kd);
+  if (pick.error) { g6d_set_error(pick.error); return G6D_EINVAL; }
   const WinoArgs a{args};
   const int t = a.mm == 1 ? 0 : 1;              // operand type: bf16, fp16
   const dim3 grid((unsigned)blocks, a.Cout / 64, a.splits);
-  const size_t lds16 = wplan::w16_lds_bytes(mode, a.Cin);
-  if (mode == 0 && kd == 1 && !a.stats) {       // the trunk kernels (buffer loads): two waves per SIMD for un-split launches
+  if (pick.trunk) {
     static const Wino16Kernel one_wave[2] = {wino16_conv3x3_kernel<1, 2>, wino16_conv3x3_kernel<2, 2>};
     static const Wino16Kernel two_waves[2] = {wino16b_conv3x3_kernel<1>, wino16b_conv3x3_kernel<2>};
-    // knob wino16_2w (tests run both kernels): 0 = the one-wave-per-SIMD kernel only
-    if (g6d_knob(G6D_KNOB_WINO16_2W) != 0 && a.splits == 1) return w16_go(two_waves[t], a, grid, 512, wplan::w16b_lds_bytes(), stream);
-    return w16_go(one_wave[t], a, grid, 256, lds16, stream);
+    return w16_go(pick.two_waves ? two_waves[t] : one_wave[t], a, grid, pick.threads, pick.lds_bytes, stream);
   }
   static const Wino16Kernel conv[2][2][4] = {   // [operand type][kd == 3][mode]
     {{wino16_conv_kernel<1, 0, 1>, wino16_conv_kernel<1, 1, 1>, wino16_conv_kernel<1, 2, 1>, wino16_conv_kernel<1, 3, 1>},
@@ -698,6 +710,5 @@ int wino16_launch(const wino::Args& args, int mode, int kd, long long blocks, hi
     {{wino16_conv_kernel<2, 0, 1>, wino16_conv_kernel<2, 1, 1>, wino16_conv_kernel<2, 2, 1>, wino16_conv_kernel<2, 3, 1>},
      {wino16_conv_kernel<2, 0, 3>, wino16_conv_kernel<2, 1, 3>, wino16_conv_kernel<2, 2, 3>, nullptr}}};
   const Wino16Kernel kernel = conv[t][kd == 3][mode & 3];
-  if (!kernel) { g6d_set_error("wino16: no multiplier prologue for 3x3x3"); return G6D_EINVAL; }
-  return w16_go(kernel, a, grid, 256, lds16, stream);
+  return w16_go(kernel, a, grid, pick.threads, pick.lds_bytes, stream);      // (the table's one hole: wino16_pick refused it)
 }

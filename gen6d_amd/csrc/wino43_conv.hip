@@ -716,15 +716,21 @@ __global__ void __launch_bounds__(256, 1) wino43_kernel(const W43Args p) {
 }
 
 // ---- launch: plan (wino_plan.h), instantiation
-template <int MODE, int KD, int NT>
-int w43_launch_t(W43Args& a, long long blocks, hipStream_t stream) {
-  const size_t need = std::max(wplan::f4_lds_bytes(MODE, NT, a.Cin), (size_t)4 * 4096 * sizeof(float));      // the epilogue exchange: 16 KB per wave
-  g6d_allow_lds(reinterpret_cast<const void*>(&wino43_kernel<MODE, KD, NT>), (int)wplan::LDS_MAX - 512);      // (512 B of static LDS: the quarter table)
-  a.gx = (int)blocks; a.gy = a.Cout / (16 * NT);
+// The grid of a planned launch, chosen once (w43_prepare) for the launch and for g6d_wino_multi_route: fills a.gx, a.gy and the block-id
+// decode a.map_mode (knob w43_map; 0 when there is one channel slice or the 1-D grid would not fit 31 bits)
+struct W43Grid { dim3 grid; size_t lds_bytes; };
+W43Grid w43_grid_of(W43Args& a, int mode, int nt, long long blocks) {
+  a.gx = (int)blocks; a.gy = a.Cout / (16 * nt);
   a.map_mode = (int)g6d_knob(G6D_KNOB_W43_MAP);
   if (a.gy == 1 || (long long)a.gx * a.gy >= (1ll << 31)) a.map_mode = 0;
-  const dim3 grid = a.map_mode == 0 ? dim3((unsigned)blocks, a.gy, a.splits) : dim3((unsigned)(blocks * a.gy), 1, a.splits);
-  hipLaunchKernelGGL((wino43_kernel<MODE, KD, NT>), grid, dim3(256), need, stream, a);
+  return W43Grid{a.map_mode == 0 ? dim3((unsigned)blocks, a.gy, a.splits) : dim3((unsigned)(blocks * a.gy), 1, a.splits),
+                 std::max(wplan::f4_lds_bytes(mode, nt, a.Cin), (size_t)4 * 4096 * sizeof(float))};      // the epilogue exchange: 16 KB per wave
+}
+
+template <int MODE, int KD, int NT>
+int w43_launch_t(W43Args& a, const W43Grid& g, hipStream_t stream) {
+  g6d_allow_lds(reinterpret_cast<const void*>(&wino43_kernel<MODE, KD, NT>), (int)wplan::LDS_MAX - 512);      // (512 B of static LDS: the quarter table)
+  hipLaunchKernelGGL((wino43_kernel<MODE, KD, NT>), g.grid, dim3(256), g.lds_bytes, stream, a);
   return g6d_check_launch("wino43_conv3x3");
 }
 
@@ -736,25 +742,32 @@ wplan::F4Plan w43_plan_of(W43Args& a, int mode, int kd, bool has_workspace, size
                         G6D_WS_COUNTERS, knobs);
 }
 
-int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
-  const wplan::F4Plan pl = w43_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
+// Everything of a launch but the launch: the plan, the geometry / split fields of `a`, the grid.  G6D_EINVAL = refused (message set)
+int w43_prepare(W43Args& a, int mode, int kd, const float* workspace, size_t workspace_bytes, wplan::F4Plan& pl, W43Grid& g) {
+  pl = w43_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
   if (pl.error) { g6d_set_error(pl.error); return G6D_EINVAL; }
+  if (kd != 25 && kd != 9 && pl.nt != 4) { g6d_set_error("wino43: Cout % 64 == 0 expected"); return G6D_EINVAL; }
   a.H0 = a.seg[0].H; a.W0 = a.seg[0].W; a.ld0 = a.seg[0].ld_in;
   a.qtotal = (int)pl.q.quarters;
   a.in_bytes = (unsigned)(pl.q.in_extent * 4);
-  a.splits = pl.split.splits; a.chunks_per_split = pl.split.chunks_per_split; a.ws = workspace;
+  a.splits = pl.split.splits; a.chunks_per_split = pl.split.chunks_per_split; a.ws = const_cast<float*>(workspace);
+  g = w43_grid_of(a, mode, pl.nt, pl.blocks);
+  return G6D_OK;
+}
+
+int w43_run(W43Args& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+  wplan::F4Plan pl; W43Grid g;
+  if (int rc = w43_prepare(a, mode, kd, workspace, workspace_bytes, pl, g)) return rc;
   if (g6d_knob(G6D_KNOB_WINO_DEBUG) == 1)
     fprintf(stderr, "wino43 %d seg, %dx%dx%d->%d kd=%d mode=%d: grid %lld x %d splits of %d chunks\n", a.nseg, a.seg[0].H, a.seg[0].W, a.Cin,
             a.Cout, kd, mode, pl.grid2, a.splits, a.chunks_per_split);
-  const long long blocks = pl.blocks;
   const int nt = pl.nt;
-  if (kd == 25) return nt == 4 ? w43_launch_t<0, 25, 4>(a, blocks, stream) : w43_launch_t<0, 25, 2>(a, blocks, stream);
-  if (kd == 9) return nt == 4 ? w43_launch_t<0, 9, 4>(a, blocks, stream) : w43_launch_t<0, 9, 2>(a, blocks, stream);
-  if (nt != 4) { g6d_set_error("wino43: Cout % 64 == 0 expected"); return G6D_EINVAL; }
-  if (kd == 3) return mode == 2 ? w43_launch_t<2, 3, 4>(a, blocks, stream) : mode == 1 ? w43_launch_t<1, 3, 4>(a, blocks, stream) : w43_launch_t<0, 3, 4>(a, blocks, stream);
-  if (mode == 2) return w43_launch_t<2, 1, 4>(a, blocks, stream);
-  if (mode == 1) return w43_launch_t<1, 1, 4>(a, blocks, stream);
-  return w43_launch_t<0, 1, 4>(a, blocks, stream);
+  if (kd == 25) return nt == 4 ? w43_launch_t<0, 25, 4>(a, g, stream) : w43_launch_t<0, 25, 2>(a, g, stream);
+  if (kd == 9) return nt == 4 ? w43_launch_t<0, 9, 4>(a, g, stream) : w43_launch_t<0, 9, 2>(a, g, stream);
+  if (kd == 3) return mode == 2 ? w43_launch_t<2, 3, 4>(a, g, stream) : mode == 1 ? w43_launch_t<1, 3, 4>(a, g, stream) : w43_launch_t<0, 3, 4>(a, g, stream);
+  if (mode == 2) return w43_launch_t<2, 1, 4>(a, g, stream);
+  if (mode == 1) return w43_launch_t<1, 1, 4>(a, g, stream);
+  return w43_launch_t<0, 1, 4>(a, g, stream);
 }
 
 }  // namespace
@@ -771,16 +784,21 @@ extern "C" int g6d_w43_timing_read(unsigned long long* out) {      // [4 waves][
 // One trunk layer over up to 4 map sizes in ONE launch, as g6d_wino_conv3x3_multi, on the F(4x4,3x3) kernel.  U43 = the filters
 // transformed on the host (backbone.winograd43_filters): [Cin/8][2][Cout/64][18][2][4][16][4] (include/gen6d_hip.h).
 // Replaces features[4..27] of vgg11_bn on the detector's image pyramid (network/pretrain_models.py:17-25, network/detector.py:236-241).
-extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U43, const float* bias, int Cout, int relu,
-                                        float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+static int w43_multi_args(const G6dWinoSeg* segs, int nseg, int Cin, const float* U43, const float* bias, int Cout, int relu, W43Args& a) {
   if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U43 || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U43)) {
     g6d_set_error("wino43_conv3x3_multi: bad args (1..4 segments, Cin % 8 == 0, Cout % 64 == 0)"); return G6D_EINVAL;
   }
   G6dSegTable t;
   if (int rc = g6d_seg_table("wino43_conv3x3_multi", "segment", G6D_SAME_KINDS, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
-  W43Args a = {};
+  a = W43Args{};
   a.U = U43; a.bias = bias; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1;
   wplan::segments(t, a.seg, a.nseg, a.in, a.out_full, a.out_pool);
+  return G6D_OK;
+}
+extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U43, const float* bias, int Cout, int relu,
+                                        float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+  W43Args a;
+  if (int rc = w43_multi_args(segs, nseg, Cin, U43, bias, Cout, relu, a)) return rc;
   return w43_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -789,8 +807,7 @@ extern "C" int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Ci
 // as 3x3 blocks — the 7x7 level with its filters zero-extended by one tap on every side: 9 * 36 / 16 = 20.25 multiplications instead of 49.  Maps as g6d_corr2d_wino_multi;
 // U43 = the 25 sub-filter banks transformed like g6d_wino43_conv3x3_multi's, CHUNK-major: [Cin/8 * 25][2][Cout/CB][18][CB/32][4][16][4], row
 // c * 25 + b = 8-channel chunk c of block b = 5 bi + bj holding w[:, 3bi..3bi+2, 3bj..3bj+2, :]; Cout % 32 == 0.
-extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin, const float* U43, int Cout, int kblocks, float* workspace,
-                                       size_t workspace_bytes, g6d_stream_t stream) {
+static int w43_corr_args(const G6dCorrSeg* segs, int nseg, int Cin, const float* U43, int Cout, int kblocks, W43Args& a) {
   if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U43 || (kblocks != 5 && kblocks != 3) || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 31) || !g6d_aligned16(U43)) {
     g6d_set_error("corr2d_wino43_multi: bad args (1..4 map sizes, 15x15 = 5 blocks or 9x9 = 3 blocks, Cin % 8 == 0, Cout % 32 == 0)"); return G6D_EINVAL;
   }
@@ -798,10 +815,34 @@ extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin
     if (segs[k].ld_in != segs[0].ld_in) return g6d_bad_seg("corr2d_wino43_multi", "map", G6D_SHARED_LD_IN);
   G6dSegTable t;
   if (int rc = g6d_seg_table("corr2d_wino43_multi", "map", G6D_SHARED_LD_IN, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
-  W43Args a = {};
+  a = W43Args{};
   a.U = U43; a.bias = nullptr; a.Cin = Cin; a.Cout = Cout; a.relu = 0; a.D = 1;
   wplan::segments(t, a.seg, a.nseg, a.in, a.out_full, a.out_pool);
+  return G6D_OK;
+}
+extern "C" int g6d_corr2d_wino43_multi(const G6dCorrSeg* segs, int nseg, int Cin, const float* U43, int Cout, int kblocks, float* workspace,
+                                       size_t workspace_bytes, g6d_stream_t stream) {
+  W43Args a;
+  if (int rc = w43_corr_args(segs, nseg, Cin, U43, Cout, kblocks, a)) return rc;
   return w43_run(a, 0, kblocks * kblocks, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+// g6d_wino_multi_route (wino_conv.hip) for the two entry points above: their own argument checks and segment table, then w43_prepare
+int g6d_w43_multi_route(bool corr, const void* segs, int nseg, int Cin, const void* U, int Cout, int kblocks, const float* workspace,
+                        size_t workspace_bytes, G6dWinoRoute& r) {
+  W43Args a;
+  const float* U43 = static_cast<const float*>(U);
+  const int kd = corr ? kblocks * kblocks : 1;
+  if (int rc = corr ? w43_corr_args(static_cast<const G6dCorrSeg*>(segs), nseg, Cin, U43, Cout, kblocks, a)
+                    : w43_multi_args(static_cast<const G6dWinoSeg*>(segs), nseg, Cin, U43, nullptr, Cout, 0, a)) return rc;
+  wplan::F4Plan pl; W43Grid g;
+  if (int rc = w43_prepare(a, 0, kd, workspace, workspace_bytes, pl, g)) return rc;
+  r = G6dWinoRoute{};
+  r.family = 3; r.kd = kd; r.nq = wplan::F4_NQ; r.nwn = pl.nt;
+  r.grid2 = pl.grid2; r.blocks = (int)pl.blocks; r.nchunks = pl.nchunks; r.splits = a.splits; r.chunks_per_split = a.chunks_per_split;
+  r.map_mode = a.map_mode; r.lds_bytes = (int)g.lds_bytes;
+  for (int k = 0; k < a.nseg; ++k) { r.seg[k].qstart = a.seg[k].qstart; r.seg[k].QH = a.seg[k].QH; r.seg[k].QW = a.seg[k].QW; }
+  return G6D_OK;
 }
 
 // ---- the conv family on the F(4x4,3x3) kernel (called by g6d_conv_igemm when G6dConv.weight_wino43 is set): kernel (1,3,3) on 2-D maps

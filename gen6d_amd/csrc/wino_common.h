@@ -47,6 +47,11 @@ struct Args {
 // The 16-bit kernels (wino16_conv.hip) on a planned launch (geometry and split fields of `a` filled, `blocks` blocks of four quarters):
 // the two trunk kernels (mode 0, 2-D, no statistics) or the conv-family one; kd = 1 or 3, mode as the kernels' MODE.
 int wino16_launch(const wino::Args& a, int mode, int kd, long long blocks, hipStream_t stream);
+// Which of them that launch runs (wino16_launch itself and g6d_wino_multi_route ask): error = the launch's refusal, or nullptr
+namespace wino {
+struct Pick16 { const char* error; bool trunk, two_waves; int threads; size_t lds_bytes; };
+}  // namespace wino
+wino::Pick16 wino16_pick(const wino::Args& a, int mode, int kd);
 
 namespace {
 

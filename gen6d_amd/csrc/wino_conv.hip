@@ -470,21 +470,25 @@ __global__ void __launch_bounds__(64 * NWM * NWN, 1) wino_conv3x3_kernel(const W
 }
 
 // ---- launch: plan (wino_plan.h), instantiation
+// The instantiation of a planned launch, chosen once (wino_prepare) for the launch and for g6d_wino_multi_route: family as
+// G6dWinoRoute.family; NWN x NWM waves per block (wide: 4 x 1), the 16-bit kernels: wino16_pick's answer
+struct WinoPick { int family, nwn, nwm; size_t lds_bytes; };
+
 template <int MODE, int KD, int NWN, int NWM = 2>
-int wino_launch_t(WinoArgs& a, long long blocks, hipStream_t stream) {
+int wino_launch_t(WinoArgs& a, long long blocks, const WinoPick& pick, hipStream_t stream) {
   constexpr int THREADS = 64 * NWM * NWN;
   g6d_allow_lds(reinterpret_cast<const void*>(&wino_conv3x3_kernel<MODE, KD, NWN, NWM>), (int)wplan::LDS_MAX);
   hipLaunchKernelGGL((wino_conv3x3_kernel<MODE, KD, NWN, NWM>), dim3((unsigned)blocks, a.Cout / (32 * NWN), a.splits), dim3(THREADS),
-                     wplan::f2_lds_bytes(MODE, NWN, NWM, a.Cin), stream, a);
+                     pick.lds_bytes, stream, a);
   return g6d_check_launch("wino_conv3x3");
 }
 
 template <int MODE, int KD>
-int wino_launch_w(WinoArgs& a, long long blocks, int nwn, hipStream_t stream) {
-  return nwn == 1 ? wino_launch_t<MODE, KD, 1>(a, blocks, stream) : wino_launch_t<MODE, KD, 2>(a, blocks, stream);
+int wino_launch_w(WinoArgs& a, long long blocks, const WinoPick& pick, hipStream_t stream) {
+  return pick.nwn == 1 ? wino_launch_t<MODE, KD, 1>(a, blocks, pick, stream) : wino_launch_t<MODE, KD, 2>(a, blocks, pick, stream);
 }
 
-// The plan of one launch under the current knobs (wino_run; g6d_wino_route): completes a one-map argument block's segment list first
+// The plan of one launch under the current knobs (wino_prepare; g6d_wino_route): completes a one-map argument block's segment list first
 wplan::F2Plan wino_plan_of(WinoArgs& a, int mode, int kd, bool has_workspace, size_t workspace_bytes) {
   if (a.nseg == 0) {          // one map size: the launch's own fields
     a.nseg = 1;
@@ -497,28 +501,51 @@ wplan::F2Plan wino_plan_of(WinoArgs& a, int mode, int kd, bool has_workspace, si
                         wplan::room(has_workspace, workspace_bytes, G6D_WS_COUNTER_BYTES), G6D_WS_COUNTERS, knobs);
 }
 
-// Fills the geometry / split fields of `a` and launches.  kd = 1, 3 or 25; mode as the kernel's MODE.
-int wino_run(WinoArgs& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
-  const wplan::F2Plan pl = wino_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
+// Everything of a launch but the launch: the plan, the geometry / split fields of `a`, the instantiation.  G6D_EINVAL = refused (message
+// set).  kd = 1, 3 or 25; mode as the kernel's MODE.
+int wino_prepare(WinoArgs& a, int mode, int kd, const float* workspace, size_t workspace_bytes, wplan::F2Plan& pl, WinoPick& pick) {
+  pl = wino_plan_of(a, mode, kd, workspace != nullptr, workspace_bytes);
   if (pl.error) { g6d_set_error(pl.error); return G6D_EINVAL; }
   a.QH = a.seg[0].QH; a.QW = a.seg[0].QW;
   a.qtotal = (int)pl.q.quarters;
   a.in_bytes = (unsigned)(pl.q.in_extent * 4);
-  a.splits = pl.split.splits; a.chunks_per_split = pl.split.chunks_per_split; a.ws = workspace;
+  a.splits = pl.split.splits; a.chunks_per_split = pl.split.chunks_per_split; a.ws = const_cast<float*>(workspace);
+  if (a.mm) {
+    const wino::Pick16 p16 = wino16_pick(a, mode, kd);
+    if (p16.error) { g6d_set_error(p16.error); return G6D_EINVAL; }
+    pick = WinoPick{p16.two_waves ? 2 : 1, pl.shape.nwn, 2, p16.lds_bytes};
+    return G6D_OK;
+  }
+  const int nwm = pl.shape.wide ? 1 : 2;
+  pick = WinoPick{0, pl.shape.nwn, nwm, wplan::f2_lds_bytes(mode, pl.shape.nwn, nwm, a.Cin)};
+  return G6D_OK;
+}
+
+int wino_run(WinoArgs& a, int mode, int kd, float* workspace, size_t workspace_bytes, hipStream_t stream) {
+  wplan::F2Plan pl; WinoPick pick;
+  if (int rc = wino_prepare(a, mode, kd, workspace, workspace_bytes, pl, pick)) return rc;
   if (g6d_knob(G6D_KNOB_WINO_DEBUG) == 1)
     fprintf(stderr, "wino %d seg, N=%d %dx%dx%d->%d kd=%d mode=%d: grid %lld x %d splits of %d chunks\n", a.nseg, a.N, a.H, a.W, a.Cin,
             a.Cout, kd, mode, pl.grid2, a.splits, a.chunks_per_split);
   const long long blocks = pl.blocks;
-  const int nwn = pl.shape.nwn;
   if (a.mm) return wino16_launch(a, mode, kd, blocks, stream);
-  if (kd == 25) return wino_launch_w<0, 25>(a, blocks, nwn, stream);
-  if (kd == 3) return mode == 2 ? wino_launch_w<2, 3>(a, blocks, nwn, stream)
-                    : mode == 1 ? wino_launch_w<1, 3>(a, blocks, nwn, stream) : wino_launch_w<0, 3>(a, blocks, nwn, stream);
-  if (mode == 3) return wino_launch_w<3, 1>(a, blocks, nwn, stream);
-  if (mode == 2) return wino_launch_w<2, 1>(a, blocks, nwn, stream);
-  if (mode == 1) return wino_launch_w<1, 1>(a, blocks, nwn, stream);
-  if (pl.shape.wide) return wino_launch_t<0, 1, 4, 1>(a, blocks, stream);
-  return wino_launch_w<0, 1>(a, blocks, nwn, stream);
+  if (kd == 25) return wino_launch_w<0, 25>(a, blocks, pick, stream);
+  if (kd == 3) return mode == 2 ? wino_launch_w<2, 3>(a, blocks, pick, stream)
+                    : mode == 1 ? wino_launch_w<1, 3>(a, blocks, pick, stream) : wino_launch_w<0, 3>(a, blocks, pick, stream);
+  if (mode == 3) return wino_launch_w<3, 1>(a, blocks, pick, stream);
+  if (mode == 2) return wino_launch_w<2, 1>(a, blocks, pick, stream);
+  if (mode == 1) return wino_launch_w<1, 1>(a, blocks, pick, stream);
+  if (pick.nwn == 4) return wino_launch_t<0, 1, 4, 1>(a, blocks, pick, stream);
+  return wino_launch_w<0, 1>(a, blocks, pick, stream);
+}
+
+// What g6d_wino_multi_route reports of a prepared launch
+void wino_report(const WinoArgs& a, int entry, int kd, const wplan::F2Plan& pl, const WinoPick& pick, G6dWinoRoute& r) {
+  r = G6dWinoRoute{};
+  r.entry = entry; r.family = pick.family; r.kd = kd; r.wide = pl.shape.wide; r.nq = pl.shape.nq; r.nwn = pl.shape.nwn;
+  r.grid2 = pl.grid2; r.blocks = (int)pl.blocks; r.nchunks = pl.nchunks; r.splits = a.splits; r.chunks_per_split = a.chunks_per_split;
+  r.lds_bytes = (int)pick.lds_bytes;
+  for (int k = 0; k < a.nseg; ++k) { r.seg[k].qstart = a.seg[k].qstart; r.seg[k].QH = a.seg[k].QH; r.seg[k].QW = a.seg[k].QW; }
 }
 
 // The segment list and bases of a multi-map launch from its validated table (seg_table.h); the scalar fields = segment 0
@@ -537,50 +564,67 @@ void wino_segments(WinoArgs& a, const G6dSegTable& t) {
 //   out_pool (optional) [N][H/2][W/2][ld_pool] <- 2x2 max-pool of y (floor, as F.max_pool2d)
 //   workspace (optional): split partial outputs for grids that would not fill the chip (splits*N*H*W*Cout floats)
 // Replaces features[4..27] of vgg11_bn (conv + folded BatchNorm + ReLU + MaxPool), network/pretrain_models.py:17-25,66-72.
-extern "C" int g6d_wino_conv3x3(const float* in, int N, int H, int W, int Cin, int ld_in, const float* U, const float* bias,
-                                int Cout, int relu, float* out_full, int ld_full, float* out_pool, int ld_pool,
-                                float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+static int wino_single_args(const float* in, int N, int H, int W, int Cin, int ld_in, const float* U, const float* bias, int Cout, int relu,
+                            float* out_full, int ld_full, float* out_pool, int ld_pool, WinoArgs& a) {
   if (!in || !U || (!out_full && !out_pool) || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7) || (ld_in & 3) || ld_in < Cin ||
       Cout <= 0 || (Cout & 63) || (out_full && ld_full < Cout) || (out_pool && (ld_pool < Cout || H < 2 || W < 2)) ||
       !g6d_aligned16(in) || !g6d_aligned16(U) || (long long)N * H * W * ld_in >= (1ll << 29)) {
     g6d_set_error("wino_conv3x3: bad args (Cin % 8 == 0, Cout % 64 == 0, 16-byte aligned operands)"); return G6D_EINVAL;
   }
-  WinoArgs a = {};
+  a = WinoArgs{};
   a.in = in; a.U = U; a.bias = bias; a.out_full = out_full; a.out_pool = out_pool;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ld_in = ld_in; a.Cout = Cout; a.ld_full = ld_full; a.ld_pool = ld_pool; a.relu = relu;
   a.D = 1;
+  return G6D_OK;
+}
+extern "C" int g6d_wino_conv3x3(const float* in, int N, int H, int W, int Cin, int ld_in, const float* U, const float* bias,
+                                int Cout, int relu, float* out_full, int ld_full, float* out_pool, int ld_pool,
+                                float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+  WinoArgs a;
+  if (int rc = wino_single_args(in, N, H, W, Cin, ld_in, U, bias, Cout, relu, out_full, ld_full, out_pool, ld_pool, a)) return rc;
   return wino_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The same layer over up to 4 map sizes in ONE launch (G6dWinoSeg, include/gen6d_hip.h): the scales of the detector's image
 // pyramid (network/detector.py:236-241) run every trunk layer with the same filters.
-extern "C" int g6d_wino_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U, const float* bias, int Cout, int relu,
-                                      float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+static int wino_multi_args(const G6dWinoSeg* segs, int nseg, int Cin, const float* U, const float* bias, int Cout, int relu, WinoArgs& a) {
   if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U)) {
     g6d_set_error("wino_conv3x3_multi: bad args (1..4 segments, Cin % 8 == 0, Cout % 64 == 0)"); return G6D_EINVAL;
   }
   G6dSegTable t;
   if (int rc = g6d_seg_table("wino_conv3x3_multi", "segment", G6D_SAME_KINDS, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
-  WinoArgs a = {};
+  a = WinoArgs{};
   a.U = U; a.bias = bias; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1;
   wino_segments(a, t);
+  return G6D_OK;
+}
+extern "C" int g6d_wino_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U, const float* bias, int Cout, int relu,
+                                      float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+  WinoArgs a;
+  if (int rc = wino_multi_args(segs, nseg, Cin, U, bias, Cout, relu, a)) return rc;
   return wino_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Reduced-precision variant of g6d_wino_conv3x3_multi (math_mode 1 = bf16, 2 = fp16 operands, fp32 accumulation and outputs): U16 =
 // the filters transformed AND rounded on the host, [Cin/16][16][Cout][16] 16-bit values in the layout of g6d_wino_conv3x3's U with a
 // chunk of 16 input channels (rows with co & 8 carry their two 16-byte halves swapped); Cin % 16 == 0, Cout % 64 == 0.
-extern "C" int g6d_wino16_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const void* U16, const float* bias, int Cout, int relu,
-                                        int math_mode, float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+static int wino16_multi_args(const G6dWinoSeg* segs, int nseg, int Cin, const void* U16, const float* bias, int Cout, int relu, int math_mode,
+                             WinoArgs& a) {
   if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U16 || Cin <= 0 || (Cin & 15) || Cout <= 0 || (Cout & 63) || !g6d_aligned16(U16) ||
       (math_mode != 1 && math_mode != 2)) {
     g6d_set_error("wino16_conv3x3_multi: bad args (1..4 segments, Cin % 16 == 0, Cout % 64 == 0, math_mode 1 or 2)"); return G6D_EINVAL;
   }
   G6dSegTable t;
   if (int rc = g6d_seg_table("wino16_conv3x3_multi", "segment", G6D_SAME_KINDS, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
-  WinoArgs a = {};
+  a = WinoArgs{};
   a.U = reinterpret_cast<const float*>(U16); a.bias = bias; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.D = 1; a.mm = math_mode;
   wino_segments(a, t);
+  return G6D_OK;
+}
+extern "C" int g6d_wino16_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const void* U16, const float* bias, int Cout, int relu,
+                                        int math_mode, float* workspace, size_t workspace_bytes, g6d_stream_t stream) {
+  WinoArgs a;
+  if (int rc = wino16_multi_args(segs, nseg, Cin, U16, bias, Cout, relu, math_mode, a)) return rc;
   return wino_run(a, 0, 1, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -589,8 +633,7 @@ extern "C" int g6d_wino16_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Ci
 // g6d_corr2d_patch.  Maps as in g6d_corr2d_patch_multi (up to 4 sizes, N maps each); U = the 25 sub-filter banks transformed like
 // g6d_wino_conv3x3's, CHUNK-major: [Cin/8 * 25][16][Cout][8], row c * 25 + b = 8-channel chunk c of block b = 5 bi + bj, which holds
 // w[:, 3bi..3bi+2, 3bj..3bj+2, 8c..8c+7] (include/gen6d_hip.h, backbone.winograd_corr_filters; the kernel walks kd = chunk % 25 innermost).
-extern "C" int g6d_corr2d_wino_multi(const G6dCorrSeg* segs, int nseg, int Cin, const float* U, int Cout, int kblocks, float* workspace,
-                                     size_t workspace_bytes, g6d_stream_t stream) {
+static int wino_corr_args(const G6dCorrSeg* segs, int nseg, int Cin, const float* U, int Cout, int kblocks, WinoArgs& a) {
   if (!segs || nseg < 1 || nseg > wplan::MAX_SEG || !U || kblocks != 5 || Cin <= 0 || (Cin & 7) || Cout <= 0 || (Cout & 31) || !g6d_aligned16(U)) {
     g6d_set_error("corr2d_wino_multi: bad args (1..4 map sizes, 15x15 = 5 blocks, Cin % 8 == 0, Cout % 32 == 0)"); return G6D_EINVAL;
   }
@@ -598,11 +641,48 @@ extern "C" int g6d_corr2d_wino_multi(const G6dCorrSeg* segs, int nseg, int Cin, 
     if (segs[k].ld_in != segs[0].ld_in) return g6d_bad_seg("corr2d_wino_multi", "map", G6D_SHARED_LD_IN);
   G6dSegTable t;
   if (int rc = g6d_seg_table("corr2d_wino_multi", "map", G6D_SHARED_LD_IN, segs, nseg, Cin, Cout, G6D_REACH_BUFFER_LOAD, t)) return rc;
-  WinoArgs a = {};
+  a = WinoArgs{};
   a.U = U; a.bias = nullptr; a.Cin = Cin; a.Cout = Cout; a.relu = 0; a.D = 1;
   wino_segments(a, t);
+  return G6D_OK;
+}
+extern "C" int g6d_corr2d_wino_multi(const G6dCorrSeg* segs, int nseg, int Cin, const float* U, int Cout, int kblocks, float* workspace,
+                                     size_t workspace_bytes, g6d_stream_t stream) {
+  WinoArgs a;
+  if (int rc = wino_corr_args(segs, nseg, Cin, U, Cout, kblocks, a)) return rc;
   return wino_run(a, 0, kblocks * kblocks, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
+
+// The host's choice for a launch of one of the entry points above or of wino43_conv.hip, without the launch (include/gen6d_hip.h): the
+// entry's own argument checks and segment table, then wino_prepare — what the launch itself runs before hipLaunchKernelGGL
+int g6d_w43_multi_route(bool corr, const void* segs, int nseg, int Cin, const void* U, int Cout, int kblocks, const float* workspace,
+                        size_t workspace_bytes, G6dWinoRoute& route);      // (wino43_conv.hip)
+extern "C" int g6d_wino_multi_route(int entry, const void* segs, int nseg, int Cin, const void* U, int Cout, int kblocks, int math_mode,
+                                    const float* workspace, size_t workspace_bytes, G6dWinoRoute* route) {
+  if (!route) { g6d_set_error("wino_multi_route: route expected"); return G6D_EINVAL; }
+  if (entry < 0 || entry > 5) { g6d_set_error("wino_multi_route: entry 0 ... 5 expected"); return G6D_EINVAL; }
+  if (entry == 3 || entry == 5) {
+    const int rc = g6d_w43_multi_route(entry == 5, segs, nseg, Cin, U, Cout, kblocks, workspace, workspace_bytes, *route);
+    route->entry = entry;
+    return rc;
+  }
+  const G6dWinoSeg* ws = static_cast<const G6dWinoSeg*>(segs);
+  const float* Uf = static_cast<const float*>(U);
+  WinoArgs a;
+  int rc, kd = 1;
+  if (entry == 1) {
+    if (!ws || nseg != 1) { g6d_set_error("wino_multi_route: one G6dWinoSeg row expected for g6d_wino_conv3x3"); return G6D_EINVAL; }
+    rc = wino_single_args(ws->in, ws->N, ws->H, ws->W, Cin, ws->ld_in, Uf, nullptr, Cout, 0, ws->out_full, ws->ld_full, ws->out_pool, ws->ld_pool, a);
+  } else if (entry == 0) rc = wino_multi_args(ws, nseg, Cin, Uf, nullptr, Cout, 0, a);
+  else if (entry == 2) rc = wino16_multi_args(ws, nseg, Cin, U, nullptr, Cout, 0, math_mode, a);
+  else { rc = wino_corr_args(static_cast<const G6dCorrSeg*>(segs), nseg, Cin, Uf, Cout, kblocks, a); kd = kblocks * kblocks; }
+  if (rc) return rc;
+  wplan::F2Plan pl; WinoPick pick;
+  if ((rc = wino_prepare(a, 0, kd, workspace, workspace_bytes, pl, pick))) return rc;
+  wino_report(a, entry, kd, pl, pick, *route);
+  return G6D_OK;
+}
+extern "C" int g6d_sizeof_wino_route(void) { return (int)sizeof(G6dWinoRoute); }
 
 // ---- the conv family on the Winograd kernel (called by g6d_conv_igemm when G6dConv.weight_wino is set)
 // Eligible: kernel (1,3,3) on 2-D maps or (3,3,3), stride 1, "same" padding, Cin % 8 == 0, Cout % 32 == 0, maps of at least

@@ -76,6 +76,22 @@ class G6dConv16Route(C.Structure):
                 ("seg", G6dConv16RouteSeg * 4)]
 
 
+class G6dWinoRouteSeg(C.Structure):
+    _fields_ = [("qstart", C.c_int32), ("QH", C.c_int32), ("QW", C.c_int32)]
+
+
+class G6dWinoRoute(C.Structure):
+    """include/gen6d_hip.h: what g6d_wino_multi_route reports about a launch of one of the Winograd entry points (WINO_ROUTE_ENTRIES)."""
+    _fields_ = [("entry", C.c_int32), ("family", C.c_int32), ("kd", C.c_int32), ("wide", C.c_int32), ("nq", C.c_int32), ("nwn", C.c_int32),
+                ("grid2", C.c_int64), ("blocks", C.c_int32), ("nchunks", C.c_int32), ("splits", C.c_int32), ("chunks_per_split", C.c_int32),
+                ("map_mode", C.c_int32), ("lds_bytes", C.c_int32), ("seg", G6dWinoRouteSeg * 4)]
+
+
+# g6d_wino_multi_route's `entry` argument: the launch it stands for
+WINO_ROUTE_ENTRIES = {"g6d_wino_conv3x3_multi": 0, "g6d_wino_conv3x3": 1, "g6d_wino16_conv3x3_multi": 2, "g6d_wino43_conv3x3_multi": 3,
+                      "g6d_corr2d_wino_multi": 4, "g6d_corr2d_wino43_multi": 5}
+
+
 class G6dConv(C.Structure):
     _fields_ = [
         ("in_", C.c_void_p), ("mul", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p),
@@ -147,6 +163,7 @@ SIGNATURES = {
     "g6d_wino_conv3x3_multi": [_P, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P],
     "g6d_wino16_conv3x3_multi": [_P, _I, _I, _P, _P, _I, _I, _I, _P, C.c_size_t, _P],
     "g6d_wino43_conv3x3_multi": [_P, _I, _I, _P, _P, _I, _I, _P, C.c_size_t, _P],
+    "g6d_wino_multi_route": [_I, _P, _I, _I, _P, _I, _I, _I, _P, C.c_size_t, C.POINTER(G6dWinoRoute)],
     "g6d_corr2d_wino43_multi": [_P, _I, _I, _P, _I, _I, _P, C.c_size_t, _P],
     "g6d_l2norm_rows": [_P, _I, _I, _I, _P],
     "g6d_nchw_to_nhwc": [_P, _I, _I, _I, _I, _I, _P, _I, _P],
@@ -226,6 +243,9 @@ def load():
     lib.g6d_sizeof_conv16_route.restype = C.c_int
     if lib.g6d_sizeof_conv16_route() != C.sizeof(G6dConv16Route):
         raise RuntimeError("libgen6d_hip.so: G6dConv16Route layout differs from the ctypes binding (stale build?)")
+    lib.g6d_sizeof_wino_route.restype = C.c_int
+    if lib.g6d_sizeof_wino_route() != C.sizeof(G6dWinoRoute):
+        raise RuntimeError("libgen6d_hip.so: G6dWinoRoute layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_frame_desc() != C.sizeof(G6dFrame):
         raise RuntimeError("libgen6d_hip.so: G6dFrame layout differs from the ctypes binding (stale build?)")
     if lib.g6d_sizeof_mesh_desc() != C.sizeof(G6dMesh):

@@ -482,6 +482,39 @@ int g6d_l2norm_split16(const float* in, int ld_in, int rows, int C, void* out, i
 int g6d_wino43_conv3x3_multi(const G6dWinoSeg* segs, int nseg, int Cin, const float* U43, const float* bias, int Cout, int relu,
                              float* workspace, size_t workspace_bytes, g6d_stream_t stream);
 
+/* What the host chooses for a launch of one of the Winograd entry points under the current knobs (additive to ABI v12; launches nothing,
+   reads no operand, makes no HIP call, and is the launchers' own validation and decision code, not a restatement of it): the entry's
+   argument checks, the segment table, the plan (block form, split of the chunk list), the kernel instantiation and, for F(4x4,3x3), the
+   block-id decode.  Returns G6D_OK, or G6D_EINVAL with the launch's message where the launch would be refused (the fields are then not
+   meaningful).  `entry` says which launch is meant and how `segs` is read:
+     0  g6d_wino_conv3x3_multi     G6dWinoSeg rows      3  g6d_wino43_conv3x3_multi   G6dWinoSeg rows
+     1  g6d_wino_conv3x3           ONE G6dWinoSeg row    4  g6d_corr2d_wino_multi      G6dCorrSeg rows
+        holding its scalar arguments (nseg = 1)          5  g6d_corr2d_wino43_multi    G6dCorrSeg rows
+     2  g6d_wino16_conv3x3_multi   G6dWinoSeg rows
+   U: the launch's filter pointer (only its value is checked); kblocks: entries 4 and 5, else 0; math_mode: entry 2, else 0; workspace,
+   workspace_bytes: as handed to the launch.  tests/wino_sweep.py files its cases by it. */
+typedef struct G6dWinoRoute {
+  int32_t entry;           /* as passed */
+  int32_t family;          /* the kernel: 0 F(2x2,3x3) fp32, 1 16-bit operands with one wave per SIMD, 2 16-bit operands with two waves per SIMD
+                              (un-split trunk launches, knob wino16_2w), 3 F(4x4,3x3) */
+  int32_t kd;              /* sub-filter blocks accumulated in the transform domain: 1, or kblocks^2 = 25 / 9 */
+  int32_t wide;            /* family 0: 1 = blocks of two quarters x 128 channels (knob wino_wide); otherwise 0 */
+  int32_t nq;              /* quarters (8x8 output pixels) of the flat list per block: 4, 2 (wide) or 8 (family 3) */
+  int32_t nwn;             /* channel width of a block: families 0 - 2 in 32s (1, 2 or 4), family 3 in 16s (nt = 2 or 4) */
+  int64_t grid2;           /* blocks x channel slices: the tile counters a split launch uses */
+  int32_t blocks;          /* blocks over the quarter list */
+  int32_t nchunks;         /* kd x input-channel chunks (8 channels; 16 for families 1 and 2) */
+  int32_t splits;          /* parts of the chunk list = gridDim.z (1: no split) */
+  int32_t chunks_per_split;       /* chunks of every part but the last, which has nchunks - (splits - 1) * chunks_per_split */
+  int32_t map_mode;        /* family 3: the block-id decode that runs (knob w43_map; 0 whenever there is one channel slice); otherwise 0 */
+  int32_t lds_bytes;       /* dynamic LDS asked for */
+  struct { int32_t qstart, QH, QW; } seg[4];      /* first quarter of the segment in the flat list, quarters per map column / row;
+                                                     segments past nseg: zeros */
+} G6dWinoRoute;
+int g6d_wino_multi_route(int entry, const void* segs, int nseg, int Cin, const void* U, int Cout, int kblocks, int math_mode,
+                         const float* workspace, size_t workspace_bytes, G6dWinoRoute* route);
+int g6d_sizeof_wino_route(void);
+
 /* In-place L2 normalisation over C of channels-last rows x[rows][ld] (F.normalize eps 1e-12, network/selector.py:118,
  * network/refiner.py:69-71,165).  16-byte accesses when x is 16-byte aligned and ld % 4 == 0 (then C % 4 == 0 is required),
  * scalar accesses otherwise (the [qn][7] rows of the regressor output).  ld >= C, rows <= 2^31 - 4. */

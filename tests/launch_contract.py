@@ -422,9 +422,23 @@ E("g6d_wino16_conv3x3_multi",
   wino_multi_cases(16) + [rej("mode", "math_mode=0", math_mode=0), rej("mode", "math_mode=3", math_mode=3), acc("mode", "math_mode=1", math_mode=1)])
 E("g6d_wino43_conv3x3_multi", [T("segs", lib.G6dWinoSeg, wino_rows(8, 64), WINO_FIELDS), I("nseg", 1), N("Cin", 8), P("U43", "req"), *WINO_TAIL, *WS, S()],
   wino_multi_cases(8))
+# g6d_wino_multi_route is the entry points' own argument checks, segment table and plan run without the launch: the same refusals as the
+# launch `entry` stands for (baseline: 0 = g6d_wino_conv3x3_multi), nothing launched and no operand read, and it needs its out struct.  The
+# G6dCorrSeg tables of entries 4 and 5 are issued by tests/test_wino_sweep_cpu.py (every correlation case, and the kblocks = 3 probe).
+E("g6d_wino_multi_route",
+  [I("entry", 0), T("segs", lib.G6dWinoSeg, wino_rows(8, 64), WINO_FIELDS), I("nseg", 1), N("Cin", 8), P("U", "req"), N("Cout", 64),
+   X("kblocks", 0, "read for entries 4 and 5 only (G6dCorrSeg tables: tests/test_wino_sweep_cpu.py issues them, kblocks = 3 refused on entry 4)"),
+   I("math_mode", 0), *WS, H("route", C.c_int64, [0] * 13)],
+  wino_multi_cases(8) + [rej("mode", "entry=-1", entry=-1), rej("mode", "entry=6", entry=6), acc("mode", "entry=3: F(4x4,3x3)", entry=3),
+                         acc("mode", "entry=1: the one-map launch on a one-row table", entry=1), rej("extent", "entry=1 with two rows", entry=1, nseg=2),
+                         rejk("reach", "entry=1: N * H * W * ld_in = 2^29", {"entry": 1, "segs[0].N": 1 << 6, "segs[0].H": 1 << 10, "segs[0].W": 1 << 10}),
+                         rejk("mode", "entry=2 with math_mode=0", {"entry": 2, "Cin": 16, "segs[0].ld_in": 16, "math_mode": 0}),
+                         rejk("mode", "entry=2 with math_mode=3", {"entry": 2, "Cin": 16, "segs[0].ld_in": 16, "math_mode": 3}),
+                         acck("mode", "entry=2 with math_mode=1", {"entry": 2, "Cin": 16, "segs[0].ld_in": 16, "math_mode": 1}),
+                         rej("extent", "entry=2 with Cin=8 off the 16-channel chunk", entry=2, math_mode=2)])
 
 # ---------------------------------------------------------------------------------------------------------- selector
-SEL = [N("D", 6), N("HW", 16), N("C", 8)]
+SEL =[N("D", 6), N("HW", 16), N("C", 8)]
 E("g6d_selector_ref_sums", [P("refs"), *SEL, P("r1"), P("r2"), S()],
   [rej("reach", "HW * C = 2^32", HW=1 << 16, C=1 << 16), rej("reach", "HW * C = 2^31", HW=1 << 16, C=1 << 15), acc("reach", "HW * C = 2^30", HW=1 << 15, C=1 << 15)])
 E("g6d_selector_prod_affine", [P("que"), P("r1"), P("r2"), *SEL, F("eps", 1e-5), P("scale"), P("shift"), S()],

@@ -25,7 +25,7 @@ def test_header_symbols_exported():
         assert hasattr(l, n), f"{n} declared in gen6d_hip.h but not exported by libgen6d_hip.so"
     assert l.g6d_abi_version() == 12
     # every typed binding corresponds to a declared symbol and vice versa
-    assert set(lib.SIGNATURES) | {"g6d_abi_version", "g6d_last_error", "g6d_sizeof_conv_desc", "g6d_sizeof_conv_route", "g6d_sizeof_conv16_route", "g6d_set_knob", "g6d_get_knob",
+    assert set(lib.SIGNATURES) | {"g6d_abi_version", "g6d_last_error", "g6d_sizeof_conv_desc", "g6d_sizeof_conv_route", "g6d_sizeof_conv16_route", "g6d_sizeof_wino_route", "g6d_set_knob", "g6d_get_knob",
                                   "g6d_reset_knobs"} == set(names)
 
 
@@ -65,6 +65,9 @@ def test_struct_layout_matches_header():
     assert C.sizeof(lib.G6dConvRoute) == 8 * 4 == lib.load().g6d_sizeof_conv_route()
     # g6d_conv16_direct_route's report: ten int32 for the launch, six for each of four segments
     assert C.sizeof(lib.G6dConv16Route) == (10 + 4 * 6) * 4 == lib.load().g6d_sizeof_conv16_route()
+    # g6d_wino_multi_route's report: six int32, the int64 grid2 on its natural alignment, six int32, three for each of four segments
+    assert C.sizeof(lib.G6dWinoRoute) == 6 * 4 + 8 + 6 * 4 + 4 * 3 * 4 == lib.load().g6d_sizeof_wino_route()
+    assert lib.G6dWinoRoute.grid2.offset == 24 and lib.G6dWinoRoute.blocks.offset == 32 and lib.G6dWinoRoute.seg.offset == 56
 
 
 def test_null_descriptor_is_rejected_without_gpu():

@@ -162,7 +162,7 @@ FRAMES = "byte-pixel frame kernel: its own tests run unaligned bases and odd pit
 TWIN = "the _ex form is in the case table"
 
 EXEMPT = {
-    "g6d_marker": NO_MAPS, "g6d_zero_bytes": NO_MAPS, "g6d_conv_plan": NO_MAPS, "g6d_conv_route": NO_MAPS, "g6d_conv16_direct_plan": NO_MAPS, "g6d_conv16_direct_route": NO_MAPS, "g6d_corr_fft_plan": NO_MAPS,
+    "g6d_marker": NO_MAPS, "g6d_zero_bytes": NO_MAPS, "g6d_conv_plan": NO_MAPS, "g6d_conv_route": NO_MAPS, "g6d_conv16_direct_plan": NO_MAPS, "g6d_conv16_direct_route": NO_MAPS, "g6d_wino_multi_route": NO_MAPS, "g6d_corr_fft_plan": NO_MAPS,
     "g6d_stats_finalize": NO_MAPS, "g6d_sizeof_frame_desc": NO_MAPS, "g6d_sizeof_mesh_desc": NO_MAPS, "g6d_sizeof_sink_desc": NO_MAPS,
     "g6d_chain_crop_from_detection": TABLES, "g6d_chain_pose_from_selection": TABLES, "g6d_chain_refine_prepare": TABLES,
     "g6d_chain_refine_update": TABLES, "g6d_track_gather": TABLES, "g6d_track_commit": TABLES, "g6d_track_gate": TABLES,
